@@ -11,7 +11,11 @@ inside the timed region (qecmc.sharding.PteqShard: the library's own sharded cal
     python bench.py --gpus 8             starts 8 ranks itself (python -m torch.distributed.run ... bench.py --gpus 8)
     python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8      the driver's form: ranks already exist
     python bench.py --config 3|4|5       the other BASELINE configurations (one line each, same fields)
+    python bench.py --full               the same line with its companions: CPU baseline, oracle histogram match, transfers, scan = 0 kernel
+    python bench.py --dump-outputs DIR   also writes the last timed step's outputs (DIR/<name>.npy) for output-for-output comparisons
 
+A plain run sets up, warms up, times --steps steps and prints the line; whatever else is measured or checked runs only with --full
+(or, for the scan = 1 kernel, with its own switch --sweep).
 Prints ONE JSON line (rank 0).  `value` = chain-sweeps/s over all ranks, a sweep being G Metropolis proposals on one chain,
 G = number of stabilizer generators (2 L^2 toric, L^2 - 1 xzzx / rotated).
 """
@@ -170,6 +174,23 @@ def rank_records(dist, use_dist, world, rank, device_name, device_uuid, kernel_m
     return got
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one float64 .npy per array (exact for the u32 records), rows = syndromes.  Over DUMP_BYTES in all, every
+    array keeps the same fixed, seeded sample of rows, whose indices go to rows.npy, so that two builds compare row for row."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(8 * int(np.prod(a.shape[1:])) for a in arrays.values())
+    budget = DUMP_BYTES - 4096                                  # (the .npy headers)
+    if n * row_bytes > budget:
+        rows = np.sort(np.random.default_rng(0).choice(n, budget // (row_bytes + 8), replace=False))
+        arrays = dict({k: a[rows] for k, a in arrays.items()}, rows=rows)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def cpu_model():
     try:
         for ln in open("/proc/cpuinfo"):
@@ -251,22 +272,32 @@ def criterion_bench(args, L_, PteqShard, torch, dist, use_dist, world, rank, loc
         k_ms = float(np.mean(kernel_ms))
         sd = sh.steps_done.cpu().numpy().astype(np.float64)
         conv = sh.converged.cpu().numpy().astype(bool)
+        if args.dump_outputs:
+            res = sh.result()
+            if world == 1:      # (the stopping step and flag are not gathered: rank 0 holds its own shard's only)
+                res.update(steps_done=sd, converged=conv)
+            dump_outputs(args.dump_outputs, res)
         useful_props_launch = float(sd.sum()) * Nc * args.iters                          # this rank's launch
         useful_total = float(useful_steps.item()) * Nc * args.iters * args.steps          # all ranks, all timed launches
         algo_bytes = useful_props_launch * ALGO_BYTES_PER_PROPOSAL + N * (nq + 4 * ncls)
         achieved = algo_bytes / (k_ms * 1e-3) / 1e9
-        # the same kernel family at fixed length on the first 65 536 syndromes: what a ladder step costs without the criterion, the queue
-        # and its tail (time after a workgroup's queue ran dry)
-        n_fix = min(N, 65536)
-        shf = PteqShard(init_h[:n_fix], p_dec, first, n_total=n_fix, steps=10000, **common)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        fix_ms = []
-        for rep in range(3):
-            e0.record(stream); shf.launch(stream); e1.record(stream)
-            torch.cuda.synchronize()
-            fix_ms.append(e0.elapsed_time(e1))
-        shf.close()
-        fixed_rate = n_fix * Nc * args.iters * 10000 / (float(np.mean(fix_ms[1:])) * 1e-3)
+        fixed = {}
+        if args.full:
+            # the same kernel family at fixed length on the first 65 536 syndromes: what a ladder step costs without the criterion, the queue
+            # and its tail (time after a workgroup's queue ran dry)
+            n_fix = min(N, 65536)
+            shf = PteqShard(init_h[:n_fix], p_dec, first, n_total=n_fix, steps=10000, **common)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            fix_ms = []
+            for rep in range(3):
+                e0.record(stream); shf.launch(stream); e1.record(stream)
+                torch.cuda.synchronize()
+                fix_ms.append(e0.elapsed_time(e1))
+            shf.close()
+            fixed_rate = n_fix * Nc * args.iters * 10000 / (float(np.mean(fix_ms[1:])) * 1e-3)
+            # useful rate / the fixed-length rate of the same kernel family on this box: what the criterion, the queue and its tail cost together
+            fixed = {"efficiency_vs_fixed_length": (useful_props_launch / (k_ms * 1e-3)) / fixed_rate,
+                     "fixed_length_proposals_per_s": fixed_rate}
         out = {
             "metric": metric_name(args) + " -- criterion-stopped (decoders.py:25 conv_criteria='error_based', SEQ=2, TOPS=10, eps=0.1)",
             "value": useful_total / n_gen / elapsed,
@@ -288,13 +319,11 @@ def criterion_bench(args, L_, PteqShard, torch, dist, use_dist, world, rank, loc
                          "algorithmic_bytes_per_launch": algo_bytes,
                          "note": "8 B per USEFUL proposal (SURVEY.md 8d convention): steps a ladder ran before it stopped; idle lanes, the two "
                                  "steps a lane waits between ladders and the tail after a workgroup's queue ran dry are time, not work"},
-            # useful rate / the fixed-length rate of the same kernel family on this box: what the criterion, the queue and its tail cost together
-            "efficiency_vs_fixed_length": (useful_props_launch / (k_ms * 1e-3)) / fixed_rate,
-            "fixed_length_proposals_per_s": fixed_rate,
+            **fixed,
             "comm": {"backend": (dist.get_backend() + " (RCCL)") if use_dist else None, "world": dist.get_world_size() if use_dist else 1},
             "ranks": ranks,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle import oracle as orc
             ocode = {"toric": orc.TORIC, "xzzx": orc.XZZX, "rotated": orc.ROTATED, "planar": orc.PLANAR}[args.code]
             cores = os.cpu_count() or 1
@@ -338,8 +367,15 @@ def spawn_ranks(n, argv):
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 5; 2 with --criterion)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default 1; 0 with --criterion)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the companion measurements and checks after the timed steps: the CPU baseline and the oracle's histogram match "
+                         "(unless --no-cpu-baseline), the host-pointer transfer timing, the scan = 0 kernel beside a scan = wave line, the "
+                         "fixed-length rate beside a criterion line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step (class counts, samples, tops0; with --criterion also the "
+                         "stopping step and flag) as float64 DIR/<name>.npy, at most 64 MB in all")
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS), help="BASELINE.json configuration (2 = the metric's)")
     ap.add_argument("--ladder-steps", type=int, default=10000, help="ladder steps per pass (decoders.py `steps`; SURVEY.md 8d: 1e4 for throughput)")
     ap.add_argument("--syndromes", type=int, default=None, help="syndromes per GPU")
@@ -383,8 +419,12 @@ def parse_args(argv=None):
             args.syndromes = (16 if args.alpha_route else 8) * cfg["syndromes"]
         if args.ladder_steps == 10000:
             args.ladder_steps = 262144
-        if args.steps == 5 and args.warmup == 1:      # (a launch runs for seconds: two timed ones, the first launch of the process among them)
+        if args.steps is None and args.warmup is None:      # (a launch runs for seconds: two timed ones, the first launch of the process among them)
             args.steps, args.warmup = 2, 0
+    args.steps = 5 if args.steps is None else args.steps
+    args.warmup = 1 if args.warmup is None else args.warmup
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     for k in ("code", "L", "p", "Nc", "syndromes", "eta"):
         if getattr(args, k) is None:
             setattr(args, k, cfg[k])
@@ -501,6 +541,8 @@ def main():
     if use_dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sh.result())          # (before the --full companions, which reuse the record buffer)
 
     total_proposals = proposals_per_pass * args.steps * world
     sweeps_per_s = total_proposals / n_gen / elapsed
@@ -515,18 +557,23 @@ def main():
         algo_bytes = proposals_per_pass * ALGO_BYTES_PER_PROPOSAL + N * (nq + 4 * ncls)
         achieved = algo_bytes / (k_ms * 1e-3) / 1e9
         pc = profile_counters(args) or {}
-        # the host-pointer boundary (what a caller holding NumPy arrays pays): H2D of the batch + kernel + D2H of the records
-        pinned = torch.from_numpy(init_h.reshape(N, -1)).pin_memory()
-        rec_h = torch.empty_like(sh.rec, device="cpu").pin_memory()
-        incl = []
-        for _ in range(3):
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            sh.d_init.copy_(pinned, non_blocking=True)
-            sh.launch(stream)
-            rec_h.copy_(sh.rec, non_blocking=True)
-            torch.cuda.synchronize()
-            incl.append((time.perf_counter() - t1) * 1e3)
+        transfers = {}
+        if args.full:
+            # the host-pointer boundary (what a caller holding NumPy arrays pays): H2D of the batch + kernel + D2H of the records
+            pinned = torch.from_numpy(init_h.reshape(N, -1)).pin_memory()
+            rec_h = torch.empty_like(sh.rec, device="cpu").pin_memory()
+            incl = []
+            for _ in range(3):
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                sh.d_init.copy_(pinned, non_blocking=True)
+                sh.launch(stream)
+                rec_h.copy_(sh.rec, non_blocking=True)
+                torch.cuda.synchronize()
+                incl.append((time.perf_counter() - t1) * 1e3)
+            transfers = {"ms_per_step_incl_transfers": float(np.median(incl)),
+                         "transfers_note": "pinned H2D of the %.1f MB batch + kernel + D2H of the %.1f MB records, 1 GPU, median of 3 (never `value`)"
+                                           % (init_h.nbytes / 1e6, sh.rec.numel() * 4 / 1e6)}
         out = {
             "metric": metric_name(args),
             "value": sweeps_per_s,
@@ -546,9 +593,7 @@ def main():
             "ranks": ranks,
             "ladder_sweeps_per_s": sweeps_per_s / Nc,
             "kernel_ms_per_launch": k_ms,
-            "ms_per_step_incl_transfers": float(np.median(incl)),
-            "transfers_note": "pinned H2D of the %.1f MB batch + kernel + D2H of the %.1f MB records, 1 GPU, median of 3 (never `value`)"
-                              % (init_h.nbytes / 1e6, sh.rec.numel() * 4 / 1e6),
+            **transfers,
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": pc.get("traffic"),
                          "traffic_unit": "bytes per launch (rocprofv3 2 x FETCH_SIZE + WRITE_SIZE: the gfx950 correction of MI355X_MICROARCH.md; profiles/)",
@@ -562,7 +607,7 @@ def main():
             "mixing": {"frac_syndromes_past_burn_in": float(np.mean(samples > 0)),
                        "mean_tops0": float(np.mean(tops0)), "frac_tops0_ge_10": float(np.mean(tops0 >= 10))},
         }
-        if world == 1 and not args.no_cpu_baseline and args.scan in ("random", "wave"):
+        if args.full and world == 1 and not args.no_cpu_baseline and args.scan in ("random", "wave"):
             out["cpu_baseline"] = cpu_baseline(args, init_h, n_gen)
             if args.p_logical == 0.5:
                 # the metric's "eq-class histogram match": the oracle (the checker, on the same Philox streams) must give the
@@ -592,7 +637,7 @@ def main():
                                           "final_states_bit_identical_to_cpu_oracle": bool(np.array_equal(again["states"], ref["states"])),
                                           "match": bool(same and hist0 and np.array_equal(tops0[:n_chk].astype(np.uint64), ref["tops0"].astype(np.uint64)) and
                                                         np.array_equal(again["states"], ref["states"]))}
-        if world == 1 and args.scan == "wave":
+        if args.full and world == 1 and args.scan == "wave":
             # the same batch through the scan = 0 kernel (the chain pinned draw for draw to the reference's injected-stream fixtures), for the record
             pr0 = L_.make_params(code=code_id, L=L, Nc=Nc, p=p_dec, p_logical=args.p_logical, iters=args.iters, steps=args.ladder_steps, tops_burn=2,
                                  seed=args.seed, device=local_rank, scan=L_.SCAN_RANDOM, flags=args.flags, **rkw)

@@ -126,3 +126,63 @@ def test_bench_argument_defaults_of_the_criterion_and_alpha_routes():
     assert bench.parse_args(["--config", "2", "--code", "xzzx"]).scan == "wave" and bench.parse_args(["--config", "2", "--code", "xzzx", "--iters", "7"]).scan == "random"
     assert bench.parse_args(["--syndromes", "1000"]).scan == "random"
     assert bench.parse_args(["--iters", "7"]).scan == "random" and bench.parse_args(["--iters", "7", "--Nc", "9"]).scan == "wave"
+
+
+def test_bench_steps_are_what_the_caller_asked_for():
+    """--steps / --warmup are taken as given in every mode (a criterion run's own defaults apply only when neither is given)"""
+    sys.path.insert(0, ROOT)
+    import bench
+    for extra in ([], ["--criterion"], ["--alpha-route", "--criterion"]):
+        a = bench.parse_args(extra + ["--steps", "5", "--warmup", "1"])
+        assert (a.steps, a.warmup) == (5, 1)
+        a = bench.parse_args(extra + ["--steps", "7", "--warmup", "0"])
+        assert (a.steps, a.warmup) == (7, 0)
+    assert (bench.parse_args(["--criterion", "--steps", "3"]).warmup, bench.parse_args(["--steps", "3"]).warmup) == (1, 1)
+    assert bench.parse_args([]).full is False and bench.parse_args(["--full"]).full is True
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_bench_dump_outputs_exact_and_bounded(tmp_path):
+    """--dump-outputs: u32 records as exact float64; above the cap every array keeps the same seeded rows, listed in rows.npy"""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(1)
+    small = dict(counts=rng.integers(0, 2**32, (100, 16), dtype=np.uint32), samples=np.arange(100, dtype=np.uint32))
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    got = np.load(tmp_path / "a" / "counts.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.uint64), small["counts"].astype(np.uint64))
+    assert not (tmp_path / "a" / "rows.npy").exists()
+    n = 600000                                                   # 600 000 x (16 + 2) x 8 B = 86 MB > 64 MB
+    big = dict(counts=np.tile(np.arange(n, dtype=np.uint32)[:, None], (1, 16)), samples=np.arange(n, dtype=np.uint32),
+               tops0=np.arange(n, dtype=np.uint32))
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    total = sum(os.path.getsize(p) for p in (tmp_path / "b").iterdir())
+    assert total <= 64 << 20
+    rows = np.load(tmp_path / "b" / "rows.npy")
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "rows.npy")) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "b" / "samples.npy"), rows) and np.array_equal(np.load(tmp_path / "b" / "counts.npy")[:, 3], rows)
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_timed_path_results(tmp_path):
+    """A plain run with --dump-outputs, in a fresh child process: the files hold the last timed step's class counts, samples and tops0,
+    equal to the CPU oracle's on the same Philox streams; the line carries no --full companion."""
+    sys.path.insert(0, ROOT)
+    import bench
+    # (3000 ladder steps: long enough that the oracle's rows are not all zero -- at a few hundred no ladder passes the burn-in)
+    argv = ["--steps", "2", "--warmup", "1", "--syndromes", "4096", "--ladder-steps", "3000"]
+    r = _run(*argv, "--dump-outputs", str(tmp_path))
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert not {"cpu_baseline", "histogram_match", "random_scan", "ms_per_step_incl_transfers"} & set(out)
+    got = {k: np.load(tmp_path / (k + ".npy")) for k in ("counts", "samples", "tops0")}
+    assert got["counts"].shape == (4096, 16) and all(v.dtype == np.float64 for v in got.values())
+    a = bench.parse_args(argv)
+    init = bench.make_batch(a, 0)[:64]
+    ref = bench.oracle_batch(a, init, a.ladder_steps, 16)
+    assert ref["counts"].sum() > 0 and (ref["samples"] > 0).any() and (ref["tops0"] > 0).any()      # a comparison that can fail
+    for k in ("counts", "samples", "tops0"):
+        assert np.array_equal(got[k][:64].astype(np.uint64), np.asarray(ref[k]).astype(np.uint64)), k

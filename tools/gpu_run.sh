@@ -35,7 +35,7 @@ case "$1" in
     for c in "$@"; do bash tools/profile_round.sh $tag $c > gpurun_out/prof_${tag}_cfg$c.log 2>&1 || exit 1; tail -2 gpurun_out/prof_${tag}_cfg$c.log; done
     ;;
   criterion)    # criterion [bench args]: the reference's default route (bench.py --criterion), the line kept under gpurun_out/
-    shift
+    shift; set -- --full "$@"     # the line with its companions: fixed-length rate, CPU baseline, oracle check
     timeout -k 10 1000 python bench.py --criterion "$@" > gpurun_out/criterion_bench.json 2> gpurun_out/criterion_bench.err; tail -c 1500 gpurun_out/criterion_bench.json
     ;;
   bench-all)    # every bench mode once, condensed (a regression guard after a kernel change: a layout change that costs one mode a workgroup per CU shows here)

@@ -24,7 +24,7 @@ sys.argv = ["bench.py", "--config", str(cfg)] + sys.argv[3:]
 sys.path.insert(0, ".")
 import bench
 a = bench.parse_args(sys.argv[1:])
-# the DOMINANT ladder kernel of the run (bench.py also launches companions: the scan = 0 kernel beside a scan = wave headline, the
+# the DOMINANT ladder kernel of the run (with --full, bench.py also launches companions: the scan = 0 kernel beside a scan = wave headline, the
 # fixed-length kernel beside a criterion run): the one of the line's own scan that the kernel trace gives the largest total time
 dominant = None
 for r in csv.DictReader(open(out + "/kernel_stats.csv")):
@@ -44,6 +44,6 @@ summ['_workload'] = {k: getattr(a, k) for k in ("code", "L", "p", "eta", "Nc", "
 json.dump(summ, open(out + "/pmc_summary.json", "w"), indent=1, sort_keys=True)
 print(json.dumps(summ, sort_keys=True)[:1500])
 PY
-python3 bench.py --config $cfg --steps 5 --warmup 1 "$@" > $out/bench.json 2> $out/bench.err
+python3 bench.py --config $cfg --full "$@" > $out/bench.json 2> $out/bench.err      # (default steps: 5 + 1 warmup, 2 + 0 with --criterion)
 rm -rf $out/kt $out/pmc_?
 ls -la $out
