@@ -214,26 +214,9 @@ int build_plan(const qecmc_params *p, qecmc_plan *pl)
     }
     pl->lds_bytes = p->scan == QECMC_SCAN_COLOUR ? sizeof(uint32_t) * ((size_t)Nc * W + 4 * (size_t)Nc + (size_t)ncls)   // (ladder_colour.hip: one ladder per workgroup)
                   : p->scan == QECMC_SCAN_WAVE ? wu_lds_bytes(Nc, W, ncls, L, p->conv_mode != 0, alpha)
-                                                 : ladder_lds_bytes(L, Nc, W, ncls, ladder_gen_dwords(p->code, p->noise, p->scan, n_gen, Nc, nq, a.n_types));
+                                                 : ladder_lds_bytes(Nc, W, ncls, ladder_gen_dwords(p->code, p->noise, p->scan, n_gen, Nc, nq, a.n_types));
     if (pl->lds_bytes > 160 * 1024)
         return fail(QECMC_ERR_UNSUPPORTED, "L=%d Nc=%d needs %zu B of LDS per workgroup (> 160 KiB)", L, Nc, pl->lds_bytes);
-    const bool wave_queue = p->scan == QECMC_SCAN_WAVE && p->conv_mode != 0;      // (ladder_wu.hpp: the workgroups' own work queues)
-    if (ladder_uses_queue(p->code, p->noise, p->scan, p->conv_mode, L, Nc, p->p_logical) || wave_queue) {
-        // runs that stop by the convergence criterion: a persistent grid (what one launch keeps resident) fed from a counter
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, p->device));
-        // (waves per CU: 8 per SIMD for the 512-thread depolarizing kernels, 4 for the 1024-thread ones and for the biased / alpha
-        // queue kernels, which run at 128 VGPRs: ladder_biased.hip)
-        const size_t per_cu_lds = (160 * 1024) / pl->lds_bytes,
-                     per_cu_waves = (size_t)(wave_queue ? (alpha ? 4 * kWuAlphaQueueWaves : W > 12 ? 24 : 32)      // (ladder_wu.hpp wu_pick_it: 8 waves per SIMD, 6 at 16 words)
-                                                        : (Nc * 64 <= 512 && !p->noise) ? 32 : 16) / (size_t)Nc;
-        size_t per_cu = per_cu_lds < per_cu_waves ? per_cu_lds : per_cu_waves;
-        if (per_cu < 1) per_cu = 1;
-        pl->queue_grid = (uint32_t)(per_cu * (size_t)prop.multiProcessorCount);
-        if (p->flags >> 16) pl->queue_grid = p->flags >> 16;   // tests: force refills on small batches
-        if (pl->queue_grid == 0) pl->queue_grid = 1;
-        if (!wave_queue) HIP_TRY(pl->queue.alloc(sizeof(uint32_t)));
-    }
 
     std::vector<double> pladder, pdiff;
     // p_top = 0.75 (mcmc.py:62) or (eta+1)/(2 eta+1) (mcmc_biased.py:81)
@@ -357,10 +340,26 @@ int build_plan(const qecmc_params *p, qecmc_plan *pl)
     a.acc_tbl_top = pl->acc_top.as<uint32_t>();
     a.swap_thr = pl->swap_thr.as<uint64_t>();
     a.lmask = pl->lmask.as<uint32_t>();
-    if (p->scan == QECMC_SCAN_WAVE && (!wu_supported(a) || pl->lds_bytes > 160 * 1024))
+    KernelShape shape = kernel_shape(a);
+    if (p->scan == QECMC_SCAN_WAVE && (!choose_kernel(shape).ok() || pl->lds_bytes > 160 * 1024))
         return fail(QECMC_ERR_UNSUPPORTED, "scan = wave: L=%d Nc=%d p=%g is outside what it is built for (depolarizing rule: a top rung that accepts every move, at most "
                     "16 packed state words per rung -- toric / planar L <= 11, xzzx / rotated L <= 16 --, fixed-length runs of up to 8 rungs 32 words -- toric L <= 16, xzzx / rotated L <= 22; alpha rule: xzzx / rotated L <= 11, "
                     "4 iters max|log2 ratio| <= 2000 --, %zu B of LDS)", L, Nc, p->p, pl->lds_bytes);
+    // runs that stop by the convergence criterion, where the kernel takes a work queue: a persistent grid (what one launch keeps resident) fed
+    // from a counter (scan = wave: the workgroups' own shares of the batch), of as many workgroups as the LDS and the kernel's occupancy let a CU hold
+    shape.queue = 1;
+    const KernelKey queue_kernel = choose_kernel(shape);
+    if (queue_kernel.takes_queue()) {
+        hipDeviceProp_t prop;
+        HIP_TRY(hipGetDeviceProperties(&prop, p->device));
+        const size_t per_cu_lds = (160 * 1024) / pl->lds_bytes, per_cu_waves = (size_t)(4 * queue_kernel.minw) / (size_t)Nc;
+        size_t per_cu = per_cu_lds < per_cu_waves ? per_cu_lds : per_cu_waves;
+        if (per_cu < 1) per_cu = 1;
+        pl->queue_grid = (uint32_t)(per_cu * (size_t)prop.multiProcessorCount);
+        if (p->flags >> 16) pl->queue_grid = p->flags >> 16;   // tests: force refills on small batches
+        if (pl->queue_grid == 0) pl->queue_grid = 1;
+        if (queue_kernel.family == kFamLadder) HIP_TRY(pl->queue.alloc(sizeof(uint32_t)));
+    }
     return 0;
 }
 
@@ -731,7 +730,7 @@ static int ladder_step_impl(const qecmc_params *params, uint64_t N, uint8_t *sta
     a.N = N; a.first_syndrome = p.first_syndrome; a.step0 = step0; a.prop0 = prop0; a.nsteps = nsteps;
     a.seed_lo = (uint32_t)p.seed; a.seed_hi = (uint32_t)(p.seed >> 32);      // (the cached tables do not depend on the seed: patched per call)
     a.resume = 1; a.write_states = 1;
-    HIP_TRY(launch_ladder_rs_toric(a, 0));
+    HIP_TRY(launch_ladder(a, 0));
     HIP_TRY(hipMemcpy(h.data(), d.p, total, hipMemcpyDeviceToHost));
     if (neff_inout) std::memcpy(neff_inout, h.data(), N * Nc * 4);
     std::memcpy(tops0_inout, h.data() + o_t0, N * 4);
@@ -889,7 +888,7 @@ int qecmc_pteq_launch_dev(qecmc_plan *plan, const void *d_init, uint64_t N, uint
         a.queue = plan->queue.as<uint32_t>();
         a.grid_cap = plan->queue_grid;
     }
-    HIP_TRY(launch_ladder_rs_toric(a, strm));
+    HIP_TRY(launch_ladder(a, strm));
     return 0;
 }
 
@@ -926,7 +925,7 @@ int qecmc_pteq_resume_dev(qecmc_plan *plan, void *d_states, void *d_flags, void 
     a.N = N; a.first_syndrome = first_syndrome;
     a.step0 = step0; a.prop0 = step0 * plan->prm.iters; a.nsteps = plan->prm.steps;
     a.resume = 1; a.write_states = 1; a.accumulate = 1;
-    HIP_TRY(launch_ladder_rs_toric(a, static_cast<hipStream_t>(hip_stream)));
+    HIP_TRY(launch_ladder(a, static_cast<hipStream_t>(hip_stream)));
     return 0;
 }
 
@@ -1103,7 +1102,7 @@ int qecmc_ptdc_batch_xyz(const qecmc_params *params, const uint8_t *init, uint64
     a.uset_xyz = xyz_out ? dxyz.as<uint32_t>() : nullptr; a.uset_xyz_cnt = xyz_out ? dxc.as<uint32_t>() : nullptr; a.uset_xyz_stride = maxu;
     a.xyz_thr = xyz_thr.empty() ? nullptr : dthr.as<uint64_t>();
     {
-        const hipError_t e = launch_ladder_rs_toric(a, 0);
+        const hipError_t e = launch_ladder(a, 0);
         if (e != hipSuccess) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return fail(QECMC_ERR_HIP, "PTDC launch: %s", hipGetErrorString(e)); }
     }
     HIP_TRY(hipEventRecord(e1, 0));

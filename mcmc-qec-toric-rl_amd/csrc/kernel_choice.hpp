@@ -1,0 +1,284 @@
+// Which kernel a ladder launch runs: the one place that decides it.  Host C++ only (like tables.hpp): capi.hip and the launch
+// path (ladder_rs.hip) ask choose_kernel(), and tables_test_api.cpp builds it alone with g++ so that tests/test_kernel_choice.py can
+// enumerate every shape the C-ABI accepts.  The LDS carve-ups the choice depends on live here too; the kernels include them from here.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "stencil_bytes.hpp"   // kCode* constants
+
+namespace qecmc {
+
+constexpr int kSwapFast = 64;       // swap-threshold entries per rung pair kept in LDS (d < kSwapFast)
+constexpr uint32_t kMaxGenLds = 2048;   // generator tables up to this many entries are staged in LDS
+constexpr int kLutTypes = 8;        // rows of the plaquette codes' dE look-up table (Pauli patterns of their generators; more: no table)
+constexpr int kGenSplit = 255;      // ds_read2_b64's second offset is an 8-bit count of 8-byte units
+
+// The variants of ladder_kernel<MAXT, MINW, CODE, FLAGS> (ladder_kernel.hpp describes each)
+enum LadderFlag : uint32_t {
+    kConv = 1u << 0, kGsplit = 1u << 1, kBiased = 1u << 2, kScan = 1u << 3, kGentop = 1u << 4, kUset = 1u << 5, kAlpha = 1u << 6,
+    kPre = 1u << 7, kDelut = 1u << 8, kQueue = 1u << 9, kSsw = 1u << 10,
+};
+
+// ladder_kernel: dwords of one group (keep in sync with the kernel)
+__host__ __device__ inline int ladder_group_dwords(int Nc, int W, int ncls, int gen_dwords)
+{
+    // st + info[2] + swx[2] + hist + thrT + swapT + stop flag (16) + generator table
+    int d = Nc * W * 64 + 4 * Nc * 64 + ncls * 64 + Nc * 9 + Nc * kSwapFast + 16;
+    d = (d + 3) & ~3;          // 16-byte aligned generator table (ds_read_b128 entries)
+    return d + ((gen_dwords + 3) & ~3);
+}
+inline size_t ladder_stats_lds_bytes(int Nc) { return sizeof(uint32_t) * 64u * (size_t)(2 * Nc); }   // [Nc] swap accepts (row Nc-1 idle) + [Nc] error sums
+// dwords of the LDS generator table: the toric random-scan kernels expand each generator to 4 x u32
+// (byte offset << 16 | pauli fields | bit shift), the other paths keep the plan's 4 x u16 form.  Up to kGenSplit
+// generators the expanded table is stored as two halves kGenSplit entries apart (sites 0,1 | sites 2,3).
+// alpha noise appends the double-buffered n_eff records [2][Nc][64] to the region
+// ... and the biased / alpha rules' count-change table uint2[n_types][256] and packed per-state counts uint32[Nc][64]
+// lattice size of a plaquette code from its qubit count (xzzx / rotated: L x L; planar: 2 L^2 with an idle row and column)
+inline int nq_L(int code, int nq) { int L = 1; while ((code == 3 ? 2 * L * L : L * L) < nq) ++L; return L; }
+inline int ladder_gen_dwords(int code, int noise, int scan, uint32_t n_gen, int Nc, int nq = 0, int n_types = 0)
+{
+    // depolarizing random scan: the expanded table of the non-top proposal loop; the plaquette codes also keep the plan's
+    // form for their top-chain / general paths
+    const bool wide = !scan;                                   // (biased / alpha kernels: unsplit, next to the plan's form)
+    // (toric, unsplit: 128 dwords behind the table for the dE look-up table, which the split form keeps between its halves)
+    // (plaquette codes: 256 bytes per Pauli pattern behind their expanded table)
+    const int lut_tail = noise ? 0 : code == 0 ? ((int)n_gen > kGenSplit ? 128 : 0) : 64 * kLutTypes;
+    // (the xzzx / rotated / planar kernels are never built with kGsplit and carve 4 G dwords: this reserves the split size for them too)
+    const int wide_dw = ((!noise && (int)n_gen <= kGenSplit) ? 2 * (kGenSplit + (int)n_gen) : 4 * (int)n_gen) + lut_tail;
+    int d = wide ? (code == 0 ? wide_dw : ((2 * (int)n_gen + 3) & ~3) + wide_dw) : 2 * (int)n_gen;
+    if (noise == 2) d = ((d + 3) & ~3) + 2 * Nc * 64;
+    // (8 bytes per count-change entry; + the X / Z logical masks [2][L+1][W]; xzzx: + the logical operators' fields per generator)
+    if (noise) d = ((d + 3) & ~3) + 512 * n_types + Nc * 64 + 2 * (nq_L(code, nq) + 1) * ((nq + 15) / 16) + (code == 1 ? (((int)n_gen + 1) & ~1) + 3 * 64 : 0);
+    return d;
+}
+inline size_t ladder_lds_bytes(int Nc, int W, int ncls, int gen_dwords) { return sizeof(uint32_t) * (size_t)ladder_group_dwords(Nc, W, ncls, gen_dwords); }
+
+// ladder_colour_kernel: LDS of one workgroup (dwords): states, records, swap uniforms, histogram, then the tables every phase reads -- the
+// phase table, the generator table, the logical masks, the swap thresholds (32-bit where they fit) -- so that the serial path of a
+// step never waits for global memory
+// (noise != 0: the rule's 81 thresholds per rung; the alpha rule's n_eff records by step parity)
+inline size_t colour_lds_dwords(int Nc, int W, int ncls, uint32_t n_phases, uint32_t n_gen, int L, int nq, bool swap32, int noise = 0)
+{
+    return (size_t)Nc * W + 4 * (size_t)Nc + ncls + 32u * n_phases + 2u * n_gen + 4u * (L + 1) * W +
+           (swap32 ? 1u : 2u) * (size_t)(Nc > 1 ? Nc - 1 : 0) * (nq + 1) + 2 + 4 +   // (+ 2: the stop flag by step parity)
+           (noise ? (size_t)Nc * 81 + 2 * (size_t)Nc : 0);
+}
+
+// ladder_wu_kernel: LDS carve-up of one workgroup (dwords): the exchange buffer (W words per rung), records, swap uniforms, histogram, acceptance
+// rows, swap rows, logical masks (rows padded to WV words, + 64: the frame reads a row with all 64 lanes), stop / refill flags, and -- the
+// criterion kernels -- wave 0's per-ladder bookkeeping [kWuBk][64] and the refill mailbox [2][64]
+struct WuLds { int xbuf, rec, swd, hist, thr, swapT, lml, stop, bk, mail, bot, cht, nef, lnb, bot2, total; };
+constexpr int kWuBk = 13;      // tops0, samples, burn, conv_start, conv_streak, sumA lo / hi, sumB lo / hi, state (done | pending << 1 | has << 3),
+                               // steps_done, converged, the lane's ladder (QUEUE)
+constexpr int kWuBkAlpha = 17; // ... and the alpha rule's second pair of window sums (n_x + n_y): sumAxy lo / hi, sumBxy lo / hi
+__host__ __device__ inline int wu_words(int W) { return W <= 4 ? 4 : W <= 8 ? 8 : W <= 12 ? 12 : W <= 16 ? 16 : 32; }   // WV: state words per rung, padded
+constexpr int kWuHalf = 16;                                                                               // rows per rung of a 32-word kernel's exchange buffer
+// rows per rung of the exchange buffer.  The fixed-length kernels give a rung the kernel's padded width (16 per half of a 32-word state): the padding
+// words travel with the rest (they are zero), so that no transfer tests the lattice's width at run time on the scalar unit, the busiest unit of these
+// kernels (-30 tests per step at 29 words).  The criterion kernels keep the tight layout -- W rows, a transfer of a word at or beyond wu_words_min
+// tests the width --: padded rows cost the headline shape's criterion kernel its fourth workgroup per CU (42 KB instead of 39.9) and the route 11 %.
+__host__ __device__ inline int wu_rows(int W, bool conv) { return W > 16 ? kWuHalf : conv ? W : wu_words(W); }
+// (alpha rule: the 9 x 9 table of a proposal's count change as two fp16 numbers, the slots' n_eff attributes as doubles [Nc][64], ln(pz_i / pz_i+1),
+// and -- criterion runs -- slot 0's n_eff record by step parity)
+__host__ __device__ inline WuLds wu_lds(int Nc, int W, int ncls, int L, bool conv, bool alpha = false)
+{
+    const int WV = wu_words(W);
+    WuLds o;
+    o.xbuf = 0;
+    o.rec = o.xbuf + Nc * wu_rows(W, conv) * 64;
+    o.swd = o.rec + Nc * 64;
+    o.hist = o.swd + Nc * 64;
+    o.thr = o.hist + ncls * 64;               // [Nc][2][9]: high 13 / low 32 bits of ceil(f^dE 2^44), dE + 4 = 0 .. 8
+    o.swapT = o.thr + Nc * 18;
+    o.lml = o.swapT + Nc * kSwapFast;
+    o.stop = o.lml + 4 * (L + 1) * WV + 64;
+    o.bk = o.stop + 4;
+    o.mail = o.bk + (conv ? (alpha ? kWuBkAlpha : kWuBk) * 64 : 0);   // [2][64] refill orders by step parity
+    o.bot = o.mail + (conv ? 2 * 64 : 0);                    // [2][64] the record that landed in rung 0, by step parity
+    o.cht = o.bot + (conv ? 2 * 64 : 0);
+    o.nef = (o.cht + (alpha ? 84 : 0) + 1) & ~1;             // (doubles: 8-byte aligned)
+    o.lnb = o.nef + (alpha ? Nc * 128 : 0);
+    o.bot2 = o.lnb + (alpha ? 2 * Nc : 0);
+    o.total = o.bot2 + (alpha && conv ? 2 * 64 : 0);
+    return o;
+}
+inline size_t wu_lds_bytes(int Nc, int W, int ncls, int L, bool conv, bool alpha) { return sizeof(uint32_t) * (size_t)wu_lds(Nc, W, ncls, L, conv, alpha).total; }
+
+// What the choice reads of a launch (kernel_shape(LadderArgs), ladder_rs.hip).  top_acc / lower_acc: the top rung / some rung below it accepts every
+// proposal (acc_all_mask); logical: thr_logical != 0; queue: a work queue is offered (a.queue; build_plan asks with 1 whether a plan takes one);
+// uset / xyz / stats / neff: a.uset_tab / a.xyz_thr / a.swap_acc / a.neff given; f32ok: every rung below the top may take the single-precision
+// acceptance estimate (bias_f32ok); tune: the developer bits of qecmc_params.flags (include/qecmc.h qecmc_flag)
+struct KernelShape {
+    int code, noise, scan, L, Nc, W, nq, ncls, n_gen, n_types, gen_type, top_acc, lower_acc, logical, conv, queue, uset, xyz, stats, resume, neff, f32ok,
+        swap_fast_ok, iters, tune;
+};
+
+// The kernel a shape runs: ladder_kernel<maxt, minw, code, flags>, ladder_wu_kernel<maxt, minw, code, wv, conv, queue = conv, it, alpha> or
+// ladder_colour_kernel<code, conv, rule, maxt, minw>; family kRefused: no kernel is built for the shape (`why` names the rule)
+enum KernelFamily : int { kRefused = 0, kFamLadder = 1, kFamWave = 2, kFamColour = 3 };
+struct KernelKey {
+    int family, maxt, minw, code;
+    uint32_t flags;
+    int wv, conv, it, alpha, rule;
+    const char *why;
+    bool ok() const { return family != kRefused; }
+    bool takes_queue() const { return family == kFamLadder ? (flags & kQueue) != 0 : family == kFamWave && conv; }   // (scan = wave: its own queue)
+    bool operator==(const KernelKey &o) const
+    {
+        return family == o.family && maxt == o.maxt && minw == o.minw && code == o.code && flags == o.flags && wv == o.wv && conv == o.conv && it == o.it &&
+               alpha == o.alpha && rule == o.rule;
+    }
+};
+inline KernelKey refuse(const char *why) { return {kRefused, 0, 0, 0, 0u, 0, 0, 0, 0, 0, why}; }
+inline KernelKey ladder_key(int maxt, int minw, int code, uint32_t flags) { return {kFamLadder, maxt, minw, code, flags, 0, 0, 0, 0, 0, nullptr}; }
+inline KernelKey wave_key(int maxt, int minw, int code, int wv, bool conv, int it, bool alpha) { return {kFamWave, maxt, minw, code, 0u, wv, conv, it, alpha, 0, nullptr}; }
+inline KernelKey colour_key(int code, bool conv, int rule) { return {kFamColour, 1024, 4, code, 0u, 0, conv, 0, 0, rule, nullptr}; }
+
+// dynamic LDS of a ladder_kernel workgroup (+ the per-lane statistics counters behind the group's region)
+inline size_t ladder_launch_lds(const KernelShape &s)
+{
+    return ladder_lds_bytes(s.Nc, s.W, s.ncls, ladder_gen_dwords(s.code, s.noise, s.scan, s.n_gen, s.Nc, s.nq, s.n_types)) + (s.stats ? ladder_stats_lds_bytes(s.Nc) : 0);
+}
+// PRE (the top chain's Philox blocks drawn ahead: 105-119 VGPRs, 4 waves per SIMD) for ladders of up to 8 rungs whose LDS footprint leaves a CU at most
+// two workgroups anyway.  (A longer ladder would get ONE: toric L = 9, Nc = 9 / 12 / 16 measured 0.31 / 0.39 / 0.44 with PRE against 0.37 / 0.59 / 0.45.)
+inline bool ladder_wants_pre(const KernelShape &s) { return s.Nc >= 3 && s.Nc * 64 <= 512 && 3 * ladder_launch_lds(s) > 160 * 1024 && s.logical && !(s.tune & 2); }
+// a criterion run offered a work queue takes it: depolarizing rule, random scan, the framed top chain (toric L <= 16, plaquette codes L <= 32; a top
+// rung at p = 0.75, i.e. Nc >= 2, with logical moves) ... and the biased / alpha rules on the xzzx / rotated codes (any L, Nc)
+inline bool ladder_takes_queue(const KernelShape &s)
+{
+    if (!s.queue || s.scan || !s.conv || s.uset) return false;
+    return s.noise ? s.code == kCodeXzzx || s.code == kCodeRotated : s.L <= (s.code == kCodeToric ? 16 : 32) && s.Nc >= 2 && s.logical;
+}
+
+// the toric code, depolarizing rule, the reference's random scan: the headline kernel family
+inline KernelKey choose_ladder_toric(const KernelShape &s)
+{
+    const bool big = s.Nc * 64 > 512;                    // 9 .. 16 rungs: 1024-thread workgroups at 4 waves per SIMD
+    // the general top-chain path is needed only for L > 16 or a top chain below p = 0.75 (1-chain ladder)
+    const bool gentop = s.logical && (s.L > 16 || !s.top_acc);
+    const bool gsplit = s.n_gen <= kGenSplit;            // the table layout of ladder_gen_dwords()
+    const size_t lds = ladder_launch_lds(s);
+    // the dE look-up table (DELUT): between the halves of a split table (L <= 9) or behind an unsplit one (L >= 12), ladder_gen_dwords
+    // (three workgroups per CU -- L = 10 ... 12 at 8 temperatures -- are the LDS-bound shapes: -1.5 % with the table)
+    const bool lut = !(s.tune & 4) && (!gsplit || s.n_gen + 64 <= kGenSplit) && (160 * 1024) / lds != 3;
+    uint32_t want = (s.conv ? kConv : 0u) | (gsplit ? kGsplit : 0u);
+    if (s.queue) {
+        if (gentop) return refuse("toric work queue: no general top-chain path");
+        want |= kQueue | ((!big && gsplit && s.n_gen + 64 <= kGenSplit) ? kDelut : 0u);
+    } else if (gentop) {
+        want |= kGentop;
+    } else if (ladder_wants_pre(s)) {
+        return ladder_key(512, 4, kCodeToric, want | kPre | (lut ? kDelut : 0u));
+    } else if (!s.conv && !big && 4 * lds <= 160 * 1024 && !(s.tune & 8) && gsplit) {
+        want |= kSsw | (lut ? kDelut : 0u);              // the swap sweep run once by wave 0 (SSW) pays where four workgroups share a CU
+    } else if (lut) {
+        want |= kDelut;
+    }
+    return big ? ladder_key(1024, 4, kCodeToric, want) : ladder_key(512, 8, kCodeToric, want);
+}
+
+// xzzx, rotated and planar codes, depolarizing rule, random scan: always the table-driven general top-chain path
+inline KernelKey choose_ladder_surf(const KernelShape &s)
+{
+    const bool big = s.Nc * 64 > 512;
+    const size_t lds = ladder_launch_lds(s);
+    // dE of a proposal from the look-up table behind the expanded generator table (DELUT, one row per Pauli pattern)
+    // (measured: +8 % xzzx L = 9, +7.7 % rotated L = 9, +5.6 % rotated L = 13, +1 % planar L = 9 -- four workgroups per CU, bound by VALU
+    // issue; 0 % rotated L = 21 -- two; -4 % xzzx L = 15 -- three per CU, where the LDS pipe is the busier one)
+    const bool lut = !(s.tune & 4) && s.gen_type && s.n_types > 0 && s.n_types <= kLutTypes && (160 * 1024) / lds != 3;
+    uint32_t want = kGentop | (s.conv ? kConv : 0u);
+    if (s.queue) {
+        if (!s.top_acc) return refuse("plaquette-code work queue: no top chain below p = 0.75");   // (built on the blind top chain)
+        want |= kQueue;
+    } else if (ladder_wants_pre(s) && s.top_acc) {       // (the blind path is what the blocks drawn ahead feed)
+        return ladder_key(512, 4, s.code, want | kPre | (lut ? kDelut : 0u));
+    } else if (!s.conv && !big && 4 * lds <= 160 * 1024 && !(s.tune & 8)) {
+        want |= kSsw | (lut ? kDelut : 0u);
+    } else if (lut) {
+        want |= kDelut;
+    }
+    return big ? ladder_key(1024, 4, s.code, want) : ladder_key(512, 8, s.code, want);
+}
+
+// the biased (src/mcmc_biased.py) and alpha (src/mcmc_alpha.py) acceptance rules on the xzzx / rotated codes
+inline KernelKey choose_ladder_biased(const KernelShape &s)
+{
+    if (s.code != kCodeXzzx && s.code != kCodeRotated) return refuse("biased / alpha rule: xzzx and rotated codes only");
+    const bool big = s.Nc * 64 > 512;
+    uint32_t want = kBiased | kGentop | (s.conv ? kConv : 0u) | (s.noise == 2 ? kAlpha : 0u);
+    // (the queue kernels carry the criterion's window sums, the refill state and the biased rule's counts: at 64 VGPRs they would
+    // spill 130-250 B per lane into their hot loops, so they run at 128 VGPRs / 4 waves per SIMD whatever the workgroup size)
+    if (s.queue) return ladder_key(big ? 1024 : 512, 4, s.code, want | kQueue);
+    if (!big && !s.conv && 4 * ladder_launch_lds(s) <= 160 * 1024 && !(s.tune & 8)) want |= kSsw;
+    return big ? ladder_key(1024, 4, s.code, want) : ladder_key(512, 8, s.code, want);
+}
+
+// scan = 1: the systematic generator sweep (depolarizing rule, every code; toric: the general top-chain path as on the random scan)
+inline KernelKey choose_ladder_sweep(const KernelShape &s)
+{
+    const bool gentop = s.code != kCodeToric || (s.logical && (s.L > 16 || !s.top_acc));
+    const uint32_t want = kScan | (s.conv ? kConv : 0u) | (gentop ? kGentop : 0u);
+    return s.Nc * 64 > 512 ? ladder_key(1024, 4, s.code, want) : ladder_key(512, 8, s.code, want);
+}
+
+// the unique-chain set insertion of PTDC / STDC / PTRC / STRC (direct counting)
+inline KernelKey choose_ladder_uset(const KernelShape &s)
+{
+    if ((s.noise && s.noise != 2) || s.scan || s.conv || s.logical) return refuse("uset: depolarizing or alpha rule, random scan, fixed length, no logical moves");
+    if (s.xyz && (s.code == kCodeToric || s.Nc != 1 || s.noise)) return refuse("uset: Chain_xyz runs single chains of the table-driven codes");
+    if (s.noise == 2) {   // STDC_droplet_alpha (decoders.py:510-534)
+        if (s.Nc != 1 || (s.code != kCodeXzzx && s.code != kCodeRotated)) return refuse("uset, alpha rule: single chains of the xzzx / rotated codes");
+        return ladder_key(1024, 4, s.code, kUset | kBiased | kAlpha | kGentop);
+    }
+    const uint32_t want = kUset | (s.n_gen <= kGenSplit ? kGsplit : 0u);
+    return s.Nc * 64 > 512 ? ladder_key(1024, 4, s.code, want) : ladder_key(512, 8, s.code, want);
+}
+
+// scan = 2: one workgroup of 1 024 threads at 4 waves per SIMD per ladder, whatever its length (512 threads at 6 or 8 waves per SIMD:
+// profiles/r04_colour_occupancy_ab.json)
+inline KernelKey choose_colour(const KernelShape &s)
+{
+    if (s.uset) return refuse("uset: not with scan = colour");
+    if (s.noise < 0 || s.noise > 2 || s.resume) return refuse("scan = colour: no resumed ladders");
+    if (s.noise != 0 && s.code != kCodeXzzx && s.code != kCodeRotated) return refuse("biased / alpha rule: xzzx and rotated codes only");
+    return colour_key(s.code, s.conv, s.noise);
+}
+
+// scan = 3 (ladder_wu.hpp): the depolarizing rule with a top rung that accepts every move (Nc >= 2, p_top = 0.75) and rungs at distinct
+// temperatures, up to 16 state words per rung (toric / planar L <= 11, xzzx / rotated L <= 16), fixed-length runs of up to 8 rungs also up to 32
+// (toric L <= 16, xzzx / rotated L <= 22); the alpha rule (top rung at pz_tilde = 1) on the xzzx / rotated codes up to 8 words, where every rung
+// below the top may take the single-precision acceptance estimate; 1 <= iters <= 128
+inline bool wu_supported(const KernelShape &s)
+{
+    if (s.noise == 2)
+        return (s.code == kCodeXzzx || s.code == kCodeRotated) && s.Nc >= 2 && s.Nc <= 16 && s.W <= 8 && s.n_gen <= 1023 && s.iters >= 1 && s.iters <= 128 &&
+               s.f32ok && !s.uset && !s.stats && !s.resume && !s.neff && wu_lds_bytes(s.Nc, s.W, s.ncls, s.L, s.conv, true) <= 160 * 1024;
+    return s.noise == 0 && s.Nc >= 2 && s.top_acc && !s.lower_acc && (s.W <= 16 || (s.W <= 32 && !s.conv && s.Nc <= 8 && s.code != kCodePlanar)) &&
+           s.n_gen <= 1023 && s.iters >= 1 && s.iters <= 128 && s.swap_fast_ok && !s.uset && !s.stats && wu_lds_bytes(s.Nc, s.W, s.ncls, s.L, s.conv, false) <= 160 * 1024;
+}
+// the padded state width (wu_words); 8 waves per SIMD up to 12 words, 6 at 16 and 32 words and for the alpha rule's criterion kernels (scratch
+// reloaded every step at 8: profiles/r04_crit_occupancy_ab.json); 9 .. 16 rungs: the same code under a launch bound of 1 024 threads; IT = 10: the
+// unrolled proposal loop of iters = 10 (decoders.py:25); conv: the criterion kernel on its persistent grid, with its own work queue
+inline KernelKey choose_wave(const KernelShape &s)
+{
+    if (!wu_supported(s)) return refuse("scan = wave: outside what it is built for");
+    const int maxt = s.Nc * 64 > 512 ? 1024 : 512, it = s.iters == 10 ? 10 : 0, wv = wu_words(s.W);
+    if (s.noise == 2) return wave_key(maxt, s.conv ? 6 : 8, s.code, wv, s.conv, it, true);
+    return wave_key(maxt, wv <= 12 ? 8 : 6, s.code, wv, s.conv, it, false);
+}
+
+// the kernel a launch of this shape runs, or why none is built for it
+inline KernelKey choose_kernel(const KernelShape &s)
+{
+    if (s.scan == 3) return choose_wave(s);
+    if (s.scan == 2) return choose_colour(s);
+    // (a plain kernel never runs on the capped grid of a work queue)
+    if (s.queue && !ladder_takes_queue(s)) return refuse("work queue offered to a shape without queue kernels");
+    if (s.uset) return choose_ladder_uset(s);
+    if (s.noise) return s.scan ? refuse("the sweep is built for the depolarizing rule only") : choose_ladder_biased(s);
+    if (s.scan) return choose_ladder_sweep(s);
+    return s.code == kCodeToric ? choose_ladder_toric(s) : choose_ladder_surf(s);
+}
+
+}  // namespace qecmc

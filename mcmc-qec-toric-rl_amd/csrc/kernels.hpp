@@ -3,11 +3,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kernel_choice.hpp"
+
 namespace qecmc {
 
 constexpr int kMaxNc = 16;          // one wavefront per ladder slot, <= 1024 threads per workgroup
 constexpr int kSynPerBlock = 64;    // one lane per syndrome
-constexpr int kSwapFast = 64;       // swap-threshold entries per rung pair kept in LDS (d < kSwapFast)
 
 // Arguments of the random-scan ladder kernel (passed by value; fits the kernarg segment).
 struct LadderArgs {
@@ -99,57 +100,13 @@ struct LadderArgs {
     uint32_t *nerr_sum;       // [N][Nc]
 };
 
-size_t ladder_lds_bytes(int L, int Nc, int W, int ncls, int gen_dwords);
-inline size_t ladder_stats_lds_bytes(int Nc) { return sizeof(uint32_t) * 64u * (size_t)(2 * Nc); }   // [Nc] swap accepts (row Nc-1 idle) + [Nc] error sums
-constexpr uint32_t kMaxGenLds = 2048;   // generator tables up to this many entries are staged in LDS
-// dwords of the LDS generator table: the toric random-scan kernels expand each generator to 4 x u32
-// (byte offset << 16 | pauli fields | bit shift), the other paths keep the plan's 4 x u16 form.  Up to kGenSplit
-// generators the expanded table is stored as two halves kGenSplit entries apart (sites 0,1 | sites 2,3).
-// alpha noise appends the double-buffered n_eff records [2][Nc][64] to the region
-constexpr int kLutTypes = 8;        // rows of the plaquette codes' dE look-up table (Pauli patterns of their generators; more: no table)
-constexpr int kGenSplit = 255;      // ds_read2_b64's second offset is an 8-bit count of 8-byte units
-// ... and the biased / alpha rules' count-change table uint2[n_types][256] and packed per-state counts uint32[Nc][64]
-// lattice size of a plaquette code from its qubit count (xzzx / rotated: L x L; planar: 2 L^2 with an idle row and column)
-inline int nq_L(int code, int nq) { int L = 1; while ((code == 3 ? 2 * L * L : L * L) < nq) ++L; return L; }
-inline int ladder_gen_dwords(int code, int noise, int scan, uint32_t n_gen, int Nc, int nq = 0, int n_types = 0)
-{
-    // depolarizing random scan: the expanded table of the non-top proposal loop; the plaquette codes also keep the plan's
-    // form for their top-chain / general paths
-    const bool wide = !scan;                                   // (biased / alpha kernels: unsplit, next to the plan's form)
-    // (toric, unsplit: 128 dwords behind the table for the dE look-up table, which the split form keeps between its halves)
-    // (plaquette codes: 256 bytes per Pauli pattern behind their expanded table)
-    const int lut_tail = noise ? 0 : code == 0 ? ((int)n_gen > kGenSplit ? 128 : 0) : 64 * kLutTypes;
-    const int wide_dw = ((!noise && (int)n_gen <= kGenSplit) ? 2 * (kGenSplit + (int)n_gen) : 4 * (int)n_gen) + lut_tail;
-    int d = wide ? (code == 0 ? wide_dw : ((2 * (int)n_gen + 3) & ~3) + wide_dw) : 2 * (int)n_gen;
-    if (noise == 2) d = ((d + 3) & ~3) + 2 * Nc * 64;
-    // (8 bytes per count-change entry; + the X / Z logical masks [2][L+1][W]; xzzx: + the logical operators' fields per generator)
-    if (noise) d = ((d + 3) & ~3) + 512 * n_types + Nc * 64 + 2 * (nq_L(code, nq) + 1) * ((nq + 15) / 16) + (code == 1 ? (((int)n_gen + 1) & ~1) + 3 * 64 : 0);
-    return d;
-}
-// the shapes the work-queue kernels exist for: depolarizing rule, random scan, error_based criterion, the framed top chain
-// (toric L <= 16, plaquette codes L <= 32; a top rung at p = 0.75, i.e. Nc >= 2, with logical moves)
-// ... and the biased / alpha rules on the xzzx / rotated codes (any L, Nc: no framed top chain there)
-inline bool ladder_uses_queue(int code, int noise, int scan, int conv_mode, int L, int Nc, double p_logical)
-{
-    if (noise != 0) return scan == 0 && conv_mode != 0 && (code == 1 || code == 2);
-    return scan == 0 && conv_mode != 0 && L <= (code == 0 ? 16 : 32) && Nc >= 2 && p_logical > 0.0;
-}
-// LDS of one workgroup (dwords): states, records, swap uniforms, histogram, then the tables every phase reads -- the phase
-// table, the generator table, the logical masks, the swap thresholds (32-bit where they fit) -- so that the serial path of a
-// step never waits for global memory
-// (noise != 0: the rule's 81 thresholds per rung; the alpha rule's n_eff records by step parity)
-inline size_t colour_lds_dwords(int Nc, int W, int ncls, uint32_t n_phases, uint32_t n_gen, int L, int nq, bool swap32, int noise = 0)
-{
-    return (size_t)Nc * W + 4 * (size_t)Nc + ncls + 32u * n_phases + 2u * n_gen + 4u * (L + 1) * W +
-           (swap32 ? 1u : 2u) * (size_t)(Nc > 1 ? Nc - 1 : 0) * (nq + 1) + 2 + 4 +   // (+ 2: the stop flag by step parity)
-           (noise ? (size_t)Nc * 81 + 2 * (size_t)Nc : 0);
-}
-
-hipError_t launch_ladder_rs_toric(const LadderArgs &a, hipStream_t stream);
-// scan = 3 (ladder_wu.hip): what it is built for, and the LDS of one workgroup
-bool wu_supported(const LadderArgs &a);
-size_t wu_lds_bytes(int Nc, int W, int ncls, int L, bool conv, bool alpha);
-constexpr int kWuAlphaQueueWaves = 6;   // waves per SIMD the alpha rule's criterion kernels of scan = 3 are built for (ladder_wu.hpp wu_pick_alpha): sizes their persistent grid
+hipError_t launch_ladder(const LadderArgs &a, hipStream_t stream);     // ladder_rs.hip: the kernel choose_kernel() picks, on its grid
+KernelShape kernel_shape(const LadderArgs &a);                        // ... what the choice reads of a launch
+// the instantiation units, one per kernel family (built in parallel): the kernel of `k` if the unit builds it, else nullptr -- ladder_kernel
+// (ladder_{toric,surf,biased,sweep,uset}.hip), ladder_colour_kernel (ladder_colour.hip), ladder_wu_kernel (ladder_wu{,_xzzx,_rotated,_planar,_alpha}.hip)
+const void *ladder_toric_kernel(const KernelKey &), *ladder_surf_kernel(const KernelKey &), *ladder_biased_kernel(const KernelKey &),
+    *ladder_sweep_kernel(const KernelKey &), *ladder_uset_kernel(const KernelKey &), *colour_kernel(const KernelKey &), *wave_toric_kernel(const KernelKey &),
+    *wave_xzzx_kernel(const KernelKey &), *wave_rotated_kernel(const KernelKey &), *wave_planar_kernel(const KernelKey &), *wave_alpha_kernel(const KernelKey &);
 
 // byte-state primitive kernels (primitives.hip); all pointers are device pointers
 hipError_t launch_apply_stabilizer(int code, int L, uint64_t N, const uint8_t *in, uint8_t *out, const int32_t *rows,

@@ -58,7 +58,7 @@ __device__ __forceinline__ int wave_sum(int v)
 #define QECMC_CSTAMP(k) ((void)0)
 #endif
 
-// MAXT / MINW: 1 024 threads at 4 waves per SIMD (a development build can give ladders of up to 8 rungs 512 threads at 6 or 8: launch_ladder_colour)
+// MAXT / MINW: 1 024 threads at 4 waves per SIMD whatever the ladder's length (choose_colour, kernel_choice.hpp)
 template <int CODE, bool CONV, int RULE = 0, int MAXT = 1024, int MINW = 4>
 __global__ __launch_bounds__(MAXT, MINW) void ladder_colour_kernel(const LadderArgs a)
 {
@@ -469,44 +469,19 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_colour_kernel(const LadderA
     if (a.flags != nullptr && lane == 0) a.flags[ladder * NC + slot] = (uint8_t)(fin[slot] >> 31);
 }
 
-hipError_t launch_ladder_colour(const LadderArgs &a, hipStream_t stream)
-{
-    if (a.phase_tab == nullptr || a.n_phases == 0 || a.noise < 0 || a.noise > 2 || a.resume) return hipErrorInvalidValue;
-    if (a.conv_mode != 0 && a.nlog == nullptr) return hipErrorInvalidValue;
-    if (a.noise != 0 && (a.col_thr == nullptr || a.bias_tbl == nullptr || (a.code != kCodeXzzx && a.code != kCodeRotated) || (a.noise == 2 && a.alpha_lnb == nullptr)))
-        return hipErrorInvalidValue;
-    const bool conv = a.conv_mode != 0;
-    // (development knob: -DQECMC_COLOUR_SMALL_MINW=6|8 builds ladders of up to 8 rungs for 512 threads at that many waves per SIMD -- three / four
-    // workgroups per CU instead of two.  Measured, profiles/r04_colour_occupancy_ab.json: +15 ... 28 % ladder steps per second from 1 024 ladders on,
-    // -8 % at 256 and below (20-160 B of scratch on a lone workgroup's path): the layout exists for few syndromes, so the default stays 4.)
-#ifndef QECMC_COLOUR_SMALL_MINW
-#define QECMC_COLOUR_SMALL_MINW 4
-#endif
-#if QECMC_COLOUR_SMALL_MINW != 4
-    const bool small = a.Nc <= 8;
-#define QECMC_KR(code, rule) (small ? (conv ? (const void *)ladder_colour_kernel<code, true, rule, 512, QECMC_COLOUR_SMALL_MINW> : (const void *)ladder_colour_kernel<code, false, rule, 512, QECMC_COLOUR_SMALL_MINW>) \
-                                    : (conv ? (const void *)ladder_colour_kernel<code, true, rule> : (const void *)ladder_colour_kernel<code, false, rule>))
-#else
-#define QECMC_KR(code, rule) (conv ? (const void *)ladder_colour_kernel<code, true, rule> : (const void *)ladder_colour_kernel<code, false, rule>)
-#endif
-#define QECMC_KC(code) QECMC_KR(code, 0)
-    const void *fn = a.noise == 1 ? (a.code == kCodeXzzx ? QECMC_KR(kCodeXzzx, 1) : QECMC_KR(kCodeRotated, 1))
-                   : a.noise == 2 ? (a.code == kCodeXzzx ? QECMC_KR(kCodeXzzx, 2) : QECMC_KR(kCodeRotated, 2))
-                   : a.code == kCodeToric ? QECMC_KC(kCodeToric) : a.code == kCodeXzzx ? QECMC_KC(kCodeXzzx)
-                   : a.code == kCodeRotated ? QECMC_KC(kCodeRotated) : a.code == kCodePlanar ? QECMC_KC(kCodePlanar) : nullptr;
-#undef QECMC_KC
-#undef QECMC_KR
-    if (!fn) return hipErrorInvalidValue;
-    const size_t lds = sizeof(uint32_t) * colour_lds_dwords(a.Nc, a.W, a.ncls, a.n_phases, a.n_gen, a.L, a.nq, a.swap_fast_ok != 0, a.noise);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
+template <int CODE, int RULE>
+struct ColourSet {   // ladder_colour_kernel<CODE, CONV, RULE> for CONV = false, true
+    static const void *find(const KernelKey &k)
+    {
+        if (!(k == colour_key(CODE, k.conv, RULE))) return nullptr;
+        return k.conv ? (const void *)ladder_colour_kernel<CODE, true, RULE> : (const void *)ladder_colour_kernel<CODE, false, RULE>;
     }
-    void *kargs[] = {const_cast<LadderArgs *>(&a)};
-    hipError_t e = hipLaunchKernel(fn, dim3((unsigned)a.N), dim3((unsigned)a.Nc * 64u), kargs, lds, stream);
-    if (e != hipSuccess) return e;
-    return hipGetLastError();
+};
+
+const void *colour_kernel(const KernelKey &k)
+{
+    return find_kernel<ColourSet<kCodeToric, 0>, ColourSet<kCodeXzzx, 0>, ColourSet<kCodeRotated, 0>, ColourSet<kCodePlanar, 0>,
+                       ColourSet<kCodeXzzx, 1>, ColourSet<kCodeRotated, 1>, ColourSet<kCodeXzzx, 2>, ColourSet<kCodeRotated, 2>>(k);
 }
 
 }  // namespace qecmc

@@ -38,15 +38,6 @@
 
 namespace qecmc {
 
-// LDS carve-up in dwords (keep in sync with the kernel)
-__host__ __device__ inline int ladder_group_dwords(int Nc, int W, int ncls, int gen_dwords)
-{
-    // st + info[2] + swx[2] + hist + thrT + swapT + stop flag (16) + generator table
-    int d = Nc * W * 64 + 4 * Nc * 64 + ncls * 64 + Nc * 9 + Nc * kSwapFast + 16;
-    d = (d + 3) & ~3;          // 16-byte aligned generator table (ds_read_b128 entries)
-    return d + ((gen_dwords + 3) & ~3);
-}
-
 __device__ __forceinline__ uint32_t nnz2(uint32_t x) { return __popc((x | (x >> 1)) & 0x55555555u); }
 
 __device__ __forceinline__ uint32_t sel4(const u32x4 &b, int i)
@@ -251,13 +242,9 @@ __device__ inline bool alpha_series_close(uint64_t z2, uint64_t xy2, uint32_t de
 // whose LDS footprint leaves 4 waves per SIMD anyway).  The draws do not depend on the state, so nothing changes but who
 // is the step's longest wave: at L = 15 the top wave's 10 blocks + frame flush were 2.6 x a non-top wave's step.
 //
-// The variant is named, not positional: ladder_kernel<MAXT, MINW, CODE, kConv | kDelut | ...> (LadderFlag below).  A
-// translation unit lists the flag sets it instantiates in one select_ladder_kernel<...>() call and asks for one of them at
-// run time; a set that is not on the list yields no kernel (an error), never a neighbouring one.
-enum LadderFlag : uint32_t {
-    kConv = 1u << 0, kGsplit = 1u << 1, kBiased = 1u << 2, kScan = 1u << 3, kGentop = 1u << 4, kUset = 1u << 5, kAlpha = 1u << 6,
-    kPre = 1u << 7, kDelut = 1u << 8, kQueue = 1u << 9, kSsw = 1u << 10,
-};
+// The variant is named, not positional: ladder_kernel<MAXT, MINW, CODE, kConv | kDelut | ...> (LadderFlag, kernel_choice.hpp).
+// choose_kernel() decides which one a launch runs; a translation unit lists the ones it instantiates (LadderSet below), and a
+// key that is not on a list yields no kernel (an error), never a neighbouring one.
 
 // Diagnostic build only (tools/steptrace.hip): shader-clock stamps of one workgroup's waves at the phase boundaries of 32 ladder steps,
 // behind the per-workgroup stamps of QECMC_TIMELINE in a.dbg.
@@ -1990,72 +1977,26 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_kernel(const LadderArgs a)
     }
 }
 
-// dynamic LDS of one workgroup
-inline size_t ladder_launch_lds(const LadderArgs &a)
-{
-    size_t lds = sizeof(uint32_t) * (size_t)ladder_group_dwords(a.Nc, a.W, a.ncls, ladder_gen_dwords(a.code, a.noise, a.scan, a.n_gen, a.Nc, a.nq, a.n_types));
-    if (a.swap_acc != nullptr) lds += ladder_stats_lds_bytes(a.Nc);   // per-lane counters behind the group's region
-    return lds;
-}
-// a workgroup whose LDS footprint lets at most two of them share a CU (or which has more than 8 waves) runs at most 4 waves
-// per SIMD whatever its register count: such shapes take the 128-VGPR instantiations that draw the top chain's Philox blocks
-// ahead (PRE)
-inline bool ladder_wants_pre(const LadderArgs &a)
-{
-    // (up to 8 rungs whose LDS footprint leaves a CU two workgroups anyway: the PRE kernels' 105-119 VGPRs mean 4 waves per SIMD, which is also two
-    // workgroups of 8 waves.  A longer ladder would get ONE: measured at toric L = 9, Nc = 9 / 12 / 16: 0.31 / 0.39 / 0.44 with PRE against
-    // 0.37 / 0.59 / 0.45 without -- round 4; those shapes took PRE until then)
-    return a.Nc >= 3 && a.Nc * 64 <= 512 && 3 * ladder_launch_lds(a) > 160 * 1024 && a.thr_logical != 0 && !(a.tune & 2u);
-}
-
-// launch `fn` (one of the instantiations above) on the grid the arguments imply
-// (`persistent`: fn is a QUEUE instantiation -- only those run on the capped grid and take the rest of the batch from the
-// counter; a.queue without such a kernel is an error here, so a plain kernel can never run on a grid that skips ladders)
-inline hipError_t launch_ladder_fn(const void *fn, const LadderArgs &a, hipStream_t stream, bool persistent)
-{
-    unsigned grid = (unsigned)((a.N + 63) / 64);
-    const unsigned block = (unsigned)a.Nc * 64u;
-    if ((a.queue != nullptr) != persistent) return hipErrorInvalidValue;
-    if (persistent && a.grid_cap && grid > a.grid_cap) grid = a.grid_cap;
-    const size_t lds = ladder_launch_lds(a);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {   // beyond the default dynamic-LDS window (160 KiB per CU on gfx950)
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    void *kargs[] = {const_cast<LadderArgs *>(&a)};
-    hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(block), kargs, lds, stream);
-    if (e != hipSuccess) return e;
-    return hipGetLastError();
-}
-
-// the instantiation <MAXT, MINW, CODE, want> if `want` is one of the listed flag sets Fs..., else nullptr
-template <int MAXT, int MINW, int CODE, uint32_t... Fs>
-inline const void *select_ladder_kernel(uint32_t want)
-{
-    const void *fn = nullptr;
-    ((want == Fs ? (void)(fn = (const void *)ladder_kernel<MAXT, MINW, CODE, Fs>) : (void)0), ...);
-    return fn;
-}
-// ... the same over the code models Cs... (`code` picks)
-template <int MAXT, int MINW, uint32_t... Fs>
-struct LadderKernels {
-    template <int... Cs>
-    static const void *of(int code, uint32_t want)
+// instantiations ladder_kernel<MAXT, MINW, CODE, F> for F in Fs... and CODE in the bit set CODES (1 << kCode*): find() is the
+// kernel of `k` if it is one of them, else nullptr
+template <int MAXT, int MINW, unsigned CODES, uint32_t... Fs>
+struct LadderSet {
+    template <int CODE> static const void *of(uint32_t flags)
     {
         const void *fn = nullptr;
-        ((code == Cs ? (void)(fn = select_ladder_kernel<MAXT, MINW, Cs, Fs...>(want)) : (void)0), ...);
+        if constexpr ((CODES >> CODE) & 1u) ((flags == Fs ? (void)(fn = (const void *)ladder_kernel<MAXT, MINW, CODE, Fs>) : (void)0), ...);
         return fn;
     }
+    static const void *find(const KernelKey &k)
+    {
+        if (k.family != kFamLadder || k.maxt != MAXT || k.minw != MINW) return nullptr;
+        return k.code == kCodeToric ? of<kCodeToric>(k.flags) : k.code == kCodeXzzx ? of<kCodeXzzx>(k.flags)
+             : k.code == kCodeRotated ? of<kCodeRotated>(k.flags) : k.code == kCodePlanar ? of<kCodePlanar>(k.flags) : nullptr;
+    }
 };
-
-// one translation unit per kernel family (parallel builds): each picks among its own instantiations
-hipError_t launch_ladder_toric(const LadderArgs &a, hipStream_t stream);      // ladder_toric.hip: toric, depolarizing, random scan
-hipError_t launch_ladder_sweep(const LadderArgs &a, hipStream_t stream);      // ladder_sweep.hip: scan = 1, every code
-hipError_t launch_ladder_surf(const LadderArgs &a, hipStream_t stream);       // ladder_surf.hip: xzzx / rotated / planar, depolarizing, random scan
-hipError_t launch_ladder_biased(const LadderArgs &a, hipStream_t stream);     // ladder_biased.hip: biased and alpha rules
-hipError_t launch_ladder_uset(const LadderArgs &a, hipStream_t stream);       // ladder_uset.hip: the unique-chain estimators' set insertion
-hipError_t launch_ladder_colour(const LadderArgs &a, hipStream_t stream);     // ladder_colour.hip: scan = 2, one workgroup per ladder, colour-parallel phases
-hipError_t launch_ladder_wu(const LadderArgs &a, hipStream_t stream);         // ladder_wu.hip: scan = 3, wave-uniform generator picks, states in registers
+constexpr unsigned kT = 1u << kCodeToric, kX = 1u << kCodeXzzx, kR = 1u << kCodeRotated, kP = 1u << kCodePlanar;
+// the first of the sets that holds `k`
+template <class... Sets> inline const void *find_kernel(const KernelKey &k) { const void *fn = nullptr; ((fn = fn ? fn : Sets::find(k)), ...); return fn; }
+template <class... Sets> struct KernelList { static const void *find(const KernelKey &k) { return find_kernel<Sets...>(k); } };
 
 }  // namespace qecmc

@@ -1,27 +1,78 @@
-// Dispatcher of the parallel-tempering ladder kernel (ladder_kernel.hpp): the instantiations live in one translation unit per
-// kernel family (ladder_toric / ladder_sweep / ladder_surf / ladder_biased / ladder_uset .hip) so that they build in parallel.
-#include "ladder_kernel.hpp"
+// The one launch path of the ladder kernels: choose_kernel() (kernel_choice.hpp) names the kernel of a launch, the instantiation units
+// (ladder_toric / ladder_surf / ladder_biased / ladder_sweep / ladder_uset / ladder_colour / ladder_wu*.hip, built in parallel) hold it,
+// and the launch runs it on the grid its family implies.  A key no unit holds is an error, never a neighbouring kernel.
+#include "kernels.hpp"
 
 namespace qecmc {
 
-size_t ladder_lds_bytes(int L, int Nc, int W, int ncls, int gen_dwords)
+KernelShape kernel_shape(const LadderArgs &a)
 {
-    (void)L;   // per group of 64 syndromes
-    return sizeof(uint32_t) * (size_t)ladder_group_dwords(Nc, W, ncls, gen_dwords);
+    const uint32_t lower = (1u << (a.Nc - 1)) - 1u;      // rungs below the top
+    return {a.code, a.noise, a.scan, a.L, a.Nc, a.W, a.nq, a.ncls, (int)a.n_gen, a.n_types, a.gen_type != nullptr, (int)((a.acc_all_mask >> (a.Nc - 1)) & 1u),
+            (a.acc_all_mask & lower) != 0, a.thr_logical != 0, a.conv_mode != 0, a.queue != nullptr, a.uset_tab != nullptr, a.xyz_thr != nullptr,
+            a.swap_acc != nullptr, a.resume != 0, a.neff != nullptr, (a.bias_f32ok & lower) == lower, a.swap_fast_ok != 0,
+            a.iters > 0x7FFFFFFFu ? 0x7FFFFFFF : (int)a.iters, (int)a.tune};
 }
 
-hipError_t launch_ladder_rs_toric(const LadderArgs &a, hipStream_t stream)
+namespace {
+
+const void *kernel_of(const KernelKey &k)
+{
+    const void *fn = nullptr;
+    for (auto unit : {ladder_toric_kernel, ladder_surf_kernel, ladder_biased_kernel, ladder_sweep_kernel, ladder_uset_kernel, colour_kernel,
+                      wave_toric_kernel, wave_xzzx_kernel, wave_rotated_kernel, wave_planar_kernel, wave_alpha_kernel})
+        fn = fn ? fn : unit(k);
+    return fn;
+}
+
+hipError_t launch_fn(const void *fn, const LadderArgs &a, hipStream_t stream, unsigned grid, size_t lds)
+{
+    if (lds > 64 * 1024) {   // beyond the default dynamic-LDS window (160 KiB per CU on gfx950)
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    void *kargs[] = {const_cast<LadderArgs *>(&a)};
+    const hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3((unsigned)a.Nc * 64u), kargs, lds, stream);
+    return e != hipSuccess ? e : hipGetLastError();
+}
+
+}  // namespace
+
+// ladder_kernel: one 64-syndrome group (Nc waves) per workgroup (two per workgroup measured slower at every batch size); `persistent`: fn is a
+// QUEUE instantiation -- only those run on the capped grid, and a.queue without one is an error: a plain kernel never skips ladders
+hipError_t launch_ladder_fn(const void *fn, const LadderArgs &a, hipStream_t stream, bool persistent)
+{
+    unsigned grid = (unsigned)((a.N + 63) / 64);
+    if ((a.queue != nullptr) != persistent) return hipErrorInvalidValue;
+    if (persistent && a.grid_cap && grid > a.grid_cap) grid = a.grid_cap;
+    const size_t lds = ladder_launch_lds(kernel_shape(a));
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    return launch_fn(fn, a, stream, grid, lds);
+}
+
+hipError_t launch_ladder(const LadderArgs &a, hipStream_t stream)
 {
     if (a.N == 0) return hipSuccess;
-    // One 64-syndrome group (Nc waves) per workgroup.  (Two groups per workgroup, sharing only the barrier, paid off while a
-    // one-round grid ended in a long tail; with the current proposal loop the 8-wave workgroups are faster at every batch
-    // size: +1.6 % at 65 536 syndromes, +5 % at 262 144.)
-    if (a.scan == 3) return launch_ladder_wu(a, stream);
-    if (a.scan == 2) return a.uset_tab != nullptr ? hipErrorInvalidValue : launch_ladder_colour(a, stream);
-    if (a.uset_tab != nullptr) return launch_ladder_uset(a, stream);
-    if (a.noise) return a.scan ? hipErrorInvalidValue : launch_ladder_biased(a, stream);   // the sweep is built for the depolarizing rule only
-    if (a.scan) return launch_ladder_sweep(a, stream);
-    return a.code == kCodeToric ? launch_ladder_toric(a, stream) : launch_ladder_surf(a, stream);
+    const KernelKey k = choose_kernel(kernel_shape(a));
+    const void *fn = k.ok() ? kernel_of(k) : nullptr;
+    if (!fn) return hipErrorInvalidValue;
+    if (k.family == kFamWave) {
+        // scan = 3: batches start on a multiple of 64 (a wavefront shares its generator picks); the criterion runs on a persistent grid of
+        // a.grid_cap workgroups (capi.hip), each owning a.wu_chunk ladders of the batch
+        if (a.wu_desc == nullptr || (a.first_syndrome & 63u) || (a.noise == 2 && (a.bias_tbl == nullptr || a.alpha_lnb == nullptr))) return hipErrorInvalidValue;
+        if (k.conv && (a.nlog == nullptr || a.resume || a.write_states || a.wu_chunk < 64u || (a.wu_chunk & 63u))) return hipErrorInvalidValue;
+        const uint64_t per = k.conv ? a.wu_chunk : 64u;
+        return launch_fn(fn, a, stream, (unsigned)((a.N + per - 1) / per), wu_lds_bytes(a.Nc, a.W, a.ncls, a.L, k.conv, k.alpha));
+    }
+    if (k.family == kFamColour) {
+        // scan = 2: one ladder per workgroup
+        if (a.phase_tab == nullptr || a.n_phases == 0 || (a.conv_mode != 0 && a.nlog == nullptr)) return hipErrorInvalidValue;
+        if (a.noise != 0 && (a.col_thr == nullptr || a.bias_tbl == nullptr || (a.noise == 2 && a.alpha_lnb == nullptr))) return hipErrorInvalidValue;
+        const size_t lds = sizeof(uint32_t) * colour_lds_dwords(a.Nc, a.W, a.ncls, a.n_phases, a.n_gen, a.L, a.nq, a.swap_fast_ok != 0, a.noise);
+        if (lds > 160 * 1024) return hipErrorInvalidValue;
+        return launch_fn(fn, a, stream, (unsigned)a.N, lds);
+    }
+    return launch_ladder_fn(fn, a, stream, k.takes_queue());
 }
 
 }  // namespace qecmc

@@ -160,45 +160,8 @@ __device__ __forceinline__ void wu_xor(typename WuVec<WV>::type &st, uint32_t d0
 #undef M
 }
 
-// LDS carve-up of one workgroup (dwords): the exchange buffer (W words per rung), records, swap uniforms, histogram, acceptance rows,
-// swap rows, logical masks (rows padded to WV words, + 64: the frame reads a row with all 64 lanes), stop / refill flags, and -- the
-// criterion kernels -- wave 0's per-ladder bookkeeping [kWuBk][64] and the refill mailbox [2][64]
-struct WuLds { int xbuf, rec, swd, hist, thr, swapT, lml, stop, bk, mail, bot, cht, nef, lnb, bot2, total; };
-constexpr int kWuBk = 13;      // tops0, samples, burn, conv_start, conv_streak, sumA lo / hi, sumB lo / hi, state (done | pending << 1 | has << 3),
-                               // steps_done, converged, the lane's ladder (QUEUE)
-constexpr int kWuBkAlpha = 17; // ... and the alpha rule's second pair of window sums (n_x + n_y): sumAxy lo / hi, sumBxy lo / hi
-__host__ __device__ inline int wu_words(int W) { return W <= 4 ? 4 : W <= 8 ? 8 : W <= 12 ? 12 : W <= 16 ? 16 : 32; }   // WV: state words per rung, padded
+// (the LDS carve-up of one workgroup, wu_lds, and the padded state width wu_words: kernel_choice.hpp)
 __host__ __device__ inline int wu_words_min(int WV) { return WV == 4 ? 1 : WV == 32 ? 17 : WV - 3; }      // the narrowest W a WV-word kernel serves
-constexpr int kWuHalf = 16;                                                                               // rows per rung of a 32-word kernel's exchange buffer
-// rows per rung of the exchange buffer.  The fixed-length kernels give a rung the kernel's padded width (16 per half of a 32-word state): the padding
-// words travel with the rest (they are zero), so that no transfer tests the lattice's width at run time on the scalar unit, the busiest unit of these
-// kernels (-30 tests per step at 29 words).  The criterion kernels keep the tight layout -- W rows, a transfer of a word at or beyond wu_words_min
-// tests the width --: padded rows cost the headline shape's criterion kernel its fourth workgroup per CU (42 KB instead of 39.9) and the route 11 %.
-__host__ __device__ inline int wu_rows(int W, bool conv) { return W > 16 ? kWuHalf : conv ? W : wu_words(W); }
-// (alpha rule: the 9 x 9 table of a proposal's count change as two fp16 numbers, the slots' n_eff attributes as doubles [Nc][64], ln(pz_i / pz_i+1),
-// and -- criterion runs -- slot 0's n_eff record by step parity)
-__host__ __device__ inline WuLds wu_lds(int Nc, int W, int ncls, int L, bool conv, bool alpha = false)
-{
-    const int WV = wu_words(W);
-    WuLds o;
-    o.xbuf = 0;
-    o.rec = o.xbuf + Nc * wu_rows(W, conv) * 64;
-    o.swd = o.rec + Nc * 64;
-    o.hist = o.swd + Nc * 64;
-    o.thr = o.hist + ncls * 64;               // [Nc][2][9]: high 13 / low 32 bits of ceil(f^dE 2^44), dE + 4 = 0 .. 8
-    o.swapT = o.thr + Nc * 18;
-    o.lml = o.swapT + Nc * kSwapFast;
-    o.stop = o.lml + 4 * (L + 1) * WV + 64;
-    o.bk = o.stop + 4;
-    o.mail = o.bk + (conv ? (alpha ? kWuBkAlpha : kWuBk) * 64 : 0);   // [2][64] refill orders by step parity
-    o.bot = o.mail + (conv ? 2 * 64 : 0);                    // [2][64] the record that landed in rung 0, by step parity
-    o.cht = o.bot + (conv ? 2 * 64 : 0);
-    o.nef = (o.cht + (alpha ? 84 : 0) + 1) & ~1;             // (doubles: 8-byte aligned)
-    o.lnb = o.nef + (alpha ? Nc * 128 : 0);
-    o.bot2 = o.lnb + (alpha ? 2 * Nc : 0);
-    o.total = o.bot2 + (alpha && conv ? 2 * 64 : 0);
-    return o;
-}
 
 // A Philox block whose key schedule is formed where it is used (two scalar adds per round) instead of being hoisted out of the
 // step loop into twenty scalar registers per call site: the kernel runs at 8 waves per SIMD on ~80 SGPRs.
@@ -1050,67 +1013,20 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_wu_kernel(const LadderArgs 
 #undef QECMC_WU_TAKE_HI
 }
 
-// the kernel for a shape: the padded state width (4, 8, 12 or 16 words: toric L <= 11, the one-layer codes L <= 16), 8 waves per SIMD up
-// to 8 rungs and 4 beyond; IT = 10: the unrolled proposal loop of `iters` = 10 (decoders.py:25) on up to 8 rungs; QUEUE: the criterion runs (every criterion launch takes the queue kernel: a batch no larger than the grid gives each ladder
-// a lane of its own)
-template <int CODE, bool CONV, bool QUEUE, int IT>
-inline const void *wu_pick_it(int Nc, int W)
-{
-    const bool big = Nc * 64 > 512;
-#ifdef QECMC_WU_DEV     // development builds: the headline shape only
-#ifndef QECMC_WU_DEV_QUEUE_MINW
-#define QECMC_WU_DEV_QUEUE_MINW 8
-#endif
-    return (!big && W > 8 && W <= 12) ? (const void *)ladder_wu_kernel<512, (QUEUE ? QECMC_WU_DEV_QUEUE_MINW : 8), CODE, 12, CONV, QUEUE, IT> : nullptr;
-#else
-    // (9 .. 16 rungs: the same 64-VGPR code with a launch bound of 1 024 threads -- three workgroups of 9 waves, two of 12 .. 16 per CU.  The round's
-    // first build had given them 4 waves per SIMD: one workgroup per CU and 0.37 at toric L = 9 with the reference's default Nc = L = 9.)
-    if (W <= 4) return big ? (const void *)ladder_wu_kernel<1024, 8, CODE, 4, CONV, QUEUE, IT> : (const void *)ladder_wu_kernel<512, 8, CODE, 4, CONV, QUEUE, IT>;
-    if (W <= 8) return big ? (const void *)ladder_wu_kernel<1024, 8, CODE, 8, CONV, QUEUE, IT> : (const void *)ladder_wu_kernel<512, 8, CODE, 8, CONV, QUEUE, IT>;
-    if (W <= 12) return big ? (const void *)ladder_wu_kernel<1024, 8, CODE, 12, CONV, QUEUE, IT> : (const void *)ladder_wu_kernel<512, 8, CODE, 12, CONV, QUEUE, IT>;
-    if (W <= 16) return big ? (const void *)ladder_wu_kernel<1024, 6, CODE, 16, CONV, QUEUE, IT> : (const void *)ladder_wu_kernel<512, 6, CODE, 16, CONV, QUEUE, IT>;
-    // 17 .. 32 words (toric L <= 16, the one-layer codes L <= 22): fixed-length runs of up to 8 rungs, 80 VGPRs at 6 waves per SIMD, the state
-    // through the exchange buffer in two halves (52 KB of LDS: three workgroups per CU); not built for the planar code
-    if constexpr (!CONV && !QUEUE && CODE != kCodePlanar) { if (!big) return (const void *)ladder_wu_kernel<512, 6, CODE, 32, false, false, IT>; }
-    return nullptr;
-#endif
-}
-// variant: 0 fixed length, 2 criterion on the persistent grid
-template <int CODE>
-inline const void *wu_pick(int variant, int Nc, int W, uint32_t iters)
-{
-    if (W > 32 || (variant != 0 && variant != 2)) return nullptr;
-    // iters = 10 (decoders.py:25): the unrolled proposal loop, for every code and ladder length (same-box A/B at L = 9, config 2's shape: xzzx 0.85 against
-    // 0.61 with the general loop -- and 0.73 with the random scan's kernel --, rotated 0.85 / 0.61 / 0.72, planar 0.82 / 0.60 / 0.68)
-    if (iters == 10u) return variant == 2 ? wu_pick_it<CODE, true, true, 10>(Nc, W) : wu_pick_it<CODE, false, false, 10>(Nc, W);
-    return variant == 2 ? wu_pick_it<CODE, true, true, 0>(Nc, W) : wu_pick_it<CODE, false, false, 0>(Nc, W);
-}
-
-// the alpha rule's kernels: xzzx / rotated codes up to 8 state words per rung (L <= 11)
-// (IT = 10: PTEQ_alpha's default iters, decoders_biasednoise.py:175)
-template <int CODE, int IT>
-inline const void *wu_pick_alpha(int variant, int Nc, int W)
-{
-    if (W > 8 || (variant != 0 && variant != 2)) return nullptr;
-    const bool big = Nc * 64 > 512;          // (9 .. 16 rungs -- Ladder_alpha's default is Nc = L, decoders_biasednoise.py:175 --: the same code under a 1 024-thread bound)
-    // (the criterion kernels of the alpha rule at 6 waves per SIMD -- 80 VGPRs, 102 SGPRs --: 96-120 B of scratch reloaded every step at 8, 28-40 B at 6,
-    // and 4 % faster on the PTEQ_alpha route, same-box A/B; kWuAlphaQueueWaves tells the plan how many workgroups a CU then holds)
-#ifndef QECMC_WU_ALPHA_CONV_MINW
-#define QECMC_WU_ALPHA_CONV_MINW kWuAlphaQueueWaves
-#endif
-    if (variant == 2) {
-        if (big) return W <= 4 ? (const void *)ladder_wu_kernel<1024, QECMC_WU_ALPHA_CONV_MINW, CODE, 4, true, true, IT, true> : (const void *)ladder_wu_kernel<1024, QECMC_WU_ALPHA_CONV_MINW, CODE, 8, true, true, IT, true>;
-        return W <= 4 ? (const void *)ladder_wu_kernel<512, QECMC_WU_ALPHA_CONV_MINW, CODE, 4, true, true, IT, true> : (const void *)ladder_wu_kernel<512, QECMC_WU_ALPHA_CONV_MINW, CODE, 8, true, true, IT, true>;
+// the instantiations ladder_wu_kernel<MAXT, MINW, CODE, WV, CONV, QUEUE = CONV, IT, ALPHA> for IT = 10 (the unrolled proposal loop of iters = 10)
+// and IT = 0 (any iters): find() is the kernel of `k` if it is one of them, else nullptr
+template <int MAXT, int MINW, int CODE, int WV, bool CONV, bool ALPHA = false>
+struct WaveSet {
+    static const void *find(const KernelKey &k)
+    {
+        if (!(k == wave_key(MAXT, MINW, CODE, WV, CONV, k.it, ALPHA))) return nullptr;
+        return k.it == 10 ? (const void *)ladder_wu_kernel<MAXT, MINW, CODE, WV, CONV, CONV, 10, ALPHA>
+             : k.it == 0  ? (const void *)ladder_wu_kernel<MAXT, MINW, CODE, WV, CONV, CONV, 0, ALPHA> : nullptr;
     }
-    if (big) return W <= 4 ? (const void *)ladder_wu_kernel<1024, 8, CODE, 4, false, false, IT, true> : (const void *)ladder_wu_kernel<1024, 8, CODE, 8, false, false, IT, true>;
-    return W <= 4 ? (const void *)ladder_wu_kernel<512, 8, CODE, 4, false, false, IT, true> : (const void *)ladder_wu_kernel<512, 8, CODE, 8, false, false, IT, true>;
-}
-
-// one translation unit per code family (parallel builds)
-const void *wu_kernel_toric(int variant, int Nc, int W, uint32_t iters);            // ladder_wu.hip
-const void *wu_kernel_xzzx(int variant, int Nc, int W, uint32_t iters);             // ladder_wu_xzzx.hip
-const void *wu_kernel_rotated(int variant, int Nc, int W, uint32_t iters);          // ladder_wu_rotated.hip
-const void *wu_kernel_planar(int variant, int Nc, int W, uint32_t iters);           // ladder_wu_planar.hip
-const void *wu_kernel_alpha(int code, int variant, int Nc, int W, uint32_t iters);   // ladder_wu_alpha.hip
+};
+// a code's kernels of 4 .. 16 state words per rung on MAXT threads (choose_wave, kernel_choice.hpp): fixed-length and criterion runs
+template <int MAXT, int CODE>
+using WaveWords = KernelList<WaveSet<MAXT, 8, CODE, 4, false>, WaveSet<MAXT, 8, CODE, 8, false>, WaveSet<MAXT, 8, CODE, 12, false>, WaveSet<MAXT, 6, CODE, 16, false>,
+                             WaveSet<MAXT, 8, CODE, 4, true>, WaveSet<MAXT, 8, CODE, 8, true>, WaveSet<MAXT, 8, CODE, 12, true>, WaveSet<MAXT, 6, CODE, 16, true>>;
 
 }  // namespace qecmc

@@ -1,13 +1,15 @@
-// scan = 3 under the alpha noise model (src/mcmc_alpha.py): the xzzx / rotated instantiations.  The kernel: ladder_wu.hpp.
+// scan = 3 under the alpha noise model (src/mcmc_alpha.py): the xzzx / rotated instantiations of 4 and 8 state words.  The kernel: ladder_wu.hpp.
 #include "ladder_wu.hpp"
 
 namespace qecmc {
 
-const void *wu_kernel_alpha(int code, int variant, int Nc, int W, uint32_t iters)
+template <int MAXT, int CODE>   // fixed-length kernels at 8 waves per SIMD, criterion kernels at 6
+using WaveAlpha = KernelList<WaveSet<MAXT, 8, CODE, 4, false, true>, WaveSet<MAXT, 8, CODE, 8, false, true>, WaveSet<MAXT, 6, CODE, 4, true, true>,
+                             WaveSet<MAXT, 6, CODE, 8, true, true>>;
+
+const void *wave_alpha_kernel(const KernelKey &k)
 {
-    if (iters == 10u)
-        return code == kCodeXzzx ? wu_pick_alpha<kCodeXzzx, 10>(variant, Nc, W) : code == kCodeRotated ? wu_pick_alpha<kCodeRotated, 10>(variant, Nc, W) : nullptr;
-    return code == kCodeXzzx ? wu_pick_alpha<kCodeXzzx, 0>(variant, Nc, W) : code == kCodeRotated ? wu_pick_alpha<kCodeRotated, 0>(variant, Nc, W) : nullptr;
+    return find_kernel<WaveAlpha<512, kCodeXzzx>, WaveAlpha<1024, kCodeXzzx>, WaveAlpha<512, kCodeRotated>, WaveAlpha<1024, kCodeRotated>>(k);
 }
 
 }  // namespace qecmc

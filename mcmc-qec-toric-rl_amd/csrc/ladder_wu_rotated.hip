@@ -3,6 +3,6 @@
 
 namespace qecmc {
 
-const void *wu_kernel_rotated(int variant, int Nc, int W, uint32_t iters) { return wu_pick<kCodeRotated>(variant, Nc, W, iters); }
+const void *wave_rotated_kernel(const KernelKey &k) { return find_kernel<WaveWords<512, kCodeRotated>, WaveWords<1024, kCodeRotated>, WaveSet<512, 6, kCodeRotated, 32, false>>(k); }
 
 }  // namespace qecmc

@@ -3,6 +3,6 @@
 
 namespace qecmc {
 
-const void *wu_kernel_xzzx(int variant, int Nc, int W, uint32_t iters) { return wu_pick<kCodeXzzx>(variant, Nc, W, iters); }
+const void *wave_xzzx_kernel(const KernelKey &k) { return find_kernel<WaveWords<512, kCodeXzzx>, WaveWords<1024, kCodeXzzx>, WaveSet<512, 6, kCodeXzzx, 32, false>>(k); }
 
 }  // namespace qecmc

@@ -1,6 +1,8 @@
 // C test API over the host-side table builders (tables.hpp), compiled ALONE by g++ -- no HIP runtime, no device -- with
 // -fsanitize=address,undefined (make tables_asan) or plainly (make tables): tests/test_host_tables.py checks every table the
-// plan precomputes for the kernels against values the CPU oracle computes.  Not part of libqecmc.so.
+// plan precomputes for the kernels against values the CPU oracle computes; tests/test_kernel_choice.py asks choose_kernel()
+// (kernel_choice.hpp) which kernel every shape runs.  Not part of libqecmc.so.
+#include "kernel_choice.hpp"
 #include "tables.hpp"
 
 #include <cstring>
@@ -63,4 +65,14 @@ int qt_colour_phases(int code, int L, uint16_t *out, int cap)
     const std::vector<uint16_t> ph = colour_phases(gen_table(code, L), n_phases);
     return put(ph, out, cap) < 0 ? -1 : n_phases;
 }
+// choose_kernel() of n shapes: 11 numbers per shape -- family, maxt, minw, code, flags, wv, conv, it, alpha, rule, why (a const char *)
+void qt_choose_kernels(const KernelShape *shapes, int n, int64_t *keys)
+{
+    for (int i = 0; i < n; ++i) {
+        const KernelKey k = choose_kernel(shapes[i]);
+        const int64_t v[11] = {k.family, k.maxt, k.minw, k.code, k.flags, k.wv, k.conv, k.it, k.alpha, k.rule, (int64_t)(intptr_t)k.why};
+        std::memcpy(keys + 11 * (size_t)i, v, sizeof v);
+    }
+}
+int qt_kernel_shape_ints(void) { return (int)(sizeof(KernelShape) / sizeof(int)); }
 }

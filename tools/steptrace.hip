@@ -12,9 +12,14 @@
 #include "../mcmc-qec-toric-rl_amd/csrc/ladder_colour.hip"
 #include "../mcmc-qec-toric-rl_amd/csrc/primitives.hip"
 namespace qecmc {   // the families this tool does not trace
-hipError_t launch_ladder_sweep(const LadderArgs &, hipStream_t) { return hipErrorInvalidValue; }
-hipError_t launch_ladder_biased(const LadderArgs &, hipStream_t) { return hipErrorInvalidValue; }
-hipError_t launch_ladder_uset(const LadderArgs &, hipStream_t) { return hipErrorInvalidValue; }
+const void *ladder_biased_kernel(const KernelKey &) { return nullptr; }
+const void *ladder_sweep_kernel(const KernelKey &) { return nullptr; }
+const void *ladder_uset_kernel(const KernelKey &) { return nullptr; }
+const void *wave_toric_kernel(const KernelKey &) { return nullptr; }
+const void *wave_xzzx_kernel(const KernelKey &) { return nullptr; }
+const void *wave_rotated_kernel(const KernelKey &) { return nullptr; }
+const void *wave_planar_kernel(const KernelKey &) { return nullptr; }
+const void *wave_alpha_kernel(const KernelKey &) { return nullptr; }
 }
 #include <algorithm>
 
@@ -46,7 +51,7 @@ int main(int argc, char **argv)
         a.init = di; a.counts = dc; a.samples = ds; a.tops0 = dt; a.states = nullptr; a.write_states = 0; a.N = N;
         a.nsteps = steps; a.dbg = dbg;
         hipMemset(dbg, 0, ndbg * 8);
-        hipError_t e = launch_ladder_rs_toric(a, 0);
+        hipError_t e = launch_ladder(a, 0);
         if (e != hipSuccess) { printf("launch: %s\n", hipGetErrorString(e)); return 1; }
         if (hipDeviceSynchronize() != hipSuccess) { printf("sync failed\n"); return 1; }
     }

@@ -7,11 +7,16 @@
 #include "../mcmc-qec-toric-rl_amd/csrc/ladder_toric.hip"
 #include "../mcmc-qec-toric-rl_amd/csrc/primitives.hip"
 namespace qecmc {   // the families this tool does not launch
-hipError_t launch_ladder_surf(const LadderArgs &, hipStream_t) { return hipErrorInvalidValue; }
-hipError_t launch_ladder_sweep(const LadderArgs &, hipStream_t) { return hipErrorInvalidValue; }
-hipError_t launch_ladder_biased(const LadderArgs &, hipStream_t) { return hipErrorInvalidValue; }
-hipError_t launch_ladder_uset(const LadderArgs &, hipStream_t) { return hipErrorInvalidValue; }
-hipError_t launch_ladder_colour(const LadderArgs &, hipStream_t) { return hipErrorInvalidValue; }
+const void *ladder_surf_kernel(const KernelKey &) { return nullptr; }
+const void *ladder_biased_kernel(const KernelKey &) { return nullptr; }
+const void *ladder_sweep_kernel(const KernelKey &) { return nullptr; }
+const void *ladder_uset_kernel(const KernelKey &) { return nullptr; }
+const void *colour_kernel(const KernelKey &) { return nullptr; }
+const void *wave_toric_kernel(const KernelKey &) { return nullptr; }
+const void *wave_xzzx_kernel(const KernelKey &) { return nullptr; }
+const void *wave_rotated_kernel(const KernelKey &) { return nullptr; }
+const void *wave_planar_kernel(const KernelKey &) { return nullptr; }
+const void *wave_alpha_kernel(const KernelKey &) { return nullptr; }
 }
 #include <map>
 #include <algorithm>
@@ -38,7 +43,7 @@ int main(int argc, char **argv)
         a.init = di; a.counts = dc; a.samples = ds; a.tops0 = dt; a.states = nullptr; a.write_states = 0; a.N = N;
         a.nsteps = steps; a.dbg = dbg;
         hipMemset(dbg, 0, grid * 32);
-        launch_ladder_rs_toric(a, 0);
+        launch_ladder(a, 0);
         hipDeviceSynchronize();
     }
     std::vector<uint64_t> h(grid * 4);
