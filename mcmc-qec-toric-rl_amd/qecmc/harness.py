@@ -251,14 +251,53 @@ def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_
     if file_path is not None:
         np.savez_compressed(file_path, params=np.array([repr(params)]), **out)
     out["metrics"] = batch_metrics(code, size, Nc, int(pteq_kw.get("iters", 10)), res, wall, out["success"],
-                                   replicas=int(pteq_kw.get("replicas", 1)))
+                                   replicas=int(pteq_kw.get("replicas", 1)), scan=pteq_kw.get("scan", "random"),
+                                   first_syndrome=int(pteq_kw.get("first_syndrome", 0)))
     return out
 
 
-def batch_metrics(code, size, Nc, iters, res, wall_s, success=None, replicas=1):
+def wavefront_clusters(n, replicas=1, first_syndrome=0):
+    """scan = "wave" shares the generator picks of the 64 ladders whose global indices lie in one group of 64 (ladder l of
+    syndrome s: first_syndrome + s * replicas + r), so the results of the syndromes with ladders in one group are correlated.
+    Returns int64[n]: a cluster id per syndrome -- syndromes that share a group, directly or through a neighbour, share an id."""
+    R = max(int(replicas), 1)
+    start = int(first_syndrome) + np.arange(int(n), dtype=np.int64) * R
+    g0, g1 = start // 64, (start + R - 1) // 64
+    new = np.ones(int(n), dtype=bool)
+    new[1:] = g0[1:] > g1[:-1]
+    return np.cumsum(new) - 1
+
+
+def _is_wave(scan):
+    return scan in ("wave", L_.SCAN_WAVE)
+
+
+def success_err(success, scan="random", replicas=1, first_syndrome=0, clusters=None):
+    """Standard error of the success rate -> (err, binomial err, method).  scan = "wave": over the clusters of syndromes that share
+    picks (wavefront_clusters; the ratio estimator's cluster variance K/(K-1) sum_k (y_k - p n_k)^2 / n^2, which is the standard
+    error of the cluster means when the clusters are equal), nan for a single cluster; other scans: the binomial error."""
+    s = np.asarray(success, dtype=np.float64)
+    n = len(s)
+    k = float(s.mean()) if n else float("nan")
+    binom = float(np.sqrt(max(k * (1 - k), 0.0) / n)) if n else float("nan")
+    if not _is_wave(scan):
+        return binom, binom, "binomial"
+    cl = wavefront_clusters(n, replicas, first_syndrome) if clusters is None else np.asarray(clusters)
+    _, cl = np.unique(cl, return_inverse=True)
+    K = int(cl.max()) + 1 if n else 0
+    if K < 2:
+        return float("nan"), binom, "wavefront_clusters"
+    y, m = np.bincount(cl, weights=s, minlength=K), np.bincount(cl, minlength=K).astype(np.float64)
+    return float(np.sqrt(K / (K - 1.0) * np.sum((y - k * m) ** 2)) / n), binom, "wavefront_clusters"
+
+
+def batch_metrics(code, size, Nc, iters, res, wall_s, success=None, replicas=1, scan="random", first_syndrome=0):
     """The per-batch metrics line (SURVEY.md 5 "Metrics / logging"; the reference only prints a progress counter,
     generate_data.py:266): proposals, seconds, chain-sweeps/s, swap acceptance per rung pair, mean error count per rung,
-    the tops0 histogram, and the success rate when the true classes are known.  JSON-serialisable."""
+    the tops0 histogram, and the success rate when the true classes are known.  JSON-serialisable.
+    success_rate_err is the binomial error, except on scan = "wave", where the syndromes of a wavefront share their generator
+    picks and the error is taken over the clusters of syndromes that share them (success_err); success_rate_err_method says which,
+    success_rate_err_binomial keeps the binomial value."""
     n_gen = 2 * size * size if code == L_.TORIC else 2 * size * (size - 1) if code == L_.PLANAR else size * size - 1
     steps_run = res["steps_done"].astype(np.float64)
     proposals = float(steps_run.sum()) * Nc * iters * max(int(replicas), 1)
@@ -275,7 +314,8 @@ def batch_metrics(code, size, Nc, iters, res, wall_s, success=None, replicas=1):
     if success is not None and len(success):
         k, n = int(np.sum(success)), len(success)
         m["success_rate"] = k / n
-        m["success_rate_err"] = float(np.sqrt(max(k / n * (1 - k / n), 0.0) / n))
+        err, binom, how = success_err(success, scan, replicas, first_syndrome)
+        m["success_rate_err"], m["success_rate_err_binomial"], m["success_rate_err_method"] = err, binom, how
     return m
 
 
@@ -317,24 +357,31 @@ def threshold_curve(params, p_list, n, seed=0, **gen_kw):
     """Logical success rate against the physical error rate (the p_error scan of generate_data.py:57-60,121-141,276-296 --
     the reference loops p over [0.05, 0.20] in its job script and evaluates argmax(distr) == true class offline):
     for every p in p_list, n syndromes at p_error = p decoded in one batched call.
-    Returns dict(p, n, success_rate, err (binomial standard error), converged_frac, metrics [one dict per p]) and, beside the raw
+    Returns dict(p, n, success_rate, err (standard error), converged_frac, metrics [one dict per p]) and, beside the raw
     rate, success_rate_sampled / err_sampled / frac_sampled: the rate among the syndromes whose ladder got past the burn-in
     (samples > 0).  The reference's burn-in trap (decoders.py:63,89: a ladder that never sees tops0 >= tops_burn returns an all-zero
-    vector, argmax 0) counts as a failure in the raw rate; at low p and a short horizon it, not the decoder, sets that number."""
-    rate, err, conv, met, rate_s, err_s, frac_s = [], [], [], [], [], [], []
+    vector, argmax 0) counts as a failure in the raw rate; at low p and a short horizon it, not the decoder, sets that number.
+    err / err_sampled are binomial except on scan = "wave" (errors over the clusters of syndromes that share generator picks,
+    success_err); err_binomial / err_sampled_binomial keep the binomial values and err_method says which is reported."""
+    rate, err, conv, met, rate_s, err_s, frac_s, err_b, err_sb = [], [], [], [], [], [], [], [], []
+    scan, R, first = gen_kw.get("scan", "random"), int(gen_kw.get("replicas", 1)), int(gen_kw.get("first_syndrome", 0))
+    how = "binomial"
     for i, p in enumerate(p_list):
         out = generate(dict(params, p_error=float(p)), n, seed=seed + i, **gen_kw)
         k = float(np.mean(out["success"]))
-        rate.append(k); err.append(float(np.sqrt(max(k * (1 - k), 0.0) / n)))
+        e, eb, how = success_err(out["success"], scan, R, first)
+        rate.append(k); err.append(e); err_b.append(eb)
         conv.append(float(np.mean(out["converged"])) if "converged" in out else float("nan"))
         met.append(out.get("metrics"))
         sampled = out["samples"] > 0 if "samples" in out else np.ones(len(out["success"]), dtype=bool)
         ns = int(sampled.sum())
         ks = float(np.mean(out["success"][sampled])) if ns else float("nan")
-        rate_s.append(ks); err_s.append(float(np.sqrt(max(ks * (1 - ks), 0.0) / ns)) if ns else float("nan")); frac_s.append(ns / max(n, 1))
+        es, esb, _ = success_err(out["success"][sampled], scan, clusters=wavefront_clusters(len(sampled), R, first)[sampled]) if ns \
+            else (float("nan"),) * 3
+        rate_s.append(ks); err_s.append(es); err_sb.append(esb); frac_s.append(ns / max(n, 1))
     return dict(p=np.asarray(p_list, dtype=np.float64), n=int(n), success_rate=np.array(rate), err=np.array(err),
                 converged_frac=np.array(conv), metrics=met, success_rate_sampled=np.array(rate_s), err_sampled=np.array(err_s),
-                frac_sampled=np.array(frac_s))
+                frac_sampled=np.array(frac_s), err_binomial=np.array(err_b), err_sampled_binomial=np.array(err_sb), err_method=how)
 
 
 class LadderRun:

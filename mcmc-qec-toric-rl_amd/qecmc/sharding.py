@@ -131,14 +131,14 @@ class PteqShard:
         params.setdefault("p_logical", 0.5)            # decoders.py:52
         params.setdefault("steps", 1000)
         params["Nc"] = params.get("Nc") or size        # decoders.py:30
+        if isinstance(params.get("scan"), str):         # (make_params takes the integer form)
+            params["scan"] = L_.SCANS[params["scan"]]
         self.pr = L_.make_params(L=size, p=float(p), device=dev, first_syndrome=0, **params)
         self.first = int(first_syndrome)
         self.plan = C.c_void_p()
         L_.check(L_.lib().qecmc_plan_create(self.pr, C.byref(self.plan)))
         self.d_init = torch.from_numpy(a.reshape(self.n, int(np.prod(a.shape[1:])))).to(self.dev)
         self.n_total = int(n_total if n_total is not None else self.n * self.world)
-        if isinstance(params.get("scan"), str):
-            params["scan"] = L_.SCANS[params["scan"]]
         self.align = 64 if params.get("scan") == L_.SCAN_WAVE else 1
         self.max_rows = max(shard_bounds(self.n_total, self.world, r, self.align)[1] - shard_bounds(self.n_total, self.world, r, self.align)[0]
                             for r in range(self.world))                                # equal-size buffers for the collective

@@ -275,3 +275,100 @@ def test_wave_scan_at_the_full_size_of_baseline_configs_2_and_3(q, orc, L, N, st
         for s in (lo, lo + 37):
             ref = orc.pteq_batch(orc.TORIC, init[s:s + 1], 0.15, Nc, steps, iters=10, tops_burn=0, seed=9, first_syndrome=s, return_states=True, scan=3)
             assert np.array_equal(got["counts"][s], ref["counts"][0]) and np.array_equal(got["states"][s], ref["states"][0])
+
+
+# ---- the law of scan = wave at the widths no enumeration or fixture reaches (12 and 29 / 28 words per rung) --------------------------
+def _final_counts(q, name, states):
+    from qecmc import toric_model as tm
+    R, Nc = states.shape[:2]
+    if name == "toric":
+        return np.stack([tm.count_errors(np.ascontiguousarray(states[:, c])) for c in range(Nc)], axis=1).astype(np.float64)
+    return np.count_nonzero(states.reshape(R, Nc, -1), axis=2).astype(np.float64)
+
+
+@pytest.mark.parametrize("name,L,Nc,p,steps", [("toric", 9, 8, 0.15, 20000), ("toric", 15, 8, 0.18, 40000), ("rotated", 21, 8, 0.17, 40000)])
+def test_wave_scan_has_the_random_scans_law_full_width(q, name, L, Nc, p, steps):
+    """BASELINE configs 2, 3 and 5's shapes: 4 096 distinct syndromes (64 wavefronts) decoded by scan = "wave" and by scan = "random", the
+    final error count of every rung paired per syndrome.  Per syndrome the two are the same Markov chain (the pick does not depend on the
+    state), so wave minus random averages to zero at any run length; the 64 wavefront means of the difference carry its error (the
+    syndromes of a wavefront share their picks).  A pick that never reaches some generators -- at large G only, where the bit-exact tests
+    against the oracle's restatement cannot see it -- moves the high rungs by tens of errors.  The random scan's rule is pinned to the
+    reference draw for draw (F2) and statistically at L = 9 (F5); the random scan's half-length run shows that <n> has equilibrated
+    (at L = 15 and 21 the middle rungs still drift by 2 % between 3 000 and 6 000 steps, hence the 40 000).
+    Runtime: 3 runs of 4096 x steps x 8 rungs x 10 proposals, up to 1.3e10 proposals each: a few seconds per case."""
+    rng = np.random.default_rng(L * 31 + Nc)
+    code = {"toric": q.TORIC, "rotated": q.ROTATED}[name]
+    N = 4096
+    init = _init(rng, name, N, L, p)
+    kw = dict(Nc=Nc, iters=10, tops_burn=1, seed=91, code=code, return_states=True)
+    n = {}
+    for scan, T in (("wave", steps), ("random", steps), ("random", steps // 2)):
+        n[scan, T] = _final_counts(q, name, q.pteq_batch(init, p, steps=T, scan=scan, **kw)["states"])      # [N, Nc]
+    scale = n["random", steps].mean(axis=0)
+    # equilibrated: the run of steps / 2 and the run of steps (its continuation) agree per rung
+    d = n["random", steps] - n["random", steps // 2]
+    assert np.all(np.abs(d.mean(axis=0)) <= 5 * d.std(axis=0, ddof=1) / np.sqrt(N) + 0.005 * scale), (d.mean(axis=0), scale)
+    # the law: the paired difference over the 64 wavefront means
+    g = (n["wave", steps] - n["random", steps]).reshape(N // 64, 64, Nc).mean(axis=1)
+    m, se = g.mean(axis=0), g.std(axis=0, ddof=1) / np.sqrt(g.shape[0])
+    assert np.all(np.abs(m) <= 5 * se + 0.002 * scale), (m, se, scale)           # (floor: 0.2 % of the rung's mean error count)
+
+
+# ---- the error bar of a success rate on scan = "wave" (qecmc.harness.success_err) --------------------------------------------------------
+def test_wave_success_rate_error_is_honest(q):
+    """K = 32 independent batches of 4 096 fresh toric L = 5 syndromes on scan = "wave" (fixed length, every step recorded): the standard
+    error the metrics line reports must match the batch-to-batch spread of the success rate.  For 31 degrees of freedom the sampling range
+    of the ratio is roughly [0.78, 1.29]; the bound [0.6, 1.8] is not flaky.  Runtime: 32 x 4096 x 10 000 x 5 rungs x 10 = 6.6e10
+    proposals plus the host's syndrome draws, about 10 s."""
+    from qecmc import harness
+    params = {"code": "toric", "size": 5, "p_error": 0.12, "noise": "depolarizing"}
+    rates, errs, binom = [], [], []
+    for k in range(32):
+        out = harness.generate(params, 4096, seed=100 + k, rng=np.random.default_rng([7, k]), steps=10000, conv_criteria=None, tops_burn=0,
+                               scan="wave")
+        m = out["metrics"]
+        assert m["success_rate_err_method"] == "wavefront_clusters"
+        rates.append(m["success_rate"]); errs.append(m["success_rate_err"]); binom.append(m["success_rate_err_binomial"])
+    sd = np.std(rates, ddof=1)
+    ratio = np.mean(errs) / sd
+    print("success %.4f, sd over batches %.5f, reported %.5f, binomial %.5f" % (np.mean(rates), sd, np.mean(errs), np.mean(binom)))
+    assert 0.6 <= ratio <= 1.8, (ratio, np.mean(rates), sd, np.mean(errs), np.mean(binom))
+
+
+# ---- PteqShard with a string scan (qecmc/sharding.py) ---------------------------------------------------------------------------------
+_SHARDED_WAVE_CHILD = r"""
+import json, os, sys
+sys.path[:0] = [sys.argv[1], os.path.join(sys.argv[1], "mcmc-qec-toric-rl_amd")]
+import numpy as np, torch, torch.distributed as dist
+import qecmc
+from qecmc.sharding import pteq_batch_sharded
+torch.cuda.set_device(0)
+dist.init_process_group("nccl", rank=0, world_size=1, init_method="tcp://127.0.0.1:" + sys.argv[2])
+rng = np.random.default_rng(12)
+init = (rng.integers(1, 4, size=(100, 2, 5, 5)) * (rng.random((100, 2, 5, 5)) < 0.1)).astype(np.uint8)
+kw = dict(Nc=5, steps=2000, iters=10, tops_burn=1, p_logical=0.5, seed=3)
+got = pteq_batch_sharded(init, 0.1, scan="wave", **kw)
+ref = qecmc.pteq_batch(init, 0.1, scan="wave", **kw)
+same = {k: bool(np.array_equal(got[k], ref[k])) for k in ("counts", "samples", "tops0")}
+dist.destroy_process_group()
+print(json.dumps(dict(same=same, samples=int(ref["samples"].sum()))))
+"""
+
+
+def test_pteq_batch_sharded_takes_scan_wave_as_a_string(q):
+    """pteq_batch_sharded(init, p, scan="wave") in a world-1 RCCL group equals pteq_batch(init, p, scan="wave") for a ragged N = 100 (the
+    string used to reach make_params unconverted: a ctypes TypeError).  A fresh child process under a time limit, as the bench's world-1
+    torchrun case.  Runtime: a few seconds, mostly process start-up."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from qecmc.sharding import free_port
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    e = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR"):
+        e.pop(k, None)
+    r = subprocess.run([sys.executable, "-c", _SHARDED_WAVE_CHILD, root, str(free_port())], capture_output=True, text=True, timeout=300, env=e)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert all(out["same"].values()) and out["samples"] > 0, out

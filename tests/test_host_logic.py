@@ -84,3 +84,76 @@ def test_shard_names_and_bench_configs():
         assert (a.code, a.L, a.syndromes, a.Nc, a.ladder_steps) == (code, L, N, 8, 10000)
     assert bench.parse_args(["--config", "4"]).eta == 100.0 and bench.parse_args([]).config == 2
     assert bench.parse_args(["--config", "3", "--Nc", "15"]).Nc == 15
+
+
+def _res(n):
+    z = np.zeros(n, dtype=np.uint32)
+    return dict(counts=np.zeros((n, 16), np.uint32), samples=z + 10, tops0=z + 3, steps_done=z + 10, converged=np.ones(n, bool))
+
+
+def test_batch_metrics_error_on_the_wave_scan_is_over_the_pick_clusters():
+    """scan = "wave": the 64 ladders of a wavefront share their generator picks, so a success rate's error is taken over the clusters of
+    syndromes that share picks.  Each group of 64 all-success or all-fail: the reported error is the standard error of the group means
+    (here 8x the binomial one); on scan = "random" the binomial one."""
+    from qecmc import harness
+    n = 64 * 40
+    groups = np.random.default_rng(3).random(40) < 0.7
+    success = np.repeat(groups, 64)
+    se_groups = groups.astype(float).std(ddof=1) / np.sqrt(40)
+    k = success.mean()
+    binom = np.sqrt(k * (1 - k) / n)
+    m = harness.batch_metrics(0, 5, 5, 10, _res(n), 1.0, success, scan="wave")
+    assert m["success_rate_err_method"] == "wavefront_clusters"
+    assert abs(m["success_rate_err"] - se_groups) < 1e-12 and abs(m["success_rate_err_binomial"] - binom) < 1e-15
+    assert m["success_rate_err"] > 6 * binom
+    for scan in ("random", "sweep", "colour"):
+        m = harness.batch_metrics(0, 5, 5, 10, _res(n), 1.0, success, scan=scan)
+        assert m["success_rate_err_method"] == "binomial" and m["success_rate_err"] == m["success_rate_err_binomial"] and abs(m["success_rate_err"] - binom) < 1e-15
+    # the integer scan code means the same thing; a batch that starts mid-group shifts the clusters with it
+    assert harness.batch_metrics(0, 5, 5, 10, _res(n), 1.0, success, scan=3)["success_rate_err_method"] == "wavefront_clusters"
+    shifted = harness.batch_metrics(0, 5, 5, 10, _res(n), 1.0, success, scan="wave", first_syndrome=32)["success_rate_err"]
+    assert shifted < m["success_rate_err"] * 8 and not np.isclose(shifted, se_groups)
+
+
+def test_wavefront_clusters_follow_the_global_ladder_index():
+    from qecmc.harness import wavefront_clusters
+    assert wavefront_clusters(130).tolist() == [0] * 64 + [1] * 64 + [2] * 2
+    assert wavefront_clusters(130, first_syndrome=64)[:65].tolist() == [0] * 64 + [1]
+    assert wavefront_clusters(4, replicas=64).tolist() == [0, 1, 2, 3]              # R >= 64: every syndrome its own cluster
+    assert wavefront_clusters(4, replicas=64, first_syndrome=32).tolist() == [0, 0, 0, 0]   # ... unless the groups straddle them
+    assert wavefront_clusters(6, replicas=32).tolist() == [0, 0, 1, 1, 2, 2]
+    assert wavefront_clusters(10, replicas=20).tolist() == [0] * 10          # ladders 60..79 straddle two groups, 120..139 too: one chain
+
+
+def test_threshold_curve_reports_the_scan_s_error(monkeypatch):
+    from qecmc import harness
+    success = np.repeat(np.arange(8) % 2 == 0, 64)
+    def fake_generate(params, n, seed=0, **kw):
+        return dict(success=success[:n], samples=np.ones(n, np.uint32), converged=np.ones(n, bool), metrics={})
+    monkeypatch.setattr(harness, "generate", fake_generate)
+    for scan, method in (("wave", "wavefront_clusters"), ("random", "binomial")):
+        tc = harness.threshold_curve({"code": "toric", "size": 5}, [0.1, 0.12], 512, scan=scan)
+        assert tc["err_method"] == method
+        assert np.allclose(tc["err_binomial"], np.sqrt(0.25 / 512)) and np.allclose(tc["err_sampled_binomial"], tc["err_binomial"])
+        want = np.sqrt(0.25 / 512) if scan == "random" else (np.arange(8) % 2 == 0).std(ddof=1) / np.sqrt(8)
+        assert np.allclose(tc["err"], want) and np.allclose(tc["err_sampled"], want)
+
+
+def test_pteq_shard_converts_a_string_scan_before_make_params(monkeypatch):
+    """PteqShard(..., scan="wave") used to hand the string to make_params (a ctypes TypeError on the GPU path).  The parameter block is
+    built here with the real make_params and the constructor stopped right after, before anything touches a device."""
+    from qecmc import _lib, sharding
+    seen = {}
+    real = _lib.make_params
+
+    class Stop(Exception):
+        pass
+
+    def spy(**kw):
+        seen["pr"] = real(**kw)
+        raise Stop
+    monkeypatch.setattr(_lib, "make_params", spy)
+    for scan, want in (("wave", _lib.SCAN_WAVE), ("colour", _lib.SCAN_COLOUR), (_lib.SCAN_WAVE, _lib.SCAN_WAVE)):
+        with pytest.raises(Stop):
+            sharding.PteqShard(np.zeros((3, 2, 5, 5), np.uint8), 0.1, 0, device=0, scan=scan, Nc=5, steps=10)
+        assert seen.pop("pr").scan == want

@@ -145,3 +145,80 @@ class SurfEnumeration:
                 break
             pi = nxt
         return pi.reshape(4, -1).sum(axis=1)
+
+
+# ---- plaquette codes up to G = 24 generators (L = 5): meet-in-the-middle weight enumerator -------------------------------------------
+# SurfEnumeration above holds every configuration (4 x 2^G x L^2 bytes) and is meant for L = 3.  Every weight used here depends on a
+# configuration only through n_xy = #X + #Y and n_z = #Z (depolarizing, biased with px = py, alpha), so a class is summarised exactly by
+# the integer histogram H[c, n_xy, n_z] over its 2^G members.  A member is rep_c ^ a ^ b with a from the span of the first half of the
+# generators and b from the span of the second: 2^(G/2) x 2^(G/2) popcounts per class, bit-packed (x bit: Paulis 1, 2; z bit: 2, 3).
+
+def _pack(flat):
+    flat = np.asarray(flat, dtype=np.uint8).ravel()
+    w = np.uint64(1) << np.arange(flat.size, dtype=np.uint64)
+    return int(np.sum(w[(flat == 1) | (flat == 2)])), int(np.sum(w[(flat == 2) | (flat == 3)]))
+
+
+def _span_packed(gens):
+    xs, zs = np.zeros(1, np.uint64), np.zeros(1, np.uint64)
+    for gx, gz in gens:
+        xs, zs = np.concatenate([xs, xs ^ np.uint64(gx)]), np.concatenate([zs, zs ^ np.uint64(gz)])
+    return xs, zs
+
+
+class PlaquetteWeightEnumerator:
+    """Exact class law of one syndrome of an L x L xzzx / rotated code for any weight w(n_xy, n_z), G <= 24.  `api` as for
+    SurfEnumeration.  H[c, n_xy, n_z]: number of configurations of class c with those counts (int64, sums to 2^G per class)."""
+
+    def __init__(self, code, init, api, block=256):
+        init = np.asarray(init, dtype=np.uint8)
+        self.code, self.L = code, init.shape[-1]
+        L = self.L
+        self.nq = nq = L * L
+        assert nq <= 64
+        zero = np.zeros((L, L), dtype=np.uint8)
+        self.G = G = api.ngen(code, L)
+        assert G <= 24, "meet in the middle over 2^12 x 2^12 at most"
+        gens = [_pack(api.apply_stabilizer(code, zero, *api.gen_rco(code, L, g))[0]) for g in range(G)]
+        ax, az = _span_packed(gens[:G // 2])
+        bx, bz = _span_packed(gens[G // 2:])
+        reps = [None] * 4
+        for k in range(4):                              # apply_logical(m, k, 0, 0) maps class c -> c ^ k (SURVEY.md section 4)
+            r = np.asarray(api.apply_logical(code, init, k, 0, 0)[0], dtype=np.uint8)
+            reps[int(api.eq_class(code, r))] = _pack(r)
+        assert all(r is not None for r in reps)
+        self.H = np.zeros((4, nq + 1, nq + 1), dtype=np.int64)
+        for c, (rx, rz) in enumerate(reps):
+            h = np.zeros((nq + 1) * (nq + 1), dtype=np.int64)
+            for lo in range(0, len(bx), block):
+                x = (bx[lo:lo + block, None] ^ np.uint64(rx)) ^ ax[None, :]
+                z = (bz[lo:lo + block, None] ^ np.uint64(rz)) ^ az[None, :]
+                nxy = np.bitwise_count(x).astype(np.int64)
+                nz = np.bitwise_count(z & ~x).astype(np.int64)
+                h += np.bincount((nxy * (nq + 1) + nz).ravel(), minlength=h.size)
+            self.H[c] = h.reshape(nq + 1, nq + 1)
+        # the group has 2^G distinct members: no two classes (cosets) share a configuration, checked on the histograms' totals
+        assert np.all(self.H.sum(axis=(1, 2)) == 1 << G)
+
+    def class_probabilities(self, weight):
+        """weight(n_xy, n_z) -> float64 array, broadcast over the (nq + 1) x (nq + 1) grid of counts"""
+        n = np.arange(self.nq + 1, dtype=np.float64)
+        W = np.asarray(weight(n[:, None], n[None, :]), dtype=np.float64)
+        z = np.einsum("cij,ij->c", self.H.astype(np.float64), W)
+        return z / z.sum()
+
+
+def depolarizing_counts_weight(p):
+    f = (p / 3.0) / (1.0 - p)
+    return lambda nxy, nz: f ** (nxy + nz)
+
+
+def biased_counts_weight(p, eta, nq):
+    """biased_weight with px = py, as a function of (n_xy, n_z)"""
+    pz, px = p * eta / (eta + 1.0), p / (2.0 * (eta + 1.0))
+    return lambda nxy, nz: np.where(nxy + nz <= nq, px ** nxy * pz ** nz * (1.0 - p) ** np.maximum(nq - nxy - nz, 0), 0.0)
+
+
+def alpha_counts_weight(pz_tilde, alpha):
+    """the alpha noise model's weight pz_tilde^(n_z + alpha (n_x + n_y)) (src/mcmc_alpha.py: n_eff = n_z + alpha (n_x + n_y))"""
+    return lambda nxy, nz: pz_tilde ** (nz + alpha * nxy)
