@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "plan_host.hpp"
 #include "stencil_bytes.hpp"
 #include "tables.hpp"
 
@@ -110,17 +111,29 @@ struct DevBuf {
     template <class T> T *as() const { return static_cast<T *>(p); }
 };
 
-int check_code_L(int code, int L)
-{
-    if (code != QECMC_TORIC && code != QECMC_XZZX && code != QECMC_ROTATED && code != QECMC_PLANAR)
-        return fail(QECMC_ERR_INVALID, "code %d unknown (0 toric, 1 xzzx, 2 rotated, 3 planar)", code);
-    if (L < 2 || L > 64) return fail(QECMC_ERR_INVALID, "L=%d out of range [2,64]", L);
-    if ((code == QECMC_XZZX || code == QECMC_ROTATED) && (L < 3 || L % 2 == 0))
-        return fail(QECMC_ERR_INVALID, "L=%d: the xzzx / rotated models need odd L >= 3 (their half-plaquette indexing, xzzx_model.py:444)", L);
-    return 0;
-}
+// kernel time of a launch on the null stream between start() and stop(); the events go on every path
+struct EventTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventTimer() = default;
+    EventTimer(const EventTimer &) = delete;
+    EventTimer &operator=(const EventTimer &) = delete;
+    ~EventTimer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    hipError_t start()
+    {
+        if (hipError_t e = hipEventCreate(&e0)) return e;
+        if (hipError_t e = hipEventCreate(&e1)) return e;
+        return hipEventRecord(e0, 0);
+    }
+    hipError_t stop(float *ms)
+    {
+        if (hipError_t e = hipEventRecord(e1, 0)) return e;
+        if (hipError_t e = hipEventSynchronize(e1)) return e;
+        return hipEventElapsedTime(ms, e0, e1);
+    }
+};
 
-inline size_t code_nq(int code, int L) { return (size_t)code_nq_of(code, L); }
+// a refusal of the host-only checks (plan_host.hpp), handed to qecmc_last_error()
+int report(const Refusal &r) { return r.code ? fail(r.code, "%s", r.msg.c_str()) : 0; }
 
 }  // namespace
 
@@ -131,234 +144,44 @@ struct qecmc_plan {
     uint32_t queue_grid = 0;                                   // persistent grid of the work-queue kernels (0: not a queue plan)
     size_t lds_bytes;
     uint32_t *d_swap_acc = nullptr, *d_nerr_sum = nullptr;   // qecmc_plan_set_stats (caller-owned)
+    // (plan_host.hpp: whether a launch runs on the persistent grid, and THE workspace formula of the criterion runs)
+    bool takes_queue(bool wants_states_or_stats) const { return launch_takes_queue(queue_grid, prm.steps, wants_states_or_stats); }
+    uint64_t workspace(uint64_t N, bool queue) const { return workspace_need(prm, queue_grid, N, queue); }
 };
 
 namespace {
 
-int validate_params(const qecmc_params *p)
-{
-    if (!p) return fail(QECMC_ERR_INVALID, "params is NULL");
-    if (p->abi_size != sizeof(qecmc_params))
-        return fail(QECMC_ERR_INVALID, "params->abi_size=%u, this library expects %zu", p->abi_size, sizeof(qecmc_params));
-    if (int rc = check_code_L(p->code, p->L)) return rc;
-    if (p->Nc < 1 || p->Nc > kMaxNc) return fail(QECMC_ERR_INVALID, "Nc=%d out of range [1,%d]", p->Nc, kMaxNc);
-    if (p->noise != QECMC_NOISE_DEPOLARIZING && p->noise != QECMC_NOISE_BIASED && p->noise != QECMC_NOISE_ALPHA) return fail(QECMC_ERR_INVALID, "noise model %d unknown", p->noise);
-    if (p->noise == QECMC_NOISE_ALPHA) {
-        if (!(p->alpha > 0.0)) return fail(QECMC_ERR_INVALID, "alpha=%g must be positive", p->alpha);
-        if (!(p->p > 0.0) || !(p->p <= 1.0)) return fail(QECMC_ERR_INVALID, "pz_tilde=%g must be in (0, 1]", p->p);
-        if (p->code == QECMC_TORIC || p->code == QECMC_PLANAR) return fail(QECMC_ERR_UNSUPPORTED, "alpha noise is built for the xzzx and rotated codes (the reference sizes its weights for L^2 qubits, mcmc_alpha.py:27)");
-    } else
-    if (p->noise == QECMC_NOISE_BIASED) {
-        if (!(p->eta > 0.0)) return fail(QECMC_ERR_INVALID, "eta=%g must be positive", p->eta);
-        if (!(p->p > 0.0) || !(p->p < (p->eta + 1) / (2 * p->eta + 1))) return fail(QECMC_ERR_INVALID, "p=%g must be in (0, (eta+1)/(2 eta+1))", p->p);
-        if (p->code == QECMC_TORIC || p->code == QECMC_PLANAR) return fail(QECMC_ERR_UNSUPPORTED, "biased noise is built for the xzzx and rotated codes (BASELINE config 4)");
-    } else if (!(p->p > 0.0) || !(p->p <= 0.75)) return fail(QECMC_ERR_INVALID, "p=%g must be in (0, 0.75]", p->p);
-    if (!(p->p_logical >= 0.0) || !(p->p_logical <= 1.0)) return fail(QECMC_ERR_INVALID, "p_logical=%g must be in [0,1]", p->p_logical);
-    if (p->scan != QECMC_SCAN_RANDOM && p->scan != QECMC_SCAN_SWEEP && p->scan != QECMC_SCAN_COLOUR && p->scan != QECMC_SCAN_WAVE) return fail(QECMC_ERR_INVALID, "scan mode %d unknown", p->scan);
-    if (p->scan != QECMC_SCAN_RANDOM && p->noise != QECMC_NOISE_DEPOLARIZING && !(p->scan == QECMC_SCAN_WAVE && p->noise == QECMC_NOISE_ALPHA) && p->scan != QECMC_SCAN_COLOUR)
-        return fail(QECMC_ERR_UNSUPPORTED, "the sweep scan is built for the depolarizing rule only, the wave scan for the depolarizing and alpha rules");
-    if (p->scan == QECMC_SCAN_WAVE) {
-        if (p->Nc < 2) return fail(QECMC_ERR_UNSUPPORTED, "scan = wave needs a ladder whose top rung sits at p = 0.75 (Nc >= 2)");
-        if (p->first_syndrome & 63u) return fail(QECMC_ERR_INVALID, "scan = wave shares a generator pick among the 64 ladders of a wavefront: first_syndrome=%u must be a multiple of 64", p->first_syndrome);
-    }
-    if (p->scan == QECMC_SCAN_COLOUR) {
-        if (p->p_logical > 0.0 && p->Nc < 2 && p->noise != QECMC_NOISE_BIASED) return fail(QECMC_ERR_UNSUPPORTED, "scan = colour needs the top rung at p = 0.75 (Nc >= 2) when logical moves are on");
-    }
-    if (p->conv_mode != QECMC_CONV_NONE && p->conv_mode != QECMC_CONV_ERROR_BASED) return fail(QECMC_ERR_INVALID, "conv_mode %d unknown", p->conv_mode);
-    if (p->conv_mode == QECMC_CONV_ERROR_BASED && (p->TOPS < 0 || p->SEQ < 0 || !(p->eps >= 0))) return fail(QECMC_ERR_INVALID, "TOPS, SEQ and eps must be non-negative");
-    if (p->iters == 0 || p->iters > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "iters out of range");
-    if (p->tops_burn < 0) return fail(QECMC_ERR_INVALID, "tops_burn must be >= 0");
-    if (p->replicas < 0 || p->replicas > 65536) return fail(QECMC_ERR_INVALID, "replicas=%d out of range [0, 65536]", p->replicas);
-    // the R ladders of a syndrome add their class counts / samples / tops0 into uint32 outputs: at most `steps` each
-    if (p->replicas > 1 && (uint64_t)p->replicas * p->steps > 0xFFFFFFFFull)
-        return fail(QECMC_ERR_INVALID, "replicas * steps = %llu overflows the summed 32-bit class counts: lower one of them",
-                    (unsigned long long)((uint64_t)p->replicas * p->steps));
-    return 0;
-}
-
+// the plan of a parameter block validate_params() accepts: plan_host() decides everything, this uploads its tables
 int build_plan(const qecmc_params *p, qecmc_plan *pl)
 {
     pl->prm = *p;
-    LadderArgs &a = pl->args;
-    std::memset(&a, 0, sizeof a);
-    const int L = p->L, Nc = p->Nc, nq = (int)code_nq(p->code, L), W = (nq + 15) / 16, ncls = p->code == QECMC_TORIC ? 16 : 4;
-    const bool alpha = p->noise == QECMC_NOISE_ALPHA;
-    const bool biased = p->noise == QECMC_NOISE_BIASED || alpha;     // table-driven acceptance pn / pb
-    a.code = p->code; a.noise = p->noise; a.alpha = p->alpha;
-    a.replicas = p->replicas > 1 ? (uint32_t)p->replicas : 1u;
-    a.tune = p->flags & 0xFFFFu;                                // developer switches (qecmc_flag): which variant runs, never what it computes
-    a.L = L; a.Nc = Nc; a.W = W; a.nq = nq; a.ncls = ncls;
-    a.iters = (uint32_t)p->iters;
-    a.seed_lo = (uint32_t)p->seed; a.seed_hi = (uint32_t)(p->seed >> 32);
-    a.tops_burn = (uint32_t)p->tops_burn;
-    a.conv_mode = p->conv_mode; a.TOPS = (uint32_t)p->TOPS; a.SEQ = (uint32_t)p->SEQ; a.eps = p->eps;
-    a.thr_logical = p->p_logical > 0 ? thr64(p->p_logical) : 0;
-    const uint32_t n_gen = p->code == QECMC_TORIC ? 2u * L * L : (uint32_t)surf_ngen(p->code, L);
-    if (n_gen > kMaxGenLds)   // every kernel path stages the generator table in LDS
-        return fail(QECMC_ERR_UNSUPPORTED, "L=%d: %u generators exceed the LDS table of %u (needed by scan=1 and by the xzzx / rotated codes)", L, n_gen, kMaxGenLds);
-    const std::vector<uint32_t> gt = p->code == QECMC_TORIC ? toric_generator_table(L) : surf_generator_table(p->code, L);
-    std::vector<uint8_t> gen_type(gt.size() / 2, 0);
-    std::vector<uint32_t> xyz_lut;
-    const bool typed = biased || (p->code != QECMC_TORIC && !p->scan);   // the generators' Pauli patterns: the biased rules' count-change table,
-    std::vector<uint32_t> patterns;                                      // the plaquette codes' dE table (ladder_kernel.hpp, DELUT)
-    if (typed) {
-        generator_patterns(gt, gen_type, patterns);
-        if (patterns.size() > 16) return fail(QECMC_ERR_UNSUPPORTED, "%zu distinct generator Pauli patterns (> 16)", patterns.size());
-        a.n_types = (int)patterns.size();
-        for (size_t t = 0; t < patterns.size(); ++t) a.type_ops[t] = (uint8_t)patterns[t];
-    }
-    if (biased) {
-        // the biased / alpha rules' table of count changes (tables.hpp)
-        if (nq > 511) return fail(QECMC_ERR_UNSUPPORTED, "biased / alpha noise packs the error counts in 10-bit fields: nq=%d", nq);
-        xyz_lut = count_change_table(patterns);
-    }
-    pl->lds_bytes = p->scan == QECMC_SCAN_COLOUR ? sizeof(uint32_t) * ((size_t)Nc * W + 4 * (size_t)Nc + (size_t)ncls)   // (ladder_colour.hip: one ladder per workgroup)
-                  : p->scan == QECMC_SCAN_WAVE ? wu_lds_bytes(Nc, W, ncls, L, p->conv_mode != 0, alpha)
-                                                 : ladder_lds_bytes(Nc, W, ncls, ladder_gen_dwords(p->code, p->noise, p->scan, n_gen, Nc, nq, a.n_types));
-    if (pl->lds_bytes > 160 * 1024)
-        return fail(QECMC_ERR_UNSUPPORTED, "L=%d Nc=%d needs %zu B of LDS per workgroup (> 160 KiB)", L, Nc, pl->lds_bytes);
-
-    std::vector<double> pladder, pdiff;
-    // p_top = 0.75 (mcmc.py:62) or (eta+1)/(2 eta+1) (mcmc_biased.py:81)
-    // ... or pz_tilde_top = 1 (mcmc_alpha.py:94)
-    ladder_probabilities(p->p, alpha ? 1.0 : biased ? (p->eta + 1) / (2 * p->eta + 1) : 0.75, Nc, pladder, pdiff);   // mcmc.py:62-69
-    if (alpha) pdiff.assign(pdiff.size(), 0.0);      // the depolarizing tables below are unused by the table-driven rules
-    for (int c = 0; c < Nc && !biased; ++c) {
-        const double f = chain_factor(pladder[c]);
-        if (f >= 1.0 && !biased) a.acc_all_mask |= 1u << c;
-        for (int d = 1; d <= 4; ++d) {
-            a.acc_thr[c][d - 1] = thr32(std::pow(f, (double)d));                     // mcmc.py:42
-            a.acc_thr44[c][d - 1] = thr44(std::pow(f, (double)d));
-        }
-    }
-    std::vector<uint32_t> top_tbl(nq + 1, 0u);                             // mcmc.py:34 for a top chain below p = 0.75
-    for (int d = 1; d <= nq && !biased; ++d) top_tbl[d] = thr32(std::pow(chain_factor(pladder[Nc - 1]), (double)d));
-    const std::vector<uint64_t> sw = swap_thresholds(pdiff, nq);             // mcmc.py:149
-    for (int i = 0; i + 1 < Nc; ++i) {
-        const double l2 = std::log2(pdiff[i]);
-        a.swap_inv_log2[i] = (std::isfinite(l2) && l2 < 0) ? (float)(1.0 / l2) : 0.0f;
-    }
-    a.swap_fast_ok = 1;
-    for (int i = 0; i + 1 < Nc; ++i)
-        if (nq >= 1 && sw[(size_t)i * (nq + 1) + 1] > 0xFFFFFFFFull) a.swap_fast_ok = 0;
-    const std::vector<uint32_t> lm = p->code == QECMC_TORIC ? toric_logical_masks(L, W) : surf_logical_masks(p->code, L, W);
-    a.scan = p->scan;
-    if (p->scan == QECMC_SCAN_COLOUR) {
-        // the colour phases: groups of mutually disjoint generators, one wavefront pass each (tables.hpp)
-        int n_phases = 0;
-        const std::vector<uint16_t> ph = colour_phases(gt, n_phases);
-        HIP_TRY(pl->phases.alloc(ph.size() * sizeof(uint16_t)));
-        HIP_TRY(hipMemcpy(pl->phases.p, ph.data(), ph.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        a.phase_tab = pl->phases.as<uint16_t>();
-        a.n_phases = (uint32_t)n_phases;
-        // Ladder_alpha's top rung sits at pz_tilde = 1 (mcmc_alpha.py:94): every weight ratio is 1, it takes the coin like the depolarizing top rung
-        if (alpha && Nc >= 2) a.acc_all_mask |= 1u << (Nc - 1);
-        pl->lds_bytes = sizeof(uint32_t) * colour_lds_dwords(Nc, W, ncls, a.n_phases, (uint32_t)(gt.size() / 2), L, nq, a.swap_fast_ok != 0, p->noise);
-        if (pl->lds_bytes > 160 * 1024)
-            return fail(QECMC_ERR_UNSUPPORTED, "scan = colour: L=%d Nc=%d needs %zu B of LDS per workgroup (> 160 KiB)", L, Nc, pl->lds_bytes);
-        if (p->p_logical > 0.0 && p->noise != QECMC_NOISE_BIASED && !((a.acc_all_mask >> (Nc - 1)) & 1u))
-            return fail(QECMC_ERR_UNSUPPORTED, "scan = colour needs a top rung that accepts every move (p_top = 0.75) when logical moves are on");
-    }
-    if (p->scan == QECMC_SCAN_WAVE) {
-        // the wave-uniform random scan (ladder_wu.hpp): one scalar-loadable descriptor per generator; states in registers
-        const std::vector<uint32_t> wd = wave_descriptors(gt);
-        a.n_gen = (uint32_t)(gt.size() / 2);
-        pl->lds_bytes = wu_lds_bytes(Nc, W, ncls, L, p->conv_mode != 0, alpha);
-        a.conv_mode = p->conv_mode;
-        if (wd.empty()) return fail(QECMC_ERR_UNSUPPORTED, "scan = wave: a generator with three different Paulis");
-        HIP_TRY(pl->wu_desc.alloc(wd.size() * sizeof(uint32_t)));
-        HIP_TRY(hipMemcpy(pl->wu_desc.p, wd.data(), wd.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        a.wu_desc = pl->wu_desc.as<uint32_t>();
-    }
-    {
-        a.n_gen = (uint32_t)(gt.size() / 2);
-        HIP_TRY(pl->gen.alloc(gt.size() * sizeof(uint32_t)));
-        HIP_TRY(hipMemcpy(pl->gen.p, gt.data(), gt.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        a.gen = pl->gen.as<uint2>();
-    }
-    if (biased) {
-        std::vector<double> bt;
-        for (int c = 0; c < Nc; ++c) {
-            const std::vector<double> t = alpha ? alpha_tables(pladder[c], p->alpha, (size_t)nq) : bias_tables(pladder[c], p->eta, (size_t)nq);
-            bt.insert(bt.end(), t.begin(), t.end());
-        }
-        HIP_TRY(pl->bias.alloc(bt.size() * sizeof(double)));
-        HIP_TRY(hipMemcpy(pl->bias.p, bt.data(), bt.size() * sizeof(double), hipMemcpyHostToDevice));
-        a.bias_tbl = pl->bias.as<double>();
-        for (int c = 0; c < Nc; ++c) {
-            // log2(px / pI), log2(pz / pI) of rung c (px = py in both models: bias_tables / alpha_tables): the fast test's slopes
-            const double *t = &bt[(size_t)c * 4 * (nq + 1)];
-            a.bias_l2[c][0] = std::log2(t[1] / t[3 * (nq + 1) + 1]);
-            a.bias_l2[c][1] = std::log2(t[2 * (nq + 1) + 1] / t[3 * (nq + 1) + 1]);
-            a.bias_l2f[c][0] = (float)a.bias_l2[c][0];
-            a.bias_l2f[c][1] = (float)a.bias_l2[c][1];
-            // the fast test may run in single precision / fp16 count changes on this rung (ladder_kernel.hpp: a count changes by at
-            // most 4 per proposal since loop entry; fp16 holds integers up to 2048; |l d| <= 2000 keeps the exponent's error below a unit)
-            if (a.iters <= 512u && 4.0 * (double)a.iters * std::max(std::fabs(a.bias_l2[c][0]), std::fabs(a.bias_l2[c][1])) <= 2000.0)
-                a.bias_f32ok |= 1u << c;
-        }
-        if (p->scan == QECMC_SCAN_COLOUR) {
-            // scan = 2 under these rules (ladder_colour.hip): a generator is a Metropolis move for the model's own weight, accepted iff
-            // u < (px / pI)^dxy (pz / pI)^dz -- as integers, u <= ceil(ratio 2^32) - 1 -- for its changes (dz, dxy) of n_z and n_x + n_y
-            std::vector<uint32_t> ct((size_t)Nc * 81);
-            for (int c = 0; c < Nc; ++c) {
-                const double *t = &bt[(size_t)c * 4 * (nq + 1)];
-                const double fxy = t[1] / t[3 * (nq + 1) + 1], fz = t[2 * (nq + 1) + 1] / t[3 * (nq + 1) + 1];
-                for (int dz = -4; dz <= 4; ++dz)
-                    for (int dxy = -4; dxy <= 4; ++dxy) {
-                        const uint64_t th = thr64(std::pow(fxy, (double)dxy) * std::pow(fz, (double)dz));
-                        if (th == 0) return fail(QECMC_ERR_UNSUPPORTED, "scan = colour: an acceptance ratio of rung %d underflows", c);
-                        ct[(size_t)c * 81 + 9 * (dz + 4) + (dxy + 4)] = (uint32_t)(th - 1);
-                    }
-            }
-            HIP_TRY(pl->col_thr.alloc(ct.size() * sizeof(uint32_t)));
-            HIP_TRY(hipMemcpy(pl->col_thr.p, ct.data(), ct.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            a.col_thr = pl->col_thr.as<uint32_t>();
-        }
-        HIP_TRY(pl->xyz_lut.alloc(xyz_lut.size() * sizeof(uint32_t)));
-        HIP_TRY(hipMemcpy(pl->xyz_lut.p, xyz_lut.data(), xyz_lut.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        a.xyz_lut = pl->xyz_lut.as<uint32_t>();
-    }
-    if (typed) {
-        HIP_TRY(pl->gen_type.alloc(gen_type.size()));
-        HIP_TRY(hipMemcpy(pl->gen_type.p, gen_type.data(), gen_type.size(), hipMemcpyHostToDevice));
-        a.gen_type = pl->gen_type.as<uint8_t>();
-    }
-    if (alpha) {
-        std::vector<double> lnb(Nc > 1 ? Nc - 1 : 1, 0.0);
-        for (int i = 0; i + 1 < Nc; ++i) lnb[i] = std::log(pladder[i] / pladder[i + 1]);   // mcmc_alpha.py:123
-        HIP_TRY(pl->lnb.alloc(lnb.size() * sizeof(double)));
-        HIP_TRY(hipMemcpy(pl->lnb.p, lnb.data(), lnb.size() * sizeof(double), hipMemcpyHostToDevice));
-        a.alpha_lnb = pl->lnb.as<double>();
-    }
-    HIP_TRY(pl->swap_thr.alloc(sw.size() * sizeof(uint64_t)));
-    HIP_TRY(pl->lmask.alloc(lm.size() * sizeof(uint32_t)));
-    HIP_TRY(hipMemcpy(pl->swap_thr.p, sw.data(), sw.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(pl->lmask.p, lm.data(), lm.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(pl->acc_top.alloc(top_tbl.size() * sizeof(uint32_t)));
-    HIP_TRY(hipMemcpy(pl->acc_top.p, top_tbl.data(), top_tbl.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    a.acc_tbl_top = pl->acc_top.as<uint32_t>();
-    a.swap_thr = pl->swap_thr.as<uint64_t>();
-    a.lmask = pl->lmask.as<uint32_t>();
-    KernelShape shape = kernel_shape(a);
-    if (p->scan == QECMC_SCAN_WAVE && (!choose_kernel(shape).ok() || pl->lds_bytes > 160 * 1024))
-        return fail(QECMC_ERR_UNSUPPORTED, "scan = wave: L=%d Nc=%d p=%g is outside what it is built for (depolarizing rule: a top rung that accepts every move, at most "
-                    "16 packed state words per rung -- toric / planar L <= 11, xzzx / rotated L <= 16 --, fixed-length runs of up to 8 rungs 32 words -- toric L <= 16, xzzx / rotated L <= 22; alpha rule: xzzx / rotated L <= 11, "
-                    "4 iters max|log2 ratio| <= 2000 --, %zu B of LDS)", L, Nc, p->p, pl->lds_bytes);
-    // runs that stop by the convergence criterion, where the kernel takes a work queue: a persistent grid (what one launch keeps resident) fed
-    // from a counter (scan = wave: the workgroups' own shares of the batch), of as many workgroups as the LDS and the kernel's occupancy let a CU hold
-    shape.queue = 1;
-    const KernelKey queue_kernel = choose_kernel(shape);
-    if (queue_kernel.takes_queue()) {
+    HostPlan hp;
+    if (int rc = report(plan_host(*p, hp))) return rc;
+    LadderArgs &a = pl->args = hp.args;
+    pl->lds_bytes = hp.lds_bytes;
+    // (an empty table of the optional ones is one the plan does not have: its pointer stays null, which the launch path and the kernels test)
+    auto upload = [](DevBuf &d, const auto &v, auto &dst, bool optional) -> int {
+        if (optional && v.empty()) return 0;
+        const size_t bytes = v.size() * sizeof v[0];
+        HIP_TRY(d.alloc(bytes));
+        HIP_TRY(hipMemcpy(d.p, v.data(), bytes, hipMemcpyHostToDevice));
+        dst = static_cast<std::remove_reference_t<decltype(dst)>>(d.p);
+        return 0;
+    };
+    int rc = 0;
+    if ((rc = upload(pl->phases, hp.phases, a.phase_tab, true)) || (rc = upload(pl->wu_desc, hp.wu_desc, a.wu_desc, true)) ||
+        (rc = upload(pl->gen, hp.gen, a.gen, false)) || (rc = upload(pl->bias, hp.bias, a.bias_tbl, true)) ||
+        (rc = upload(pl->col_thr, hp.col_thr, a.col_thr, true)) || (rc = upload(pl->xyz_lut, hp.xyz_lut, a.xyz_lut, true)) ||
+        (rc = upload(pl->gen_type, hp.gen_type, a.gen_type, true)) || (rc = upload(pl->lnb, hp.lnb, a.alpha_lnb, true)) ||
+        (rc = upload(pl->swap_thr, hp.swap_thr, a.swap_thr, false)) || (rc = upload(pl->lmask, hp.lmask, a.lmask, false)) ||
+        (rc = upload(pl->acc_top, hp.acc_top, a.acc_tbl_top, false)))
+        return rc;
+    if (!same_shape(kernel_shape(a), hp.shape)) return fail(QECMC_ERR_HIP, "internal: the uploaded plan's kernel shape differs from the host plan's");
+    if (hp.takes_queue) {
         hipDeviceProp_t prop;
         HIP_TRY(hipGetDeviceProperties(&prop, p->device));
-        const size_t per_cu_lds = (160 * 1024) / pl->lds_bytes, per_cu_waves = (size_t)(4 * queue_kernel.minw) / (size_t)Nc;
-        size_t per_cu = per_cu_lds < per_cu_waves ? per_cu_lds : per_cu_waves;
-        if (per_cu < 1) per_cu = 1;
-        pl->queue_grid = (uint32_t)(per_cu * (size_t)prop.multiProcessorCount);
-        if (p->flags >> 16) pl->queue_grid = p->flags >> 16;   // tests: force refills on small batches
-        if (pl->queue_grid == 0) pl->queue_grid = 1;
-        if (queue_kernel.family == kFamLadder) HIP_TRY(pl->queue.alloc(sizeof(uint32_t)));
+        pl->queue_grid = queue_grid(hp, prop.multiProcessorCount, p->flags);
+        if (hp.queue_family == kFamLadder) HIP_TRY(pl->queue.alloc(sizeof(uint32_t)));
     }
     return 0;
 }
@@ -378,7 +201,7 @@ int qecmc_device_count(void)
 
 // ---------------------------------------------------------------- primitives
 #define PRIM_PROLOGUE()                                   \
-    if (int rc = check_code_L(code, L)) return rc;        \
+    if (int rc = report(check_code_L(code, L))) return rc; \
     if (int rc = use_device(0)) return rc;                \
     const size_t nq = code_nq(code, L);                   \
     (void)nq;                                             \
@@ -489,7 +312,7 @@ int qecmc_syndrome(int code, int L, uint64_t N, const uint8_t *in, uint8_t *defe
 static int generate_args(int code, int L, uint64_t N, double p_x, double p_y, double p_z, int hide_class, uint64_t seed,
                          uint32_t first_syndrome, GenArgs &a)
 {
-    if (int rc = check_code_L(code, L)) return rc;
+    if (int rc = report(check_code_L(code, L))) return rc;
     if (!(p_x >= 0.0) || !(p_y >= 0.0) || !(p_z >= 0.0) || !(p_x + p_y + p_z <= 1.0))
         return fail(QECMC_ERR_INVALID, "(p_x, p_y, p_z) = (%g, %g, %g) must be non-negative with a sum <= 1", p_x, p_y, p_z);
     if (code == QECMC_TORIC && !(p_x == p_y && p_y == p_z))
@@ -630,12 +453,7 @@ int qecmc_chain_update_xyz(int code, int L, uint64_t N, uint8_t *states_inout, c
     const double tot = (p_xyz[0] + p_xyz[1]) + p_xyz[2];
     if (!(p_xyz[0] > 0) || !(p_xyz[1] > 0) || !(p_xyz[2] > 0) || !(tot < 1.0)) return fail(QECMC_ERR_INVALID, "p_xyz=(%g,%g,%g) must be positive with a sum below 1", p_xyz[0], p_xyz[1], p_xyz[2]);
     if (slot >= 0x100u) return fail(QECMC_ERR_INVALID, "slot %u collides with the swap stream id", slot);
-    const double f[3] = {p_xyz[0] / (1.0 - tot), p_xyz[1] / (1.0 - tot), p_xyz[2] / (1.0 - tot)};          // mcmc.py:110
-    std::vector<uint64_t> thr(729);
-    for (int dx = -4; dx <= 4; ++dx)
-        for (int dy = -4; dy <= 4; ++dy)
-            for (int dz = -4; dz <= 4; ++dz)
-                thr[((dx + 4) * 9 + (dy + 4)) * 9 + (dz + 4)] = thr44((std::pow(f[0], (double)dx) * std::pow(f[1], (double)dy)) * std::pow(f[2], (double)dz));   // :170
+    const std::vector<uint64_t> thr = xyz_thresholds(p_xyz);          // mcmc.py:110,170
     ChainArgs a;
     std::memset(&a, 0, sizeof a);
     DevBuf dthr, dst;
@@ -653,17 +471,7 @@ int qecmc_chain_update_xyz(int code, int L, uint64_t N, uint8_t *states_inout, c
 // The step entry points' plan cache: keyed by the whole parameter block (the fields a plan does not depend on -- seed, first_syndrome,
 // steps -- are constant for one ladder anyway), a handful of entries, least recently used out first.  Plans are immutable once
 // built (a launch works on a copy of `args`), so concurrent callers may share one.
-// (the key: exactly the fields build_plan reads, in a zeroed struct -- not the caller's block with its padding, seed, first_syndrome
-// and step count, which would make a cache miss of every ladder with its own seed)
-static qecmc_params plan_key(const qecmc_params &p)
-{
-    qecmc_params k;
-    std::memset(&k, 0, sizeof k);
-    k.abi_size = p.abi_size; k.code = p.code; k.L = p.L; k.Nc = p.Nc; k.noise = p.noise; k.scan = p.scan; k.conv_mode = p.conv_mode; k.device = p.device;
-    k.iters = p.iters; k.tops_burn = p.tops_burn; k.TOPS = p.TOPS; k.SEQ = p.SEQ; k.replicas = p.replicas; k.eps = p.eps; k.p = p.p; k.eta = p.eta;
-    k.alpha = p.alpha; k.p_logical = p.p_logical; k.flags = p.flags;
-    return k;
-}
+// (the key: plan_key(), plan_host.hpp)
 static int cached_plan(const qecmc_params &pin, std::shared_ptr<const qecmc_plan> *out)
 {
     const qecmc_params p = plan_key(pin);
@@ -699,7 +507,7 @@ static int ladder_step_impl(const qecmc_params *params, uint64_t N, uint8_t *sta
     p.iters = iters;
     p.conv_mode = QECMC_CONV_NONE;
     p.replicas = 0;
-    if (int rc = validate_params(&p)) return rc;
+    if (int rc = report(validate_params(&p))) return rc;
     if (p.scan == QECMC_SCAN_COLOUR) return fail(QECMC_ERR_UNSUPPORTED, "scan = colour starts its ladders from seed configurations (qecmc_pteq_batch / qecmc_pteq_launch_dev)");
     if (!states_inout || !flags_inout || !tops0_inout) return fail(QECMC_ERR_INVALID, "NULL buffer");
     if ((p.noise == QECMC_NOISE_ALPHA) != (neff_inout != nullptr))
@@ -758,7 +566,7 @@ int qecmc_plan_create(const qecmc_params *params, qecmc_plan **plan_out)
 {
     if (!plan_out) return fail(QECMC_ERR_INVALID, "plan_out is NULL");
     *plan_out = nullptr;
-    if (int rc = validate_params(params)) return rc;
+    if (int rc = report(validate_params(params))) return rc;
     if (int rc = use_device(params->device)) return rc;
     qecmc_plan *pl = new (std::nothrow) qecmc_plan();
     if (!pl) return fail(QECMC_ERR_INVALID, "out of host memory");
@@ -791,43 +599,12 @@ int qecmc_plan_info(const qecmc_plan *plan, uint32_t *lds_bytes, uint32_t *block
     return 0;
 }
 
-// THE workspace formula of the criterion runs (the one place it lives): one log entry per (ladder step, column) -- the bottom chain's
-// error count (u16), or for alpha noise the two counts behind n_eff (2 x u16) -- with one column per ladder (rounded up to whole
-// 64-lane groups), or, when the launch runs on the plan's persistent grid with a work queue, one per lane of that grid.
-static bool launch_takes_queue(const qecmc_plan *plan, bool wants_states_or_stats)
-{
-    return plan->queue_grid != 0 && !wants_states_or_stats && plan->prm.steps > 0;
-}
-// the persistent grid a scan = wave criterion launch of M ladders runs on, and the ladders each of its workgroups owns
-static void wave_queue_shape(const qecmc_plan *plan, uint64_t M, uint32_t *grid, uint32_t *chunk)
-{
-    // (whole groups of 64 per workgroup: a batch that gives every ladder a lane of its own is laid out like a launch without the queue,
-    // ladder l in lane l & 63 of workgroup l >> 6, and gives the same results whatever the grid)
-    const uint64_t groups = (M + 63) / 64, g = std::max<uint64_t>(1, std::min<uint64_t>(plan->queue_grid, groups)), c = ((M + g - 1) / g + 63) / 64 * 64;
-    *chunk = (uint32_t)c;
-    *grid = (uint32_t)((M + c - 1) / c);
-}
-static uint64_t workspace_need(const qecmc_plan *plan, uint64_t N, bool queue)
-{
-    if (plan->prm.conv_mode != QECMC_CONV_ERROR_BASED) return 0;
-    const uint64_t M = N * plan->args.replicas;
-    uint64_t cols = (M + 63) / 64 * 64;
-    if (queue && plan->args.scan == QECMC_SCAN_WAVE) {
-        uint32_t grid, chunk;
-        wave_queue_shape(plan, M, &grid, &chunk);
-        cols = (uint64_t)grid * 64u;
-    } else if (queue) {
-        cols = std::min<uint64_t>(cols, (uint64_t)plan->queue_grid * 64u);
-    }
-    return (plan->prm.noise == QECMC_NOISE_ALPHA ? 4ull : 2ull) * cols * plan->prm.steps;
-}
-
 int qecmc_plan_workspace_bytes(const qecmc_plan *plan, uint64_t N, int with_final_states, uint64_t *bytes_out)
 {
     if (!plan || !bytes_out) return fail(QECMC_ERR_INVALID, "NULL argument");
     // what qecmc_pteq_launch_dev(plan, N syndromes, d_final_states given or not) will ask for: a launch that may take the plan's work
     // queue logs one column per lane of the persistent grid, any other one column per ladder
-    *bytes_out = workspace_need(plan, N, launch_takes_queue(plan, with_final_states != 0 || plan->d_swap_acc != nullptr));
+    *bytes_out = plan->workspace(N, plan->takes_queue(with_final_states != 0 || plan->d_swap_acc != nullptr));
     return 0;
 }
 
@@ -842,9 +619,9 @@ int qecmc_pteq_launch_dev(qecmc_plan *plan, const void *d_init, uint64_t N, uint
     if (M + first_syndrome > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "global ladder index (first_syndrome + N * replicas) exceeds 32 bits");
     if (plan->args.scan == QECMC_SCAN_WAVE && (first_syndrome & 63u))
         return fail(QECMC_ERR_INVALID, "scan = wave: first_syndrome=%u must be a multiple of 64 (a wavefront shares its generator picks)", first_syndrome);
-    const bool takes_queue = launch_takes_queue(plan, plan->d_swap_acc != nullptr || d_final_states != nullptr);
+    const bool takes_queue = plan->takes_queue(plan->d_swap_acc != nullptr || d_final_states != nullptr);
     {
-        const uint64_t need = workspace_need(plan, N, takes_queue);
+        const uint64_t need = plan->workspace(N, takes_queue);
         if (need && !d_workspace) return fail(QECMC_ERR_INVALID, "conv_mode error_based needs the workspace of qecmc_plan_workspace_bytes()");
         if (workspace_bytes < need)
             return fail(QECMC_ERR_INVALID, "workspace of %llu bytes, this launch logs %llu (qecmc_plan_workspace_bytes: 2 or 4 bytes per ladder step and column)",
@@ -881,7 +658,7 @@ int qecmc_pteq_launch_dev(qecmc_plan *plan, const void *d_init, uint64_t N, uint
                     "states or per-ladder statistics with conv_mode error_based (and steps must be > 0)");
     if (takes_queue && plan->args.scan == QECMC_SCAN_WAVE) {
         // (the workgroups of the persistent grid own contiguous shares of the batch: no global counter)
-        wave_queue_shape(plan, M, &a.grid_cap, &a.wu_chunk);
+        wave_queue_shape(plan->queue_grid, M, &a.grid_cap, &a.wu_chunk);
     } else if (takes_queue) {
         // (one launch at a time per plan: the counter belongs to the plan)
         HIP_TRY(hipMemsetAsync(plan->queue.p, 0, sizeof(uint32_t), strm));
@@ -949,7 +726,7 @@ int qecmc_pteq_batch_stats(const qecmc_params *params, const uint8_t *init, uint
     if (!init || !counts_out || !samples_out) return fail(QECMC_ERR_INVALID, "NULL buffer");
     const size_t nq = pl->args.nq, Nc = pl->args.Nc, ncls = pl->args.ncls, R = pl->args.replicas;
     // (the work-queue kernels log one column per lane of the persistent grid, not per ladder: workspace_need knows)
-    const uint64_t ws_bytes = workspace_need(pl, N, launch_takes_queue(pl, swap_accepts_out || nerr_sums_out || final_states_out));
+    const uint64_t ws_bytes = pl->workspace(N, pl->takes_queue(swap_accepts_out || nerr_sums_out || final_states_out));
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     if (ws_bytes > free_b / 2)
@@ -967,17 +744,13 @@ int qecmc_pteq_batch_stats(const qecmc_params *params, const uint8_t *init, uint
         if (int rc = qecmc_plan_set_stats(pl, dsa.p, nerr_sums_out ? dns.p : nullptr)) return rc;
     }
     HIP_TRY(hipMemcpy(di.p, init, N * nq, hipMemcpyHostToDevice));
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, 0));
+    EventTimer timer;
+    HIP_TRY(timer.start());
     int rc = qecmc_pteq_launch_dev(pl, di.p, N, params->first_syndrome, dc.p, ds.p, dt.p, dsd.p, dcv.p,
                                    final_states_out ? df.p : nullptr, ws_bytes ? dw.p : nullptr, ws_bytes, nullptr);
-    if (rc) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return rc; }
-    HIP_TRY(hipEventRecord(e1, 0));
-    HIP_TRY(hipEventSynchronize(e1));
+    if (rc) return rc;
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    HIP_TRY(timer.stop(&ms));
     HIP_TRY(hipMemcpy(counts_out, dc.p, N * ncls * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(samples_out, ds.p, N * 4, hipMemcpyDeviceToHost));
     if (tops0_out) HIP_TRY(hipMemcpy(tops0_out, dt.p, N * 4, hipMemcpyDeviceToHost));
@@ -1026,14 +799,7 @@ int qecmc_ptdc_batch_xyz(const qecmc_params *params, const uint8_t *init, uint64
         if (!(q[0] > 0) || !(q[1] > 0) || !(q[2] > 0) || !(tot < 1.0)) return fail(QECMC_ERR_INVALID, "p_xyz_sampling=(%g,%g,%g) must be positive with a sum below 1", q[0], q[1], q[2]);
         if (p.Nc != 1) return fail(QECMC_ERR_INVALID, "Chain_xyz is a single chain (mcmc.py:106): Nc=%d must be 1", p.Nc);
         if (p.code == QECMC_TORIC) return fail(QECMC_ERR_UNSUPPORTED, "Chain_xyz is built for the planar, xzzx and rotated codes (the reference's runs the planar stencil, mcmc.py:164)");
-        const double f[3] = {q[0] / (1.0 - tot), q[1] / (1.0 - tot), q[2] / (1.0 - tot)};
-        xyz_thr.resize(729);
-        for (int dx = -4; dx <= 4; ++dx)
-            for (int dy = -4; dy <= 4; ++dy)
-                for (int dz = -4; dz <= 4; ++dz) {
-                    const double w = (std::pow(f[0], (double)dx) * std::pow(f[1], (double)dy)) * std::pow(f[2], (double)dz);
-                    xyz_thr[((dx + 4) * 9 + (dy + 4)) * 9 + (dz + 4)] = thr44(w);      // u < w  <=>  v44 < ceil(w 2^44)
-                }
+        xyz_thr = xyz_thresholds(q);
         p.p = tot <= 0.75 ? tot : 0.75;                                           // unused by the rule; keeps the plan's tables valid
     }
     if (p.noise == QECMC_NOISE_ALPHA) {
@@ -1088,9 +854,8 @@ int qecmc_ptdc_batch_xyz(const qecmc_params *params, const uint8_t *init, uint64
     if (m_out) { HIP_TRY(dm.alloc(sets * (nq + 1) * 4)); HIP_TRY(hipMemset(dm.p, 0, sets * (nq + 1) * 4)); }
     HIP_TRY(hipMemcpy(ds.p, st.data(), st.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(dtab.p, 0, sets * cap * 8)); HIP_TRY(hipMemset(dh.p, 0, sets * (nq + 1) * 4));
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, 0));
+    EventTimer timer;
+    HIP_TRY(timer.start());
     // ONE launch: the ladder kernel inserts every rung's configuration into its set after every step (USET instantiation)
     LadderArgs a = pl->args;
     a.init = ds.as<uint8_t>();
@@ -1103,13 +868,10 @@ int qecmc_ptdc_batch_xyz(const qecmc_params *params, const uint8_t *init, uint64
     a.xyz_thr = xyz_thr.empty() ? nullptr : dthr.as<uint64_t>();
     {
         const hipError_t e = launch_ladder(a, 0);
-        if (e != hipSuccess) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); return fail(QECMC_ERR_HIP, "PTDC launch: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) return fail(QECMC_ERR_HIP, "PTDC launch: %s", hipGetErrorString(e));
     }
-    HIP_TRY(hipEventRecord(e1, 0));
-    HIP_TRY(hipEventSynchronize(e1));
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    HIP_TRY(timer.stop(&ms));
     HIP_TRY(hipMemcpy(hist_out, dh.p, sets * (nq + 1) * 4, hipMemcpyDeviceToHost));
     if (m_out) HIP_TRY(hipMemcpy(m_out, dm.p, sets * (nq + 1) * 4, hipMemcpyDeviceToHost));
     if (steps_done_out) HIP_TRY(hipMemcpy(steps_done_out, dsd.p, M * 4, hipMemcpyDeviceToHost));

@@ -105,8 +105,8 @@ __host__ __device__ inline WuLds wu_lds(int Nc, int W, int ncls, int L, bool con
 }
 inline size_t wu_lds_bytes(int Nc, int W, int ncls, int L, bool conv, bool alpha) { return sizeof(uint32_t) * (size_t)wu_lds(Nc, W, ncls, L, conv, alpha).total; }
 
-// What the choice reads of a launch (kernel_shape(LadderArgs), ladder_rs.hip).  top_acc / lower_acc: the top rung / some rung below it accepts every
-// proposal (acc_all_mask); logical: thr_logical != 0; queue: a work queue is offered (a.queue; build_plan asks with 1 whether a plan takes one);
+// What the choice reads of a launch (kernel_shape(LadderArgs), plan_host.hpp).  top_acc / lower_acc: the top rung / some rung below it accepts every
+// proposal (acc_all_mask); logical: thr_logical != 0; queue: a work queue is offered (a.queue; plan_host() asks with 1 whether a plan takes one);
 // uset / xyz / stats / neff: a.uset_tab / a.xyz_thr / a.swap_acc / a.neff given; f32ok: every rung below the top may take the single-precision
 // acceptance estimate (bias_f32ok); tune: the developer bits of qecmc_params.flags (include/qecmc.h qecmc_flag)
 struct KernelShape {

@@ -100,8 +100,7 @@ struct LadderArgs {
     uint32_t *nerr_sum;       // [N][Nc]
 };
 
-hipError_t launch_ladder(const LadderArgs &a, hipStream_t stream);     // ladder_rs.hip: the kernel choose_kernel() picks, on its grid
-KernelShape kernel_shape(const LadderArgs &a);                        // ... what the choice reads of a launch
+hipError_t launch_ladder(const LadderArgs &a, hipStream_t stream);     // ladder_rs.hip: the kernel choose_kernel() picks for kernel_shape(a) (plan_host.hpp), on its grid
 // the instantiation units, one per kernel family (built in parallel): the kernel of `k` if the unit builds it, else nullptr -- ladder_kernel
 // (ladder_{toric,surf,biased,sweep,uset}.hip), ladder_colour_kernel (ladder_colour.hip), ladder_wu_kernel (ladder_wu{,_xzzx,_rotated,_planar,_alpha}.hip)
 const void *ladder_toric_kernel(const KernelKey &), *ladder_surf_kernel(const KernelKey &), *ladder_biased_kernel(const KernelKey &),

@@ -2,17 +2,9 @@
 // (ladder_toric / ladder_surf / ladder_biased / ladder_sweep / ladder_uset / ladder_colour / ladder_wu*.hip, built in parallel) hold it,
 // and the launch runs it on the grid its family implies.  A key no unit holds is an error, never a neighbouring kernel.
 #include "kernels.hpp"
+#include "plan_host.hpp"   // kernel_shape(): what the choice reads of a launch
 
 namespace qecmc {
-
-KernelShape kernel_shape(const LadderArgs &a)
-{
-    const uint32_t lower = (1u << (a.Nc - 1)) - 1u;      // rungs below the top
-    return {a.code, a.noise, a.scan, a.L, a.Nc, a.W, a.nq, a.ncls, (int)a.n_gen, a.n_types, a.gen_type != nullptr, (int)((a.acc_all_mask >> (a.Nc - 1)) & 1u),
-            (a.acc_all_mask & lower) != 0, a.thr_logical != 0, a.conv_mode != 0, a.queue != nullptr, a.uset_tab != nullptr, a.xyz_thr != nullptr,
-            a.swap_acc != nullptr, a.resume != 0, a.neff != nullptr, (a.bias_f32ok & lower) == lower, a.swap_fast_ok != 0,
-            a.iters > 0x7FFFFFFFu ? 0x7FFFFFFF : (int)a.iters, (int)a.tune};
-}
 
 namespace {
 

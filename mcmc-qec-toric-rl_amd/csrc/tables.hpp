@@ -67,6 +67,20 @@ inline uint32_t thr32(double v)
     return t > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)t;
 }
 
+// Chain_xyz (mcmc.py:106-114,162-173): factors = p_xyz / (1 - p_xyz.sum()), accept iff u < (factors ** change).prod() -- as integers,
+// v44 < ceil(w 2^44) -- for the changes (dx, dy, dz) of a proposal, each in -4 .. 4: [9][9][9]
+inline std::vector<uint64_t> xyz_thresholds(const double p_xyz[3])
+{
+    const double tot = (p_xyz[0] + p_xyz[1]) + p_xyz[2];
+    const double f[3] = {p_xyz[0] / (1.0 - tot), p_xyz[1] / (1.0 - tot), p_xyz[2] / (1.0 - tot)};
+    std::vector<uint64_t> thr(729);
+    for (int dx = -4; dx <= 4; ++dx)
+        for (int dy = -4; dy <= 4; ++dy)
+            for (int dz = -4; dz <= 4; ++dz)
+                thr[((dx + 4) * 9 + (dy + 4)) * 9 + (dz + 4)] = thr44((std::pow(f[0], (double)dx) * std::pow(f[1], (double)dy)) * std::pow(f[2], (double)dz));
+    return thr;
+}
+
 // np.linspace(p_bottom, p_top, Nc) and Ladder.p_diff (src/mcmc.py:65,69)
 inline void ladder_probabilities(double p_bottom, double p_top, int Nc, std::vector<double> &pl, std::vector<double> &pd)
 {

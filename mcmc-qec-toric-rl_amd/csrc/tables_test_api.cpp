@@ -1,10 +1,13 @@
 // C test API over the host-side table builders (tables.hpp), compiled ALONE by g++ -- no HIP runtime, no device -- with
 // -fsanitize=address,undefined (make tables_asan) or plainly (make tables): tests/test_host_tables.py checks every table the
 // plan precomputes for the kernels against values the CPU oracle computes; tests/test_kernel_choice.py asks choose_kernel()
-// (kernel_choice.hpp) which kernel every shape runs.  Not part of libqecmc.so.
+// (kernel_choice.hpp) which kernel every shape runs, and plan_host() (plan_host.hpp) which plan -- or which refusal -- a parameter block gets.
+// Not part of libqecmc.so.
 #include "kernel_choice.hpp"
+#include "plan_host.hpp"
 #include "tables.hpp"
 
+#include <cstdio>
 #include <cstring>
 
 using namespace qecmc;
@@ -16,6 +19,12 @@ template <class T> int put(const std::vector<T> &v, T *out, int cap)
     if ((int)v.size() > cap) return -(int)v.size();
     std::memcpy(out, v.data(), v.size() * sizeof(T));
     return (int)v.size();
+}
+int answer(const Refusal &r, const KernelShape &s, int32_t *shape_ints, char *msg, int msg_cap)
+{
+    if (msg && msg_cap > 0) std::snprintf(msg, (size_t)msg_cap, "%s", r.msg.c_str());
+    if (!r.code && shape_ints) std::memcpy(shape_ints, &s, sizeof s);
+    return r.code;
 }
 std::vector<uint32_t> gen_table(int code, int L) { return code == QECMC_TORIC ? toric_generator_table(L) : surf_generator_table(code, L); }
 }  // namespace
@@ -75,4 +84,45 @@ void qt_choose_kernels(const KernelShape *shapes, int n, int64_t *keys)
     }
 }
 int qt_kernel_shape_ints(void) { return (int)(sizeof(KernelShape) / sizeof(int)); }
+// validate_params(), then the first phase of plan_host(): the QECMC_ERR_* code and message; accepted: the shape's static fields (the others 0)
+int qt_plan_dims(const qecmc_params *p, int32_t *shape_ints, char *msg, int msg_cap)
+{
+    HostPlan hp;
+    Refusal r = validate_params(p);
+    if (!r.code) r = plan_dims(*p, hp);
+    KernelShape s = {};
+    if (!r.code) {
+        s = kernel_shape(hp.args);
+        s.gen_type = !hp.gen_type.empty();
+    }
+    return answer(r, s, shape_ints, msg, msg_cap);
+}
+// validate_params(), then plan_host(): accepted, the plan's shape, LDS bytes and persistent grid on a device of cu_count CUs
+int qt_plan(const qecmc_params *p, int cu_count, int32_t *shape_ints, uint64_t *lds_bytes, uint32_t *grid, char *msg, int msg_cap)
+{
+    HostPlan hp;
+    Refusal r = validate_params(p);
+    if (!r.code) r = plan_host(*p, hp);
+    if (!r.code) { *lds_bytes = hp.lds_bytes; *grid = queue_grid(hp, cu_count, p->flags); }
+    return answer(r, hp.shape, shape_ints, msg, msg_cap);
+}
+int qt_plan_key_equal(const qecmc_params *a, const qecmc_params *b)
+{
+    const qecmc_params ka = plan_key(*a), kb = plan_key(*b);
+    return std::memcmp(&ka, &kb, sizeof ka) == 0;
+}
+// 1: the host plans of two accepted blocks are the same -- every table, lds_bytes, shape, queue fields, and args apart from the seed words
+// (which a launch through the plan cache patches, see plan_key) --, 0: they differ, -1: a block is refused
+int qt_plan_equal(const qecmc_params *pa, const qecmc_params *pb)
+{
+    HostPlan a, b;
+    if (validate_params(pa).code || validate_params(pb).code || plan_host(*pa, a).code || plan_host(*pb, b).code) return -1;
+    a.args.seed_lo = a.args.seed_hi = b.args.seed_lo = b.args.seed_hi = 0;
+    return std::memcmp(&a.args, &b.args, sizeof a.args) == 0 && a.gen == b.gen && a.xyz_lut == b.xyz_lut && a.wu_desc == b.wu_desc && a.col_thr == b.col_thr &&
+           a.lmask == b.lmask && a.acc_top == b.acc_top && a.gen_type == b.gen_type && a.phases == b.phases && a.bias == b.bias && a.lnb == b.lnb &&
+           a.swap_thr == b.swap_thr && same_shape(a.shape, b.shape) && a.lds_bytes == b.lds_bytes && a.takes_queue == b.takes_queue &&
+           a.queue_family == b.queue_family && a.queue_per_cu == b.queue_per_cu;
+}
+uint64_t qt_workspace_need(const qecmc_params *p, uint32_t grid, uint64_t N, int queue) { return workspace_need(*p, grid, N, queue != 0); }
+int qt_launch_takes_queue(uint32_t grid, uint64_t steps, int wants_states_or_stats) { return launch_takes_queue(grid, steps, wants_states_or_stats != 0); }
 }

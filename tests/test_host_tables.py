@@ -1,11 +1,13 @@
 """The host side of libqecmc under test and under sanitizers (SURVEY.md 5 "-fsanitize=address on host lib"):
 every table the plan precomputes for the kernels -- generator tables, logical-operator masks, acceptance / swap thresholds,
 ladder temperatures, the biased rules' power and count-change tables, the colour phases of scan = 2 -- is built by
-csrc/tables.hpp, compiled here ALONE by g++ (no HIP, no GPU) and compared with values the oracle computes.  The last test
+csrc/tables.hpp and put together into a plan by csrc/plan_host.hpp, both compiled here ALONE by g++ (no HIP, no GPU); the tables are
+compared with values the oracle computes.  The last test
 re-runs this file in a child process against the -fsanitize=address,undefined build."""
 import ctypes as C
 import math
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -14,6 +16,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
+from qecmc import _lib as L_
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mcmc-qec-toric-rl_amd", "csrc")
@@ -33,6 +36,9 @@ def T():
     lib.qt_thr44.restype = C.c_uint64; lib.qt_thr44.argtypes = [C.c_double]
     lib.qt_thr32.restype = C.c_uint32; lib.qt_thr32.argtypes = [C.c_double]
     lib.qt_chain_factor.restype = C.c_double; lib.qt_chain_factor.argtypes = [C.c_double]
+    lib.qt_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
+    lib.qt_plan_key_equal.argtypes = lib.qt_plan_equal.argtypes = [C.c_void_p, C.c_void_p]
+    lib.qt_workspace_need.restype = C.c_uint64; lib.qt_workspace_need.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_int]
     return lib
 
 
@@ -231,6 +237,101 @@ def test_wave_descriptors_are_the_oracles_stencil(T, code, L):
         dz = int(np.sum(ref == 3)) - int(np.sum(m == 3))
         dxy = int(np.sum((ref == 1) | (ref == 2))) - int(np.sum((m == 1) | (m == 2)))
         assert off == 4 * ((dz + 4) + 9 * (dxy + 4))
+
+
+def _params(**kw):
+    return L_.make_params(**dict(dict(p=0.1, eta=3.0, alpha=1.5, iters=10, steps=10, p_logical=0.5), **kw))
+
+
+def _plan(T, pr, cu_count=256):
+    """validate_params() and plan_host() (csrc/plan_host.hpp): rc, message, the plan's kernel shape, lds_bytes, the persistent grid"""
+    shape, msg, lds, grid = np.zeros(25, np.int32), C.create_string_buffer(600), C.c_uint64(), C.c_uint32()
+    rc = T.qt_plan(C.byref(pr), cu_count, shape.ctypes.data, C.byref(lds), C.byref(grid), msg, len(msg))
+    return rc, msg.value.decode(), shape, lds.value, grid.value
+
+
+@pytest.mark.parametrize("code,L", SHAPES)
+def test_plan_host_answers_every_block(T, code, L):
+    """every rule, scan and ladder length: a plan, or a refusal with its code and a message"""
+    plans = 0
+    for noise, scan, Nc, conv in [(n, s, c, v) for n in range(3) for s in range(4) for c in (1, 2, 8, 16) for v in (0, 1)]:
+        rc, msg, shape, lds, grid = _plan(T, _params(code=code, L=L, noise=noise, scan=scan, Nc=Nc, conv_mode=conv))
+        assert rc in (0, -1, -4) and (rc == 0) == (msg == ""), (noise, scan, Nc, conv, rc, msg)
+        if rc == 0:
+            plans += 1
+            assert 0 < lds <= 160 * 1024 and list(shape[:5]) == [code, noise, scan, L, Nc] and shape[6] == _nq(code, L)
+            assert grid == 0 or conv
+    assert plans >= 20
+
+
+# the refusals of plan_host() that parameter blocks reach (validate_params() accepts each of these blocks), in the words they always had
+@pytest.mark.parametrize("kw,text", [
+    (dict(code=TORIC, L=33), "L=33: 2178 generators exceed the LDS table of 2048 (needed by scan=1 and by the xzzx / rotated codes)"),
+    (dict(code=XZZX, L=23, noise=1), "biased / alpha noise packs the error counts in 10-bit fields: nq=529"),
+    (dict(code=ROTATED, L=23, noise=2, scan=3, Nc=2), "biased / alpha noise packs the error counts in 10-bit fields: nq=529"),
+    (dict(code=TORIC, L=32, Nc=16), "L=32 Nc=16 needs # B of LDS per workgroup (> 160 KiB)"),
+    (dict(code=TORIC, L=32, Nc=16, scan=2), "scan = colour: L=32 Nc=16 needs # B of LDS per workgroup (> 160 KiB)"),
+    (dict(code=XZZX, L=5, Nc=2, noise=1, scan=2, p=1e-100), "scan = colour: an acceptance ratio of rung 0 underflows"),
+    (dict(code=TORIC, L=17, Nc=4, scan=3),
+     "scan = wave: L=17 Nc=4 p=0.1 is outside what it is built for (depolarizing rule: a top rung that accepts every move, at most 16 packed state "
+     "words per rung -- toric / planar L <= 11, xzzx / rotated L <= 16 --, fixed-length runs of up to 8 rungs 32 words -- toric L <= 16, xzzx / "
+     "rotated L <= 22; alpha rule: xzzx / rotated L <= 11, 4 iters max|log2 ratio| <= 2000 --, # B of LDS)"),
+])
+def test_plan_refusals_keep_their_words(T, kw, text):
+    rc, msg, _, _, _ = _plan(T, _params(**kw))
+    rx = re.escape(text).replace(re.escape("#"), r"\d+")       # (#: a byte count; everything else to the letter)
+    assert rc == -4 and re.fullmatch(rx, msg), msg
+
+
+PLANS = [dict(code=TORIC, L=5, Nc=5), dict(code=XZZX, L=5, Nc=3, noise=1), dict(code=ROTATED, L=5, Nc=4, noise=2, scan=3, conv_mode=1),
+         dict(code=XZZX, L=5, Nc=3, noise=2, scan=2), dict(code=PLANAR, L=4, Nc=8, scan=1)]
+
+
+@pytest.mark.parametrize("kw", PLANS)
+def test_plan_key_drops_what_no_plan_depends_on(T, kw):
+    """blocks that differ in seed, first_syndrome or steps share a key and a host plan (tables, scalars, lds_bytes, shape, queue; the seed itself,
+    which plan_host() copies into the launch arguments and the cached step path patches per call, set aside)"""
+    a = _params(**kw)
+    for other in (dict(seed=7), dict(first_syndrome=128), dict(steps=99), dict(seed=2 ** 40 + 3, first_syndrome=64, steps=1)):
+        b = _params(**dict(kw, **other))
+        assert T.qt_plan_key_equal(C.byref(a), C.byref(b)) == 1 and T.qt_plan_equal(C.byref(a), C.byref(b)) == 1, other
+
+
+@pytest.mark.parametrize("field,base,other", [
+    ("code", dict(code=TORIC, L=5), PLANAR), ("L", dict(L=5), 6), ("Nc", dict(L=5), 6), ("noise", dict(code=XZZX, L=5), 1), ("scan", dict(L=5), 1),
+    ("conv_mode", dict(L=5), 1), ("iters", dict(L=5), 11), ("tops_burn", dict(L=5), 3), ("TOPS", dict(L=5), 11), ("SEQ", dict(L=5), 3),
+    ("replicas", dict(L=5), 2), ("eps", dict(L=5), 0.2), ("p", dict(L=5), 0.11), ("eta", dict(code=XZZX, L=5, noise=1), 4.0),
+    ("alpha", dict(code=XZZX, L=5, noise=2), 1.6), ("p_logical", dict(L=5), 0.4), ("flags", dict(L=5), 2), ("device", dict(L=5), 1)])
+def test_plan_key_keeps_what_a_plan_depends_on(T, field, base, other):
+    """each field of the key: two accepted blocks that differ in it have different keys -- and different host plans, but for the device, which only
+    says where the tables go"""
+    a, b = _params(Nc=5, **base), _params(**dict(dict(Nc=5, **base), **{field: other}))
+    assert T.qt_plan_key_equal(C.byref(a), C.byref(a)) == 1 and T.qt_plan_key_equal(C.byref(a), C.byref(b)) == 0
+    assert T.qt_plan_equal(C.byref(a), C.byref(b)) == (1 if field == "device" else 0)
+
+
+@pytest.mark.parametrize("kw", [dict(code=TORIC, L=9, Nc=8), dict(code=XZZX, L=5, Nc=5, noise=2),
+                                dict(code=TORIC, L=9, Nc=8, scan=3), dict(code=XZZX, L=5, Nc=5, noise=2, scan=3)])
+def test_workspace_need_is_its_closed_form(T, kw):
+    """2 bytes (alpha: 4) per ladder step and column; a column per ladder, rounded up to whole groups of 64 -- with the work queue, a column per lane
+    of the persistent grid: the ladder family's grid, capped by the batch; scan = wave's as many workgroups as own a whole number of 64-ladder
+    groups each"""
+    steps = 37
+    rc, msg, _, _, grid = _plan(T, _params(conv_mode=1, steps=steps, **kw))
+    assert rc == 0 and grid > 0, msg
+    up64 = lambda v: (v + 63) // 64 * 64
+    for replicas, N, queue in [(r, n, q) for r in (1, 3) for n in (1, 64, 1000, 65536) for q in (0, 1)]:
+        M = N * replicas
+        cols = up64(M)
+        if queue and kw.get("scan") == 3:
+            g = max(1, min(grid, up64(M) // 64))
+            chunk = up64(-(-M // g))
+            cols = -(-M // chunk) * 64
+        elif queue:
+            cols = min(cols, grid * 64)
+        pr = _params(conv_mode=1, steps=steps, replicas=replicas, **kw)
+        assert T.qt_workspace_need(C.byref(pr), grid, N, queue) == (4 if kw.get("noise") == 2 else 2) * cols * steps, (replicas, N, queue)
+        assert T.qt_workspace_need(C.byref(_params(steps=steps, replicas=replicas, **kw)), grid, N, queue) == 0       # fixed-length runs log nothing
 
 
 def test_host_tables_under_asan_ubsan():

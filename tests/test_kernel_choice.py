@@ -1,11 +1,13 @@
 """Which kernel every launch runs, on the CPU: csrc/kernel_choice.hpp choose_kernel(), compiled alone by g++ (make tables), over every
-shape the C-ABI accepts -- each code over its supported L, Nc = 1 .. 16, every noise / scan / conv / queue / stats / uset / resume
+shape the C-ABI accepts -- each code, rule and scan over the L of which validate_params() and plan_host() (csrc/plan_host.hpp, asked with real
+parameter blocks) make plans, Nc = 1 .. 16, every noise / scan / conv / queue / stats / uset / resume
 combination a plan or a launch can present, the temperature ladders' accept-all and swap-threshold bits, iters 10 / another one within
 and one beyond what scan = wave is built for, and all 8 combinations of the developer bits the choice reads.
 
   (a) every kernel chosen is built (csrc/build/*.res), and the shapes no kernel is built for are refused for a named reason;
   (b) every ladder / wave / colour kernel in the build is chosen by at least one shape (what none chooses is not built);
-  (c) the kernels of BASELINE configurations 2-5 at the shapes `bench.py --config N` resolves to by default."""
+  (c) the kernels of BASELINE configurations 2-5 at the shapes `bench.py --config N` resolves to by default;
+  (d) what plan_host() itself says of the sweep: which of its blocks get no plan and why, the ladders its plans present, the persistent grid."""
 import ctypes as C
 import importlib.util
 import itertools
@@ -15,6 +17,8 @@ import subprocess
 
 import numpy as np
 import pytest
+
+from qecmc import _lib as L_
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mcmc-qec-toric-rl_amd", "csrc")
@@ -56,6 +60,8 @@ def T():
     lib = C.CDLL(path)
     assert lib.qt_kernel_shape_ints() == len(FIELDS)
     lib.qt_choose_kernels.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.qt_plan_dims.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
+    lib.qt_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
     return lib
 
 
@@ -82,31 +88,39 @@ def choose(T, shapes):
     return {label(keys[i]): int(n) for i, n in zip(first, counts)}
 
 
-def patterns(T, code, L):
-    gt, pat = (C.c_uint8 * 8192)(), (C.c_uint32 * 64)()
-    return T.qt_patterns(code, L, gt, 8192, pat, 64)
+def params(**kw):
+    """a real parameter block (qecmc_params): p, eta and alpha inside every rule's range unless given"""
+    return L_.make_params(**dict(dict(p=0.1, eta=3.0, alpha=1.5, iters=10, steps=10), **kw))
 
 
-def supported_L(code):
-    # check_code_L (capi.hip) and the LDS generator table of at most 2 048 entries
-    return range(2, 33) if code in (TORIC, PLANAR) else range(3, 46, 2)
+def plan_dims(T, pr):
+    """validate_params() and the first phase of plan_host() (csrc/plan_host.hpp) on a parameter block: (rc, message, the shape's static fields)"""
+    shape, msg = np.zeros(len(FIELDS), dtype=np.int32), C.create_string_buffer(600)
+    rc = T.qt_plan_dims(C.byref(pr), shape.ctypes.data, msg, len(msg))
+    return rc, msg.value.decode(), dict(zip(FIELDS, (int(x) for x in shape)))
+
+
+def plan(T, pr, cu_count=1):
+    """validate_params() and plan_host() on a parameter block: (rc, message, the plan's shape, lds_bytes, the persistent grid on cu_count CUs)"""
+    shape, msg, lds, grid = np.zeros(len(FIELDS), dtype=np.int32), C.create_string_buffer(600), C.c_uint64(), C.c_uint32()
+    rc = T.qt_plan(C.byref(pr), cu_count, shape.ctypes.data, C.byref(lds), C.byref(grid), msg, len(msg))
+    return rc, msg.value.decode(), dict(zip(FIELDS, (int(x) for x in shape))), lds.value, grid.value
 
 
 def code_shape(T, code, L, noise, scan):
-    nq = 2 * L * L if code in (TORIC, PLANAR) else L * L
-    n_gen = 2 * L * L if code == TORIC else 2 * L * (L - 1) if code == PLANAR else L * L - 1
-    typed = noise != 0 or (code != TORIC and scan == 0)              # build_plan: the generators' Pauli patterns
-    return dict(code=code, noise=noise, scan=scan, L=L, W=(nq + 15) // 16, nq=nq, ncls=16 if code == TORIC else 4, n_gen=n_gen,
-                n_types=patterns(T, code, L) if typed else 0, gen_type=int(typed))
+    """the static fields of the shape of the plans of (code, L, rule, scan), or None where the library makes no plan of them: validate_params()
+    refuses the block (asked with a two-rung ladder without logical moves, which no rule about Nc or p_logical objects to) or the generator
+    table exceeds its LDS bound"""
+    rc, _, dims = plan_dims(T, params(code=code, L=L, Nc=2, noise=noise, scan=scan))
+    return None if rc else {f: dims[f] for f in ("code", "noise", "scan", "L", "W", "nq", "ncls", "n_gen", "n_types", "gen_type")}
 
 
-def rule_scans():
-    # validate_params: the biased rule on scan = 0 / colour, the alpha rule also on scan = wave; both on the xzzx / rotated codes only
-    for code in range(4):
-        for noise in ((0, 1, 2) if code in (XZZX, ROTATED) else (0,)):
-            for scan in range(4):
-                if noise == 0 or scan in (0, 2) or (scan == 3 and noise == 2):
-                    yield code, noise, scan
+def blocks(T):
+    """the static shape fields of every code, rule, scan and L the library makes plans of"""
+    for code, noise, scan, L in itertools.product(range(4), range(3), range(4), range(0, 70)):
+        base = code_shape(T, code, L, noise, scan)
+        if base is not None:
+            yield base
 
 
 def launch_modes(scan):
@@ -133,17 +147,15 @@ def ladders(noise, scan, Nc):
 
 def all_shapes(T):
     """every shape, in blocks of one code, L, rule and scan"""
-    for code, noise, scan in rule_scans():
-        for L in supported_L(code):
-            base = code_shape(T, code, L, noise, scan)
-            rows = []
-            for Nc in range(1, 17):
-                for (top, lower, sfo, f32), (conv, queue, uset, xyz, stats, resume), logical, iters, tune in itertools.product(
-                        ladders(noise, scan, Nc), launch_modes(scan), (0, 1), (10, 7, 200), range(0, 16, 2)):
-                    s = dict(base, Nc=Nc, top_acc=top, lower_acc=lower, swap_fast_ok=sfo, f32ok=f32, conv=conv, queue=queue, uset=uset, xyz=xyz,
-                             stats=stats, resume=resume, neff=int(resume and noise == 2), logical=logical, iters=iters, tune=tune)
-                    rows.append([s[f] for f in FIELDS])
-            yield np.array(rows, dtype=np.int32)
+    for base in blocks(T):
+        noise, scan, rows = base["noise"], base["scan"], []
+        for Nc in range(1, 17):
+            for (top, lower, sfo, f32), (conv, queue, uset, xyz, stats, resume), logical, iters, tune in itertools.product(
+                    ladders(noise, scan, Nc), launch_modes(scan), (0, 1), (10, 7, 200), range(0, 16, 2)):
+                s = dict(base, Nc=Nc, top_acc=top, lower_acc=lower, swap_fast_ok=sfo, f32ok=f32, conv=conv, queue=queue, uset=uset, xyz=xyz,
+                         stats=stats, resume=resume, neff=int(resume and noise == 2), logical=logical, iters=iters, tune=tune)
+                rows.append([s[f] for f in FIELDS])
+        yield np.array(rows, dtype=np.int32)
 
 
 def built_kernels():
@@ -164,13 +176,75 @@ def built_kernels():
 
 
 @pytest.fixture(scope="module")
-def chosen(T):
-    """label -> number of shapes that choose it ("refused: why" for the shapes without a kernel)"""
-    seen = {}
+def sweep(T):
+    """one pass over all_shapes(): label -> number of shapes that choose it ("refused: why" for the shapes without a kernel), and the pass's size"""
+    seen, n_blocks = {}, 0
     for block in all_shapes(T):
+        n_blocks += 1
         for lab, n in choose(T, block).items():
             seen[lab] = seen.get(lab, 0) + n
-    return seen
+    return dict(chosen=seen, shapes=sum(seen.values()), blocks=n_blocks)
+
+
+@pytest.fixture(scope="module")
+def chosen(sweep):
+    return sweep["chosen"]
+
+
+def test_the_sweep_is_as_large_as_it_was(sweep):
+    # what all_shapes() yielded while it restated validate_params and build_plan in Python: taking the enumeration from plan_host() must not shrink it
+    assert (sweep["shapes"], sweep["blocks"]) == (8143872, 644)
+
+
+# what validate_params() / plan_host() answer to the (code, L, rule, scan, Nc) of the sweep that get no plan: the sweep is a superset of the plans,
+# and the chooser answers for all of it
+PLAN_REFUSALS = {
+    "wave, one rung": r"^scan = wave needs a ladder whose top rung sits at p = 0\.75 \(Nc >= 2\)$",
+    "colour, one rung, logical moves": r"^scan = colour needs the top rung at p = 0\.75 \(Nc >= 2\) when logical moves are on$",
+    "table-driven rules, nq > 511": r"^biased / alpha noise packs the error counts in 10-bit fields: nq=\d+$",
+    "LDS": r"^L=\d+ Nc=\d+ needs \d+ B of LDS per workgroup \(> 160 KiB\)$",
+    "LDS, colour": r"^scan = colour: L=\d+ Nc=\d+ needs \d+ B of LDS per workgroup \(> 160 KiB\)$",
+    "wave, not built": r"^scan = wave: L=\d+ Nc=\d+ p=0\.1 is outside what it is built for \(depolarizing rule: a top rung that accepts every move, at most 16 packed",
+}
+
+
+def test_plans_refused_within_the_sweep(T):
+    met, n = {}, 0
+    for base in blocks(T):
+        for Nc in range(1, 17):
+            rc, msg, shape, lds, _ = plan(T, params(code=base["code"], L=base["L"], noise=base["noise"], scan=base["scan"], Nc=Nc, p_logical=0.5))
+            n += 1
+            if rc == 0:
+                assert {f: shape[f] for f in base} == base and shape["Nc"] == Nc and 0 < lds <= 160 * 1024
+                continue
+            # (the colour kernel's LDS holds what build_plan once tested first, states + records + histogram, and more: far from 160 KiB at every
+            # colour shape of the sweep, that first test never answered before the colour kernel's own)
+            assert base["scan"] != 2 or 4 * (Nc * base["W"] + 4 * Nc + base["ncls"]) <= 160 * 1024
+            why = [name for name, rx in PLAN_REFUSALS.items() if re.search(rx, msg)]
+            assert rc == -4 and len(why) == 1, msg
+            met[why[0]] = met.get(why[0], 0) + 1
+    assert n == 644 * 16
+    for name, k in sorted(met.items()):
+        print("%5d of %d (code, L, rule, scan, Nc) refused: %s" % (k, n, name))
+    assert set(met) == set(PLAN_REFUSALS)
+
+
+@pytest.mark.parametrize("kw", [dict(code=TORIC, L=5, noise=0, p=0.1), dict(code=TORIC, L=5, noise=0, p=0.75), dict(code=ROTATED, L=5, noise=0, p=0.1),
+                                dict(code=XZZX, L=5, noise=1, eta=3.0, iters=10), dict(code=XZZX, L=5, noise=1, eta=1e6, iters=400),
+                                dict(code=XZZX, L=5, noise=1, eta=3.0, iters=1000), dict(code=ROTATED, L=5, noise=2, alpha=1.5, iters=10),
+                                dict(code=ROTATED, L=5, noise=2, alpha=6.0, iters=128), dict(code=XZZX, L=5, noise=2, alpha=1.5, iters=600)])
+def test_plans_present_the_ladders_the_sweep_claims(T, kw):
+    """ladders(): (top_acc, lower_acc, swap_fast_ok, f32ok) of a real plan is one of the tuples the sweep runs for its rule, scan and Nc -- both
+    depolarizing ladders (p below and at 0.75), the table-driven rules on each side of the single-precision bound (4 iters max|log2 ratio| <= 2000,
+    iters <= 512), the alpha rule's accept-all top rung on scan = colour"""
+    seen = set()
+    for scan, Nc in itertools.product(range(4), (1, 2, 8)):
+        rc, msg, shape, _, _ = plan(T, params(scan=scan, Nc=Nc, **kw))
+        if rc == 0:
+            got = tuple(shape[f] for f in ("top_acc", "lower_acc", "swap_fast_ok", "f32ok"))
+            assert got in ladders(kw["noise"], scan, Nc), (scan, Nc, got)
+            seen.add(got[3])
+    assert seen       # (some scan and Nc of every case makes a plan)
 
 
 def test_every_chosen_kernel_is_built_and_every_refusal_is_named(chosen):
@@ -200,17 +274,23 @@ def test_baseline_kernels(T, name):
 
 
 def test_queue_grid_waves_per_cu(T):
-    # the persistent grid of a work-queue plan (capi.hip build_plan) holds 4 SIMDs x MINW waves of the kernel chosen with the queue offered: 8 per
+    # the persistent grid of a work-queue plan (plan_host.hpp) holds 4 SIMDs x MINW waves of the kernel chosen with the queue offered: 8 per
     # SIMD for the 512-thread depolarizing ladder kernels, 4 for the 1024-thread ones and the biased / alpha queue kernels; scan = wave 8, 6 from 13
-    # words on and for the alpha rule's criterion kernels
+    # words on and for the alpha rule's criterion kernels -- or as many workgroups as their LDS lets a CU hold, if that is fewer, and at least one
     def waves(**kw):
-        s = bench_shape(T, **{k: kw.pop(k) for k in ("code", "L", "Nc", "scan", "noise") if k in kw})
-        for k, v in dict(kw, conv=1, queue=1).items():
+        s = bench_shape(T, **{k: kw[k] for k in ("code", "L", "Nc", "scan", "noise") if k in kw})
+        for k, v in dict({k: v for k, v in kw.items() if k in ("top_acc", "f32ok", "logical")}, conv=1, queue=1).items():
             s[FIELDS.index(k)] = v
         keys = np.zeros(11, dtype=np.int64)
         T.qt_choose_kernels(np.array(s, dtype=np.int32).ctypes.data, 1, keys.ctypes.data)
         family, minw, flags, conv = keys[0], keys[2], keys[4], keys[6]
-        return 4 * minw // s[FIELDS.index("Nc")] if (family == 1 and flags & 512) or (family == 2 and conv) else 0
+        per_cu = 4 * minw // s[FIELDS.index("Nc")] if (family == 1 and flags & 512) or (family == 2 and conv) else 0
+        # ... and what the plan of such a parameter block says itself, on a device of one CU
+        rc, msg, _, lds, grid = plan(T, params(code=kw["code"], L=kw["L"], Nc=kw["Nc"], scan=kw["scan"], noise=kw.get("noise", 0), conv_mode=1,
+                                               p_logical=0.5 * kw.get("logical", 1)))
+        assert rc == 0, msg
+        assert grid == (max(1, min(per_cu, 160 * 1024 // lds)) if per_cu else 0)
+        return per_cu
     assert waves(code=TORIC, L=9, Nc=8, scan=0) == 32 // 8 and waves(code=TORIC, L=9, Nc=12, scan=0) == 16 // 12
     assert waves(code=XZZX, L=9, Nc=8, scan=0, noise=1, top_acc=0) == 16 // 8
     assert waves(code=TORIC, L=9, Nc=8, scan=3) == 32 // 8 and waves(code=TORIC, L=11, Nc=4, scan=3) == 24 // 4
