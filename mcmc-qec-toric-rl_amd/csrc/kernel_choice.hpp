@@ -268,6 +268,19 @@ inline KernelKey choose_wave(const KernelShape &s)
     return wave_key(maxt, wv <= 12 ? 8 : 6, s.code, wv, s.conv, it, false);
 }
 
+// scan = 3: who walks the swap cascade of a step (ladder_wu.hpp, the lean step tail).  true: the top rung's wave once for the workgroup, its result handed to the other waves behind a third barrier; false: every wave replays it down to its own rung.  Not part of the
+// kernel key: both forms live in the one kernel behind a wave-uniform test of LadderArgs::wu_once, which the launch sets from here.  Where ladder_kernel's
+// SSW variant would be eligible (choose_ladder_toric: fixed length, depolarizing rule, at most 16 words, workgroups of up to 512 threads of which four fit
+// a CU -- the serial section is covered by the CU's other workgroups) the measurement decides, and it turns on the ladder's length alone, whatever the code
+// and the state width: once per workgroup gains 2.6 - 5.2 % at 5, 6 and 7 rungs and loses 0.5 - 3.8 % at 2, 3, 4 -- too few replays to pay
+// for the barrier -- and at 8, where a workgroup's waves fall on the same SIMDs in every workgroup of the CU.  QECMC_FLAG_NO_SSW (tune & 8): the replay.
+inline bool wave_cascade_once(const KernelShape &s)
+{
+    const KernelKey k = choose_wave(s);
+    return s.scan == 3 && k.ok() && !k.conv && !k.alpha && k.wv <= 16 && s.Nc >= 5 && s.Nc <= 7 && !(s.tune & 8) &&
+           4 * wu_lds_bytes(s.Nc, s.W, s.ncls, s.L, false, false) <= 160 * 1024;
+}
+
 // the kernel a launch of this shape runs, or why none is built for it
 inline KernelKey choose_kernel(const KernelShape &s)
 {

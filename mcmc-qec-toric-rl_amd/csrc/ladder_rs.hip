@@ -54,7 +54,9 @@ hipError_t launch_ladder(const LadderArgs &a, hipStream_t stream)
         if (a.wu_desc == nullptr || (a.first_syndrome & 63u) || (a.noise == 2 && (a.bias_tbl == nullptr || a.alpha_lnb == nullptr))) return hipErrorInvalidValue;
         if (k.conv && (a.nlog == nullptr || a.resume || a.write_states || a.wu_chunk < 64u || (a.wu_chunk & 63u))) return hipErrorInvalidValue;
         const uint64_t per = k.conv ? a.wu_chunk : 64u;
-        return launch_fn(fn, a, stream, (unsigned)((a.N + per - 1) / per), wu_lds_bytes(a.Nc, a.W, a.ncls, a.L, k.conv, k.alpha));
+        LadderArgs b = a;
+        b.wu_once = wave_cascade_once(kernel_shape(a)) ? 1u : 0u;
+        return launch_fn(fn, b, stream, (unsigned)((a.N + per - 1) / per), wu_lds_bytes(a.Nc, a.W, a.ncls, a.L, k.conv, k.alpha));
     }
     if (k.family == kFamColour) {
         // scan = 2: one ladder per workgroup

@@ -116,6 +116,30 @@ template <int WV> __device__ __forceinline__ void wu_ds_wait(typename WuVec<WV>:
     WU_BY_WV(M)
 #undef M
 }
+// the whole state to / from a rung's region of the exchange buffer (row w: word w) as ONE asm statement of WV instructions -- between two asm
+// statements that name the pinned tuple the compiler places a hazard s_nop, eleven per transfer at 12 words; the read waits for its data itself
+#define WU_ROWS4(M) M(0, 0) M(1, 256) M(2, 512) M(3, 768)
+#define WU_ROWS8(M) WU_ROWS4(M) M(4, 1024) M(5, 1280) M(6, 1536) M(7, 1792)
+#define WU_ROWS12(M) WU_ROWS8(M) M(8, 2048) M(9, 2304) M(10, 2560) M(11, 2816)
+#define WU_ROWS16(M) WU_ROWS12(M) M(12, 3072) M(13, 3328) M(14, 3584) M(15, 3840)
+#define WU_PUT1(w, off) "ds_write_b32 %[a], v[%c[b]+" #w "] offset:" #off "\n\t"
+#define WU_TAKE1(w, off) "ds_read_b32 v[%c[b]+" #w "], %[a] offset:" #off "\n\t"
+template <int WV> __device__ __forceinline__ void wu_put_all(typename WuVec<WV>::type &st, uint32_t addr)
+{
+    static_assert(WV <= 16, "a 32-word state passes through the buffer in two halves");
+#define M(ROWS, PIN) asm volatile(ROWS(WU_PUT1) : "+" PIN(st) : [a] "v"(addr), [b] "i"(wu_base<WV>()) : "memory");
+    if constexpr (WV == 4) { M(WU_ROWS4, "{v[60:63]}") } else if constexpr (WV == 8) { M(WU_ROWS8, "{v[56:63]}") }
+    else if constexpr (WV == 12) { M(WU_ROWS12, "{v[52:63]}") } else { M(WU_ROWS16, "{v[48:63]}") }
+#undef M
+}
+template <int WV> __device__ __forceinline__ void wu_take_all(typename WuVec<WV>::type &st, uint32_t addr)
+{
+    static_assert(WV <= 16, "a 32-word state passes through the buffer in two halves");
+#define M(ROWS, PIN) asm volatile(ROWS(WU_TAKE1) "s_waitcnt lgkmcnt(0)" : "+" PIN(st) : [a] "v"(addr), [b] "i"(wu_base<WV>()) : "memory");
+    if constexpr (WV == 4) { M(WU_ROWS4, "{v[60:63]}") } else if constexpr (WV == 8) { M(WU_ROWS8, "{v[56:63]}") }
+    else if constexpr (WV == 12) { M(WU_ROWS12, "{v[52:63]}") } else { M(WU_ROWS16, "{v[48:63]}") }
+#undef M
+}
 // the four old fields of a generator's sites, one per byte of F (junk above bit 1 of every byte): site i sits in word d_i[7:0]
 // at bit d_i[12:8]
 template <int WV>
@@ -375,6 +399,27 @@ __device__ __forceinline__ void wu_stage_lds(const LadderArgs &a, uint64_t lad, 
     if (CODE == kCodeXzzx) cls = cls == 0 ? 0u : cls == 1 ? 1u : cls == 2 ? 3u : 2u;   // the internal value v with class = v ^ (v >> 1)
 }
 
+// One rung pair of the swap sweep (mcmc.py:97-99, _r_flip :146-149) under the depolarizing rule: do slots i and i + 1 trade states?  car / lo: the
+// records slots i + 1 / i hold, x: the pair's uniform, trow: LDS byte address of the pair's row of swapT.  x < ceil(p_diff[i]^d 2^32) from the row for
+// d < kSwapFast -- its entry 0 never passes, and d <= 0 flips anyway --: the one read that depends on the records.  If some pair of the wave is
+// kSwapFast or more apart (rare once a ladder has settled; the first steps of a run have them), every lane looks its d up in the plan's table in global
+// memory -- whose entries fit 32 bits: swap_fast_ok, wu_supported() -- and the lanes that far apart take that value: one test the wave shares, no
+// exec-mask region, the global address formed behind the test (the laundered i keeps it from being stepped along the cascade).
+__device__ __forceinline__ bool wu_pair_flips(const LadderArgs &a, uint32_t car, uint32_t lo, uint32_t x, uint32_t trow, int i)
+{
+    const int d = (int)(car & 0xFFFFu) - (int)(lo & 0xFFFFu);                        // ne_hi - ne_lo
+    const int dt = d < 0 ? 0 : d > kSwapFast - 1 ? kSwapFast - 1 : d;
+    uint32_t thr = *(wu_lds_ptr)(uintptr_t)(trow + 4u * (uint32_t)dt);
+    if (__builtin_amdgcn_sicmp(d, kSwapFast - 1, 38) != 0) {                         // (ICMP_SGT, over the wave)
+        int il = i, nql = a.nq;
+        asm volatile("" : "+s"(il), "+s"(nql));
+        const int dg = d < 0 ? 0 : d > nql ? nql : d;
+        const uint32_t far = (uint32_t)a.swap_thr[(size_t)il * (size_t)(nql + 1) + (size_t)dg];
+        thr = d >= kSwapFast ? far : thr;
+    }
+    return d <= 0 || x < thr;
+}
+
 // the step loop of one wave: TOP = the rung that accepts every move (its stabilizers unseen, its logical operators through a frame);
 // IT = 10: `iters` known at compile time (decoders.py:25 iters=10), the proposal loop unrolled without guards; IT = 0: any 1 <= iters <= 128.
 // QUEUE (with CONV): a persistent grid; a lane whose ladder has ended takes the next one of its workgroup's share of the batch (in lane
@@ -392,6 +437,7 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
     const uint32_t lds0 = ev.lds0, slot = ev.slot, grp = ev.grp;
     const int lane = ev.lane;
     constexpr bool top = TOP;
+    constexpr bool LEAN = !CONV && !ALPHA && WV <= 16;                            // the kernels whose step tail is the lean one below
     const uint32_t G = a.n_gen;
     const uint32_t m55 = 0x55555555u;
     uint32_t n4 = cx.n4, cls = cx.cls, flag = cx.flag;
@@ -562,6 +608,86 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
         // the next step's pick window (state-independent; before the barrier, where the other waves are still busy)
         if (++ws == S) { ws = 0; ++wi; refresh(); }
 
+        if constexpr (LEAN) {
+        // ---- Ladder.step's swap sweep (mcmc.py:96-103) of the fixed-length kernels of up to 16 words under the depolarizing rule.  A rung's region of
+        // the exchange buffer is WV rows (wu_rows), so everything the tail addresses sits at a multiple of Nc behind one per-lane base: a few
+        // scalar instructions per step, formed here from laundered copies of the shape -- hoisted, they would be spilled across the proposal loop.
+        int NCl = a.Nc, ncl = a.ncls;
+        uint32_t slotl = ev.slot, lds0l = ev.lds0, once = a.wu_once;
+        asm volatile("" : "+s"(NCl), "+s"(ncl), "+s"(slotl), "+s"(lds0l), "+s"(once));
+        const int NC = NCl;
+        const uint32_t slot = slotl;
+        const WuLds ol = wu_lds(NC, WV, ncl, 0, false, false);                       // (the offsets up to swapT: functions of Nc, WV and ncls alone)
+        constexpr uint32_t xstride = (uint32_t)WV * 256u;                            // bytes of one rung in the exchange buffer
+        const uint32_t xaddr = lds0l + (uint32_t)lane * 4u;
+        wu_lds_rw const recl = (wu_lds_rw)(uintptr_t)(xaddr + (uint32_t)ol.rec * 4u), swdl = recl + NC * 64;   // rec[lane], swd[lane]
+        const uint32_t tb0 = lds0l + (uint32_t)ol.swapT * 4u;
+        const int swb = NC - 1 - (int)slot;                 // the top rungs draw the swap uniforms: block swb = pairs 4 swb .. 4 swb + 3
+        u32x4 sb{0, 0, 0, 0};
+        const bool duty = swb >= 0 && swb < 4 && swb * 4 < NC - 1;
+        if (duty) sb = wu_philox(T, (uint32_t)swb, syn, kSwapStream, a.seed_lo, a.seed_hi);
+        __syncthreads();                                   // (everybody has read the exchange buffer, the records and the swap uniforms of the step before)
+        wu_put_all<WV>(st, xaddr + slot * xstride);
+        recl[slot * 64u] = pack_info(n4 >> 2, slot, cls, flag);
+        if (duty) {
+            wu_lds_rw p = swdl + (uint32_t)(swb * 4) * 64u;
+            const int left = NC - 1 - swb * 4;
+            p[0] = sb.x;
+            if (left > 1) p[64] = sb.y;
+            if (left > 2) p[128] = sb.z;
+            if (left > 3) p[192] = sb.w;
+        }
+        wu_ds_wait<WV>(st);                                 // (the asm stores of the exchange are not in the compiler's count)
+        __syncthreads();
+        uint32_t mine;
+        if (once) {
+            // the cascade once per workgroup: the top rung's wave -- its step is the shortest -- walks the pairs top-down and leaves in rec[i] the
+            // record slot i now holds (rec[i + 1] is dead once pair i is decided: `car` has it); behind a third barrier a wave reads its slot's
+            if constexpr (TOP) {
+                wu_lds_rw pr = recl + (NC - 2) * 64, px = swdl + (NC - 2) * 64;
+                uint32_t trow = tb0 + (uint32_t)(NC - 2) * (uint32_t)(kSwapFast * 4);
+                uint32_t car = pr[64], lo = pr[0], x = px[0];
+                for (int i = NC - 2; i >= 0; --i) {                                  // mcmc.py:96
+                    // (the next pair's record and uniform travel while this one is decided; behind pair 0: a row of the region in front, dropped)
+                    const uint32_t lo_n = pr[-64], x_n = px[-64];
+                    const bool flip = wu_pair_flips(a, car, lo, x, trow, i);
+                    pr[64] = flip ? lo : car;                                        // what slot i + 1 now holds (:98-99)
+                    car = flip ? car : lo;
+                    lo = lo_n; x = x_n; pr -= 64; px -= 64; trow -= (uint32_t)(kSwapFast * 4);
+                }
+                pr[64] = car;
+            }
+            __syncthreads();
+            mine = recl[slot * 64u];
+        } else {
+            // every wave replays the top-down cascade on the published records: the pairs above its slot move `car` alone, the pair below it decides
+            wu_lds_ptr pr = recl + (NC - 2) * 64, px = swdl + (NC - 2) * 64;
+            uint32_t trow = tb0 + (uint32_t)(NC - 2) * (uint32_t)(kSwapFast * 4);
+            uint32_t car = pr[64];
+            for (int i = NC - 2; i >= (int)slot; --i) {                              // mcmc.py:96
+                const uint32_t lo = pr[0];
+                car = wu_pair_flips(a, car, lo, px[0], trow, i) ? car : lo;
+                pr -= 64; px -= 64; trow -= (uint32_t)(kSwapFast * 4);
+            }
+            mine = car;
+            if (slot != 0) {
+                const uint32_t lo = pr[0];
+                if (wu_pair_flips(a, car, lo, px[0], trow, (int)slot - 1)) mine = lo;   // what slot i + 1 now holds (:98-99)
+            }
+        }
+        wu_take_all<WV>(st, xaddr + ((mine >> 16) & 0xFFu) * xstride);               // this rung's new state: the words of the rung it comes from
+        n4 = (mine & 0xFFFFu) << 2; cls = (mine >> 24) & 0x3Fu; flag = mine >> 31;
+        if (top) flag = 1;                                                           // chains[-1].flag = 1, mcmc.py:100
+        if (slot == 0) {                                                             // ladder + PTEQ bookkeeping on rung 0's new state
+            tops0 += (NC == 1) | flag;                                               // :101-102
+            if (a.counts != nullptr && tops0 >= a.tops_burn) {                       // decoders.py:60-67
+                wu_lds_rw const hist = (wu_lds_rw)(uintptr_t)(xaddr + (uint32_t)ol.hist * 4u);
+                hist[(CODE == kCodeXzzx ? (cls ^ (cls >> 1)) : cls) * 64] += 1;
+                samples++;
+            }
+            flag = 0;                                                                // :103
+        }
+        } else {
         // ---- Ladder.step's swap sweep (mcmc.py:96-103)
         // (per-step work: its table addresses are formed here, from laundered copies of the shape, instead of being hoisted out of the
         // step loop and kept -- spilled -- in scalar registers across the proposal loop, which runs at 8 waves per SIMD on ~80 SGPRs)
@@ -581,21 +707,10 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
         const uint32_t xaddr = lds0l + (uint32_t)lane * 4u;
         constexpr bool PAD = WV == 32 || !CONV;                                      // (wu_rows: padded rows, transfers without width tests)
         const uint32_t xstride = (uint32_t)(WV == 32 ? kWuHalf : PAD ? WV : Wl) * 256u;  // bytes of one rung in the exchange buffer
-#ifdef QECMC_WU_TOP_SWAPS
-        // the swap uniforms -- block b = pairs 4 b .. 4 b + 3 -- are all drawn by the TOP rung's wave, whose step is the shortest
-        const int nblk = (NC - 1 + 3) >> 2;
-        u32x4 sbs[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-        if constexpr (TOP) {
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-                if (b < nblk) sbs[b] = wu_philox(T, (uint32_t)b, syn, kSwapStream, a.seed_lo, a.seed_hi);
-        }
-#else
         const int swb = NC - 1 - (int)slot;                 // the top rungs draw the swap uniforms: block swb = pairs 4 swb .. 4 swb + 3
         u32x4 sb{0, 0, 0, 0};
         const bool duty = swb >= 0 && swb < 4 && swb * 4 < NC - 1;
         if (duty) sb = wu_philox(T, (uint32_t)swb, syn, kSwapStream, a.seed_lo, a.seed_hi);
-#endif
         __syncthreads();                                   // (everybody has read the exchange buffer and the swap uniforms of the step before)
         {
             const uint32_t xo = xaddr + slot * xstride;
@@ -605,20 +720,6 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
             WU_EACH(QECMC_WU_PUT)
             rec[slot * 64u + (uint32_t)lane] = pack_info(n4 >> 2, slot, cls, flag);
             if constexpr (ALPHA) nefd[slot * 64u] = wu_neff(nef, a.alpha);
-#ifdef QECMC_WU_TOP_SWAPS
-            if constexpr (TOP) {
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    if (b >= nblk) break;
-                    wu_lds_rw p = swd + (uint32_t)(b * 4) * 64u + (uint32_t)lane;
-                    const int left = NC - 1 - b * 4;
-                    p[0] = sbs[b].x;
-                    if (left > 1) p[64] = sbs[b].y;
-                    if (left > 2) p[128] = sbs[b].z;
-                    if (left > 3) p[192] = sbs[b].w;
-                }
-            }
-#else
             if (duty) {
                 wu_lds_rw p = swd + (uint32_t)(swb * 4) * 64u + (uint32_t)lane;
                 const int left = NC - 1 - swb * 4;
@@ -627,7 +728,6 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
                 if (left > 2) p[128] = sb.z;
                 if (left > 3) p[192] = sb.w;
             }
-#endif
         }
         wu_ds_wait<WV>(st);                                 // (the asm stores of the exchange are not in the compiler's count)
         __syncthreads();
@@ -838,6 +938,7 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
                     }
                 }
             }
+        }
         }
     }
     cx.n4 = n4; cx.cls = cls; cx.flag = flag; cx.tops0 = tops0; cx.samples = samples;

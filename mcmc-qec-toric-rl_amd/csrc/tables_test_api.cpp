@@ -83,6 +83,11 @@ void qt_choose_kernels(const KernelShape *shapes, int n, int64_t *keys)
         std::memcpy(keys + 11 * (size_t)i, v, sizeof v);
     }
 }
+// wave_cascade_once() of n shapes: 1 where the launch sets LadderArgs::wu_once
+void qt_wave_cascade_once(const KernelShape *shapes, int n, int32_t *once)
+{
+    for (int i = 0; i < n; ++i) once[i] = wave_cascade_once(shapes[i]) ? 1 : 0;
+}
 int qt_kernel_shape_ints(void) { return (int)(sizeof(KernelShape) / sizeof(int)); }
 // validate_params(), then the first phase of plan_host(): the QECMC_ERR_* code and message; accepted: the shape's static fields (the others 0)
 int qt_plan_dims(const qecmc_params *p, int32_t *shape_ints, char *msg, int msg_cap)
