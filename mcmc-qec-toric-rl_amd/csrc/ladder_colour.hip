@@ -376,7 +376,7 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_colour_kernel(const LadderA
         if (slot == 0) mine_s = carried;
         uint32_t mine = (uint32_t)__builtin_amdgcn_readlane((int)rec_l, mine_s);
         mine = (uint32_t)__builtin_amdgcn_readfirstlane((int)mine);
-        n = mine & 0xFFFFu; sid = (mine >> 16) & 0xFFu; cls = (mine >> 24) & 0x3Fu; flag = mine >> 31;
+        n = info_n(mine); sid = info_sid(mine); cls = info_cls(mine); flag = info_flag(mine);
         if ((int)slot == NC - 1) flag = 1;                                               // mcmc.py:100
         QECMC_CSTAMP(4);
         if (slot == 0 && !done) {
@@ -385,27 +385,18 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_colour_kernel(const LadderA
                 if (lane == 0) hist[CODE == kCodeXzzx ? (cls ^ (cls >> 1)) : cls] += 1;
                 samples++;
                 if constexpr (CONV) {
-                    // nbr_errors_bottom_chain[since_burn] = count_errors (:68): logged in HBM, series index i in row burn + i; the three
-                    // entries that leave / enter the windows are independent loads (one round trip on wave 0's path per step)
+                    // the series value of this step (RULE == 2: slot 0's attribute -- this wave's -- as its two counts, 4 B) goes into the log; the
+                    // three entries that leave / enter the windows are independent loads (one round trip on wave 0's path per step)
                     const size_t lN = (size_t)a.N;
-                    const uint32_t l = samples, lo1 = l - 1;
-                    const uint32_t a0 = lo1 >> 2, b0 = lo1 >> 1, c0 = (3u * lo1) >> 2, a1 = l >> 2, b1 = l >> 1, c1 = (3u * l) >> 2;
-                    if constexpr (RULE == 2) {
-                        // chains[0].n_eff (decoders_biasednoise.py:204): slot 0's attribute -- this wave's -- logged as its two counts
-                        uint32_t *mylog = reinterpret_cast<uint32_t *>(a.nlog) + ladder;
-                        mylog[(size_t)t * lN] = nef;
-                        sumB += nef & 0xFFFFu; sumBxy += nef >> 16;
-                        if (c1 != c0) { const uint32_t v = mylog[(size_t)(burn + c0) * lN]; sumB -= v & 0xFFFFu; sumBxy -= v >> 16; }
-                        if (b1 != b0) { const uint32_t v = mylog[(size_t)(burn + b0) * lN]; sumA += v & 0xFFFFu; sumAxy += v >> 16; }
-                        if (a1 != a0) { const uint32_t v = mylog[(size_t)(burn + a0) * lN]; sumA -= v & 0xFFFFu; sumAxy -= v >> 16; }
-                    } else {
-                    uint16_t *mylog = a.nlog + ladder;
-                    mylog[(size_t)t * lN] = (uint16_t)n;
-                    sumB += n;
-                    if (c1 != c0) sumB -= mylog[(size_t)(burn + c0) * lN];
-                    if (b1 != b0) sumA += mylog[(size_t)(burn + b0) * lN];
-                    if (a1 != a0) sumA -= mylog[(size_t)(burn + a0) * lN];
-                    }
+                    typedef typename std::conditional<RULE == 2, uint32_t, uint16_t>::type log_t;
+                    log_t *mylog = reinterpret_cast<log_t *>(a.nlog) + ladder;
+                    const uint32_t v0 = RULE == 2 ? nef : n;
+                    mylog[(size_t)t * lN] = (log_t)v0;
+                    const auto [a0, b0, c0, a1, b1, c1] = quartile_rows(samples);
+                    const uint32_t vc = c1 != c0 ? mylog[(size_t)(burn + c0) * lN] : 0u;
+                    const uint32_t vb = b1 != b0 ? mylog[(size_t)(burn + b0) * lN] : 0u;
+                    const uint32_t va = a1 != a0 ? mylog[(size_t)(burn + a0) * lN] : 0u;
+                    window_update<RULE == 2>(v0, vc, vb, va, sumA, sumB, sumAxy, sumBxy);
                 }
             } else {
                 burn++;                                                                  // resulting_burn_in, :71
@@ -413,20 +404,8 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_colour_kernel(const LadderA
             if (!t_reached && tops0 >= a.TOPS) t_reached = (uint32_t)t + 1u;
             if constexpr (CONV) {
                 if (tops0 >= a.TOPS) {                                                   // :74
-                    const uint32_t l = samples ? samples : 1u;
-                    const uint32_t den2 = (l >> 1) - (l >> 2), den4 = l - ((3u * l) >> 2);
-                    bool accept = false;                                                 // empty slice -> nan -> not accepted
-                    if (samples && den2 && den4) {
-                        if constexpr (RULE == 2) accept = alpha_series_close(sumA, sumAxy, den2, sumB, sumBxy, den4, a.alpha, a.eps);   // decoders_biasednoise.py:229-238
-                        else accept = fabs((double)sumA / (double)den2 - (double)sumB / (double)den4) < a.eps;   // :96-102
-                    }
-                    if (accept) {
-                        if (conv_streak >= a.SEQ) { done = 1; steps_done = (uint32_t)t + 1u; }   // :77-78
-                        else conv_streak = tops0 - conv_start;                           // :79
-                    } else {
-                        conv_streak = 0;                                                 // :81-82
-                        conv_start = tops0;
-                    }
+                    const bool accept = criterion_accepts<RULE == 2>(samples, sumA, sumAxy, sumB, sumBxy, a.alpha, a.eps);
+                    if (streak_ends(accept, tops0, a.SEQ, conv_start, conv_streak)) { done = 1; steps_done = (uint32_t)t + 1u; }
                 }
                 if (done && lane == 0) stopf[(t + 1) & 1] = 1;
             }
@@ -439,34 +418,20 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_colour_kernel(const LadderA
     if (lane == 0) fin[slot] = pack_info(n, sid, cls, flag);
     __syncthreads();
     if (slot == 0) {
-        if (a.counts != nullptr)
-            for (int c = lane; c < ncls; c += 64) {
-                if (R > 1) { if (hist[c]) atomicAdd(a.counts + row * ncls + c, hist[c]); }
-                else a.counts[row * ncls + c] = hist[c];
-            }
+        if (a.counts != nullptr) store_class_column(a.counts + row * ncls, hist, 1, lane, 64, ncls, R, false);   // (the lanes share the classes)
         if (lane == 0) {
             // steps_done / converged: the criterion's; without it, the first step with tops0 >= TOPS
             const uint32_t sd = CONV ? (done ? steps_done : (uint32_t)a.nsteps) : (t_reached ? t_reached : (uint32_t)a.nsteps);
             const bool reached = CONV ? done != 0 : t_reached != 0;
-            if (R > 1) {
-                if (a.samples != nullptr) atomicAdd(a.samples + row, samples);
-                if (a.tops0 != nullptr) atomicAdd(a.tops0 + row, tops0);
-                if (a.steps_done != nullptr) atomicMax(a.steps_done + row, sd);
-                if (a.converged != nullptr && !reached) a.converged[row] = 0;
-            } else {
-                if (a.samples != nullptr) a.samples[row] = samples;
-                if (a.tops0 != nullptr) a.tops0[row] = tops0;
-                if (a.steps_done != nullptr) a.steps_done[row] = sd;
-                if (a.converged != nullptr) a.converged[row] = reached;
-            }
+            store_ladder_results(a.samples, a.tops0, a.steps_done, a.converged, row, R, false, samples, tops0, sd, reached);
         }
     }
     if (a.write_states && a.states != nullptr) {
         uint8_t *dst = a.states + (ladder * NC + slot) * (uint64_t)nq;                   // slot order
-        const uint32_t sidc = (fin[slot] >> 16) & 0xFFu;
+        const uint32_t sidc = info_sid(fin[slot]);
         for (int q = lane; q < nq; q += 64) dst[q] = (uint8_t)((st[sidc * W + (q >> 4)] >> ((q & 15) * 2)) & 3u);
     }
-    if (a.flags != nullptr && lane == 0) a.flags[ladder * NC + slot] = (uint8_t)(fin[slot] >> 31);
+    if (a.flags != nullptr && lane == 0) a.flags[ladder * NC + slot] = (uint8_t)info_flag(fin[slot]);
 }
 
 template <int CODE, int RULE>

@@ -35,6 +35,7 @@
 #include "kernels.hpp"
 #include "philox.hpp"
 #include "stencil_bytes.hpp"   // kCode* constants
+#include "pteq_book.hpp"       // slot records, the PTEQ bookkeeping and its criterion, result write-out
 
 namespace qecmc {
 
@@ -149,13 +150,6 @@ __device__ __forceinline__ void count_xyz(uint32_t w, int &nx, int &ny, int &nz)
     nx += __popc(b0 & ~b1); ny += __popc(b1 & ~b0); nz += __popc(b0 & b1);
 }
 
-// slot record published once per ladder step: error count | state id << 16 | class << 24 | flag << 31
-// (flag = "has been at the top since it last reached the bottom", Chain.flag, mcmc.py:75,99-103)
-__device__ __forceinline__ uint32_t pack_info(uint32_t n, uint32_t sid, uint32_t cls, uint32_t flag)
-{
-    return n | (sid << 16) | (cls << 24) | (flag << 31);
-}
-
 // CONV: build with the error_based convergence criterion (its per-lane window sums cost ~10 VGPRs,
 // so fixed-step runs use the instantiation without it)
 // GSPLIT: the expanded generator table of the toric random-scan path is stored as two halves kGenSplit entries apart
@@ -199,17 +193,6 @@ __device__ inline bool alpha_flip(uint32_t x, uint32_t hi, uint32_t lo, double a
     const double ne_lo = (double)(lo & 0xFFFFu) + alpha * (double)(lo >> 16);
     const double e = ne_hi - ne_lo;
     return (double)x * (1.0 / 4294967296.0) < det_exp(e * lnb);
-}
-
-// conv_crit_error_based_PT_alpha, decoders_biasednoise.py:229-238: |mean Q2 - mean Q4| < eps on the n_eff series, each mean
-// formed as (sum n_z + alpha sum n_xy) / len from exact integer sums
-__device__ inline bool alpha_series_close(uint64_t z2, uint64_t xy2, uint32_t den2, uint64_t z4, uint64_t xy4, uint32_t den4,
-                                          double alpha, double eps)
-{
-#pragma clang fp contract(off)
-    const double q2 = ((double)z2 + alpha * (double)xy2) / (double)den2;
-    const double q4 = ((double)z4 + alpha * (double)xy4) / (double)den4;
-    return fabs(q2 - q4) < eps;
 }
 
 // CODE / BIASED: code model (toric, xzzx, rotated) and acceptance rule (src/mcmc.py or src/mcmc_biased.py).
@@ -545,7 +528,7 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_kernel(const LadderArgs a)
     [[maybe_unused]] bool q_empty = a.N <= (uint64_t)gridDim.x * 64u;                        // ... the counter is exhausted (uniform)
     if constexpr (kLaunderLane) {
         asm volatile("" : "+v"(rec0));
-        n = rec0 & 0xFFFFu; sid = (rec0 >> 16) & 0xFFu; cls = (rec0 >> 24) & 0x3Fu; flag = rec0 >> 31;
+        n = rec0 & 0xFFFFu; sid = (rec0 >> 16) & 0xFFu; cls = (rec0 >> 24) & 0x3Fu; flag = rec0 >> 31;   // (pteq_book.hpp's info_*, in place: the calls change resource rows)
     }
     for (uint64_t t = 0; QUEUE || t < a.nsteps; ++t) {
         // The lane index of this step.  In the register-starved instantiations (kLaunderLane) it is opaque to the compiler, so the
@@ -553,17 +536,7 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_kernel(const LadderArgs a)
         // uses them -- one add each -- instead of being hoisted out of the step loop into registers the 64-VGPR cap then spills.
         int lane_t = lane;
         if constexpr (kLaunderLane) { lane_t = (int)__lane_id(); asm volatile("" : "+v"(lane_t)); }   // (v_mbcnt: nothing derived from threadIdx stays live)
-        // Issue arbitration between co-resident workgroups is oldest-first, which lets the first one
-        // race ahead and leaves the last one alone (latency-bound, 2 waves per SIMD) at the end of a
-        // launch.  Lowering a workgroup's priority as it advances (cyclically, every 8 steps) narrows
-        // that spread: +6 % on a one-round grid (measured), neutral otherwise.
-        // (Tried in round 2: the top-role wave at the highest priority instead: -10 % at L = 9, +3 % at L = 15, 0 at rotated L = 21.)
-        switch (3u - (uint32_t)((t >> 3) & 3)) {    // s_setprio takes an immediate
-            case 0: __builtin_amdgcn_s_setprio(0); break;
-            case 1: __builtin_amdgcn_s_setprio(1); break;
-            case 2: __builtin_amdgcn_s_setprio(2); break;
-            default: __builtin_amdgcn_s_setprio(3); break;
-        }
+        set_step_priority(t);                       // the workgroup's issue priority falls as it advances
         QECMC_STAMP(5); QECMC_STAMP(0);
         // ---------------- Chain.update_chain(iters) on every slot (mcmc.py:81-83) -----------
         uint32_t *stw = st + sid * W * 64 + lane_t;
@@ -1649,12 +1622,7 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_kernel(const LadderArgs a)
                     if constexpr (CODE == kCodeToric || CODE == kCodePlanar) {
                         __builtin_amdgcn_s_setprio(0);
                     } else {
-                        switch (3u - (uint32_t)((t >> 3) & 3)) {
-                            case 0: __builtin_amdgcn_s_setprio(0); break;
-                            case 1: __builtin_amdgcn_s_setprio(1); break;
-                            case 2: __builtin_amdgcn_s_setprio(2); break;
-                            default: __builtin_amdgcn_s_setprio(3); break;
-                        }
+                        set_step_priority(t);
                     }
                 }
                 __syncthreads();
@@ -1677,7 +1645,7 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_kernel(const LadderArgs a)
             }
             }   // !SSW
             if (!SSW && slot_u == 0) mine = car;
-            n = mine & 0xFFFFu; sid = (mine >> 16) & 0xFFu; cls = (mine >> 24) & 0x3Fu; flag = mine >> 31;
+            n = mine & 0xFFFFu; sid = (mine >> 16) & 0xFFu; cls = (mine >> 24) & 0x3Fu; flag = mine >> 31;   // (info_*, in place as above)
             QECMC_STAMP(4);
             if ((int)slot_u == NC - 1) flag = 1;                                    // chains[-1].flag = 1, mcmc.py:100
             if (wave_u == 0 && !done) {                                             // ladder + PTEQ bookkeeping on slot 0's new state
@@ -1688,50 +1656,27 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_kernel(const LadderArgs a)
                     const uint32_t v = (car >> 24) & 0x3Fu;
                     hist[(CODE == kCodeXzzx ? (v ^ (v >> 1)) : v) * 64 + lane_t] += 1;
                     samples++;
-                    if (CONV && BIASED && alpha_noise) {
-                        // nbr_errors_bottom_chain[since_burn] = chains[0].n_eff (decoders_biasednoise.py:204): slot 0's
-                        // attribute, logged as its two counts; the window sums stay exact integers
-                        if (QUEUE ? !q_dead : lane_t < cnt) {
-                            // (QUEUE: one log column per lane of the persistent grid, rows = the ladder's own steps)
-                            const size_t lN = QUEUE ? (size_t)gridDim.x * 64u : (size_t)a.N;
-                            uint32_t *mylog = reinterpret_cast<uint32_t *>(a.nlog) + (s0 + lane_t);
-                            const uint32_t v0 = neffb[(t & 1) * NC * 64 + lane_t];
-                            mylog[(size_t)(t - t0) * lN] = v0;
-                            const uint32_t l = samples, lo1 = l - 1;
-                            const uint32_t a0 = lo1 >> 2, b0 = lo1 >> 1, c0 = (3u * lo1) >> 2, a1 = l >> 2, b1 = l >> 1, c1 = (3u * l) >> 2;
-                            sumB += v0 & 0xFFFFu; sumBxy += v0 >> 16;
-                            if (c1 != c0) { const uint32_t v = mylog[(size_t)(burn + c0) * lN]; sumB -= v & 0xFFFFu; sumBxy -= v >> 16; }
-                            if (b1 != b0) { const uint32_t v = mylog[(size_t)(burn + b0) * lN]; sumA += v & 0xFFFFu; sumAxy += v >> 16; }
-                            if (a1 != a0) { const uint32_t v = mylog[(size_t)(burn + a0) * lN]; sumA -= v & 0xFFFFu; sumAxy -= v >> 16; }
-                        }
-                    } else
                     if (CONV && (QUEUE ? !q_dead : lane_t < cnt)) {
-                        // nbr_errors_bottom_chain[since_burn] = count_errors (:68); series index i lives in log row burn+i
+                        // the series value of this step (alpha noise: slot 0's attribute as its two counts, 4 B) goes into the log
                         // (QUEUE: one log column per lane of the persistent grid, rows = the ladder's own steps)
                         const size_t lN = QUEUE ? (size_t)gridDim.x * 64u : (size_t)a.N;
-                        uint16_t *mylog = a.nlog + (s0 + lane_t);
-                        mylog[(size_t)(t - t0) * lN] = (uint16_t)n0;
-                        const uint32_t l = samples, lo1 = l - 1;
-                        const uint32_t a0 = lo1 >> 2, b0 = lo1 >> 1, c0 = (3u * lo1) >> 2, a1 = l >> 2, b1 = l >> 1, c1 = (3u * l) >> 2;
-                        sumB += n0;
-                        if (c1 != c0) sumB -= mylog[(size_t)(burn + c0) * lN];
-                        if (b1 != b0) sumA += mylog[(size_t)(burn + b0) * lN];
-                        if (a1 != a0) sumA -= mylog[(size_t)(burn + a0) * lN];
+                        typedef typename std::conditional<alpha_noise, uint32_t, uint16_t>::type log_t;
+                        log_t *mylog = reinterpret_cast<log_t *>(a.nlog) + (s0 + lane_t);
+                        uint32_t v0 = n0;
+                        if constexpr (alpha_noise) v0 = neffb[(t & 1) * NC * 64 + lane_t];
+                        mylog[(size_t)(t - t0) * lN] = (log_t)v0;
+                        const auto [a0, b0, c0, a1, b1, c1] = quartile_rows(samples);
+                        const uint32_t vc = c1 != c0 ? mylog[(size_t)(burn + c0) * lN] : 0u;
+                        const uint32_t vb = b1 != b0 ? mylog[(size_t)(burn + b0) * lN] : 0u;
+                        const uint32_t va = a1 != a0 ? mylog[(size_t)(burn + a0) * lN] : 0u;
+                        window_update<alpha_noise>(v0, vc, vb, va, sumA, sumB, sumAxy, sumBxy);
                     }
                 } else {
                     burn++;                                                         // resulting_burn_in, :71
                 }
                 if (CONV && tops0 >= a.TOPS) {                               // :74
-                    const uint32_t l = samples ? samples : 1u;
-                    const uint32_t den2 = (l >> 1) - (l >> 2), den4 = l - ((3u * l) >> 2);
-                    bool accept = false;                                            // empty slice -> nan -> not accepted
-                    if (samples && den2 && den4) {
-                        if (BIASED && alpha_noise)
-                            accept = alpha_series_close(sumA, sumAxy, den2, sumB, sumBxy, den4, a.alpha, a.eps);
-                        else
-                            accept = fabs((double)sumA / (double)den2 - (double)sumB / (double)den4) < a.eps;   // :96-102
-                    }
-                    if (accept) {
+                    const bool accept = criterion_accepts<alpha_noise>(samples, sumA, sumAxy, sumB, sumBxy, a.alpha, a.eps);
+                    if (accept) {                                                   // (pteq_book.hpp's streak_ends, in place: the call changes resource rows)
                         if (conv_streak >= a.SEQ) { done = 1; conv_ok = 1; steps_done = (uint32_t)(t - t0) + 1; }   // :77-78
                         else conv_streak = tops0 - conv_start;                      // :79
                     } else {
@@ -1763,23 +1708,8 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_kernel(const LadderArgs a)
                     if (!q_dead && !done && (t - t0) + 1 >= a.nsteps) { done = 1; steps_done = (uint32_t)a.nsteps; }
                     if (!q_dead && done && !q_flushed) {
                         const uint64_t row = (uint64_t)qi / R;
-                        for (int c = 0; c < ncls; ++c) {
-                            const uint32_t v = hist[c * 64 + lane_t];
-                            hist[c * 64 + lane_t] = 0;
-                            if (R > 1) { if (v) atomicAdd(a.counts + row * ncls + c, v); }
-                            else a.counts[row * ncls + c] = v;
-                        }
-                        if (R > 1) {
-                            atomicAdd(a.samples + row, samples);
-                            if (a.tops0 != nullptr) atomicAdd(a.tops0 + row, tops0);
-                            if (a.steps_done != nullptr) atomicMax(a.steps_done + row, steps_done);
-                            if (a.converged != nullptr && !conv_ok) a.converged[row] = 0;
-                        } else {
-                            a.samples[row] = samples;
-                            if (a.tops0 != nullptr) a.tops0[row] = tops0;
-                            if (a.steps_done != nullptr) a.steps_done[row] = steps_done;
-                            if (a.converged != nullptr) a.converged[row] = (uint8_t)conv_ok;
-                        }
+                        store_class_column(a.counts + row * ncls, hist + lane_t, 64, 0, 1, ncls, R, true);
+                        store_ladder_results(a.samples, a.tops0, a.steps_done, a.converged, row, R, false, samples, tops0, steps_done, conv_ok != 0);
                         q_flushed = true;
                         if (q_empty) q_dead = true;
                     }
@@ -1946,7 +1876,7 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_kernel(const LadderArgs a)
             else if (a.nerr_sum != nullptr) a.nerr_sum[(s0 + j) * NC + (c - (NC - 1))] = lds_all[gdw + (NC + c - (NC - 1)) * 64 + j];
         }
     }
-    if (slot_e == 0 && lane_e < cnt && R > 1) {
+    if (slot_e == 0 && lane_e < cnt && R > 1) {          // (pteq_book.hpp's store_ladder_results, in place: the call changes resource rows)
         const uint64_t row = (s0 + lane_e) / R;
         if (a.samples != nullptr) atomicAdd(a.samples + row, samples);
         if (a.tops0 != nullptr) atomicAdd(a.tops0 + row, tops0);

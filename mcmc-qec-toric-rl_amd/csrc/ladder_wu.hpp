@@ -756,7 +756,7 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
             }
             if (slot == 0) mine = car;
             // this rung's new state: the W words of the rung it comes from
-            const uint32_t xin = xaddr + ((mine >> 16) & 0xFFu) * xstride;
+            const uint32_t xin = xaddr + info_sid(mine) * xstride;
 #define QECMC_WU_TAKE(w) if constexpr (w < WV && w < kWuHalf) { if (WV == 32 || !CONV || w < wu_words_min(WV) || w < Wl) wu_ds_read<WV, w>(st, xin); }
 #define QECMC_WU_TAKE_HI(w) if constexpr (w < WV && w >= kWuHalf) wu_ds_read<WV, w, w - kWuHalf>(st, xin);
             WU_EACH(QECMC_WU_TAKE)
@@ -771,7 +771,7 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
                 WU_EACH(QECMC_WU_TAKE_HI)
                 wu_ds_wait<WV>(st);
             }
-            n4 = (mine & 0xFFFFu) << 2; cls = (mine >> 24) & 0x3Fu; flag = mine >> 31;
+            n4 = info_n(mine) << 2; cls = info_cls(mine); flag = info_flag(mine);
             if (top) flag = 1;                                                       // chains[-1].flag = 1, mcmc.py:100
             if constexpr (!CONV) {
                 if (slot == 0) {                                                     // ladder + PTEQ bookkeeping on rung 0's new state
@@ -802,8 +802,8 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
             bool ended = false;
             uint32_t conv_ok = 0;
             if (has && !done && !pending) {
-                b_tops0 += (NC == 1) | (recw >> 31);                                     // :101-102
-                const uint32_t n0 = recw & 0xFFFFu, cls0 = (recw >> 24) & 0x3Fu;
+                b_tops0 += (NC == 1) | info_flag(recw);                                  // :101-102
+                const uint32_t n0 = info_n(recw), cls0 = info_cls(recw);
                 if (a.counts != nullptr && b_tops0 >= a.tops_burn) {             // decoders.py:60-67
                     hist[(CODE == kCodeXzzx ? (cls0 ^ (cls0 >> 1)) : cls0) * 64 + lane] += 1;
                     b_samples++;
@@ -815,8 +815,8 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
                     log_t *mylog = reinterpret_cast<log_t *>(a.nlog) + ((size_t)blockIdx.x * 64u + (size_t)lane);
                     const uint32_t v0 = ALPHA ? bot2[((uint32_t)tb & 1u) * 64u + (uint32_t)lane] : n0;
                     mylog[(size_t)Town * lN] = (log_t)v0;
-                    const uint32_t l = b_samples, lo1 = l - 1;
-                    const uint32_t a0 = lo1 >> 2, b0 = lo1 >> 1, c0 = (3u * lo1) >> 2, a1 = l >> 2, b1 = l >> 1, c1 = (3u * l) >> 2;
+                    const uint32_t l = b_samples;
+                    const auto [a0, b0, c0, a1, b1, c1] = quartile_rows(l);
                     // the (up to three) entries that leave / enter the windows Q2 = series[l/4 : l/2], Q4 = series[3l/4 : l]: old rows of the
                     // log, i.e. HBM round trips -- fetched one sample ahead (below), so that they travel during the proposals of a step
                     // instead of standing on this wave's path (samples below 8 read them in place: their rows are only just written)
@@ -827,17 +827,7 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
                         vb = b1 != b0 ? mylog[(size_t)(b_burn + b0) * lN] : 0u;
                         va = a1 != a0 ? mylog[(size_t)(b_burn + a0) * lN] : 0u;
                     }
-                    if constexpr (ALPHA) {
-                        sumB += v0 & 0xFFFFu; sumBxy += v0 >> 16;
-                        sumB -= vc & 0xFFFFu; sumBxy -= vc >> 16;
-                        sumA += vb & 0xFFFFu; sumAxy += vb >> 16;
-                        sumA -= va & 0xFFFFu; sumAxy -= va >> 16;
-                    } else {
-                    sumB += n0;
-                    sumB -= vc;
-                    sumA += vb;
-                    sumA -= va;
-                    }
+                    window_update<ALPHA>(v0, vc, vb, va, sumA, sumB, sumAxy, sumBxy);
                     {   // ... and the next sample's (the burn-in is over: its offset stays)
                         const uint32_t l2 = l + 1u;
                         const uint32_t a2 = l2 >> 2, b2 = l2 >> 1, c2 = (3u * l2) >> 2;
@@ -850,14 +840,8 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
                     b_burn++;                                                    // resulting_burn_in, :71
                 }
                 if (b_tops0 >= a.TOPS) {                                         // :74
-                    const uint32_t l = b_samples ? b_samples : 1u;
-                    const uint32_t den2 = (l >> 1) - (l >> 2), den4 = l - ((3u * l) >> 2);
-                    bool accept = false;                                         // empty slice -> nan -> not accepted
-                    if (b_samples && den2 && den4) {
-                        if constexpr (ALPHA) accept = alpha_series_close(sumA, sumAxy, den2, sumB, sumBxy, den4, a.alpha, a.eps);   // decoders_biasednoise.py:229-238
-                        else accept = fabs((double)sumA / (double)den2 - (double)sumB / (double)den4) < a.eps;   // :96-102
-                    }
-                    if (accept) {
+                    const bool accept = criterion_accepts<ALPHA>(b_samples, sumA, sumAxy, sumB, sumBxy, a.alpha, a.eps);
+                    if (accept) {                                                // (pteq_book.hpp's streak_ends, in place: the call changes resource rows)
                         if (b_cstreak >= a.SEQ) { ended = true; conv_ok = 1; }   // :77-78
                         else b_cstreak = b_tops0 - b_cstart;                     // :79
                     } else {
@@ -871,7 +855,7 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
                 if (pending) pending -= 1;                                       // (a lane between two ladders: the steps it idles are not booked)
                 uint32_t give = kWuKeep;
                 const uint64_t em = __ballot(ended);
-                if (ended) {
+                if (ended) {    // (pteq_book.hpp's store_class_column / store_ladder_results, in place: the calls change resource rows)
                     // ---- a ladder that ended writes its results at once; its lane takes the workgroup's next one -- in lane order
                     // among the lanes that end at the same step, so the assignment does not depend on timing
                     const uint64_t row = (uint64_t)bk[768] / a.replicas;
@@ -1072,19 +1056,11 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_wu_kernel(const LadderArgs 
             else if (a.accumulate) a.counts[s0 * ncls + i] += v;
             else a.counts[s0 * ncls + i] = v;
         }
-    if (slot == 0 && live && R > 1) {
-        const uint64_t row = (s0 + lane) / R;
-        if (a.samples != nullptr) atomicAdd(a.samples + row, samples);
-        if (a.tops0 != nullptr) atomicAdd(a.tops0 + row, tops0);
-        if (a.steps_done != nullptr) atomicMax(a.steps_done + row, done ? steps_done : (uint32_t)a.nsteps);
-        if (a.converged != nullptr && !conv_ok) a.converged[row] = 0;
-    } else if (slot == 0 && live) {
-        if (a.samples != nullptr) a.samples[s0 + lane] = a.accumulate ? a.samples[s0 + lane] + samples : samples;
-        if (a.steps_done != nullptr) a.steps_done[s0 + lane] = done ? steps_done : (uint32_t)a.nsteps;
-        if (a.converged != nullptr) a.converged[s0 + lane] = (uint8_t)conv_ok;
-        if (a.tops0 != nullptr) a.tops0[s0 + lane] = tops0;
-        if (a.flags != nullptr)
-            for (int c = 0; c < NC; ++c) a.flags[(s0 + lane) * NC + c] = (uint8_t)(rec[c * 64 + lane] >> 31);
+    if (slot == 0 && live) {
+        store_ladder_results(a.samples, a.tops0, a.steps_done, a.converged, R > 1 ? (s0 + lane) / R : s0 + lane, R, a.accumulate != 0, samples, tops0,
+                             done ? steps_done : (uint32_t)a.nsteps, conv_ok != 0);
+        if (R <= 1 && a.flags != nullptr)
+            for (int c = 0; c < NC; ++c) a.flags[(s0 + lane) * NC + c] = (uint8_t)info_flag(rec[c * 64 + lane]);
     }
     if (a.write_states && a.states != nullptr) {
         // (the words the exchange buffer holds: all of them, or -- 32-word kernels -- the lower half, then the upper one)
