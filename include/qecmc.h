@@ -308,6 +308,32 @@ int qecmc_plan_set_stats(qecmc_plan *plan, void *d_swap_accepts, void *d_nerr_su
  * step0 = 0 (Ladder.__init__, mcmc.py:72-77); chunked runs then reproduce one long run bit for bit.  conv_mode must be NONE. */
 int qecmc_pteq_resume_dev(qecmc_plan *plan, void *d_states, void *d_flags, void *d_tops0, uint64_t N,
                           uint32_t first_syndrome, uint64_t step0, void *d_counts, void *d_samples, void *hip_stream);
+/* The same for a plan with conv_mode error_based: params->steps more ladder steps of a run that stops each ladder by the
+ * criterion (decoders.py:74-105), cut anywhere -- every stop decision and the step it is taken at are those of the one long run.
+ * Beside the state of qecmc_pteq_resume_dev the caller holds
+ *   d_record     the criterion's per-ladder record (window sums, streak, burn-in, sample count, done flag), record_bytes of
+ *                qecmc_plan_resume_conv_bytes(); all zero together with step0 = 0 is a fresh run.  Opaque otherwise: its words are
+ *                the kernels' own (some are unused by some kernels); read the run's state from the five outputs below;
+ *   d_workspace  the log, log_rows rows of [ceil64(N)] uint16 (alpha noise: uint32), row = the ladder's absolute step, so a longer
+ *                run appends rows: log_bytes of qecmc_plan_resume_conv_bytes(); step0 + steps <= log_rows;
+ *   d_neff       uint32[N][Nc], the slots' n_eff attributes as n_z | (n_x + n_y) << 16 (alpha noise; NULL otherwise); a fresh ladder: the
+ *                counts of init in every rung.
+ * d_counts is ADDED to; d_samples, d_tops0, d_steps_done (absolute) and d_converged are the run's totals so far.  A ladder that has
+ * stopped keeps its rows of all five; its d_states / d_flags rows are unspecified from then on.
+ * scan = random (every rule) and scan = sweep; replicas <= 1; never on the work queue.  Where a fresh launch of the plan runs a kernel that
+ * draws the top chain's Philox blocks ahead (3 .. 8 rungs with more than a third of a CU's LDS per workgroup, e.g. toric L >= 12 at Nc = 8,
+ * rotated L = 21), the continued launch runs the same kernel without them (as under QECMC_FLAG_NO_PRE): the same results, 20 % more
+ * kernel time at toric L = 15, Nc = 8 (profiles/r06_conv_resume_ab.json).
+ * Refused before any launch:
+ * conv_mode NONE, replicas > 1, a NULL or undersized buffer, step0 + steps > log_rows (QECMC_ERR_INVALID); scan = wave / colour
+ * (QECMC_ERR_UNSUPPORTED); no HIP device (QECMC_ERR_NO_DEVICE). */
+int qecmc_plan_resume_conv_bytes(const qecmc_plan *plan, uint64_t N, uint64_t log_rows, uint64_t *record_bytes_out,
+                                 uint64_t *log_bytes_out);
+int qecmc_pteq_resume_conv_dev(qecmc_plan *plan, void *d_states, void *d_flags, void *d_tops0, uint64_t N,
+                               uint32_t first_syndrome, uint64_t step0, void *d_counts, void *d_samples,
+                               void *d_steps_done, void *d_converged, void *d_record, uint64_t record_bytes,
+                               void *d_neff /*alpha noise only*/, void *d_workspace, uint64_t workspace_bytes,
+                               uint64_t log_rows, void *hip_stream);
 /* Host-pointer qecmc_pteq_batch with the observables of qecmc_plan_set_stats (swap_accepts_out uint32[N][Nc-1],
  * nerr_sums_out uint32[N][Nc]; either nullable). */
 int qecmc_pteq_batch_stats(const qecmc_params *params, const uint8_t *init, uint64_t N, uint32_t *counts_out,

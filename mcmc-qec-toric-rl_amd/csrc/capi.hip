@@ -706,6 +706,60 @@ int qecmc_pteq_resume_dev(qecmc_plan *plan, void *d_states, void *d_flags, void 
     return 0;
 }
 
+int qecmc_plan_resume_conv_bytes(const qecmc_plan *plan, uint64_t N, uint64_t log_rows, uint64_t *record_bytes_out, uint64_t *log_bytes_out)
+{
+    if (!plan || !record_bytes_out || !log_bytes_out) return fail(QECMC_ERR_INVALID, "NULL argument");
+    const ResumeConvBytes need = resume_conv_need(plan->prm, N, log_rows);
+    *record_bytes_out = need.record;
+    *log_bytes_out = need.log;
+    return 0;
+}
+
+int qecmc_pteq_resume_conv_dev(qecmc_plan *plan, void *d_states, void *d_flags, void *d_tops0, uint64_t N, uint32_t first_syndrome,
+                               uint64_t step0, void *d_counts, void *d_samples, void *d_steps_done, void *d_converged, void *d_record,
+                               uint64_t record_bytes, void *d_neff, void *d_workspace, uint64_t workspace_bytes, uint64_t log_rows,
+                               void *hip_stream)
+{
+    if (!plan) return fail(QECMC_ERR_INVALID, "plan is NULL");
+    if (int rc = report(resume_conv_check(plan->prm))) return rc;
+    if (qecmc_device_count() <= 0) return fail(QECMC_ERR_NO_DEVICE, "no HIP device visible: libqecmc has no CPU fallback");
+    if (N == 0) return 0;
+    if (!d_states || !d_flags || !d_tops0 || !d_counts || !d_samples || !d_steps_done || !d_converged || !d_record || !d_workspace)
+        return fail(QECMC_ERR_INVALID, "NULL device buffer");
+    const bool alpha = plan->args.noise == QECMC_NOISE_ALPHA;
+    if (alpha != (d_neff != nullptr)) return fail(QECMC_ERR_INVALID, "d_neff carries the alpha-noise ladders' n_eff attributes: needed by them, NULL otherwise");
+    if (N + first_syndrome > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "global syndrome index exceeds 32 bits");
+    const uint64_t steps = plan->prm.steps;
+    if (step0 + steps < step0 || step0 + steps > log_rows)
+        return fail(QECMC_ERR_INVALID, "step0 + steps = %llu + %llu exceeds the log's %llu rows (row = absolute ladder step: grow the log by appending rows)",
+                    (unsigned long long)step0, (unsigned long long)steps, (unsigned long long)log_rows);
+    if (step0 + steps > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "step0 + steps exceeds the 32-bit step count of steps_done");
+    const ResumeConvBytes need = resume_conv_need(plan->prm, N, log_rows);
+    if (workspace_bytes < need.log)
+        return fail(QECMC_ERR_INVALID, "workspace of %llu bytes, a log of %llu rows takes %llu (qecmc_plan_resume_conv_bytes)",
+                    (unsigned long long)workspace_bytes, (unsigned long long)log_rows, (unsigned long long)need.log);
+    if (record_bytes < need.record)
+        return fail(QECMC_ERR_INVALID, "criterion records of %llu bytes, %llu ladders take %llu (qecmc_plan_resume_conv_bytes)",
+                    (unsigned long long)record_bytes, (unsigned long long)N, (unsigned long long)need.record);
+    LadderArgs a = plan->args;
+    a.states = static_cast<uint8_t *>(d_states); a.flags = static_cast<uint8_t *>(d_flags); a.tops0 = static_cast<uint32_t *>(d_tops0);
+    a.counts = static_cast<uint32_t *>(d_counts); a.samples = static_cast<uint32_t *>(d_samples);
+    a.steps_done = static_cast<uint32_t *>(d_steps_done); a.converged = static_cast<uint8_t *>(d_converged);
+    a.crec = static_cast<uint32_t *>(d_record); a.neff = static_cast<uint32_t *>(d_neff);
+    a.nlog = static_cast<uint16_t *>(d_workspace);
+    a.N = N; a.first_syndrome = first_syndrome;
+    a.step0 = step0; a.prop0 = step0 * plan->prm.iters; a.nsteps = steps;
+    a.resume = 1; a.write_states = 1; a.accumulate = 1;
+    a.queue = nullptr; a.grid_cap = 0;                   // (never the work queue: its lanes run several ladders)
+    // (the PRE kernels have no register to spare for the record: a continued launch runs the same kernel without PRE -- the same results)
+    a.tune |= QECMC_FLAG_NO_PRE;
+    if (const KernelKey k = choose_kernel(kernel_shape(a)); !k.ok() || k.family != kFamLadder || (k.flags & (kPre | kQueue)) || !(k.flags & kConv))
+        return fail(QECMC_ERR_UNSUPPORTED, "no criterion kernel that carries its record for this plan%s%s", k.why ? ": " : "", k.why ? k.why : "");
+    if (steps == 0) return 0;
+    HIP_TRY(launch_ladder(a, static_cast<hipStream_t>(hip_stream)));
+    return 0;
+}
+
 int qecmc_pteq_batch(const qecmc_params *params, const uint8_t *init, uint64_t N, uint32_t *counts_out,
                      uint32_t *samples_out, uint32_t *tops0_out, uint32_t *steps_done_out, uint8_t *converged_out,
                      uint8_t *final_states_out, qecmc_stats *stats_out)

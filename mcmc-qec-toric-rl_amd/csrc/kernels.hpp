@@ -99,7 +99,18 @@ struct LadderArgs {
     // equilibrium observables (qecmc_plan_set_stats; nullable): accepted swaps per rung pair, sum of error counts per rung
     uint32_t *swap_acc;       // [N][Nc-1]
     uint32_t *nerr_sum;       // [N][Nc]
+    // criterion runs continued from device state (qecmc_pteq_resume_conv_dev; nullable): one record per ladder, loaded by wave 0 before
+    // the step loop and stored behind it; all zero = a ladder that has not started
+    uint32_t *crec;           // [N][conv_record_words(noise)]
 };
+
+// The per-ladder criterion record of a continued run, in 32-bit words (sums: low word first).  The alpha rule's second pair of window sums
+// follows the first; the other rules' records end before it.
+enum ConvRecWord : int {
+    kRecSamples = 0, kRecBurn, kRecConvStart, kRecConvStreak, kRecDone, kRecConvOk, kRecStepsDone, kRecReserved, kRecSumA = 8, kRecSumB = 10,
+    kRecWords = 12, kRecSumAxy = 12, kRecSumBxy = 14, kRecWordsAlpha = 16,
+};
+__host__ __device__ constexpr int conv_record_words(int noise) { return noise == 2 ? kRecWordsAlpha : kRecWords; }
 
 hipError_t launch_ladder(const LadderArgs &a, hipStream_t stream);     // ladder_rs.hip: the kernel choose_kernel() picks for kernel_shape(a) (plan_host.hpp), on its grid
 // the instantiation units, one per kernel family (built in parallel): the kernel of `k` if the unit builds it, else nullptr -- ladder_kernel

@@ -241,6 +241,38 @@ __device__ inline bool alpha_flip(uint32_t x, uint32_t hi, uint32_t lo, double a
 #define QECMC_STAMP(k) ((void)0)
 #endif
 
+// A criterion run continued from device state (a.crec): wave 0 takes the criterion of lane ln's ladder up where the last launch left it -- window sums,
+// streak, burn-in, series length, done flag; the series itself is in the log, rows = absolute ladder steps -- and leaves it for the next.  A scalar base
+// and a 32-bit lane offset.  Without a queue a ladder is done by the criterion only: done and conv_ok are one value.  (Macros, expanded where the kernel
+// uses them: as lambdas they changed the resource rows of kernels that never call them.)
+#define QECMC_LOAD_RECORD(ln)                                                                                                      \
+    do {                                                                                                                           \
+        const rec_t *rec = a.crec + s0 * kRecW + (uint32_t)(ln) * (uint32_t)kRecW;                                                 \
+        if constexpr (kLdsCounters) ctrS[ln] = rec[kRecSamples];                                                                   \
+        else samples = rec[kRecSamples];                                                                                           \
+        burn = rec[kRecBurn]; conv_start = rec[kRecConvStart]; conv_streak = rec[kRecConvStreak];                                  \
+        done = rec[kRecDone]; conv_ok = done;                                                                                      \
+        if constexpr (!kStepsOut) steps_done = rec[kRecStepsDone];                                                                 \
+        sumA = rec[kRecSumA] | ((uint64_t)rec[kRecSumA + 1] << 32); sumB = rec[kRecSumB] | ((uint64_t)rec[kRecSumB + 1] << 32);    \
+        if constexpr (alpha_noise) {                                                                                               \
+            sumAxy = rec[kRecSumAxy] | ((uint64_t)rec[kRecSumAxy + 1] << 32); sumBxy = rec[kRecSumBxy] | ((uint64_t)rec[kRecSumBxy + 1] << 32); \
+        }                                                                                                                          \
+    } while (0)
+#define QECMC_STORE_RECORD(ln)                                                                                                     \
+    do {                                                                                                                           \
+        rec_t *rec = a.crec + s0 * kRecW + (uint32_t)(ln) * (uint32_t)kRecW;                                                       \
+        if constexpr (kLdsCounters) rec[kRecSamples] = ctrS[ln];                                                                   \
+        else rec[kRecSamples] = samples;                                                                                           \
+        rec[kRecBurn] = burn; rec[kRecConvStart] = conv_start; rec[kRecConvStreak] = conv_streak;                                  \
+        rec[kRecDone] = done; rec[kRecConvOk] = conv_ok;                                                                           \
+        if constexpr (!kStepsOut) rec[kRecStepsDone] = steps_done;                                                                 \
+        rec[kRecSumA] = (uint32_t)sumA; rec[kRecSumA + 1] = (uint32_t)(sumA >> 32); rec[kRecSumB] = (uint32_t)sumB; rec[kRecSumB + 1] = (uint32_t)(sumB >> 32); \
+        if constexpr (alpha_noise) {                                                                                               \
+            rec[kRecSumAxy] = (uint32_t)sumAxy; rec[kRecSumAxy + 1] = (uint32_t)(sumAxy >> 32);                                    \
+            rec[kRecSumBxy] = (uint32_t)sumBxy; rec[kRecSumBxy + 1] = (uint32_t)(sumBxy >> 32);                                    \
+        }                                                                                                                          \
+    } while (0)
+
 template <int MAXT, int MINW, int CODE, uint32_t FLAGS>
 __global__ __launch_bounds__(MAXT, MINW) void ladder_kernel(const LadderArgs a)
 {
@@ -321,6 +353,20 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_kernel(const LadderArgs a)
     [[maybe_unused]] uint32_t qi = (uint32_t)s0 + (uint32_t)lane;      // QUEUE: that ladder's index in this launch (0xFFFFFFFF: none left)
     [[maybe_unused]] uint32_t t0 = 0;                                  // ... the workgroup step it started at
     [[maybe_unused]] uint64_t kq = 0;                                  // ... t0 * iters: its proposal indices are (t * iters + j) - kq
+    // a criterion run continued from device state (a.crec): a workgroup whose ladders had all stopped has nothing to do -- every wave sees that
+    [[maybe_unused]] constexpr int kRecW = conv_record_words((BIASED && ALPHA) ? 2 : 0);
+    // (the 64-VGPR instantiations move a record one dword at a time straight between memory and its registers -- volatile: no vector access to put together
+    // or take apart in registers they do not have; the others as the compiler likes)
+    typedef typename std::conditional<(MINW >= 8), volatile uint32_t, uint32_t>::type rec_t;
+    // ... and write a ladder's step count out at the step the criterion stops it, instead of keeping it in a register until the launch ends
+    [[maybe_unused]] constexpr bool kStepsOut = CONV && !QUEUE && MINW >= 8;
+    // The record is loaded and stored in cold blocks of the step loop's first and last step, so that the loop is entered and left with what a fresh run
+    // enters and leaves it with.  Not in the PRE instantiations, whose blocks drawn ahead leave no register for it: a continued launch sets the
+    // QECMC_FLAG_NO_PRE bit of a.tune, and the choice then names the same kernel without PRE (the same results, kernel_choice.hpp).
+    [[maybe_unused]] constexpr bool kCarry = CONV && !QUEUE && !PRE;
+    if constexpr (kCarry) {
+        if (a.crec != nullptr && __all(lane >= cnt || a.crec[(s0 + lane) * kRecW + kRecDone] != 0)) return;
+    }
 
     for (int i = tid; i < NC * W * 64; i += nthreads) st[i] = 0;
     for (int i = tid; i < ncls * 64; i += nthreads) hist[i] = 0;
@@ -1648,6 +1694,11 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_kernel(const LadderArgs a)
             n = mine & 0xFFFFu; sid = (mine >> 16) & 0xFFu; cls = (mine >> 24) & 0x3Fu; flag = mine >> 31;   // (info_*, in place as above)
             QECMC_STAMP(4);
             if ((int)slot_u == NC - 1) flag = 1;                                    // chains[-1].flag = 1, mcmc.py:100
+            if constexpr (kCarry) {
+                // a continued criterion run (a.crec): at its first step wave 0 takes the criterion up where the last launch left it.  (Here, not ahead
+                // of the loop: its variables start as the constants they are in a fresh run, and the load is a cold block behind a scalar test.)
+                if (wave_u == 0 && t == 0 && a.crec != nullptr && lane_t < cnt) { QECMC_LOAD_RECORD(lane_t); }
+            }
             if (wave_u == 0 && !done) {                                             // ladder + PTEQ bookkeeping on slot 0's new state
                 if constexpr (kLdsCounters) { tops0 = ctrT[lane_t]; samples = ctrS[lane_t]; }
                 tops0 += (NC == 1) | (car >> 31);                                   // chains[0].flag == 1, :101-102
@@ -1664,7 +1715,7 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_kernel(const LadderArgs a)
                         log_t *mylog = reinterpret_cast<log_t *>(a.nlog) + (s0 + lane_t);
                         uint32_t v0 = n0;
                         if constexpr (alpha_noise) v0 = neffb[(t & 1) * NC * 64 + lane_t];
-                        mylog[(size_t)(t - t0) * lN] = (log_t)v0;
+                        mylog[(size_t)(QUEUE ? t - t0 : a.step0 + t) * lN] = (log_t)v0;         // (a continued run: the ladder's absolute step)
                         const auto [a0, b0, c0, a1, b1, c1] = quartile_rows(samples);
                         const uint32_t vc = c1 != c0 ? mylog[(size_t)(burn + c0) * lN] : 0u;
                         const uint32_t vb = b1 != b0 ? mylog[(size_t)(burn + b0) * lN] : 0u;
@@ -1677,7 +1728,16 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_kernel(const LadderArgs a)
                 if (CONV && tops0 >= a.TOPS) {                               // :74
                     const bool accept = criterion_accepts<alpha_noise>(samples, sumA, sumAxy, sumB, sumBxy, a.alpha, a.eps);
                     if (accept) {                                                   // (pteq_book.hpp's streak_ends, in place: the call changes resource rows)
-                        if (conv_streak >= a.SEQ) { done = 1; conv_ok = 1; steps_done = (uint32_t)(t - t0) + 1; }   // :77-78
+                        if (conv_streak >= a.SEQ) {                                    // :77-78
+                            done = 1; conv_ok = 1;
+                            if constexpr (!kStepsOut) steps_done = (uint32_t)(QUEUE ? t - t0 : a.step0 + t) + 1;
+                            else if (a.steps_done != nullptr && lane_t < cnt) {
+                                // (kStepsOut: the step count goes out here, once)
+                                const uint32_t sd = (uint32_t)(a.step0 + t) + 1;
+                                if (R > 1) atomicMax(a.steps_done + (s0 + lane_t) / R, sd);
+                                else a.steps_done[s0 + lane_t] = sd;
+                            }
+                        }
                         else conv_streak = tops0 - conv_start;                      // :79
                     } else {
                         conv_streak = 0;                                            // :81-82
@@ -1719,7 +1779,15 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_kernel(const LadderArgs a)
                     f0[2 + ((t + 1) & 1)] = (!q_empty && __any(done && !q_dead) && ((t + 2) % q_period) == 0) ? 1u : 0u;
                 }
             } else
-            if (CONV && wave_u == 0 && __all(done || lane_t >= cnt)) stopf[(t + 1) & 1] = 1;
+            if (CONV && wave_u == 0) {
+                const bool all_done = __all(done || lane_t >= cnt);
+                if (all_done) stopf[(t + 1) & 1] = 1;
+                if constexpr (kCarry) {
+                    // ... and leaves it for the next launch at the end of the step that ends this one: the last, or the one that raised the stop flag
+                    // (the step's own tests first: a fresh run does not look at a.crec in any other step)
+                    if ((all_done || t + 1 == a.nsteps) && a.crec != nullptr && lane_t < cnt) { QECMC_STORE_RECORD(lane_t); }
+                }
+            }
             if (slot_u == 0) flag = 0;                                              // :103
             if constexpr (USET) {
                 const bool cm = a.uset_conv_mult != 0.0;
@@ -1880,12 +1948,14 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_kernel(const LadderArgs a)
         const uint64_t row = (s0 + lane_e) / R;
         if (a.samples != nullptr) atomicAdd(a.samples + row, samples);
         if (a.tops0 != nullptr) atomicAdd(a.tops0 + row, tops0);
-        if (a.steps_done != nullptr) atomicMax(a.steps_done + row, done ? steps_done : (uint32_t)a.nsteps);
+        if (a.steps_done != nullptr && !(kStepsOut && done)) atomicMax(a.steps_done + row, done ? steps_done : (uint32_t)a.nsteps);   // (kStepsOut: a ladder the criterion stopped wrote its step then)
         if (a.converged != nullptr && !conv_ok) a.converged[row] = 0;               // the caller presets 1: all R ladders converged
     } else
     if (slot_e == 0 && lane_e < cnt) {
-        if (a.samples != nullptr) a.samples[s0 + lane_e] = a.accumulate ? a.samples[s0 + lane_e] + samples : samples;
-        if (a.steps_done != nullptr) a.steps_done[s0 + lane_e] = USET ? (cm_done ? cm_steps : (uint32_t)a.nsteps) : done ? steps_done : (uint32_t)a.nsteps;
+        // (a continued criterion run carries its totals: `samples` is the series' length, and a ladder that goes on has run step0 + nsteps steps)
+        [[maybe_unused]] const bool carried = kCarry && a.crec != nullptr;
+        if (a.samples != nullptr) a.samples[s0 + lane_e] = (a.accumulate && !carried) ? a.samples[s0 + lane_e] + samples : samples;
+        if (a.steps_done != nullptr && !(kStepsOut && done)) a.steps_done[s0 + lane_e] = USET ? (cm_done ? cm_steps : (uint32_t)a.nsteps) : done ? steps_done : (uint32_t)((CONV ? a.step0 : 0u) + a.nsteps);
         if (a.converged != nullptr) a.converged[s0 + lane_e] = (uint8_t)conv_ok;
         if (a.tops0 != nullptr) a.tops0[s0 + lane_e] = tops0;
         if (a.flags != nullptr)

@@ -317,4 +317,29 @@ inline uint64_t workspace_need(const qecmc_params &prm, uint32_t queue_grid, uin
     return (prm.noise == QECMC_NOISE_ALPHA ? 4ull : 2ull) * cols * prm.steps;
 }
 
+// THE sizes of a criterion run continued from device state (qecmc_pteq_resume_conv_dev): the per-ladder criterion records (kernels.hpp,
+// ConvRecWord) and a log of `log_rows` rows, row = the ladder's absolute step, in the layout of workspace_need() without a queue.  Both 0
+// for a plan without the criterion.
+struct ResumeConvBytes { uint64_t record, log; };
+inline ResumeConvBytes resume_conv_need(const qecmc_params &prm, uint64_t N, uint64_t log_rows)
+{
+    if (prm.conv_mode != QECMC_CONV_ERROR_BASED) return {0, 0};
+    qecmc_params one = prm;
+    one.replicas = 0;
+    one.steps = log_rows;
+    return {sizeof(uint32_t) * (uint64_t)conv_record_words(prm.noise) * N, workspace_need(one, 0, N, false)};
+}
+// what qecmc_pteq_resume_conv_dev refuses of a plan, before it looks at a buffer
+inline Refusal resume_conv_check(const qecmc_params &prm)
+{
+    if (prm.conv_mode != QECMC_CONV_ERROR_BASED)
+        return refuse_params(QECMC_ERR_INVALID, "qecmc_pteq_resume_conv_dev continues criterion runs: conv_mode must be error_based (fixed-length chunks: qecmc_pteq_resume_dev)");
+    if (prm.scan == QECMC_SCAN_WAVE)
+        return refuse_params(QECMC_ERR_UNSUPPORTED, "scan = wave runs the criterion on its persistent grid, where a ladder's lane is reused when it has stopped: no continuation from device state");
+    if (prm.scan == QECMC_SCAN_COLOUR)
+        return refuse_params(QECMC_ERR_UNSUPPORTED, "scan = colour starts its ladders from seed configurations: no chunked continuation");
+    if (prm.replicas > 1) return refuse_params(QECMC_ERR_INVALID, "qecmc_pteq_resume_conv_dev continues single ladders: replicas must be <= 1");
+    return {};
+}
+
 }  // namespace qecmc

@@ -129,5 +129,18 @@ int qt_plan_equal(const qecmc_params *pa, const qecmc_params *pb)
            a.queue_family == b.queue_family && a.queue_per_cu == b.queue_per_cu;
 }
 uint64_t qt_workspace_need(const qecmc_params *p, uint32_t grid, uint64_t N, int queue) { return workspace_need(*p, grid, N, queue != 0); }
+// resume_conv_need(): the record and log bytes of a continued criterion run; resume_conv_check(): the QECMC_ERR_* code of the plan's refusal (0: accepted)
+void qt_resume_conv_bytes(const qecmc_params *p, uint64_t N, uint64_t log_rows, uint64_t *record_bytes, uint64_t *log_bytes)
+{
+    const ResumeConvBytes need = resume_conv_need(*p, N, log_rows);
+    *record_bytes = need.record;
+    *log_bytes = need.log;
+}
+int qt_resume_conv_check(const qecmc_params *p, char *msg, int msg_cap)
+{
+    const Refusal r = resume_conv_check(*p);
+    if (msg && msg_cap > 0) std::snprintf(msg, (size_t)msg_cap, "%s", r.msg.c_str());
+    return r.code;
+}
 int qt_launch_takes_queue(uint32_t grid, uint64_t steps, int wants_states_or_stats) { return launch_takes_queue(grid, steps, wants_states_or_stats != 0); }
 }

@@ -93,9 +93,10 @@ def PTEQ(init_code, p, Nc=None, SEQ=2, TOPS=10, tops_burn=2, eps=0.1, steps=5000
     """Drop-in for decoders.PTEQ (decoders.py:25): same arguments, returns the uint8 percent vector of
     the equivalence classes.  With the convergence criterion the run is issued with a growing horizon (2^20
     ladder steps, x16 until it converges or `steps` is reached) so that the default `steps = 5e7` never allocates
-    a 5e7-entry error-count log up front.  Philox is counter-based, so a longer horizon replays the same
-    trajectory: the answer equals that of a single run with the full `steps`; a ladder that stops within the first
-    horizon -- every default-criterion run measured -- is one launch with no repeated step (decoders.LAST_RUN).
+    a 5e7-entry error-count log up front.  On scan="random" / "sweep" with one ladder per call the ladder stays on the device and
+    a run that outlasts a horizon is continued from where it stands (qecmc_pteq_resume_conv_dev: no step runs twice).  Otherwise --
+    scan="colour" / "wave", replicas > 1 -- the longer horizon replays the same trajectory from step 0 (Philox is counter-based).
+    Either way the answer equals that of a single run with the full `steps` (decoders.LAST_RUN tells what happened).
 
     The reference decodes ONE syndrome per call (generate_data.py:136) with one ladder, which occupies one lane of each of the
     Nc wavefronts; that is the default here too (PTEQ_REPLICAS = 1).  `replicas=R` runs R independent ladders -- each with the
@@ -140,6 +141,26 @@ def _pteq(init_code, p, eta, Nc, SEQ, TOPS, tops_burn, eps, steps, iters, conv_c
     # x4, up to a third).  LAST_RUN tells what happened.
     horizon = min(int(steps), PTEQ_FIRST_HORIZON)
     launches = replayed = 0
+    if scan in ("random", "sweep") and kw["replicas"] <= 1:
+        # one ladder whose state stays on the device (harness.LadderRun, qecmc_pteq_resume_conv_dev): a ladder that outlasts a horizon is continued
+        # from where it stands -- the same trajectory and the same stop as the replay below, and no step runs twice.  The log grows with the horizon.
+        from .harness import LadderRun
+        run = LadderRun(init_code.qubit_matrix, p, Nc=kw["Nc"], iters=iters, tops_burn=tops_burn, p_logical=0.5, seed=seed, code=kw["code"],
+                        eta=eta, alpha=alpha, conv_criteria=conv_criteria, SEQ=SEQ, TOPS=TOPS, eps=eps, scan=scan, log_rows=horizon)
+        try:
+            while True:
+                run.advance(horizon - run.steps)
+                launches += 1
+                res = run.snapshot()
+                if res["converged"][0] or horizon >= int(steps):
+                    break
+                horizon = min(int(steps), horizon * PTEQ_HORIZON_GROWTH)
+        finally:
+            run.close()
+        LAST_RUN.update(launches=launches, horizon=horizon, steps_done=int(res["steps_done"][0]), replayed_steps=0)
+        if not res["converged"][0]:
+            print('\n\nWARNING: PTEQ hit max number of steps before convergence:\t', horizon, '\n\n')
+        return percent_from_counts(res["counts"], res["samples"])[0]
     while True:
         res = pteq_batch(init_code.qubit_matrix, p, steps=horizon, conv_criteria=conv_criteria, SEQ=SEQ, TOPS=TOPS,
                          eps=eps, **kw)

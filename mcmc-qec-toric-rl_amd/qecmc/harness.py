@@ -384,23 +384,52 @@ def threshold_curve(params, p_list, n, seed=0, **gen_kw):
                 frac_sampled=np.array(frac_s), err_binomial=np.array(err_b), err_sampled_binomial=np.array(err_sb), err_method=how)
 
 
+def grown_log_rows(log_rows, steps_done, steps, growth=2):
+    """The log of a criterion `LadderRun` before a chunk of `steps` ladder steps behind `steps_done`: (rows it must have, rows to carry over).
+    Rows are absolute ladder steps, so the log grows by appending rows: geometrically (x `growth`), at least to steps_done + steps; the
+    steps_done rows written so far are copied into the new buffer.  (log_rows, 0): it is large enough as it is."""
+    log_rows, steps_done, steps = int(log_rows), int(steps_done), int(steps)
+    need = steps_done + steps
+    if need <= log_rows:
+        return log_rows, 0
+    return max(need, int(growth) * log_rows), min(steps_done, log_rows)
+
+
+def packed_neff(states):
+    """uint8[..., nq] Pauli configurations -> uint32[...]: n_z | (n_x + n_y) << 16, the form the alpha-noise ladders carry their
+    n_eff attributes in (Chain_alpha.__init__, mcmc_alpha.py:18-22)"""
+    a = np.asarray(states)
+    return ((a == 3).sum(axis=-1).astype(np.uint32) | (((a == 1) | (a == 2)).sum(axis=-1).astype(np.uint32) << 16))
+
+
 class LadderRun:
     """N ladders resident in HBM, advanced in chunks by qecmc_pteq_resume_dev: chunked runs reproduce one long run bit for
     bit (Philox is addressed by the steps already done), so a 10^6-sweep study costs one pass, checkpoints are free, and no
-    single launch runs for minutes.  Device memory through torch (plumbing)."""
+    single launch runs for minutes.  Device memory through torch (plumbing).
+
+    conv_criteria="error_based" (with SEQ, TOPS, eps; alpha for the alpha rule; scan "random" or "sweep") runs the reference's stopping
+    rule instead (qecmc_pteq_resume_conv_dev): every ladder stops where the one long criterion run stops it, whatever the chunks.  The
+    criterion's per-ladder records and its log live here too; the log starts with `log_rows` rows (default: the first chunk) and grows
+    geometrically (grown_log_rows)."""
 
     def __init__(self, init, p, Nc=None, iters=10, tops_burn=2, p_logical=0.5, seed=0, first_syndrome=0, device=0,
-                 code=L_.TORIC, eta=None):
+                 code=L_.TORIC, eta=None, conv_criteria=None, SEQ=2, TOPS=10, eps=0.1, alpha=None, scan="random", log_rows=None):
         import torch
+        if conv_criteria not in (None, "error_based"):
+            raise ValueError(f"conv_criteria={conv_criteria!r}: only None and 'error_based' exist for PTEQ")
         a, _ = L_.as_states(init, 3 if code in (L_.TORIC, L_.PLANAR) else 2)
         self.N, size = a.shape[0], a.shape[-1]
         self.Nc = Nc or size
         self.ncls = 16 if code == L_.TORIC else 4
         self.shape = a.shape[1:]
         nq = int(np.prod(self.shape))
+        self.conv = conv_criteria is not None
+        noise = L_.NOISE_ALPHA if alpha is not None else L_.NOISE_DEPOLARIZING if eta is None else L_.NOISE_BIASED
         self._mk = lambda steps: L_.make_params(code=code, L=size, Nc=self.Nc, p=float(p), p_logical=float(p_logical), iters=int(iters),
                                                 steps=int(steps), tops_burn=int(tops_burn), seed=seed, device=device,
-                                                noise=L_.NOISE_DEPOLARIZING if eta is None else L_.NOISE_BIASED, eta=float(eta or 0.0))
+                                                noise=noise, eta=float(eta or 0.0), alpha=float(alpha or 0.0), scan=L_.SCANS.get(scan, scan),
+                                                conv_mode=L_.CONV_ERROR_BASED if self.conv else L_.CONV_NONE, TOPS=int(TOPS), SEQ=int(SEQ),
+                                                eps=float(eps))
         self.first = int(first_syndrome)
         dev = torch.device("cuda", device)
         st = np.broadcast_to(a.reshape(self.N, 1, nq), (self.N, self.Nc, nq))            # Ladder.__init__, mcmc.py:72
@@ -413,27 +442,85 @@ class LadderRun:
         self.steps = 0
         self._plans = {}
         self._torch = torch
+        if self.conv:
+            self.steps_done = torch.zeros(self.N, dtype=torch.int32, device=dev)
+            self.converged = torch.zeros(self.N, dtype=torch.uint8, device=dev)
+            self.neff = torch.from_numpy(packed_neff(st).view(np.int32)).to(dev) if alpha is not None else None
+            self.record = None                                                           # (sized by the library: the first chunk's plan knows)
+            self.log = None
+            self.log_rows = 0
+            self._log_rows0 = None if log_rows is None else int(log_rows)
+
+    def _plan(self, steps):
+        import ctypes as C
+        if steps not in self._plans:
+            pl = C.c_void_p()
+            L_.check(L_.lib().qecmc_plan_create(self._mk(steps), C.byref(pl)))
+            self._plans[steps] = pl
+        return self._plans[steps]
+
+    def _sizes(self, plan, rows):
+        import ctypes as C
+        rec, log = C.c_uint64(), C.c_uint64()
+        L_.check(L_.lib().qecmc_plan_resume_conv_bytes(plan, self.N, int(rows), C.byref(rec), C.byref(log)))
+        return int(rec.value), int(log.value)
+
+    def _fit_log(self, plan, steps):
+        """the criterion's records (all zero: a fresh run) and a log that holds rows [0, self.steps + steps)"""
+        torch, dev = self._torch, self.states.device
+        if self.log is None:
+            rows = max(self._log_rows0 if self._log_rows0 is not None else steps, 1)
+            rec_b, log_b = self._sizes(plan, rows)
+            self.record = torch.zeros(rec_b, dtype=torch.uint8, device=dev)
+            self.log, self.log_rows = torch.empty(log_b, dtype=torch.uint8, device=dev), rows
+        rows, keep = grown_log_rows(self.log_rows, self.steps, steps)
+        if rows != self.log_rows:
+            new = torch.empty(self._sizes(plan, rows)[1], dtype=torch.uint8, device=dev)
+            keep_b = self._sizes(plan, keep)[1]
+            new[:keep_b].copy_(self.log[:keep_b])
+            self.log, self.log_rows = new, rows
 
     def advance(self, steps):
         import ctypes as C
         steps = int(steps)
         if steps <= 0:
             return self
-        if steps not in self._plans:
-            pl = C.c_void_p()
-            L_.check(L_.lib().qecmc_plan_create(self._mk(steps), C.byref(pl)))
-            self._plans[steps] = pl
+        plan = self._plan(steps)
         stream = self._torch.cuda.current_stream(self.states.device)
-        L_.check(L_.lib().qecmc_pteq_resume_dev(self._plans[steps], self.states.data_ptr(), self.flags.data_ptr(), self.tops0.data_ptr(),
-                                                self.N, self.first, self.steps, self.counts.data_ptr(), self.samples.data_ptr(),
-                                                C.c_void_p(stream.cuda_stream)))
+        if self.conv:
+            self._fit_log(plan, steps)
+            L_.check(L_.lib().qecmc_pteq_resume_conv_dev(
+                plan, self.states.data_ptr(), self.flags.data_ptr(), self.tops0.data_ptr(), self.N, self.first, self.steps,
+                self.counts.data_ptr(), self.samples.data_ptr(), self.steps_done.data_ptr(), self.converged.data_ptr(),
+                self.record.data_ptr(), self.record.numel(), None if self.neff is None else self.neff.data_ptr(),
+                self.log.data_ptr(), self.log.numel(), self.log_rows, C.c_void_p(stream.cuda_stream)))
+        else:
+            L_.check(L_.lib().qecmc_pteq_resume_dev(plan, self.states.data_ptr(), self.flags.data_ptr(), self.tops0.data_ptr(),
+                                                    self.N, self.first, self.steps, self.counts.data_ptr(), self.samples.data_ptr(),
+                                                    C.c_void_p(stream.cuda_stream)))
         self.steps += steps
+        return self
+
+    def run_until_converged(self, max_steps, chunk):
+        """Advance in chunks of `chunk` ladder steps until every ladder has converged or `max_steps` are done (criterion runs)."""
+        if not self.conv:
+            raise ValueError("run_until_converged needs conv_criteria='error_based'")
+        max_steps, chunk = int(max_steps), int(chunk)
+        if chunk <= 0:
+            raise ValueError("chunk must be positive")
+        while self.steps < max_steps:
+            self.advance(min(chunk, max_steps - self.steps))
+            if bool(self.converged.all().item()):
+                break
         return self
 
     def snapshot(self, states=False):
         self._torch.cuda.synchronize()
         out = dict(steps=self.steps, counts=self.counts.cpu().numpy().view(np.uint32), samples=self.samples.cpu().numpy().view(np.uint32),
                    tops0=self.tops0.cpu().numpy().view(np.uint32))
+        if self.conv:
+            out["steps_done"] = self.steps_done.cpu().numpy().view(np.uint32)
+            out["converged"] = self.converged.cpu().numpy().astype(bool)
         if states:
             out["states"] = self.states.cpu().numpy().reshape((self.N, self.Nc) + self.shape)
             out["flags"] = self.flags.cpu().numpy()
