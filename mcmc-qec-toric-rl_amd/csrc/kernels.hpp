@@ -23,7 +23,7 @@ struct LadderArgs {
     uint8_t *converged;       // [N]               out (nullable)
     uint16_t *nlog;           // [nsteps][N]       bottom-chain error counts (conv_mode workspace)
     const uint64_t *swap_thr; // [Nc-1][nq+1]      ceil(p_diff[i]^d * 2^32)
-    const uint32_t *lmask;    // [4][L+1][W]       logical-operator XOR masks (row L = identity)
+    const uint32_t *lmask;    // [4][L+1][W]       logical-operator XOR masks (row L = identity); scan = 3: in the wave layout (tables.hpp wave_position)
     const uint2 *gen;         // [(L-1)^2 + 2(L-1)]  xzzx / rotated generators: 4 x u16 (site << 2 | pauli), 0 = unused
     const double *bias_tbl;   // [Nc][4][nq+1]      px^n, py^n, pz^n, pI^n per rung (biased and alpha noise)
     // unique-chain set of the direct-counting estimators (PTDC_droplet, decoders.py:146-152), filled in-kernel after every
@@ -78,7 +78,7 @@ struct LadderArgs {
     uint32_t acc_thr[kMaxNc][4];   // ceil(f_c^dE * 2^32), dE = 1..4 (sweep mode: one 32-bit word per acceptance)
     uint64_t acc_thr44[kMaxNc][4]; // ceil(f_c^dE * 2^44): random scan, the 44-bit acceptance uniform of a non-top proposal
     const uint32_t *col_thr;  // [Nc][81]           scan = 2 under the biased / alpha rules: accept iff u <= col_thr[c][9 (dz + 4) + dxy + 4] (capi.hip)
-    const uint32_t *wu_desc;       // scan = 3: [n_gen][16] generator descriptors (tables.hpp wave_descriptors)
+    const uint32_t *wu_desc;       // scan = 3: [n_gen][16] generator descriptors (tables.hpp wave_descriptors); toric: [n_gen][8] in the wave layout (toric_wave_descriptors)
     uint32_t wu_chunk;             // scan = 3, criterion runs on a persistent grid: ladders per workgroup (a multiple of 64; 0: one ladder per lane, no queue)
     uint32_t wu_once;              // scan = 3: the swap cascade is walked once per workgroup, by the top rung's wave (set per launch from wave_cascade_once(), kernel_choice.hpp)
     float swap_inv_log2[kMaxNc];   // 1 / log2(p_diff[i]): first guess of the largest d with u < p_diff[i]^d (the table decides)

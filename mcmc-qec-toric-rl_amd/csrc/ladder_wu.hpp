@@ -8,6 +8,9 @@
 //     in REGISTERS (2 bits per qubit, W dwords per lane) and be addressed with the VGPR index mode (s_set_gpr_idx_on): one
 //     VALU instruction reads a site (shift by a scalar, SDWA byte placement) and one updates it (v_xor under the accept mask);
 //     no LDS traffic, no per-lane table gathers, no address arithmetic in the proposal loop;
+//     the toric code packs its two layers interleaved (the wave layout, tables.hpp wave_position): the two qubits of a generator's own cell
+//     share a word, three index switches per read and per update instead of four, a 32-byte descriptor (wu_read_cell, wu_xor_cell);
+//     only the staging (wu_stage_lds) and the write_states epilogue know where a qubit sits;
 //   * dE from the four old fields by one v_perm_b32 (a four-entry table per Pauli, applied to the four bytes at once) and one
 //     v_sad_u8, which also adds the rung's threshold-row address: 4 (dE + 4) + base in a single instruction;
 //   * the pick costs one Philox block per TWO proposals per wavefront (lane l draws the block of proposals 2l, 2l + 1 of a
@@ -183,6 +186,47 @@ __device__ __forceinline__ void wu_xor(typename WuVec<WV>::type &st, uint32_t d0
     WU_BY_WV(M)
 #undef M
 }
+// The toric code's forms (the wave layout, tables.hpp toric_wave_descriptors): sites 0 and 1 -- the generator's own cell -- are adjacent fields of
+// ONE word, d01 = word | s << 8 | (s + 2) << 16, so a read switches the index three times instead of four ...
+template <int WV>
+__device__ __forceinline__ uint32_t wu_read_cell(typename WuVec<WV>::type &st, uint32_t d01, uint32_t d2, uint32_t d3)
+{
+    uint32_t F;
+#define M(PIN)                                                                                                                 \
+    asm volatile("s_set_gpr_idx_on %[d01], 0x2\n\t"                                                                            \
+                 "v_lshrrev_b32_sdwa %[F], %[d01], v[%c[b]] dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:DWORD\n\t"      \
+                 "v_lshrrev_b32_sdwa %[F], %[d01], v[%c[b]] dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_2 src1_sel:DWORD\n\t" \
+                 "s_set_gpr_idx_idx %[d2]\n\t"                                                                                 \
+                 "v_lshrrev_b32_sdwa %[F], %[d2], v[%c[b]] dst_sel:BYTE_2 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_1 src1_sel:DWORD\n\t" \
+                 "s_set_gpr_idx_idx %[d3]\n\t"                                                                                 \
+                 "v_lshrrev_b32_sdwa %[F], %[d3], v[%c[b]] dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:BYTE_1 src1_sel:DWORD\n\t" \
+                 "s_set_gpr_idx_off"                                                                                           \
+                 : [F] "=&v"(F), "+" PIN(st)                                                                                   \
+                 : [d01] "s"(d01), [d2] "s"(d2), [d3] "s"(d3), [b] "i"(wu_base<WV>()));
+    WU_BY_WV(M)
+#undef M
+    return F;
+}
+// ... and the accepted move is three read-modify-writes, the pair's with one value (5 P << s)
+template <int WV>
+__device__ __forceinline__ void wu_xor_cell(typename WuVec<WV>::type &st, uint32_t d01, uint32_t d2, uint32_t d3, uint32_t x01, uint32_t x2, uint32_t x3)
+{
+#define M(PIN)                                                                                                                 \
+    asm volatile("s_set_gpr_idx_on %[d01], 0xA\n\t"                                                                            \
+                 "v_xor_b32 v[%c[b]], %[x01], v[%c[b]]\n\t"                                                                    \
+                 "s_set_gpr_idx_idx %[d2]\n\t"                                                                                 \
+                 "v_xor_b32 v[%c[b]], %[x2], v[%c[b]]\n\t"                                                                     \
+                 "s_set_gpr_idx_idx %[d3]\n\t"                                                                                 \
+                 "v_xor_b32 v[%c[b]], %[x3], v[%c[b]]\n\t"                                                                     \
+                 "s_set_gpr_idx_off"                                                                                           \
+                 : "+" PIN(st)                                                                                                 \
+                 : [d01] "s"(d01), [d2] "s"(d2), [d3] "s"(d3), [x01] "s"(x01), [x2] "s"(x2), [x3] "s"(x3), [b] "i"(wu_base<WV>()));
+    WU_BY_WV(M)
+#undef M
+}
+// a toric descriptor: 32 bytes, one scalar load
+typedef uint32_t wu_desc8 __attribute__((ext_vector_type(8)));
+typedef const wu_desc8 __attribute__((address_space(4))) *wu_const_desc8;
 
 // (the LDS carve-up of one workgroup, wu_lds, and the padded state width wu_words: kernel_choice.hpp)
 __host__ __device__ inline int wu_words_min(int WV) { return WV == 4 ? 1 : WV == 32 ? 17 : WV - 3; }      // the narrowest W a WV-word kernel serves
@@ -220,15 +264,18 @@ __device__ __forceinline__ uint32_t wu_field(const u32x4 &b, int f)
     return __builtin_amdgcn_perm(hi, lo, 0x0C0C0703u) & 0xFFFu;      // byte 3 of lo | byte 3 of hi << 8
 }
 
-// one Metropolis proposal of a rung below the top (mcmc.py:38-42) on the 64 ladders of the wave: the generator of descriptor e[0..11],
+// one Metropolis proposal of a rung below the top (mcmc.py:38-42) on the 64 ladders of the wave: the generator of descriptor e[0..11] (toric: e[0..6]),
 // a12 = the lanes' leading acceptance bits.  The 12 bits decide unless they tie with the threshold's in some lane (once in 4096 per lane).
+// (toric: d0 is the own-cell pair's dword and x0 its value, d1 and x1 are unused)
 template <int CODE, int WV>
 __device__ __forceinline__ void wu_propose(typename WuVec<WV>::type &st, uint32_t &n4, uint32_t a12, uint32_t thr_base, uint32_t nbias,
                                            uint32_t d0, uint32_t d1, uint32_t d2, uint32_t d3, uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3,
                                            uint32_t tlo, uint32_t thi, uint32_t omask, uint32_t amask,
                                            uint64_t refine_k, uint32_t refine_w, uint32_t syn, uint32_t slot, uint32_t seed_lo, uint32_t seed_hi)
 {
-    const uint32_t F = wu_read<WV>(st, d0, d1, d2, d3);
+    uint32_t F;
+    if constexpr (CODE == kCodeToric) F = wu_read_cell<WV>(st, d0, d2, d3);
+    else F = wu_read<WV>(st, d0, d1, d2, d3);
     uint32_t pv;
     if constexpr (CODE == kCodeToric) pv = __builtin_amdgcn_perm(tlo, tlo, F & 0x03030303u);   // byte i: 4 (1 + change of the error count at site i)
     else pv = __builtin_amdgcn_perm(thi, tlo, (F & amask) | omask);                            // (null sites and the second Pauli's half of the table)
@@ -241,7 +288,8 @@ __device__ __forceinline__ void wu_propose(typename WuVec<WV>::type &st, uint32_
         if (a12 == Th) acc = sel4(rb, (int)refine_w) < Tl;
     }
     if (acc) {
-        wu_xor<WV>(st, d0, d1, d2, d3, x0, x1, x2, x3);
+        if constexpr (CODE == kCodeToric) wu_xor_cell<WV>(st, d0, d2, d3, x0, x2, x3);
+        else wu_xor<WV>(st, d0, d1, d2, d3, x0, x1, x2, x3);
         n4 = n4 + addr + nbias;                                                                 // n += dE
     }
 }
@@ -385,7 +433,8 @@ __device__ __forceinline__ void wu_stage_lds(const LadderArgs &a, uint64_t lad, 
         uint32_t word = 0;
 #pragma unroll 4
         for (int b = 0; b < 16; ++b) {
-            const int q = w * 16 + b;
+            // (the wave layout, tables.hpp wave_position -- toric: field b of word w is layer b & 1 of cell 8 w + (b >> 1))
+            const int cell = w * 8 + (b >> 1), q = CODE == kCodeToric ? (cell < L * L ? (b & 1) * L * L + cell : nq) : w * 16 + b;
             if (q < nq) word |= (uint32_t)(src[q] & 3u) << (2 * b);
         }
         xrow[(w - w0) * 64] = word;
@@ -465,7 +514,7 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
         // lane l: the picks of proposals 2l, 2l + 1 of the window (one Philox block), as descriptor offsets
         const u32x4 b = wu_philox(wi * 64u + (uint64_t)lane, kSubWuPick, grp, kWuPickStream + slot, a.seed_lo, a.seed_hi);
         const uint32_t g0 = scale_u32(b.y, G), g1 = scale_u32(b.w, G);
-        pk = (g0 << 6) | (g1 << 22);
+        pk = CODE == kCodeToric ? (g0 << 5) | (g1 << 21) : (g0 << 6) | (g1 << 22);
         if (top) { pa0 = b.x; pb0 = b.y; pa1 = b.z; pb1 = b.w; }
     };
     refresh();
@@ -492,7 +541,7 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
                 // base plus a constant)
                 const uint32_t r = (uint32_t)__builtin_amdgcn_readlane((int)pk, IT == 10 ? (int)((pbase >> 1) + ((c * 10u + (uint32_t)f) >> 1)) : (int)(P >> 1));
                 const uint32_t off = (P & 1u) ? r >> 16 : r & 0xFFFFu;
-                // (byte offsets: multiples of 64 -- added to the table's address as they are)
+                // (byte offsets: multiples of the descriptor's 64 bytes, toric 32 -- added to the table's address as they are)
                 typedef const char __attribute__((address_space(4))) *wu_const_bytes;
                 const wu_const_ptr e = (wu_const_ptr)((wu_const_bytes)desc + off);
                 if constexpr (top) {
@@ -526,12 +575,20 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
                         // kernels keep the branch: their merge costs nothing, and the unified form costs the headline kernel 8 B of scratch.)
                         const bool logical = thr16 != 0 && (A >> 16) < thr16;
                         if (logical) { QECMC_WU_LOGICAL() }
+                        if constexpr (CODE == kCodeToric) {
+                            const wu_desc8 d = *(wu_const_desc8)e;
+                            wu_xor_cell<WV>(st, d[0], d[1], d[2], logical ? 0u : d[3], logical ? 0u : d[4], logical ? 0u : d[5]);
+                        } else {
                         const uint32_t d0 = e[0], d1 = e[1], d2 = e[2], d3 = e[3];
                         const uint32_t x0 = logical ? 0u : e[4], x1 = logical ? 0u : e[5], x2 = logical ? 0u : e[6], x3 = logical ? 0u : e[7];
                         wu_xor<WV>(st, d0, d1, d2, d3, x0, x1, x2, x3);
+                        }
                     } else {
                         if (thr16 != 0 && (A >> 16) < thr16) {
                             QECMC_WU_LOGICAL()
+                        } else if constexpr (CODE == kCodeToric) {
+                            const wu_desc8 d = *(wu_const_desc8)e;
+                            wu_xor_cell<WV>(st, d[0], d[1], d[2], d[3], d[4], d[5]);
                         } else {
                             const uint32_t d0 = e[0], d1 = e[1], d2 = e[2], d3 = e[3], x0 = e[4], x1 = e[5], x2 = e[6], x3 = e[7];
                             wu_xor<WV>(st, d0, d1, d2, d3, x0, x1, x2, x3);
@@ -556,13 +613,23 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
                             wu_propose_alpha<CODE, WV>(a, st, al, wu_field(ab, f + 1), cht_base + cofn, lxyf, lzf, b0, b1, b2, b3, y0, y1, y2, y3, ulo, uhi, on, an,
                                                        T * nc4 + ((j + 1u) >> 2), (j + 1u) & 3u, syn, slot, m55);
                           }
+                        } else if constexpr (CODE == kCodeToric) {
+                          if ((f & 1) == 0) {
+                            // (seven scalars per proposal, one s_load_dwordx8 each)
+                            const wu_desc8 da = *(wu_const_desc8)e, db = *(wu_const_desc8)((wu_const_bytes)desc + (r >> 16));
+                            __builtin_amdgcn_sched_barrier(0);
+                            wu_propose<CODE, WV>(st, n4, wu_field(ab, f), thr_base, nbias, da[0], 0u, da[1], da[2], da[3], 0u, da[4], da[5], da[6], 0u, 0u, 0u,
+                                                 T * nc4 + (j >> 2), j & 3u, syn, slot, a.seed_lo, a.seed_hi);
+                            wu_propose<CODE, WV>(st, n4, wu_field(ab, f + 1), thr_base, nbias, db[0], 0u, db[1], db[2], db[3], 0u, db[4], db[5], db[6], 0u, 0u, 0u,
+                                                 T * nc4 + ((j + 1u) >> 2), (j + 1u) & 3u, syn, slot, a.seed_lo, a.seed_hi);
+                          }
                         } else
                         if ((f & 1) == 0) {
                             const wu_const_ptr eb = (wu_const_ptr)((wu_const_bytes)desc + (r >> 16));
                             const uint32_t d0 = e[0], d1 = e[1], d2 = e[2], d3 = e[3], x0 = e[4], x1 = e[5], x2 = e[6], x3 = e[7], tlo = e[8];
-                            const uint32_t thi = CODE == kCodeToric ? 0u : e[9], om = CODE == kCodeToric ? 0u : e[10], am = CODE == kCodeToric ? 0u : e[11];
+                            const uint32_t thi = e[9], om = e[10], am = e[11];
                             const uint32_t b0 = eb[0], b1 = eb[1], b2 = eb[2], b3 = eb[3], y0 = eb[4], y1 = eb[5], y2 = eb[6], y3 = eb[7], ulo = eb[8];
-                            const uint32_t uhi = CODE == kCodeToric ? 0u : eb[9], on = CODE == kCodeToric ? 0u : eb[10], an = CODE == kCodeToric ? 0u : eb[11];
+                            const uint32_t uhi = eb[9], on = eb[10], an = eb[11];
                             __builtin_amdgcn_sched_barrier(0);
                             wu_propose<CODE, WV>(st, n4, wu_field(ab, f), thr_base, nbias, d0, d1, d2, d3, x0, x1, x2, x3, tlo, thi, om, am,
                                                  T * nc4 + (j >> 2), j & 3u, syn, slot, a.seed_lo, a.seed_hi);
@@ -574,9 +641,13 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
                         const uint32_t am = e[11], tlo = e[12], thi = e[13], om = e[14], coff = e[15];
                         wu_propose_alpha<CODE, WV>(a, st, al, wu_field(ab, f), cht_base + coff, lxyf, lzf, d0, d1, d2, d3, x0, x1, x2, x3, tlo, thi, om, am,
                                                    T * nc4 + (j >> 2), j & 3u, syn, slot, m55);
+                    } else if constexpr (CODE == kCodeToric) {
+                        const wu_desc8 d = *(wu_const_desc8)e;
+                        wu_propose<CODE, WV>(st, n4, wu_field(ab, f), thr_base, nbias, d[0], 0u, d[1], d[2], d[3], 0u, d[4], d[5], d[6], 0u, 0u, 0u,
+                                             T * nc4 + (j >> 2), j & 3u, syn, slot, a.seed_lo, a.seed_hi);
                     } else {
                         const uint32_t d0 = e[0], d1 = e[1], d2 = e[2], d3 = e[3], x0 = e[4], x1 = e[5], x2 = e[6], x3 = e[7], tlo = e[8];
-                        const uint32_t thi = CODE == kCodeToric ? 0u : e[9], om = CODE == kCodeToric ? 0u : e[10], am = CODE == kCodeToric ? 0u : e[11];
+                        const uint32_t thi = e[9], om = e[10], am = e[11];
                         wu_propose<CODE, WV>(st, n4, wu_field(ab, f), thr_base, nbias, d0, d1, d2, d3, x0, x1, x2, x3, tlo, thi, om, am,
                                              T * nc4 + (j >> 2), j & 3u, syn, slot, a.seed_lo, a.seed_hi);
                     }
@@ -1069,8 +1140,9 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_wu_kernel(const LadderArgs 
         auto copy = [&](int w_lo, int w_hi) {
 #pragma unroll 1
             for (int i = tid; i < total; i += nthreads) {
-                const int j = i / per, rem = i - j * per, c = rem / nq, q = rem - c * nq, w = q >> 4;
-                if (w >= w_lo && w < w_hi) dst[i] = (uint8_t)((xbuf[(c * rows + (w - w_lo)) * 64 + j] >> ((q & 15) * 2)) & 3u);
+                const int j = i / per, rem = i - j * per, c = rem / nq, q = rem - c * nq;
+                const int pos = CODE == kCodeToric ? (q >= L * L ? 2 * (q - L * L) + 1 : 2 * q) : q, w = pos >> 4;   // (the wave layout, tables.hpp wave_position)
+                if (w >= w_lo && w < w_hi) dst[i] = (uint8_t)((xbuf[(c * rows + (w - w_lo)) * 64 + j] >> ((pos & 15) * 2)) & 3u);
             }
         };
         copy(0, rows);

@@ -209,7 +209,11 @@ inline Refusal plan_host(const qecmc_params &p, HostPlan &hp)
     }
     if (p.scan == QECMC_SCAN_WAVE) {
         // the wave-uniform random scan (ladder_wu.hpp): one scalar-loadable descriptor per generator; states in registers
-        hp.wu_desc = wave_descriptors(hp.gen);
+        // (a wave plan launches ladder_wu kernels only -- choose_kernel: scan = 3 is choose_wave or a refusal --, so the toric code's tables are in
+        // the wave layout, tables.hpp: the other kernel families read lmask in the flat one)
+        const bool cells = p.code == QECMC_TORIC;
+        hp.wu_desc = cells ? toric_wave_descriptors(hp.gen) : wave_descriptors(hp.gen);
+        if (cells) hp.lmask = wave_layout_rows(p.code, L, nq, W, hp.lmask);
         if (hp.wu_desc.empty()) return refuse_params(QECMC_ERR_UNSUPPORTED, "scan = wave: a generator with three different Paulis");
     }
     if (biased) {

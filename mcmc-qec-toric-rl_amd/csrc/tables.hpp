@@ -279,6 +279,58 @@ inline std::vector<uint32_t> wave_descriptors(const std::vector<uint32_t> &gt)
     return d;
 }
 
+// scan = 3, the WAVE LAYOUT of the packed state: field p of the state (word p >> 4, bit 2 (p & 15)) holds qubit q with p = wave_position(q).
+// Every toric generator holds both qubits of its own cell, (0, r, c) and (1, r, c) (toric_model.py:257-284), so the toric code interleaves its
+// two layers -- qubit (layer, r, c) at 2 (r L + c) + layer, eight cells per word -- and the pair is always two adjacent fields of one word, at
+// shifts s and s + 2 with s a multiple of 4.  The other codes have no such pair: the identity, the flat layout of every other scan.
+inline uint32_t wave_position(int code, int L, uint32_t q)
+{
+    if (code != QECMC_TORIC) return q;
+    const uint32_t LL = (uint32_t)(L * L), layer = q >= LL ? 1u : 0u;
+    return 2u * (q - layer * LL) + layer;
+}
+// a table of packed rows of W words (the logical masks) with every field moved to its wave-layout position
+inline std::vector<uint32_t> wave_layout_rows(int code, int L, int nq, int W, const std::vector<uint32_t> &flat)
+{
+    std::vector<uint32_t> m(flat.size(), 0u);
+    for (size_t row = 0; row < flat.size() / (size_t)W; ++row)
+        for (uint32_t q = 0; q < (uint32_t)nq; ++q) {
+            const uint32_t p = wave_position(code, L, q), f = (flat[row * W + (q >> 4)] >> ((q & 15u) * 2u)) & 3u;
+            m[row * W + (p >> 4)] |= f << ((p & 15u) * 2u);
+        }
+    return m;
+}
+// The toric code's descriptors in the wave layout: 32 bytes per generator (one s_load_dwordx8), seven dwords used.  0: the own-cell pair as
+// (state word) | s << 8 | (s + 2) << 16; 1, 2: the other two sites as (state word) | (bit shift) << 8; 3: the pair's value to xor, 5 P << s;
+// 4, 5: the other sites' values, P << shift; 6: the error-count table of the generator's Pauli as in wave_descriptors (dword 8).  Sites that
+// fall into one word stay correct: the kernel's updates are read-modify-writes in order.  Empty if a generator does not start with its own cell.
+inline std::vector<uint32_t> toric_wave_descriptors(const std::vector<uint32_t> &gt)
+{
+    const size_t G = gt.size() / 2;
+    int L = 0;
+    while ((size_t)(2 * L * L) < G) ++L;
+    std::vector<uint32_t> d(8 * G, 0u);
+    for (size_t g = 0; g < G; ++g) {
+        uint32_t pos[4], P = 0;
+        for (int u = 0; u < 4; ++u) {
+            const uint32_t e = (u < 2 ? gt[2 * g] >> (16 * u) : gt[2 * g + 1] >> (16 * (u - 2))) & 0xFFFFu;
+            if (u == 0) P = e & 3u;
+            if (!(e & 3u) || (e & 3u) != P) return {};
+            pos[u] = wave_position(QECMC_TORIC, L, e >> 2);
+        }
+        const uint32_t lo = std::min(pos[0], pos[1]), s = (lo & 15u) * 2u;
+        if ((pos[0] ^ pos[1]) != 1u || (lo & 1u)) return {};
+        d[8 * g] = (lo >> 4) | (s << 8) | ((s + 2u) << 16);
+        d[8 * g + 3] = (5u * P) << s;
+        for (int u = 2; u < 4; ++u) {
+            d[8 * g + u - 1] = (pos[u] >> 4) | (((pos[u] & 15u) * 2u) << 8);
+            d[8 * g + u + 2] = P << ((pos[u] & 15u) * 2u);
+        }
+        for (uint32_t f = 0; f < 4; ++f) d[8 * g + 6] |= (f == 0 ? 8u : f == P ? 0u : 4u) << (8 * f);
+    }
+    return d;
+}
+
 // scan = 2 (QECMC_SCAN_COLOUR): the generators cut into PHASES of mutually disjoint generators (no shared qubit), which one
 // wavefront proposes at once.  Greedy colouring in table order -- colour(g) = the smallest colour no earlier generator sharing
 // a qubit with g has -- then every colour class, in increasing g, in consecutive chunks of at most 64 (one lane each).

@@ -36,6 +36,23 @@ int qt_logical_masks(int code, int L, int W, uint32_t *out, int cap)
     return put(code == QECMC_TORIC ? toric_logical_masks(L, W) : surf_logical_masks(code, L, W), out, cap);
 }
 int qt_wave_descriptors(int code, int L, uint32_t *out, int cap) { return put(wave_descriptors(gen_table(code, L)), out, cap); }
+// the wave layout (scan = wave): a qubit's position, the toric descriptors, the logical masks moved to it; qt_plan_wave_tables: wu_desc and lmask
+// as plan_host() builds them for an accepted block (the sizes through n_desc / n_lmask; -1: refused or too small a buffer)
+uint32_t qt_wave_position(int code, int L, uint32_t q) { return wave_position(code, L, q); }
+int qt_toric_wave_descriptors(int L, uint32_t *out, int cap) { return put(toric_wave_descriptors(toric_generator_table(L)), out, cap); }
+int qt_wave_logical_masks(int code, int L, int W, uint32_t *out, int cap)
+{
+    const std::vector<uint32_t> flat = code == QECMC_TORIC ? toric_logical_masks(L, W) : surf_logical_masks(code, L, W);
+    return put(wave_layout_rows(code, L, (int)code_nq(code, L), W, flat), out, cap);
+}
+int qt_plan_wave_tables(const qecmc_params *p, uint32_t *desc, int desc_cap, int *n_desc, uint32_t *lmask, int lmask_cap, int *n_lmask)
+{
+    HostPlan hp;
+    if (validate_params(p).code || plan_host(*p, hp).code) return -1;
+    *n_desc = put(hp.wu_desc, desc, desc_cap);
+    *n_lmask = put(hp.lmask, lmask, lmask_cap);
+    return *n_desc < 0 || *n_lmask < 0 ? -1 : 0;
+}
 uint64_t qt_thr64(double v) { return thr64(v); }
 uint64_t qt_thr44(double v) { return thr44(v); }
 uint32_t qt_thr32(double v) { return thr32(v); }
