@@ -299,7 +299,10 @@ int qecmc_pteq_launch_dev(qecmc_plan *plan, const void *d_init, uint64_t N, uint
  *   d_swap_accepts uint32[N][Nc-1]: accepted swap tests of rung pair (i, i+1) (Ladder.step's r_flip, src/mcmc.py:96-99);
  *   d_nerr_sums    uint32[N][Nc]:   sum over the ladder steps of count_errors() of the chain in rung c after the step's
  *                                   swaps (what mcmc.py:88-89 reads) -- divide by steps for the time average.
- * Both count every ladder step of the launch (no burn-in) and need nq * steps < 2^32.  Not with replicas > 1. */
+ * Both count every ladder step of the launch (no burn-in) and need nq * steps < 2^32.  Not with replicas > 1.
+ * Every scan collects them.  scan = WAVE and scan = COLOUR count in diagnostic kernels of their own (the same chain bit for
+ * bit, slower than the fast kernels, which are untouched: DESIGN.md 4.1g): fixed-length runs only, scan = WAVE up to 16 packed
+ * state words per rung -- QECMC_ERR_UNSUPPORTED, naming the case, with conv_mode ERROR_BASED or beyond that width. */
 int qecmc_plan_set_stats(qecmc_plan *plan, void *d_swap_accepts, void *d_nerr_sums);
 /* Continue N ladders for params->steps more ladder steps from caller-held device state (exact continuation: Philox is
  * addressed by step0 = ladder steps already done): d_states uint8[N][Nc][nq] slot order in/out, d_flags uint8[N][Nc] in/out,

@@ -674,8 +674,14 @@ int qecmc_plan_set_stats(qecmc_plan *plan, void *d_swap_accepts, void *d_nerr_su
     if (!plan) return fail(QECMC_ERR_INVALID, "plan is NULL");
     if (d_nerr_sums && !d_swap_accepts) return fail(QECMC_ERR_INVALID, "d_nerr_sums needs d_swap_accepts");
     if (d_swap_accepts && plan->args.Nc < 2) return fail(QECMC_ERR_INVALID, "swap statistics need Nc >= 2");
-    if (d_swap_accepts && (plan->args.scan == QECMC_SCAN_COLOUR || plan->args.scan == QECMC_SCAN_WAVE)) return fail(QECMC_ERR_UNSUPPORTED, "swap statistics are not collected by the scan = colour / wave kernels");
-    if (d_swap_accepts && plan->lds_bytes + ladder_stats_lds_bytes(plan->args.Nc) > 160 * 1024)
+    if (d_swap_accepts && (plan->args.scan == QECMC_SCAN_COLOUR || plan->args.scan == QECMC_SCAN_WAVE)) {
+        // the wave and colour layouts count in kernels of their own (choose_wave / choose_colour, kernel_choice.hpp): the chooser says whether one is
+        // built for this plan's launches -- fixed-length runs, scan = wave up to 16 state words per rung
+        LadderArgs probe = plan->args;
+        probe.swap_acc = static_cast<uint32_t *>(d_swap_accepts);
+        const KernelKey k = choose_kernel(kernel_shape(probe));
+        if (!k.ok()) return fail(QECMC_ERR_UNSUPPORTED, "qecmc_plan_set_stats: %s", k.why);
+    } else if (d_swap_accepts && plan->lds_bytes + ladder_stats_lds_bytes(plan->args.Nc) > 160 * 1024)
         return fail(QECMC_ERR_UNSUPPORTED, "no LDS left for the statistics counters at this L / Nc");
     plan->d_swap_acc = static_cast<uint32_t *>(d_swap_accepts);
     plan->d_nerr_sum = static_cast<uint32_t *>(d_nerr_sums);

@@ -115,7 +115,8 @@ struct KernelShape {
 };
 
 // The kernel a shape runs: ladder_kernel<maxt, minw, code, flags>, ladder_wu_kernel<maxt, minw, code, wv, conv, queue = conv, it, alpha> or
-// ladder_colour_kernel<code, conv, rule, maxt, minw>; family kRefused: no kernel is built for the shape (`why` names the rule)
+// ladder_colour_kernel<code, conv, rule, maxt, minw> -- with flags = kKeyStats in the wave / colour families: ladder_wu_stats_kernel<code, wv, alpha> or
+// ladder_colour_stats_kernel<code, rule> --; family kRefused: no kernel is built for the shape (`why` names the rule)
 enum KernelFamily : int { kRefused = 0, kFamLadder = 1, kFamWave = 2, kFamColour = 3 };
 struct KernelKey {
     int family, maxt, minw, code;
@@ -134,6 +135,12 @@ inline KernelKey refuse(const char *why) { return {kRefused, 0, 0, 0, 0u, 0, 0, 
 inline KernelKey ladder_key(int maxt, int minw, int code, uint32_t flags) { return {kFamLadder, maxt, minw, code, flags, 0, 0, 0, 0, 0, nullptr}; }
 inline KernelKey wave_key(int maxt, int minw, int code, int wv, bool conv, int it, bool alpha) { return {kFamWave, maxt, minw, code, 0u, wv, conv, it, alpha, 0, nullptr}; }
 inline KernelKey colour_key(int code, bool conv, int rule) { return {kFamColour, 1024, 4, code, 0u, 0, conv, 0, 0, rule, nullptr}; }
+// The statistics kernels of the wave and colour families (qecmc_plan_set_stats: ladder_wu_stats_kernel<code, wv, alpha>, ladder_colour_stats_kernel<code,
+// rule>): kernels of their own, told from the fast ones by `flags` -- 0 in both families otherwise.  Fixed-length runs, 1 024 threads at 4 waves per SIMD
+// whatever the ladder's length, the general proposal loop (it = 0).
+constexpr uint32_t kKeyStats = 1u;
+inline KernelKey wave_stats_key(int code, int wv, bool alpha) { return {kFamWave, 1024, 4, code, kKeyStats, wv, 0, 0, alpha, 0, nullptr}; }
+inline KernelKey colour_stats_key(int code, int rule) { return {kFamColour, 1024, 4, code, kKeyStats, 0, 0, 0, 0, rule, nullptr}; }
 
 // dynamic LDS of a ladder_kernel workgroup (+ the per-lane statistics counters behind the group's region)
 inline size_t ladder_launch_lds(const KernelShape &s)
@@ -242,20 +249,25 @@ inline KernelKey choose_colour(const KernelShape &s)
     if (s.uset) return refuse("uset: not with scan = colour");
     if (s.noise < 0 || s.noise > 2 || s.resume) return refuse("scan = colour: no resumed ladders");
     if (s.noise != 0 && s.code != kCodeXzzx && s.code != kCodeRotated) return refuse("biased / alpha rule: xzzx and rotated codes only");
+    if (s.stats) {   // qecmc_plan_set_stats: a wave per slot counts its own pair and its slot's errors
+        if (s.conv) return refuse("scan = colour: swap statistics are collected in fixed-length runs only, not with the criterion");
+        if (s.Nc < 2) return refuse("swap statistics need Nc >= 2");
+        return colour_stats_key(s.code, s.noise);
+    }
     return colour_key(s.code, s.conv, s.noise);
 }
 
 // scan = 3 (ladder_wu.hpp): the depolarizing rule with a top rung that accepts every move (Nc >= 2, p_top = 0.75) and rungs at distinct
 // temperatures, up to 16 state words per rung (toric / planar L <= 11, xzzx / rotated L <= 16), fixed-length runs of up to 8 rungs also up to 32
 // (toric L <= 16, xzzx / rotated L <= 22); the alpha rule (top rung at pz_tilde = 1) on the xzzx / rotated codes up to 8 words, where every rung
-// below the top may take the single-precision acceptance estimate; 1 <= iters <= 128
+// below the top may take the single-precision acceptance estimate; 1 <= iters <= 128.  (Statistics, s.stats: choose_wave answers for them.)
 inline bool wu_supported(const KernelShape &s)
 {
     if (s.noise == 2)
         return (s.code == kCodeXzzx || s.code == kCodeRotated) && s.Nc >= 2 && s.Nc <= 16 && s.W <= 8 && s.n_gen <= 1023 && s.iters >= 1 && s.iters <= 128 &&
-               s.f32ok && !s.uset && !s.stats && !s.resume && !s.neff && wu_lds_bytes(s.Nc, s.W, s.ncls, s.L, s.conv, true) <= 160 * 1024;
+               s.f32ok && !s.uset && !s.resume && !s.neff && wu_lds_bytes(s.Nc, s.W, s.ncls, s.L, s.conv, true) <= 160 * 1024;
     return s.noise == 0 && s.Nc >= 2 && s.top_acc && !s.lower_acc && (s.W <= 16 || (s.W <= 32 && !s.conv && s.Nc <= 8 && s.code != kCodePlanar)) &&
-           s.n_gen <= 1023 && s.iters >= 1 && s.iters <= 128 && s.swap_fast_ok && !s.uset && !s.stats && wu_lds_bytes(s.Nc, s.W, s.ncls, s.L, s.conv, false) <= 160 * 1024;
+           s.n_gen <= 1023 && s.iters >= 1 && s.iters <= 128 && s.swap_fast_ok && !s.uset && wu_lds_bytes(s.Nc, s.W, s.ncls, s.L, s.conv, false) <= 160 * 1024;
 }
 // the padded state width (wu_words); 8 waves per SIMD up to 12 words, 6 at 16 and 32 words and for the alpha rule's criterion kernels (scratch
 // reloaded every step at 8: profiles/r04_crit_occupancy_ab.json); 9 .. 16 rungs: the same code under a launch bound of 1 024 threads; IT = 10: the
@@ -264,6 +276,11 @@ inline KernelKey choose_wave(const KernelShape &s)
 {
     if (!wu_supported(s)) return refuse("scan = wave: outside what it is built for");
     const int maxt = s.Nc * 64 > 512 ? 1024 : 512, it = s.iters == 10 ? 10 : 0, wv = wu_words(s.W);
+    if (s.stats) {   // qecmc_plan_set_stats: the kernels with the two counters per wave (ladder_wu.hpp STATS)
+        if (s.conv) return refuse("scan = wave: swap statistics are collected in fixed-length runs only, not with the criterion");
+        if (wv > 16) return refuse("scan = wave: no swap statistics above 16 state words per rung (the 32-word kernels' staging spills)");
+        return wave_stats_key(s.code, wv, s.noise == 2);
+    }
     if (s.noise == 2) return wave_key(maxt, s.conv ? 6 : 8, s.code, wv, s.conv, it, true);
     return wave_key(maxt, wv <= 12 ? 8 : 6, s.code, wv, s.conv, it, false);
 }
@@ -274,10 +291,11 @@ inline KernelKey choose_wave(const KernelShape &s)
 // a CU -- the serial section is covered by the CU's other workgroups) the measurement decides, and it turns on the ladder's length alone, whatever the code
 // and the state width: once per workgroup gains 2.6 - 5.2 % at 5, 6 and 7 rungs and loses 0.5 - 3.8 % at 2, 3, 4 -- too few replays to pay
 // for the barrier -- and at 8, where a workgroup's waves fall on the same SIMDs in every workgroup of the CU.  QECMC_FLAG_NO_SSW (tune & 8): the replay.
+// A statistics launch (flags = kKeyStats) always replays: its waves count the pair each of them decides.
 inline bool wave_cascade_once(const KernelShape &s)
 {
     const KernelKey k = choose_wave(s);
-    return s.scan == 3 && k.ok() && !k.conv && !k.alpha && k.wv <= 16 && s.Nc >= 5 && s.Nc <= 7 && !(s.tune & 8) &&
+    return s.scan == 3 && k.ok() && k.flags == 0 && !k.conv && !k.alpha && k.wv <= 16 && s.Nc >= 5 && s.Nc <= 7 && !(s.tune & 8) &&
            4 * wu_lds_bytes(s.Nc, s.W, s.ncls, s.L, false, false) <= 160 * 1024;
 }
 

@@ -114,10 +114,12 @@ __host__ __device__ constexpr int conv_record_words(int noise) { return noise ==
 
 hipError_t launch_ladder(const LadderArgs &a, hipStream_t stream);     // ladder_rs.hip: the kernel choose_kernel() picks for kernel_shape(a) (plan_host.hpp), on its grid
 // the instantiation units, one per kernel family (built in parallel): the kernel of `k` if the unit builds it, else nullptr -- ladder_kernel
-// (ladder_{toric,surf,biased,sweep,uset}.hip), ladder_colour_kernel (ladder_colour.hip), ladder_wu_kernel (ladder_wu{,_xzzx,_rotated,_planar,_alpha}.hip)
+// (ladder_{toric,surf,biased,sweep,uset}.hip), ladder_colour_kernel (ladder_colour.hip), ladder_wu_kernel (ladder_wu{,_xzzx,_rotated,_planar,_alpha}.hip),
+// the statistics kernels ladder_wu_stats_kernel (ladder_wu_stats{,_alpha}.hip) and ladder_colour_stats_kernel (ladder_colour_stats.hip)
 const void *ladder_toric_kernel(const KernelKey &), *ladder_surf_kernel(const KernelKey &), *ladder_biased_kernel(const KernelKey &),
     *ladder_sweep_kernel(const KernelKey &), *ladder_uset_kernel(const KernelKey &), *colour_kernel(const KernelKey &), *wave_toric_kernel(const KernelKey &),
-    *wave_xzzx_kernel(const KernelKey &), *wave_rotated_kernel(const KernelKey &), *wave_planar_kernel(const KernelKey &), *wave_alpha_kernel(const KernelKey &);
+    *wave_xzzx_kernel(const KernelKey &), *wave_rotated_kernel(const KernelKey &), *wave_planar_kernel(const KernelKey &), *wave_alpha_kernel(const KernelKey &),
+    *wave_stats_kernel(const KernelKey &), *wave_stats_alpha_kernel(const KernelKey &), *colour_stats_kernel(const KernelKey &);
 
 // byte-state primitive kernels (primitives.hip); all pointers are device pointers
 hipError_t launch_apply_stabilizer(int code, int L, uint64_t N, const uint8_t *in, uint8_t *out, const int32_t *rows,

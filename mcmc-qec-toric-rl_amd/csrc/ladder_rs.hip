@@ -1,5 +1,5 @@
 // The one launch path of the ladder kernels: choose_kernel() (kernel_choice.hpp) names the kernel of a launch, the instantiation units
-// (ladder_toric / ladder_surf / ladder_biased / ladder_sweep / ladder_uset / ladder_colour / ladder_wu*.hip, built in parallel) hold it,
+// (ladder_toric / ladder_surf / ladder_biased / ladder_sweep / ladder_uset / ladder_colour* / ladder_wu*.hip, built in parallel) hold it,
 // and the launch runs it on the grid its family implies.  A key no unit holds is an error, never a neighbouring kernel.
 #include "kernels.hpp"
 #include "plan_host.hpp"   // kernel_shape(): what the choice reads of a launch
@@ -12,7 +12,8 @@ const void *kernel_of(const KernelKey &k)
 {
     const void *fn = nullptr;
     for (auto unit : {ladder_toric_kernel, ladder_surf_kernel, ladder_biased_kernel, ladder_sweep_kernel, ladder_uset_kernel, colour_kernel,
-                      wave_toric_kernel, wave_xzzx_kernel, wave_rotated_kernel, wave_planar_kernel, wave_alpha_kernel})
+                      wave_toric_kernel, wave_xzzx_kernel, wave_rotated_kernel, wave_planar_kernel, wave_alpha_kernel, wave_stats_kernel,
+                      wave_stats_alpha_kernel, colour_stats_kernel})
         fn = fn ? fn : unit(k);
     return fn;
 }

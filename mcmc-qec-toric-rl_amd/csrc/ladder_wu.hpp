@@ -245,7 +245,10 @@ typedef uint32_t __attribute__((address_space(3))) *wu_lds_rw;
 
 constexpr uint32_t kWuDead = 0xFFFFFFFFu, kWuKeep = 0xFFFFFFFEu;      // refill mailbox: no ladder left for the lane / the lane keeps its ladder
 
-struct WuCtx { uint32_t n4, cls, flag, tops0, samples, done, conv_ok, steps_done, nef; };
+struct WuCtx {
+    uint32_t n4, cls, flag, tops0, samples, done, conv_ok, steps_done, nef;
+    uint32_t swapc = 0, nsum = 0;      // STATS: the steps in which the pair below this wave's slot traded states, the summed error counts the slot held
+};
 struct WuEnv {
     uint32_t lds0, thr_off, lml_off, cht_off, slot, grp, lad;    // lad: the lane's first ladder of this launch (kWuDead: none)
     int lane;
@@ -476,11 +479,15 @@ __device__ __forceinline__ bool wu_pair_flips(const LadderArgs &a, uint32_t car,
 // the ladder (its index, its own step), the generator picks the lane's position (group, workgroup step).
 // ALPHA: the alpha noise model's ladder (src/mcmc_alpha.py; xzzx / rotated codes): wu_propose_alpha, slot-bound n_eff attributes (Q4) -- a wave IS
 // a slot here, so its attribute is a register --, the floating-point swap test, the criterion on the logged count pairs.
-template <int CODE, int WV, bool CONV, bool QUEUE, bool TOP, int IT, bool ALPHA>
+// STATS (ladder_wu_stats_kernel): the equilibrium observables of qecmc_plan_set_stats.  The wave of slot s >= 1 itself decides pair s - 1 when it
+// replays the cascade and ends the step holding its slot's record: two counters per lane, in registers (cx.swapc, cx.nsum), no LDS, no atomics.
+template <int CODE, int WV, bool CONV, bool QUEUE, bool TOP, int IT, bool ALPHA, bool STATS = false>
 __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::type &st, WuCtx &cx, const WuEnv &ev)
 {
     static_assert(!QUEUE || CONV, "the work queue serves the runs that stop by the criterion");
     static_assert(!ALPHA || CODE != kCodeToric, "the alpha rule: xzzx / rotated codes");
+    static_assert(!STATS || (!CONV && WV <= 16), "the statistics kernels: fixed-length runs of up to 16 state words");
+    [[maybe_unused]] uint32_t swapc = 0, nsum = 0;
     const int L = a.L;
     wu_lds_ptr const lml = (wu_lds_ptr)(uintptr_t)(ev.lds0 + ev.lml_off);
     const uint32_t lds0 = ev.lds0, slot = ev.slot, grp = ev.grp;
@@ -686,6 +693,7 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
         int NCl = a.Nc, ncl = a.ncls;
         uint32_t slotl = ev.slot, lds0l = ev.lds0, once = a.wu_once;
         asm volatile("" : "+s"(NCl), "+s"(ncl), "+s"(slotl), "+s"(lds0l), "+s"(once));
+        if constexpr (STATS) once = 0;                     // (the replay: every wave decides the pair below its own slot)
         const int NC = NCl;
         const uint32_t slot = slotl;
         const WuLds ol = wu_lds(NC, WV, ncl, 0, false, false);                       // (the offsets up to swapT: functions of Nc, WV and ncls alone)
@@ -743,11 +751,15 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
             mine = car;
             if (slot != 0) {
                 const uint32_t lo = pr[0];
-                if (wu_pair_flips(a, car, lo, px[0], trow, (int)slot - 1)) mine = lo;   // what slot i + 1 now holds (:98-99)
+                if (wu_pair_flips(a, car, lo, px[0], trow, (int)slot - 1)) {
+                    mine = lo;                                                          // what slot i + 1 now holds (:98-99)
+                    if constexpr (STATS) swapc += 1u;
+                }
             }
         }
         wu_take_all<WV>(st, xaddr + ((mine >> 16) & 0xFFu) * xstride);               // this rung's new state: the words of the rung it comes from
         n4 = (mine & 0xFFFFu) << 2; cls = (mine >> 24) & 0x3Fu; flag = mine >> 31;
+        if constexpr (STATS) nsum += mine & 0xFFFFu;
         if (top) flag = 1;                                                           // chains[-1].flag = 1, mcmc.py:100
         if (slot == 0) {                                                             // ladder + PTEQ bookkeeping on rung 0's new state
             tops0 += (NC == 1) | flag;                                               // :101-102
@@ -823,7 +835,10 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
                 }
                 const uint32_t into = flip ? lo : car;                               // what slot i+1 now holds (:98-99)
                 car = flip ? car : lo;
-                if ((int)slot == i + 1) mine = into;
+                if ((int)slot == i + 1) {
+                    mine = into;
+                    if constexpr (STATS) swapc += flip ? 1u : 0u;
+                }
             }
             if (slot == 0) mine = car;
             // this rung's new state: the W words of the rung it comes from
@@ -843,6 +858,7 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
                 wu_ds_wait<WV>(st);
             }
             n4 = info_n(mine) << 2; cls = info_cls(mine); flag = info_flag(mine);
+            if constexpr (STATS) nsum += info_n(mine);
             if (top) flag = 1;                                                       // chains[-1].flag = 1, mcmc.py:100
             if constexpr (!CONV) {
                 if (slot == 0) {                                                     // ladder + PTEQ bookkeeping on rung 0's new state
@@ -998,169 +1014,37 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
     }
     cx.n4 = n4; cx.cls = cls; cx.flag = flag; cx.tops0 = tops0; cx.samples = samples;
     if constexpr (ALPHA) cx.nef = nef;
+    if constexpr (STATS) { cx.swapc = swapc; cx.nsum = nsum; }
 }
 
 template <int MAXT, int MINW, int CODE, int WV, bool CONV, bool QUEUE, int IT, bool ALPHA = false>
 __global__ __launch_bounds__(MAXT, MINW) void ladder_wu_kernel(const LadderArgs a)
 {
-    typedef typename WuVec<WV>::type vec_t;
-    extern __shared__ uint32_t lds[];
-    const int NC = a.Nc, W = a.W, L = a.L, nq = a.nq, ncls = a.ncls;
-    const int nthreads = NC * 64;
-    const int tid = (int)threadIdx.x, lane = tid & 63;
-    const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);      // this wave's rung (fixed: states move)
-    const WuLds o = wu_lds(NC, W, ncls, L, CONV, ALPHA);
-    uint32_t *xbuf = lds + o.xbuf, *rec = lds + o.rec, *hist = lds + o.hist, *thrT = lds + o.thr;
-    uint32_t *swapT = lds + o.swapT, *lml = lds + o.lml;
-    volatile uint32_t *stopf = lds + o.stop;
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(wu_lds_ptr)lds;                    // LDS byte address of the dynamic segment
-    const uint32_t R = a.replicas;
-    // the workgroup's share of the batch: 64 ladders, or -- QUEUE -- a.wu_chunk of them, taken 64 at a time
-    const uint64_t s0 = (uint64_t)blockIdx.x * (QUEUE ? (uint64_t)a.wu_chunk : 64u);
-    const uint64_t s1 = QUEUE ? (s0 + a.wu_chunk < a.N ? s0 + a.wu_chunk : a.N) : a.N;
-    const int cnt = s1 > s0 ? (int)((s1 - s0) < 64u ? (s1 - s0) : 64u) : 0;
-    const bool live = lane < cnt;
-    const bool top = slot == (uint32_t)(NC - 1);                                  // (the launcher guarantees that this rung accepts every move)
+    constexpr bool STATS = false;
+#include "ladder_wu_body.inc"
+}
 
-    // ---- tables
-    for (int i = tid; i < ncls * 64; i += nthreads) hist[i] = 0;
-    if (tid < 4) stopf[tid] = tid == 2 ? (uint32_t)s0 + 64u : 0u;   // [0], [1]: stop, by step parity; [2]: the workgroup's queue (next unassigned ladder)
-    if constexpr (CONV) {
-        uint32_t *bk = lds + o.bk, *mail = lds + o.mail;
-        for (int i = tid; i < (ALPHA ? kWuBkAlpha : kWuBk) * 64; i += nthreads) {
-            const int row = i >> 6, l = i & 63;
-            bk[i] = row == 9 ? (l < cnt ? 8u : 0u) : row == 12 ? (uint32_t)s0 + (uint32_t)l : 0u;                   // state: has; the lane's ladder
-        }
-        for (int i = tid; i < 128; i += nthreads) mail[i] = kWuKeep;
-    }
-    if constexpr (ALPHA) {
-        // (D_xy, D_z) of a proposal as two fp16 integers, at byte offset 4 ((D_z + 4) + 9 (D_xy + 4)); ln(pz_i / pz_i+1) of the rung pairs
-        for (int i = tid; i < 81; i += nthreads) {
-            const wu_half2 h = {(_Float16)(float)(i / 9 - 4), (_Float16)(float)(i % 9 - 4)};
-            lds[o.cht + i] = __builtin_bit_cast(uint32_t, h);
-        }
-        for (int i = tid; i < NC - 1; i += nthreads) reinterpret_cast<double *>(lds + o.lnb)[i] = a.alpha_lnb[i];
-    }
-    for (int i = tid; i < NC * 18 && !ALPHA; i += nthreads) {
-        const int c = i / 18, r = i - c * 18, hi = r < 9, idx = hi ? r : r - 9;
-        // dE <= 0 (idx <= 4): always accepted -- a high part no 12-bit uniform reaches; dE = 1..4: ceil(f^dE 2^44)
-        const uint64_t t44 = idx <= 4 ? (1ull << 44) : a.acc_thr44[c][idx - 5];
-        thrT[i] = hi ? (uint32_t)(t44 >> 32) : (uint32_t)t44;
-    }
-    for (int i = tid; i < (NC - 1) * kSwapFast && !ALPHA; i += nthreads) {
-        const int pr = i / kSwapFast, d = i - pr * kSwapFast;
-        swapT[i] = (d >= 1 && d <= nq) ? (uint32_t)a.swap_thr[(size_t)pr * (nq + 1) + d] : 0u;
-    }
-    for (int i = tid; i < 4 * (L + 1) * WV + 64; i += nthreads) {          // rows padded to WV words
-        const int row = i / WV, w = i - row * WV;
-        lml[i] = (row < 4 * (L + 1) && w < W) ? a.lmask[row * W + w] : 0u;
-    }
-
-    // ---- stage this rung's state into registers: Ladder.__init__ copies the seed into every rung (mcmc.py:72), or resume
-    vec_t st;
-    wu_def<WV>(st);
-    uint32_t n4 = 0, cls = 0, flag = top ? 1u : 0u;
-    const uint64_t ladder = s0 + (uint64_t)(live ? lane : 0);
-#define QECMC_WU_ZERO(w) if constexpr (w < WV) wu_set<WV, w>(st, 0u);
-    WU_EACH(QECMC_WU_ZERO)
-#undef QECMC_WU_ZERO
-    if (cnt > 0) {
-        const int rows = wu_rows(W, CONV);                            // rows of a rung's region of the exchange buffer
-        const wu_lds_rw xcol = (wu_lds_rw)(uintptr_t)lds0 + (slot * (uint32_t)rows) * 64u + (uint32_t)lane;
-        wu_stage_lds<CODE>(a, ladder, slot, xcol, n4, cls, 0, WV == 32 ? kWuHalf : W, rows);
-        const uint32_t xme = lds0 + (uint32_t)lane * 4u + slot * (uint32_t)(rows * 256);
-        const int Wl = W;
-#define QECMC_WU_MINE(w) if constexpr (w < WV && w < kWuHalf) { if (WV == 32 || !CONV || w < wu_words_min(WV) || w < Wl) wu_ds_read<WV, w>(st, xme); }
-        WU_EACH(QECMC_WU_MINE)
-#undef QECMC_WU_MINE
-        wu_ds_wait<WV>(st);
-        if constexpr (WV == 32) {
-            // (the upper half through the same rows: this lane's own column, which nobody else reads)
-            wu_stage_lds<CODE>(a, ladder, slot, xcol, n4, cls, kWuHalf, W, rows);
-#define QECMC_WU_MINE_HI(w) if constexpr (w < WV && w >= kWuHalf) wu_ds_read<WV, w, w - kWuHalf>(st, xme);
-            WU_EACH(QECMC_WU_MINE_HI)
-#undef QECMC_WU_MINE_HI
-            wu_ds_wait<WV>(st);
-        }
-        if (a.resume) flag = a.flags[ladder * NC + slot];
-    }
-    uint32_t tops0 = 0;                                               // wave 0's per-ladder bookkeeping (the criterion kernels: in LDS)
-    if (slot == 0 && a.resume && live) tops0 = a.tops0[s0 + lane];
-    __syncthreads();
-
-    uint32_t nef0 = 0;
-    if constexpr (ALPHA) { const uint32_t c3 = wu_counts_packed<WV>(st, 0x55555555u); nef0 = ((c3 >> 10) & 1023u) | ((c3 >> 20) << 16); }   // Chain_alpha.__init__, mcmc_alpha.py:18-22
-    WuCtx cx{n4, cls, flag, tops0, 0u, 0u, 0u, 0u, nef0};
-    WuEnv ev;
-    ev.lds0 = lds0; ev.thr_off = (uint32_t)((o.thr + (int)slot * 18) * 4); ev.lml_off = (uint32_t)(o.lml * 4); ev.cht_off = (uint32_t)(o.cht * 4); ev.slot = slot;
-    ev.grp = (a.first_syndrome >> 6) + (uint32_t)blockIdx.x;         // the wavefront's shared picks: its position in the grid
-    ev.lad = live ? (uint32_t)ladder : kWuDead;
-    ev.lane = lane; ev.chunk_hi = s1;
-    // (the two roles are separate loops: they meet at the step's barriers)
-    if (top) wu_run<CODE, WV, CONV, QUEUE, true, IT, ALPHA>(a, st, cx, ev);
-    else wu_run<CODE, WV, CONV, QUEUE, false, IT, ALPHA>(a, st, cx, ev);
-    if constexpr (QUEUE) return;                                      // (every ladder wrote its results when it ended)
-    n4 = cx.n4; cls = cx.cls; flag = cx.flag; tops0 = cx.tops0;
-    uint32_t samples = cx.samples, done = 0, conv_ok = 0, steps_done = 0;
-    const uint32_t xaddr = lds0 + (uint32_t)lane * 4u;
-    // ---- results
-    __syncthreads();
-    if constexpr (CONV) {
-        const uint32_t *bk = lds + o.bk + lane;
-        tops0 = bk[0]; samples = bk[64]; done = bk[576] & 1u; steps_done = bk[640]; conv_ok = bk[704];
-    }
-    const int rows = wu_rows(W, CONV);
-    {
-        const int Wl = W;
-        const uint32_t xo = xaddr + slot * (uint32_t)(rows * 256);
-        WU_EACH(QECMC_WU_PUT)
-        wu_ds_wait<WV>(st);
-        rec[slot * 64u + (uint32_t)lane] = pack_info(n4 >> 2, slot, cls, flag);
-    }
-    __syncthreads();
-    if (a.counts != nullptr)
-#pragma unroll 1
-        for (int i = tid; i < cnt * ncls; i += nthreads) {
-            const int j = i / ncls, c = i - j * ncls;
-            const uint32_t v = hist[c * 64 + j];
-            if (R > 1) { if (v) atomicAdd(a.counts + ((s0 + (uint64_t)j) / R) * ncls + c, v); }
-            else if (a.accumulate) a.counts[s0 * ncls + i] += v;
-            else a.counts[s0 * ncls + i] = v;
-        }
-    if (slot == 0 && live) {
-        store_ladder_results(a.samples, a.tops0, a.steps_done, a.converged, R > 1 ? (s0 + lane) / R : s0 + lane, R, a.accumulate != 0, samples, tops0,
-                             done ? steps_done : (uint32_t)a.nsteps, conv_ok != 0);
-        if (R <= 1 && a.flags != nullptr)
-            for (int c = 0; c < NC; ++c) a.flags[(s0 + lane) * NC + c] = (uint8_t)info_flag(rec[c * 64 + lane]);
-    }
-    if (a.write_states && a.states != nullptr) {
-        // (the words the exchange buffer holds: all of them, or -- 32-word kernels -- the lower half, then the upper one)
-        uint8_t *dst = a.states + s0 * (uint64_t)NC * nq;
-        const int per = NC * nq, total = cnt * per;
-        auto copy = [&](int w_lo, int w_hi) {
-#pragma unroll 1
-            for (int i = tid; i < total; i += nthreads) {
-                const int j = i / per, rem = i - j * per, c = rem / nq, q = rem - c * nq;
-                const int pos = CODE == kCodeToric ? (q >= L * L ? 2 * (q - L * L) + 1 : 2 * q) : q, w = pos >> 4;   // (the wave layout, tables.hpp wave_position)
-                if (w >= w_lo && w < w_hi) dst[i] = (uint8_t)((xbuf[(c * rows + (w - w_lo)) * 64 + j] >> ((pos & 15) * 2)) & 3u);
-            }
-        };
-        copy(0, rows);
-        if constexpr (WV == 32) {
-            const int Wl = W;
-            const uint32_t xo = xaddr + slot * (uint32_t)(rows * 256);
-            __syncthreads();
-            WU_EACH(QECMC_WU_PUT_HI)
-            wu_ds_wait<WV>(st);
-            __syncthreads();
-            copy(kWuHalf, W);
-        }
-    }
+// The same program with the swap and per-rung error counters of qecmc_plan_set_stats: a diagnostic kernel of its own name (choose_wave's
+// wave_stats_key), fixed-length runs, the general proposal loop, 128 VGPRs under a launch bound of 1 024 threads whatever the ladder's length
+template <int CODE, int WV, bool ALPHA>
+__global__ __launch_bounds__(1024, 4) void ladder_wu_stats_kernel(const LadderArgs a)
+{
+    constexpr bool STATS = true, CONV = false, QUEUE = false;
+    constexpr int IT = 0;
+#include "ladder_wu_body.inc"
+}
+// (the transfer macros of wu_run's general tail, which the kernels' epilogue shares)
 #undef QECMC_WU_PUT
 #undef QECMC_WU_TAKE
 #undef QECMC_WU_PUT_HI
 #undef QECMC_WU_TAKE_HI
-}
+template <int CODE, int WV, bool ALPHA = false>
+struct WaveStatsSet {
+    static const void *find(const KernelKey &k)
+    {
+        return k == wave_stats_key(CODE, WV, ALPHA) ? (const void *)ladder_wu_stats_kernel<CODE, WV, ALPHA> : nullptr;
+    }
+};
 
 // the instantiations ladder_wu_kernel<MAXT, MINW, CODE, WV, CONV, QUEUE = CONV, IT, ALPHA> for IT = 10 (the unrolled proposal loop of iters = 10)
 // and IT = 0 (any iters): find() is the kernel of `k` if it is one of them, else nullptr

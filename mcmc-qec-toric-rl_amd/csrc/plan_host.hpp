@@ -235,7 +235,7 @@ inline Refusal plan_host(const qecmc_params &p, HostPlan &hp)
             if (a.iters <= 512u && 4.0 * (double)a.iters * std::max(std::fabs(a.bias_l2[c][0]), std::fabs(a.bias_l2[c][1])) <= 2000.0)
                 a.bias_f32ok |= 1u << c;
             if (p.scan != QECMC_SCAN_COLOUR) continue;
-            // scan = 2 under these rules (ladder_colour.hip): a generator is a Metropolis move for the model's own weight, accepted iff
+            // scan = 2 under these rules (ladder_colour.hpp): a generator is a Metropolis move for the model's own weight, accepted iff
             // u < (px / pI)^dxy (pz / pI)^dz -- as integers, u <= ceil(ratio 2^32) - 1 -- for its changes (dz, dxy) of n_z and n_x + n_y
             for (int dz = -4; dz <= 4; ++dz)
                 for (int dxy = -4; dxy <= 4; ++dxy) {

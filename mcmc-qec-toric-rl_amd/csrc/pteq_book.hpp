@@ -1,5 +1,5 @@
 // The reference's PTEQ bookkeeping and its error_based stopping rule (decoders.py:60-82,93-105; decoders_biasednoise.py:204,229-238), and
-// how one ladder's results reach its syndrome's row, for ladder_kernel.hpp, ladder_colour.hip and ladder_wu.hpp.  Plain device functions on
+// how one ladder's results reach its syndrome's row, for ladder_kernel.hpp, ladder_colour.hpp and ladder_wu.hpp.  Plain device functions on
 // values: where a kernel keeps its counters is the caller's business.  Where a call changed a kernel's resource row the rule stays in place, marked there.
 #pragma once
 #include <hip/hip_runtime.h>

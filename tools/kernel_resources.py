@@ -21,6 +21,15 @@ def kernel_label(mangled):
         maxt, minw, code, wv, conv, queue, it, alpha = (int(x) for x in w.groups())
         return "wave<%d,%d,%s: %d words%s%s%s%s>" % (maxt, minw, CODES[code], wv, ", conv" if conv else "", ", queue" if queue else "", ", alpha" if alpha else "",
                                                    ", iters %d" % it if it else "")
+    # the statistics kernels (qecmc_plan_set_stats), families of their own: 1 024 threads at 4 waves per SIMD whatever the ladder's length
+    s = re.search(r"ladder_wu_stats_kernelILi(\d+)ELi(\d+)ELb([01])EE", mangled)
+    if s:   # ladder_wu_stats_kernel<CODE, WV, ALPHA> -> 'wave-stats<1024,4,toric: 12 words>'
+        code, wv, alpha = (int(x) for x in s.groups())
+        return "wave-stats<1024,4,%s: %d words%s>" % (CODES[code], wv, ", alpha" if alpha else "")
+    s = re.search(r"ladder_colour_stats_kernelILi(\d+)ELi(\d+)EE", mangled)
+    if s:   # ladder_colour_stats_kernel<CODE, RULE> -> 'colour-stats<1024,4,xzzx: rule 1>'
+        code, rule = (int(x) for x in s.groups())
+        return "colour-stats<1024,4,%s: rule %d>" % (CODES[code], rule)
     m = re.search(r"ladder_kernelILi(\d+)ELi(\d+)ELi(\d+)ELj(\d+)E", mangled)
     if not m:
         m2 = re.match(r"_ZN5qecmc\d+([A-Za-z_0-9]+?)(?:I|E)", mangled)
@@ -33,7 +42,7 @@ def kernel_label(mangled):
 def parse(path):
     """[{unit, kernel, label, VGPRs, AGPRs, SGPRs, ScratchSize, Occupancy}, ...] of one .res file"""
     rows, cur = [], None
-    keys = {"VGPRs": r"\sVGPRs: (\d+)", "AGPRs": r"\sAGPRs: (\d+)", "SGPRs": r"\sSGPRs: (\d+)",
+    keys = {"VGPRs": r"\sVGPRs: (\d+)", "AGPRs": r"\sAGPRs: (\d+)", "SGPRs": r"(?:\s|Total)SGPRs: (\d+)",
             "ScratchSize": r"ScratchSize \[bytes/lane\]: (\d+)", "Occupancy": r"Occupancy \[waves/SIMD\]: (\d+)"}
     for line in open(path, errors="replace"):
         m = re.search(r"Function Name: (\S+)", line)
