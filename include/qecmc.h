@@ -343,6 +343,30 @@ int qecmc_pteq_batch_stats(const qecmc_params *params, const uint8_t *init, uint
                            uint32_t *samples_out, uint32_t *tops0_out, uint32_t *steps_done_out,
                            uint8_t *converged_out, uint8_t *final_states_out, uint32_t *swap_accepts_out,
                            uint32_t *nerr_sums_out, qecmc_stats *stats_out);
+/* The shortest-chain statistics of PTEQ_alpha_with_shortest (decoders_biasednoise.py:93-172) for the following launches of
+ * `plan`, kept in the kernels (device pointers; all NULL switches them off again).  After every ladder step past burn-in the
+ * bottom slot is looked at: c = the class of its configuration, v = its n_eff attribute (the slot's own, as the reference
+ * reads it).  Per ladder and class:
+ *   d_short_neff double[N][4]: the smallest v seen (100000.0, the reference's sentinel: the class was never seen);
+ *   d_short_n    uint32[N][4]: the samples with that v;
+ *   d_unique_n   uint32[N][4]: the distinct configurations among them (the size of the reference's `unique` dict);
+ *   d_overflow   uint8[N]:     1 if the ladder offered more than set_capacity distinct (configuration, v) pairs to its set --
+ *                              its d_unique_n row is then unspecified; other ladders are unaffected.
+ * d_set is the ladders' sets, set_bytes >= qecmc_plan_shortest_set_bytes(plan, N, set_capacity) bytes for launches of N
+ * syndromes (the launch zeroes it).  Alpha noise with scan = WAVE or scan = COLOUR only, single fresh ladders: any other rule or
+ * scan, replicas > 1, or a plan with qecmc_plan_set_stats is refused with QECMC_ERR_UNSUPPORTED, naming the case; a NULL or
+ * undersized buffer with QECMC_ERR_INVALID, before anything is enqueued.  Launches run a kernel of their own with one lane (scan
+ * = COLOUR: one workgroup) per ladder for the whole run and log one column per ladder (the workspace formula of
+ * qecmc_plan_workspace_bytes with final states); conv_mode NONE runs `steps` steps (steps_done = steps, converged = 0);
+ * d_tops0, d_steps_done and d_converged are needed, scan = WAVE writes no final states. */
+int qecmc_plan_shortest_set_bytes(const qecmc_plan *plan, uint64_t N, uint64_t set_capacity, uint64_t *bytes_out);
+int qecmc_plan_set_shortest(qecmc_plan *plan, void *d_short_neff, void *d_short_n, void *d_unique_n, void *d_overflow,
+                            void *d_set, uint64_t set_bytes, uint64_t set_capacity);
+/* Host-pointer form: qecmc_pteq_batch with the outputs above (none nullable). */
+int qecmc_pteq_batch_shortest(const qecmc_params *params, const uint8_t *init, uint64_t N, uint64_t set_capacity,
+                              uint32_t *counts_out, uint32_t *samples_out, uint32_t *tops0_out, uint32_t *steps_done_out,
+                              uint8_t *converged_out, double *short_neff_out, uint32_t *short_n_out,
+                              uint32_t *unique_n_out, uint8_t *overflow_out, qecmc_stats *stats_out);
 /* Bytes of dynamic LDS and threads per workgroup the plan's kernel uses (for reports). */
 int qecmc_plan_info(const qecmc_plan *plan, uint32_t *lds_bytes, uint32_t *block_threads,
                     uint32_t *syndromes_per_block);

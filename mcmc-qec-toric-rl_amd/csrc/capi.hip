@@ -144,6 +144,12 @@ struct qecmc_plan {
     uint32_t queue_grid = 0;                                   // persistent grid of the work-queue kernels (0: not a queue plan)
     size_t lds_bytes;
     uint32_t *d_swap_acc = nullptr, *d_nerr_sum = nullptr;   // qecmc_plan_set_stats (caller-owned)
+    // qecmc_plan_set_shortest (caller-owned): the outputs, the ladders' sets and what a ladder may offer
+    double *d_short_neff = nullptr;
+    uint32_t *d_short_n = nullptr, *d_short_uniq = nullptr;
+    uint8_t *d_short_over = nullptr;
+    void *d_short_set = nullptr;
+    uint64_t short_set_bytes = 0, short_cap = 0;
     // (plan_host.hpp: whether a launch runs on the persistent grid, and THE workspace formula of the criterion runs)
     bool takes_queue(bool wants_states_or_stats) const { return launch_takes_queue(queue_grid, prm.steps, wants_states_or_stats); }
     uint64_t workspace(uint64_t N, bool queue) const { return workspace_need(prm, queue_grid, N, queue); }
@@ -593,7 +599,7 @@ int qecmc_plan_destroy(qecmc_plan *plan)
 int qecmc_plan_info(const qecmc_plan *plan, uint32_t *lds_bytes, uint32_t *block_threads, uint32_t *syndromes_per_block)
 {
     if (!plan) return fail(QECMC_ERR_INVALID, "plan is NULL");
-    if (lds_bytes) *lds_bytes = (uint32_t)plan->lds_bytes;
+    if (lds_bytes) *lds_bytes = (uint32_t)(plan->d_short_neff ? shortest_lds_bytes(plan->args) : plan->lds_bytes);   // (the shortest-chain kernels' own map)
     if (block_threads) *block_threads = (uint32_t)plan->args.Nc * 64u;
     if (syndromes_per_block) *syndromes_per_block = kSynPerBlock;
     return 0;
@@ -604,7 +610,7 @@ int qecmc_plan_workspace_bytes(const qecmc_plan *plan, uint64_t N, int with_fina
     if (!plan || !bytes_out) return fail(QECMC_ERR_INVALID, "NULL argument");
     // what qecmc_pteq_launch_dev(plan, N syndromes, d_final_states given or not) will ask for: a launch that may take the plan's work
     // queue logs one column per lane of the persistent grid, any other one column per ladder
-    *bytes_out = plan->workspace(N, plan->takes_queue(with_final_states != 0 || plan->d_swap_acc != nullptr));
+    *bytes_out = plan->workspace(N, plan->takes_queue(with_final_states != 0 || plan->d_swap_acc != nullptr || plan->d_short_neff != nullptr));
     return 0;
 }
 
@@ -619,7 +625,19 @@ int qecmc_pteq_launch_dev(qecmc_plan *plan, const void *d_init, uint64_t N, uint
     if (M + first_syndrome > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "global ladder index (first_syndrome + N * replicas) exceeds 32 bits");
     if (plan->args.scan == QECMC_SCAN_WAVE && (first_syndrome & 63u))
         return fail(QECMC_ERR_INVALID, "scan = wave: first_syndrome=%u must be a multiple of 64 (a wavefront shares its generator picks)", first_syndrome);
-    const bool takes_queue = plan->takes_queue(plan->d_swap_acc != nullptr || d_final_states != nullptr);
+    const bool shortest = plan->d_short_neff != nullptr;      // (qecmc_plan_set_shortest: a lane per ladder for the whole run, never the persistent grid)
+    const bool takes_queue = plan->takes_queue(plan->d_swap_acc != nullptr || d_final_states != nullptr || shortest);
+    if (shortest) {
+        if (plan->d_swap_acc || plan->d_nerr_sum) return fail(QECMC_ERR_UNSUPPORTED, "qecmc_plan_set_shortest: not together with qecmc_plan_set_stats");
+        if (int rc = report(shortest_check(plan->prm, kernel_shape(plan->args)))) return rc;
+        if (plan->prm.steps == 0 || plan->prm.steps > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "qecmc_plan_set_shortest: steps=%llu must be in [1, 2^32)", (unsigned long long)plan->prm.steps);
+        if (plan->args.scan == QECMC_SCAN_WAVE && d_final_states) return fail(QECMC_ERR_UNSUPPORTED, "qecmc_plan_set_shortest: scan = wave writes no final states");
+        if (!d_tops0 || !d_steps_done || !d_converged) return fail(QECMC_ERR_INVALID, "NULL device buffer");
+        const uint64_t need = shortest_set_need(N, plan->short_cap);
+        if (plan->short_set_bytes < need)
+            return fail(QECMC_ERR_INVALID, "set workspace of %llu bytes, %llu ladders of capacity %llu take %llu (qecmc_plan_shortest_set_bytes)",
+                        (unsigned long long)plan->short_set_bytes, (unsigned long long)N, (unsigned long long)plan->short_cap, (unsigned long long)need);
+    }
     {
         const uint64_t need = plan->workspace(N, takes_queue);
         if (need && !d_workspace) return fail(QECMC_ERR_INVALID, "conv_mode error_based needs the workspace of qecmc_plan_workspace_bytes()");
@@ -653,6 +671,14 @@ int qecmc_pteq_launch_dev(qecmc_plan *plan, const void *d_init, uint64_t N, uint
     a.write_states = d_final_states != nullptr;
     a.N = M; a.first_syndrome = first_syndrome;
     a.step0 = 0; a.prop0 = 0; a.nsteps = plan->prm.steps; a.resume = 0;
+    if (shortest) {
+        a.short_neff = plan->d_short_neff; a.short_n = plan->d_short_n; a.short_uniq = plan->d_short_uniq; a.short_over = plan->d_short_over;
+        a.short_set = static_cast<unsigned long long *>(plan->d_short_set);
+        a.short_slots = (uint32_t)shortest_set_slots(plan->short_cap); a.short_cap = (uint32_t)plan->short_cap;
+        HIP_TRY(hipMemsetAsync(plan->d_short_set, 0, shortest_set_need(N, plan->short_cap), strm));
+        HIP_TRY(launch_ladder(a, strm));
+        return 0;
+    }
     if (plan->args.scan == QECMC_SCAN_WAVE && plan->prm.conv_mode != QECMC_CONV_NONE && !takes_queue)
         return fail(QECMC_ERR_UNSUPPORTED, "scan = wave runs the criterion on its persistent grid, where a ladder's lane is reused when it has stopped: no final "
                     "states or per-ladder statistics with conv_mode error_based (and steps must be > 0)");
@@ -674,6 +700,7 @@ int qecmc_plan_set_stats(qecmc_plan *plan, void *d_swap_accepts, void *d_nerr_su
     if (!plan) return fail(QECMC_ERR_INVALID, "plan is NULL");
     if (d_nerr_sums && !d_swap_accepts) return fail(QECMC_ERR_INVALID, "d_nerr_sums needs d_swap_accepts");
     if (d_swap_accepts && plan->args.Nc < 2) return fail(QECMC_ERR_INVALID, "swap statistics need Nc >= 2");
+    if (d_swap_accepts && plan->d_short_neff) return fail(QECMC_ERR_UNSUPPORTED, "qecmc_plan_set_stats: not together with qecmc_plan_set_shortest");
     if (d_swap_accepts && (plan->args.scan == QECMC_SCAN_COLOUR || plan->args.scan == QECMC_SCAN_WAVE)) {
         // the wave and colour layouts count in kernels of their own (choose_wave / choose_colour, kernel_choice.hpp): the chooser says whether one is
         // built for this plan's launches -- fixed-length runs, scan = wave up to 16 state words per rung
@@ -685,6 +712,41 @@ int qecmc_plan_set_stats(qecmc_plan *plan, void *d_swap_accepts, void *d_nerr_su
         return fail(QECMC_ERR_UNSUPPORTED, "no LDS left for the statistics counters at this L / Nc");
     plan->d_swap_acc = static_cast<uint32_t *>(d_swap_accepts);
     plan->d_nerr_sum = static_cast<uint32_t *>(d_nerr_sums);
+    return 0;
+}
+
+int qecmc_plan_shortest_set_bytes(const qecmc_plan *plan, uint64_t N, uint64_t set_capacity, uint64_t *bytes_out)
+{
+    if (!plan || !bytes_out) return fail(QECMC_ERR_INVALID, "NULL argument");
+    if (set_capacity == 0 || set_capacity > kShortMaxCapacity)
+        return fail(QECMC_ERR_INVALID, "set_capacity=%llu must be in [1, 2^26]", (unsigned long long)set_capacity);
+    *bytes_out = shortest_set_need(N, set_capacity);
+    return 0;
+}
+
+int qecmc_plan_set_shortest(qecmc_plan *plan, void *d_short_neff, void *d_short_n, void *d_unique_n, void *d_overflow, void *d_set,
+                            uint64_t set_bytes, uint64_t set_capacity)
+{
+    if (!plan) return fail(QECMC_ERR_INVALID, "plan is NULL");
+    if (!d_short_neff && !d_short_n && !d_unique_n && !d_overflow && !d_set) {      // off again
+        plan->d_short_neff = nullptr; plan->d_short_n = plan->d_short_uniq = nullptr; plan->d_short_over = nullptr; plan->d_short_set = nullptr;
+        plan->short_set_bytes = plan->short_cap = 0;
+        return 0;
+    }
+    if (int rc = report(shortest_check(plan->prm, kernel_shape(plan->args)))) return rc;
+    if (plan->d_swap_acc || plan->d_nerr_sum) return fail(QECMC_ERR_UNSUPPORTED, "qecmc_plan_set_shortest: not together with qecmc_plan_set_stats");
+    if (!d_short_neff || !d_short_n || !d_unique_n || !d_overflow || !d_set) return fail(QECMC_ERR_INVALID, "NULL device buffer");
+    if (set_capacity == 0 || set_capacity > kShortMaxCapacity)
+        return fail(QECMC_ERR_INVALID, "set_capacity=%llu must be in [1, 2^26]", (unsigned long long)set_capacity);
+    if (shortest_lds_bytes(plan->args) > 160 * 1024)
+        return fail(QECMC_ERR_UNSUPPORTED, "qecmc_plan_set_shortest: L=%d Nc=%d needs %zu B of LDS per workgroup (> 160 KiB)", plan->args.L, plan->args.Nc,
+                    shortest_lds_bytes(plan->args));
+    if (set_bytes < shortest_set_need(1, set_capacity))
+        return fail(QECMC_ERR_INVALID, "set workspace of %llu bytes, one ladder of capacity %llu takes %llu (qecmc_plan_shortest_set_bytes)",
+                    (unsigned long long)set_bytes, (unsigned long long)set_capacity, (unsigned long long)shortest_set_need(1, set_capacity));
+    plan->d_short_neff = static_cast<double *>(d_short_neff); plan->d_short_n = static_cast<uint32_t *>(d_short_n);
+    plan->d_short_uniq = static_cast<uint32_t *>(d_unique_n); plan->d_short_over = static_cast<uint8_t *>(d_overflow);
+    plan->d_short_set = d_set; plan->short_set_bytes = set_bytes; plan->short_cap = set_capacity;
     return 0;
 }
 
@@ -822,6 +884,67 @@ int qecmc_pteq_batch_stats(const qecmc_params *params, const uint8_t *init, uint
     if (stats_out) {
         stats_out->proposals = N * R * Nc * params->iters * params->steps;   // upper bound when the criterion stops early
         stats_out->swap_tests = N * R * (Nc - 1) * params->steps;
+        stats_out->kernel_ms = ms;
+        stats_out->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return 0;
+}
+
+int qecmc_pteq_batch_shortest(const qecmc_params *params, const uint8_t *init, uint64_t N, uint64_t set_capacity, uint32_t *counts_out,
+                              uint32_t *samples_out, uint32_t *tops0_out, uint32_t *steps_done_out, uint8_t *converged_out, double *short_neff_out,
+                              uint32_t *short_n_out, uint32_t *unique_n_out, uint8_t *overflow_out, qecmc_stats *stats_out)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    // everything the host alone can refuse comes before the device is looked for
+    if (int rc = report(validate_params(params))) return rc;
+    {
+        HostPlan hp;
+        if (int rc = report(plan_host(*params, hp))) return rc;
+        if (int rc = report(shortest_check(*params, hp.shape))) return rc;
+    }
+    if (set_capacity == 0 || set_capacity > kShortMaxCapacity)
+        return fail(QECMC_ERR_INVALID, "set_capacity=%llu must be in [1, 2^26]", (unsigned long long)set_capacity);
+    if (params->steps == 0 || params->steps > 0xFFFFFFFFull)
+        return fail(QECMC_ERR_INVALID, "qecmc_plan_set_shortest: steps=%llu must be in [1, 2^32)", (unsigned long long)params->steps);
+    if (N != 0 && (!init || !counts_out || !samples_out || !short_neff_out || !short_n_out || !unique_n_out || !overflow_out))
+        return fail(QECMC_ERR_INVALID, "NULL buffer");
+    qecmc_plan *pl = nullptr;
+    if (int rc = qecmc_plan_create(params, &pl)) return rc;
+    struct Guard { qecmc_plan *p; ~Guard() { qecmc_plan_destroy(p); } } guard{pl};   // (synchronises: an error return may leave the launch running)
+    if (N == 0) return 0;
+    const size_t nq = pl->args.nq, ncls = pl->args.ncls;
+    const uint64_t ws_bytes = pl->workspace(N, false), set_bytes = shortest_set_need(N, set_capacity);
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (ws_bytes + set_bytes > free_b / 2)
+        return fail(QECMC_ERR_INVALID, "the criterion's log and the ladders' sets need %llu + %llu bytes, %zu free: lower `steps`, set_capacity or the batch size",
+                    (unsigned long long)ws_bytes, (unsigned long long)set_bytes, free_b);
+    DevBuf di, dc, ds, dt, dsd, dcv, dw, dne, dsn, dun, dov, dset;
+    HIP_TRY(di.alloc(N * nq)); HIP_TRY(dc.alloc(N * ncls * 4)); HIP_TRY(ds.alloc(N * 4)); HIP_TRY(dt.alloc(N * 4));
+    HIP_TRY(dsd.alloc(N * 4)); HIP_TRY(dcv.alloc(N));
+    HIP_TRY(dne.alloc(N * 4 * 8)); HIP_TRY(dsn.alloc(N * 4 * 4)); HIP_TRY(dun.alloc(N * 4 * 4)); HIP_TRY(dov.alloc(N)); HIP_TRY(dset.alloc(set_bytes));
+    if (ws_bytes) HIP_TRY(dw.alloc(ws_bytes));
+    if (int rc = qecmc_plan_set_shortest(pl, dne.p, dsn.p, dun.p, dov.p, dset.p, set_bytes, set_capacity)) return rc;
+    HIP_TRY(hipMemcpy(di.p, init, N * nq, hipMemcpyHostToDevice));
+    EventTimer timer;
+    HIP_TRY(timer.start());
+    if (int rc = qecmc_pteq_launch_dev(pl, di.p, N, params->first_syndrome, dc.p, ds.p, dt.p, dsd.p, dcv.p, nullptr, ws_bytes ? dw.p : nullptr, ws_bytes, nullptr))
+        return rc;
+    float ms = 0;
+    HIP_TRY(timer.stop(&ms));
+    HIP_TRY(hipMemcpy(counts_out, dc.p, N * ncls * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(samples_out, ds.p, N * 4, hipMemcpyDeviceToHost));
+    if (tops0_out) HIP_TRY(hipMemcpy(tops0_out, dt.p, N * 4, hipMemcpyDeviceToHost));
+    if (steps_done_out) HIP_TRY(hipMemcpy(steps_done_out, dsd.p, N * 4, hipMemcpyDeviceToHost));
+    if (converged_out) HIP_TRY(hipMemcpy(converged_out, dcv.p, N, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(short_neff_out, dne.p, N * 4 * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(short_n_out, dsn.p, N * 4 * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(unique_n_out, dun.p, N * 4 * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(overflow_out, dov.p, N, hipMemcpyDeviceToHost));
+    if (stats_out) {
+        const size_t Nc = pl->args.Nc;
+        stats_out->proposals = N * Nc * params->iters * params->steps;   // upper bound when the criterion stops early
+        stats_out->swap_tests = N * (Nc - 1) * params->steps;
         stats_out->kernel_ms = ms;
         stats_out->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }

@@ -9,6 +9,9 @@
 
 namespace qecmc {
 
+// The shortest-chain statistics (qecmc_plan_set_shortest; shortest_book.hpp) keep kShortRows words per ladder in LDS: per class c the minimum (low, high word of
+// the double), shortest_n and the unique count at rows 4 c .. 4 c + 3, the distinct keys offered to the ladder's set at row 16, its overflow flag at row 17
+constexpr int kShortRows = 18;
 constexpr int kSwapFast = 64;       // swap-threshold entries per rung pair kept in LDS (d < kSwapFast)
 constexpr uint32_t kMaxGenLds = 2048;   // generator tables up to this many entries are staged in LDS
 constexpr int kLutTypes = 8;        // rows of the plaquette codes' dE look-up table (Pauli patterns of their generators; more: no table)
@@ -58,17 +61,25 @@ inline size_t ladder_lds_bytes(int Nc, int W, int ncls, int gen_dwords) { return
 // phase table, the generator table, the logical masks, the swap thresholds (32-bit where they fit) -- so that the serial path of a
 // step never waits for global memory
 // (noise != 0: the rule's 81 thresholds per rung; the alpha rule's n_eff records by step parity)
-inline size_t colour_lds_dwords(int Nc, int W, int ncls, uint32_t n_phases, uint32_t n_gen, int L, int nq, bool swap32, int noise = 0)
+// (shortest: the shortest-chain statistics' state of the ladder, kShortRows words behind everything else)
+inline size_t colour_lds_dwords(int Nc, int W, int ncls, uint32_t n_phases, uint32_t n_gen, int L, int nq, bool swap32, int noise = 0, bool shortest = false)
 {
     return (size_t)Nc * W + 4 * (size_t)Nc + ncls + 32u * n_phases + 2u * n_gen + 4u * (L + 1) * W +
            (swap32 ? 1u : 2u) * (size_t)(Nc > 1 ? Nc - 1 : 0) * (nq + 1) + 2 + 4 +   // (+ 2: the stop flag by step parity)
-           (noise ? (size_t)Nc * 81 + 2 * (size_t)Nc : 0);
+           (noise ? (size_t)Nc * 81 + 2 * (size_t)Nc : 0) + (shortest ? (size_t)kShortRows : 0);
+}
+// ... and where that state starts (dwords; the alpha rule's kernel: ladder_colour_body.inc carves the regions in this order, the generator table 8-byte aligned)
+__host__ __device__ inline uint32_t colour_short_at(int Nc, int W, int ncls, uint32_t n_phases, uint32_t n_gen, int L, int nq, bool swap32)
+{
+    const uint32_t head = (uint32_t)(Nc * W + 4 * Nc + ncls) + 32u * n_phases;
+    return head + (head & 1u) + 2u * n_gen + 4u * (uint32_t)((L + 1) * W) + (swap32 ? 1u : 2u) * (uint32_t)((Nc > 1 ? Nc - 1 : 0) * (nq + 1)) + 2u +
+           (uint32_t)Nc * 81u + 2u * (uint32_t)Nc;
 }
 
 // ladder_wu_kernel: LDS carve-up of one workgroup (dwords): the exchange buffer (W words per rung), records, swap uniforms, histogram, acceptance
 // rows, swap rows, logical masks (rows padded to WV words, + 64: the frame reads a row with all 64 lanes), stop / refill flags, and -- the
 // criterion kernels -- wave 0's per-ladder bookkeeping [kWuBk][64] and the refill mailbox [2][64]
-struct WuLds { int xbuf, rec, swd, hist, thr, swapT, lml, stop, bk, mail, bot, cht, nef, lnb, bot2, total; };
+struct WuLds { int xbuf, rec, swd, hist, thr, swapT, lml, stop, bk, mail, bot, cht, nef, lnb, bot2, skey, sst, total; };
 constexpr int kWuBk = 13;      // tops0, samples, burn, conv_start, conv_streak, sumA lo / hi, sumB lo / hi, state (done | pending << 1 | has << 3),
                                // steps_done, converged, the lane's ladder (QUEUE)
 constexpr int kWuBkAlpha = 17; // ... and the alpha rule's second pair of window sums (n_x + n_y): sumAxy lo / hi, sumBxy lo / hi
@@ -80,8 +91,9 @@ constexpr int kWuHalf = 16;                                                     
 // tests the width --: padded rows cost the headline shape's criterion kernel its fourth workgroup per CU (42 KB instead of 39.9) and the route 11 %.
 __host__ __device__ inline int wu_rows(int W, bool conv) { return W > 16 ? kWuHalf : conv ? W : wu_words(W); }
 // (alpha rule: the 9 x 9 table of a proposal's count change as two fp16 numbers, the slots' n_eff attributes as doubles [Nc][64], ln(pz_i / pz_i+1),
-// and -- criterion runs -- slot 0's n_eff record by step parity)
-__host__ __device__ inline WuLds wu_lds(int Nc, int W, int ncls, int L, bool conv, bool alpha = false)
+// and -- criterion runs -- slot 0's n_eff record by step parity; shortest: the key of rung 0's new state by step parity [2][2][64] beside it, and the
+// booking wave's per-lane state of the shortest-chain statistics [kShortRows][64])
+__host__ __device__ inline WuLds wu_lds(int Nc, int W, int ncls, int L, bool conv, bool alpha = false, bool shortest = false)
 {
     const int WV = wu_words(W);
     WuLds o;
@@ -100,14 +112,19 @@ __host__ __device__ inline WuLds wu_lds(int Nc, int W, int ncls, int L, bool con
     o.nef = (o.cht + (alpha ? 84 : 0) + 1) & ~1;             // (doubles: 8-byte aligned)
     o.lnb = o.nef + (alpha ? Nc * 128 : 0);
     o.bot2 = o.lnb + (alpha ? 2 * Nc : 0);
-    o.total = o.bot2 + (alpha && conv ? 2 * 64 : 0);
+    o.skey = o.bot2 + (alpha && conv ? 2 * 64 : 0);
+    o.sst = o.skey + (shortest ? 4 * 64 : 0);
+    o.total = o.sst + (shortest ? kShortRows * 64 : 0);
     return o;
 }
-inline size_t wu_lds_bytes(int Nc, int W, int ncls, int L, bool conv, bool alpha) { return sizeof(uint32_t) * (size_t)wu_lds(Nc, W, ncls, L, conv, alpha).total; }
+inline size_t wu_lds_bytes(int Nc, int W, int ncls, int L, bool conv, bool alpha, bool shortest = false)
+{
+    return sizeof(uint32_t) * (size_t)wu_lds(Nc, W, ncls, L, conv, alpha, shortest).total;
+}
 
 // What the choice reads of a launch (kernel_shape(LadderArgs), plan_host.hpp).  top_acc / lower_acc: the top rung / some rung below it accepts every
 // proposal (acc_all_mask); logical: thr_logical != 0; queue: a work queue is offered (a.queue; plan_host() asks with 1 whether a plan takes one);
-// uset / xyz / stats / neff: a.uset_tab / a.xyz_thr / a.swap_acc / a.neff given; f32ok: every rung below the top may take the single-precision
+// uset / xyz / stats / neff: a.uset_tab / a.xyz_thr / a.swap_acc / a.neff given (stats = 2: a.short_neff given instead, the shortest-chain statistics); f32ok: every rung below the top may take the single-precision
 // acceptance estimate (bias_f32ok); tune: the developer bits of qecmc_params.flags (include/qecmc.h qecmc_flag)
 struct KernelShape {
     int code, noise, scan, L, Nc, W, nq, ncls, n_gen, n_types, gen_type, top_acc, lower_acc, logical, conv, queue, uset, xyz, stats, resume, neff, f32ok,
@@ -141,6 +158,13 @@ inline KernelKey colour_key(int code, bool conv, int rule) { return {kFamColour,
 constexpr uint32_t kKeyStats = 1u;
 inline KernelKey wave_stats_key(int code, int wv, bool alpha) { return {kFamWave, 1024, 4, code, kKeyStats, wv, 0, 0, alpha, 0, nullptr}; }
 inline KernelKey colour_stats_key(int code, int rule) { return {kFamColour, 1024, 4, code, kKeyStats, 0, 0, 0, 0, rule, nullptr}; }
+
+// The shortest-chain kernels (qecmc_plan_set_shortest: ladder_wu_shortest_kernel<code, wv, it>, ladder_colour_shortest_kernel<code>): the alpha rule's criterion
+// kernels with the per-class minimum of slot 0's n_eff attribute and the set of distinct configurations seen at it -- kernels of their own again, flags =
+// kKeyShort.  They serve conv_mode NONE too (the criterion is then never consulted), so `conv` is 1 in their keys whatever the launch's.
+constexpr uint32_t kKeyShort = 2u;
+inline KernelKey wave_short_key(int code, int wv, int it) { return {kFamWave, 1024, 4, code, kKeyShort, wv, 1, it, 1, 0, nullptr}; }
+inline KernelKey colour_short_key(int code) { return {kFamColour, 1024, 4, code, kKeyShort, 0, 1, 0, 0, 2, nullptr}; }
 
 // dynamic LDS of a ladder_kernel workgroup (+ the per-lane statistics counters behind the group's region)
 inline size_t ladder_launch_lds(const KernelShape &s)
@@ -299,9 +323,27 @@ inline bool wave_cascade_once(const KernelShape &s)
            4 * wu_lds_bytes(s.Nc, s.W, s.ncls, s.L, false, false) <= 160 * 1024;
 }
 
+// stats = 2, the shortest-chain statistics of PTEQ_alpha_with_shortest: a chooser of their own (no shape the sweeps of stats = 0 / 1 present comes here).
+// The alpha rule on scan = wave -- what wu_supported() takes of it as a criterion run, on 1 024 threads at 4 waves per SIMD whatever the ladder's length --
+// and on scan = colour under choose_colour's alpha conditions.
+inline KernelKey choose_shortest(const KernelShape &s)
+{
+    if (s.noise != 2) return refuse("shortest-chain statistics: the alpha rule only (PTEQ_alpha_with_shortest)");
+    if (s.scan != 2 && s.scan != 3) return refuse("shortest-chain statistics: scan = wave or scan = colour (scan = random: the host loop of PTEQ_alpha_with_shortest)");
+    if (s.resume) return refuse("shortest-chain statistics: no resumed ladders");
+    if (s.uset) return refuse("shortest-chain statistics: not with the unique-chain estimators' set");
+    if (s.code != kCodeXzzx && s.code != kCodeRotated) return refuse("biased / alpha rule: xzzx and rotated codes only");
+    if (s.scan == 2) return colour_short_key(s.code);
+    KernelShape c = s;
+    c.conv = 1; c.stats = 0;
+    if (!wu_supported(c) || wu_lds_bytes(s.Nc, s.W, s.ncls, s.L, true, true, true) > 160 * 1024) return refuse("scan = wave: outside what it is built for");
+    return wave_short_key(s.code, wu_words(s.W), s.iters == 10 ? 10 : 0);
+}
+
 // the kernel a launch of this shape runs, or why none is built for it
 inline KernelKey choose_kernel(const KernelShape &s)
 {
+    if (s.stats == 2) return choose_shortest(s);
     if (s.scan == 3) return choose_wave(s);
     if (s.scan == 2) return choose_colour(s);
     // (a plain kernel never runs on the capped grid of a work queue)

@@ -102,6 +102,15 @@ struct LadderArgs {
     // criterion runs continued from device state (qecmc_pteq_resume_conv_dev; nullable): one record per ladder, loaded by wave 0 before
     // the step loop and stored behind it; all zero = a ladder that has not started
     uint32_t *crec;           // [N][conv_record_words(noise)]
+    // shortest-chain statistics of PTEQ_alpha_with_shortest (qecmc_plan_set_shortest; nullable; shortest_book.hpp): per ladder and class the smallest
+    // n_eff attribute slot 0 showed after burn-in, how often, and how many distinct configurations came with it
+    double *short_neff;       // [N][4]            100000.0 (the reference's sentinel): the class was never seen
+    uint32_t *short_n;        // [N][4]
+    uint32_t *short_uniq;     // [N][4]
+    uint8_t *short_over;      // [N]               the ladder offered more distinct keys than short_cap: its short_uniq row is unspecified
+    unsigned long long *short_set;   // [N][short_slots] keys, 0 = empty (zeroed by the launch path)
+    uint32_t short_slots;     //                   a power of two, >= 2 short_cap
+    uint32_t short_cap;
 };
 
 // The per-ladder criterion record of a continued run, in 32-bit words (sums: low word first).  The alpha rule's second pair of window sums
@@ -115,11 +124,13 @@ __host__ __device__ constexpr int conv_record_words(int noise) { return noise ==
 hipError_t launch_ladder(const LadderArgs &a, hipStream_t stream);     // ladder_rs.hip: the kernel choose_kernel() picks for kernel_shape(a) (plan_host.hpp), on its grid
 // the instantiation units, one per kernel family (built in parallel): the kernel of `k` if the unit builds it, else nullptr -- ladder_kernel
 // (ladder_{toric,surf,biased,sweep,uset}.hip), ladder_colour_kernel (ladder_colour.hip), ladder_wu_kernel (ladder_wu{,_xzzx,_rotated,_planar,_alpha}.hip),
-// the statistics kernels ladder_wu_stats_kernel (ladder_wu_stats{,_alpha}.hip) and ladder_colour_stats_kernel (ladder_colour_stats.hip)
+// the statistics kernels ladder_wu_stats_kernel (ladder_wu_stats{,_alpha}.hip) and ladder_colour_stats_kernel (ladder_colour_stats.hip), the shortest-chain
+// kernels ladder_wu_shortest_kernel (ladder_wu_shortest.hip) and ladder_colour_shortest_kernel (ladder_colour_shortest.hip)
 const void *ladder_toric_kernel(const KernelKey &), *ladder_surf_kernel(const KernelKey &), *ladder_biased_kernel(const KernelKey &),
     *ladder_sweep_kernel(const KernelKey &), *ladder_uset_kernel(const KernelKey &), *colour_kernel(const KernelKey &), *wave_toric_kernel(const KernelKey &),
     *wave_xzzx_kernel(const KernelKey &), *wave_rotated_kernel(const KernelKey &), *wave_planar_kernel(const KernelKey &), *wave_alpha_kernel(const KernelKey &),
-    *wave_stats_kernel(const KernelKey &), *wave_stats_alpha_kernel(const KernelKey &), *colour_stats_kernel(const KernelKey &);
+    *wave_stats_kernel(const KernelKey &), *wave_stats_alpha_kernel(const KernelKey &), *colour_stats_kernel(const KernelKey &),
+    *wave_shortest_kernel(const KernelKey &), *colour_shortest_kernel(const KernelKey &);
 
 // byte-state primitive kernels (primitives.hip); all pointers are device pointers
 hipError_t launch_apply_stabilizer(int code, int L, uint64_t N, const uint8_t *in, uint8_t *out, const int32_t *rows,

@@ -37,6 +37,7 @@
 // counts only when a move was accepted (:58,:70); the criterion on the logged attribute of slot 0 (decoders_biasednoise.py:204,229-238).
 #pragma once
 #include "ladder_kernel.hpp"
+#include "shortest_book.hpp"
 
 namespace qecmc {
 
@@ -63,7 +64,7 @@ __device__ __forceinline__ int wave_sum(int v)
 template <int CODE, bool CONV, int RULE = 0, int MAXT = 1024, int MINW = 4>
 __global__ __launch_bounds__(MAXT, MINW) void ladder_colour_kernel(const LadderArgs a)
 {
-    constexpr bool STATS = false;
+    constexpr bool STATS = false, SHORT = false;
 #include "ladder_colour_body.inc"
 }
 
@@ -73,7 +74,17 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_colour_kernel(const LadderA
 template <int CODE, int RULE>
 __global__ __launch_bounds__(1024, 4) void ladder_colour_stats_kernel(const LadderArgs a)
 {
-    constexpr bool STATS = true, CONV = false;
+    constexpr bool STATS = true, CONV = false, SHORT = false;
+#include "ladder_colour_body.inc"
+}
+
+// The alpha rule's criterion kernel with the shortest-chain statistics of qecmc_plan_set_shortest (choose_shortest's colour_short_key); conv_mode NONE runs
+// it to the horizon
+template <int CODE>
+__global__ __launch_bounds__(1024, 4) void ladder_colour_shortest_kernel(const LadderArgs a)
+{
+    constexpr bool STATS = false, CONV = true, SHORT = true;
+    constexpr int RULE = 2;
 #include "ladder_colour_body.inc"
 }
 

@@ -1,6 +1,10 @@
 // The body of the scan = 2 kernels (ladder_colour.hpp), included as text into ladder_colour_kernel and into ladder_colour_stats_kernel: one program
-// under two names, told apart by the compile-time STATS alone.  The includer provides CODE, CONV, RULE, STATS and the argument `a`.
+// under two names, told apart by the compile-time STATS alone.  The includer provides CODE, CONV, RULE, STATS, SHORT and the argument `a`.
+// SHORT (ladder_colour_shortest_kernel): the shortest-chain statistics of qecmc_plan_set_shortest (shortest_book.hpp) on the alpha rule's criterion kernel: wave 0
+// owns slot 0's class and attribute as scalars, mixes the key from the W words of the state it holds, and its lane 0 books.  conv_mode NONE: the criterion is
+// never consulted.
     static_assert(RULE == 0 || CODE == kCodeXzzx || CODE == kCodeRotated, "the biased / alpha rules: xzzx and rotated codes");
+    static_assert(!SHORT || (CONV && RULE == 2 && !STATS), "the shortest-chain kernels: the alpha rule's criterion kernel");
     extern __shared__ uint32_t lds[];
     const int NC = a.Nc, W = a.W, L = a.L, LL = L * L, nq = a.nq, ncls = a.ncls;
     const int tid = (int)threadIdx.x, lane = tid & 63;
@@ -17,6 +21,8 @@
     volatile uint32_t *stopf = swt + (swap32 ? 1 : 2) * (NC > 1 ? NC - 1 : 0) * (a.nq + 1);   // [2] "the ladder has converged", by step parity
     [[maybe_unused]] uint32_t *cthr = const_cast<uint32_t *>(stopf) + 2;                  // RULE != 0: [NC][81] accept iff u <= cthr[9 (dz + 4) + dxy + 4]
     [[maybe_unused]] uint32_t *nefr = cthr + (RULE ? NC * 81 : 0);                          // RULE == 2: [2][NC] the slots' n_eff records (n_z | n_xy << 16) by step parity
+    // SHORT: [kShortRows] the ladder's shortest-chain state (lane 0 of wave 0), behind the records: colour_lds_dwords(..., shortest) counts it
+    [[maybe_unused]] uint32_t *shs = SHORT ? lds + colour_short_at(NC, W, ncls, a.n_phases, a.n_gen, L, nq, swap32) : nullptr;
     const uint32_t R = a.replicas;
     const uint64_t ladder = blockIdx.x;                  // one workgroup per ladder
     if (ladder >= a.N) return;
@@ -41,6 +47,7 @@
     for (int i = tid; i < (int)a.n_gen; i += NC * 64) gtab[i] = a.gen[i];
     for (int i = tid; i < 4 * (L + 1) * W; i += NC * 64) lml[i] = a.lmask[i];
     if constexpr (RULE != 0) { for (int i = tid; i < NC * 81; i += NC * 64) cthr[i] = a.col_thr[i]; }
+    if constexpr (SHORT) { for (int i = tid; i < kShortRows; i += NC * 64) shs[i] = short_init_word(i); }
     for (int i = tid; i < (NC - 1) * (nq + 1); i += NC * 64) {
         if (swap32) swt[i] = (uint32_t)a.swap_thr[i];      // (entry d = 0 -- 2^32 -- is never looked up: d <= 0 always swaps)
         else { swt[2 * i] = (uint32_t)a.swap_thr[i]; swt[2 * i + 1] = (uint32_t)(a.swap_thr[i] >> 32); }
@@ -327,7 +334,16 @@
             if (a.counts != nullptr && tops0 >= a.tops_burn) {                           // decoders.py:60-67
                 if (lane == 0) hist[CODE == kCodeXzzx ? (cls ^ (cls >> 1)) : cls] += 1;
                 samples++;
-                if constexpr (CONV) {
+                if constexpr (SHORT) {
+                    // decoders_biasednoise.py:128-144 on chains[0].n_eff -- this wave's attribute -- and the key of the configuration it now holds
+                    uint64_t h = 0;
+                    for (int w = lane; w < W; w += 64) h ^= short_key_at((uint32_t)w, st[sid * W + w]);
+#pragma unroll
+                    for (int o = 32; o >= 1; o >>= 1) h ^= ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(h >> 32), o, 64) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)h, o, 64);
+                    const double v = alpha_neff(nef, a.alpha);
+                    if (lane == 0) short_book(a, ladder, shs, 1, CODE == kCodeXzzx ? (cls ^ (cls >> 1)) : cls, v, short_key_finish(h, v));
+                }
+                if constexpr (CONV) if (!SHORT || a.conv_mode != 0) {
                     // the series value of this step (RULE == 2: slot 0's attribute -- this wave's -- as its two counts, 4 B) goes into the log; the
                     // three entries that leave / enter the windows are independent loads (one round trip on wave 0's path per step)
                     const size_t lN = (size_t)a.N;
@@ -346,7 +362,7 @@
             }
             if (!t_reached && tops0 >= a.TOPS) t_reached = (uint32_t)t + 1u;
             if constexpr (CONV) {
-                if (tops0 >= a.TOPS) {                                                   // :74
+                if ((!SHORT || a.conv_mode != 0) && tops0 >= a.TOPS) {                   // :74 (SHORT, conv_mode NONE: the run goes to the horizon)
                     const bool accept = criterion_accepts<RULE == 2>(samples, sumA, sumAxy, sumB, sumBxy, a.alpha, a.eps);
                     if (streak_ends(accept, tops0, a.SEQ, conv_start, conv_streak)) { done = 1; steps_done = (uint32_t)t + 1u; }
                 }
@@ -367,6 +383,7 @@
             const uint32_t sd = CONV ? (done ? steps_done : (uint32_t)a.nsteps) : (t_reached ? t_reached : (uint32_t)a.nsteps);
             const bool reached = CONV ? done != 0 : t_reached != 0;
             store_ladder_results(a.samples, a.tops0, a.steps_done, a.converged, row, R, false, samples, tops0, sd, reached);
+            if constexpr (SHORT) short_store(a, ladder, shs, 1);
         }
     }
     if (a.write_states && a.states != nullptr) {

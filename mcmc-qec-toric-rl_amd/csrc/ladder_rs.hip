@@ -13,7 +13,7 @@ const void *kernel_of(const KernelKey &k)
     const void *fn = nullptr;
     for (auto unit : {ladder_toric_kernel, ladder_surf_kernel, ladder_biased_kernel, ladder_sweep_kernel, ladder_uset_kernel, colour_kernel,
                       wave_toric_kernel, wave_xzzx_kernel, wave_rotated_kernel, wave_planar_kernel, wave_alpha_kernel, wave_stats_kernel,
-                      wave_stats_alpha_kernel, colour_stats_kernel})
+                      wave_stats_alpha_kernel, colour_stats_kernel, wave_shortest_kernel, colour_shortest_kernel})
         fn = fn ? fn : unit(k);
     return fn;
 }
@@ -49,6 +49,21 @@ hipError_t launch_ladder(const LadderArgs &a, hipStream_t stream)
     const KernelKey k = choose_kernel(kernel_shape(a));
     const void *fn = k.ok() ? kernel_of(k) : nullptr;
     if (!fn) return hipErrorInvalidValue;
+    const bool shortest = (k.family == kFamWave || k.family == kFamColour) && k.flags == kKeyShort;   // (ladder_kernel's flags are a LadderFlag mask)
+    if (shortest) {
+        // qecmc_plan_set_shortest: every output and the ladders' sets (zeroed by the caller), fresh single ladders; the criterion needs its log
+        if (!a.short_neff || !a.short_n || !a.short_uniq || !a.short_over || !a.short_set || a.short_cap == 0 || a.short_slots < 2u * a.short_cap ||
+            (a.short_slots & (a.short_slots - 1u)) || a.replicas > 1 || a.resume || a.swap_acc || a.step0 || a.nsteps == 0 || (a.conv_mode != 0 && a.nlog == nullptr))
+            return hipErrorInvalidValue;
+    }
+    if (shortest && k.family == kFamWave) {
+        // ... on scan = 3 the queue kernel with one ladder per lane for the whole run: a workgroup owns 64 ladders, no lane is ever refilled, and the
+        // layout -- ladder l in lane l & 63 of workgroup l >> 6, one log column per ladder -- is that of a launch without the queue
+        if (a.wu_desc == nullptr || (a.first_syndrome & 63u) || a.bias_tbl == nullptr || a.alpha_lnb == nullptr || a.write_states) return hipErrorInvalidValue;
+        LadderArgs b = a;
+        b.wu_chunk = 64u; b.wu_once = 0u; b.queue = nullptr; b.grid_cap = 0u;
+        return launch_fn(fn, b, stream, (unsigned)((a.N + 63) / 64), shortest_lds_bytes(a));
+    }
     if (k.family == kFamWave) {
         // scan = 3: batches start on a multiple of 64 (a wavefront shares its generator picks); the criterion runs on a persistent grid of
         // a.grid_cap workgroups (capi.hip), each owning a.wu_chunk ladders of the batch
@@ -63,7 +78,7 @@ hipError_t launch_ladder(const LadderArgs &a, hipStream_t stream)
         // scan = 2: one ladder per workgroup
         if (a.phase_tab == nullptr || a.n_phases == 0 || (a.conv_mode != 0 && a.nlog == nullptr)) return hipErrorInvalidValue;
         if (a.noise != 0 && (a.col_thr == nullptr || a.bias_tbl == nullptr || (a.noise == 2 && a.alpha_lnb == nullptr))) return hipErrorInvalidValue;
-        const size_t lds = sizeof(uint32_t) * colour_lds_dwords(a.Nc, a.W, a.ncls, a.n_phases, a.n_gen, a.L, a.nq, a.swap_fast_ok != 0, a.noise);
+        const size_t lds = shortest ? shortest_lds_bytes(a) : sizeof(uint32_t) * colour_lds_dwords(a.Nc, a.W, a.ncls, a.n_phases, a.n_gen, a.L, a.nq, a.swap_fast_ok != 0, a.noise);
         if (lds > 160 * 1024) return hipErrorInvalidValue;
         return launch_fn(fn, a, stream, (unsigned)a.N, lds);
     }

@@ -34,6 +34,7 @@
 // Batches must start on a multiple of 64 (first_syndrome & 63 == 0) so that a wavefront is one pick group.
 #pragma once
 #include "ladder_kernel.hpp"
+#include "shortest_book.hpp"
 
 namespace qecmc {
 
@@ -340,12 +341,6 @@ template <int WV> __device__ __forceinline__ uint32_t wu_counts_packed(typename 
 #undef QECMC_WU_C3
     return nx | (nz << 10) | (nxy << 20);
 }
-// n_eff = n_z + alpha (n_x + n_y) as Chain_alpha forms it (mcmc_alpha.py:22,58) from the record n_z | n_xy << 16
-__device__ __forceinline__ double wu_neff(uint32_t rec, double alpha)
-{
-#pragma clang fp contract(off)
-    return (double)(rec & 0xFFFFu) + alpha * (double)(rec >> 16);
-}
 // Ladder_alpha.r_flip (mcmc_alpha.py:118-123) on the slots' attributes: u < (pz_lo / pz_hi) ** (n_eff_hi - n_eff_lo), the power as
 // det_exp(e ln b) like the CPU oracle -- behind a single-precision estimate of 2^32 times it that settles all but ~6e-5 of the tests
 // (the estimate's relative error stays below 5e-6: the exponent is rounded to a float of magnitude <= 32 wherever the outcome is open)
@@ -481,12 +476,16 @@ __device__ __forceinline__ bool wu_pair_flips(const LadderArgs &a, uint32_t car,
 // a slot here, so its attribute is a register --, the floating-point swap test, the criterion on the logged count pairs.
 // STATS (ladder_wu_stats_kernel): the equilibrium observables of qecmc_plan_set_stats.  The wave of slot s >= 1 itself decides pair s - 1 when it
 // replays the cascade and ends the step holding its slot's record: two counters per lane, in registers (cx.swapc, cx.nsum), no LDS, no atomics.
-template <int CODE, int WV, bool CONV, bool QUEUE, bool TOP, int IT, bool ALPHA, bool STATS = false>
+// SHORT (ladder_wu_shortest_kernel): the shortest-chain statistics of qecmc_plan_set_shortest (shortest_book.hpp) on the alpha rule's queue kernel, run with
+// one ladder per lane (wu_chunk = 64: no refill).  Wave 0, which ends a step holding rung 0's new state in registers, leaves that state's 64-bit key beside
+// bot / bot2; the booking wave, a step behind, applies the reference's rule to its lane's rows in LDS.  conv_mode NONE: the criterion is never consulted.
+template <int CODE, int WV, bool CONV, bool QUEUE, bool TOP, int IT, bool ALPHA, bool STATS = false, bool SHORT = false>
 __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::type &st, WuCtx &cx, const WuEnv &ev)
 {
     static_assert(!QUEUE || CONV, "the work queue serves the runs that stop by the criterion");
     static_assert(!ALPHA || CODE != kCodeToric, "the alpha rule: xzzx / rotated codes");
     static_assert(!STATS || (!CONV && WV <= 16), "the statistics kernels: fixed-length runs of up to 16 state words");
+    static_assert(!SHORT || (CONV && QUEUE && ALPHA && !STATS), "the shortest-chain kernels: the alpha rule's queue kernels");
     [[maybe_unused]] uint32_t swapc = 0, nsum = 0;
     const int L = a.L;
     wu_lds_ptr const lml = (wu_lds_ptr)(uintptr_t)(ev.lds0 + ev.lml_off);
@@ -779,7 +778,7 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
         asm volatile("" : "+s"(NCl), "+s"(nql), "+s"(ncl), "+s"(Ll), "+s"(slotl), "+s"(lds0l), "+s"(Wl));
         const int NC = NCl, nq = nql, ncls = ncl;
         const uint32_t slot = slotl;
-        const WuLds ol = wu_lds(NC, Wl, ncls, Ll, CONV, ALPHA);
+        const WuLds ol = wu_lds(NC, Wl, ncls, Ll, CONV, ALPHA, SHORT);
         // (LDS pointers by address space: a laundered generic pointer would turn every access below into a flat load)
         wu_lds_rw const ldsl = (wu_lds_rw)(uintptr_t)lds0l;
         wu_lds_rw const rec = ldsl + ol.rec, swd = ldsl + ol.swd, hist = ldsl + ol.hist, swapT = ldsl + ol.swapT;
@@ -787,6 +786,7 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
         [[maybe_unused]] wu_lds_rw const bk = ldsl + ol.bk + (uint32_t)lane, mail = ldsl + ol.mail, bot = ldsl + ol.bot, bot2 = ldsl + ol.bot2;
         [[maybe_unused]] wu_lds_drw const nefd = (wu_lds_drw)(ldsl + ol.nef) + (uint32_t)lane;
         [[maybe_unused]] wu_lds_dptr const lnbd = (wu_lds_dptr)(ldsl + ol.lnb);
+        [[maybe_unused]] wu_lds_rw const skey = ldsl + ol.skey + (uint32_t)lane, sst = ldsl + ol.sst + (uint32_t)lane;   // SHORT: [2][2][64] keys, [kShortRows][64] state
         const uint32_t xaddr = lds0l + (uint32_t)lane * 4u;
         constexpr bool PAD = WV == 32 || !CONV;                                      // (wu_rows: padded rows, transfers without width tests)
         const uint32_t xstride = (uint32_t)(WV == 32 ? kWuHalf : PAD ? WV : Wl) * 256u;  // bytes of one rung in the exchange buffer
@@ -802,7 +802,7 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
 #define QECMC_WU_PUT_HI(w) if constexpr (w < WV && w >= kWuHalf) wu_ds_write<WV, w, w - kWuHalf>(st, xo);
             WU_EACH(QECMC_WU_PUT)
             rec[slot * 64u + (uint32_t)lane] = pack_info(n4 >> 2, slot, cls, flag);
-            if constexpr (ALPHA) nefd[slot * 64u] = wu_neff(nef, a.alpha);
+            if constexpr (ALPHA) nefd[slot * 64u] = alpha_neff(nef, a.alpha);
             if (duty) {
                 wu_lds_rw p = swd + (uint32_t)(swb * 4) * 64u + (uint32_t)lane;
                 const int left = NC - 1 - swb * 4;
@@ -871,6 +871,16 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
             } else if (slot == 0) {
                 bot[((uint32_t)t & 1u) * 64u + (uint32_t)lane] = mine;              // (booked by the top rung's wave behind the next step's barrier)
                 if constexpr (ALPHA) bot2[((uint32_t)t & 1u) * 64u + (uint32_t)lane] = nef;   // chains[0].n_eff, decoders_biasednoise.py:204
+                if constexpr (SHORT) {
+                    // the key of (rung 0's new configuration, slot 0's attribute): the padding words are zero in every state, they travel with the rest
+                    uint64_t h = kShortKeySeed;
+#define QECMC_WU_KEY(w) if constexpr (w < WV) h = short_key_word(h, wu_get<WV, w>(st));
+                    WU_EACH(QECMC_WU_KEY)
+#undef QECMC_WU_KEY
+                    h = short_key_finish(h, alpha_neff(nef, a.alpha));
+                    skey[((uint32_t)t & 1u) * 128u] = (uint32_t)h;
+                    skey[((uint32_t)t & 1u) * 128u + 64u] = (uint32_t)(h >> 32);
+                }
             }
             if constexpr (CONV && TOP) {
                 // ---- ladder + PTEQ bookkeeping with the error_based criterion (decoders.py:60-82,93-105), by the wave of the TOP rung -- the
@@ -894,6 +904,13 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
                 if (a.counts != nullptr && b_tops0 >= a.tops_burn) {             // decoders.py:60-67
                     hist[(CODE == kCodeXzzx ? (cls0 ^ (cls0 >> 1)) : cls0) * 64 + lane] += 1;
                     b_samples++;
+                    if constexpr (SHORT) {
+                        // decoders_biasednoise.py:128-144 on chains[0].n_eff and the bottom configuration's key (the lane's ladder: bk row 12)
+                        const uint32_t kp = ((uint32_t)tb & 1u) * 128u;
+                        short_book(a, (uint64_t)bk[768], sst, 64, CODE == kCodeXzzx ? (cls0 ^ (cls0 >> 1)) : cls0,
+                                   alpha_neff(bot2[((uint32_t)tb & 1u) * 64u + (uint32_t)lane], a.alpha), (uint64_t)skey[kp] | ((uint64_t)skey[kp + 64u] << 32));
+                    }
+                    if (!SHORT || a.conv_mode != 0) {
                     // nbr_errors_bottom_chain[since_burn] = count_errors (:68), logged in HBM: series index i in row burn + i of the
                     // lane's column (QUEUE: a column per lane of the grid, rows = the ladder's own steps)
                     const size_t lN = QUEUE ? (size_t)gridDim.x * 64u : (size_t)a.N;
@@ -923,10 +940,11 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
                         pf_a = a2 != a1 ? mylog[(size_t)(b_burn + a1) * lN] : 0u;
                         pf_l = l2;
                     }
+                    }
                 } else {
                     b_burn++;                                                    // resulting_burn_in, :71
                 }
-                if (b_tops0 >= a.TOPS) {                                         // :74
+                if ((!SHORT || a.conv_mode != 0) && b_tops0 >= a.TOPS) {        // :74 (SHORT, conv_mode NONE: the run goes to the horizon)
                     const bool accept = criterion_accepts<ALPHA>(b_samples, sumA, sumAxy, sumB, sumBxy, a.alpha, a.eps);
                     if (accept) {                                                // (pteq_book.hpp's streak_ends, in place: the call changes resource rows)
                         if (b_cstreak >= a.SEQ) { ended = true; conv_ok = 1; }   // :77-78
@@ -964,6 +982,7 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
                         if (a.steps_done != nullptr) a.steps_done[row] = sd;
                         if (a.converged != nullptr) a.converged[row] = (uint8_t)conv_ok;
                     }
+                    if constexpr (SHORT) short_store(a, row, sst, 64);            // (one ladder per lane: nothing to reset)
                     b_tops0 = b_samples = b_burn = b_cstart = b_cstreak = 0; sumA = sumB = 0; sumAxy = sumBxy = 0;
                     const uint32_t cand = (uint32_t)stopf[2] + (uint32_t)__popcll(em & ((1ull << lane) - 1ull));
                     give = (uint64_t)cand < ev.chunk_hi ? cand : kWuDead;
@@ -1020,7 +1039,7 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
 template <int MAXT, int MINW, int CODE, int WV, bool CONV, bool QUEUE, int IT, bool ALPHA = false>
 __global__ __launch_bounds__(MAXT, MINW) void ladder_wu_kernel(const LadderArgs a)
 {
-    constexpr bool STATS = false;
+    constexpr bool STATS = false, SHORT = false;
 #include "ladder_wu_body.inc"
 }
 
@@ -1029,8 +1048,17 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_wu_kernel(const LadderArgs 
 template <int CODE, int WV, bool ALPHA>
 __global__ __launch_bounds__(1024, 4) void ladder_wu_stats_kernel(const LadderArgs a)
 {
-    constexpr bool STATS = true, CONV = false, QUEUE = false;
+    constexpr bool STATS = true, CONV = false, QUEUE = false, SHORT = false;
     constexpr int IT = 0;
+#include "ladder_wu_body.inc"
+}
+// The alpha rule's queue kernel with the shortest-chain statistics of qecmc_plan_set_shortest (choose_shortest's wave_short_key): launched with one ladder
+// per lane (a.wu_chunk = 64 on ceil(N / 64) workgroups), so a ladder's results depend on (seed, global ladder index) alone; 1 024 threads at 4 waves per
+// SIMD whatever the ladder's length; IT = 10 / 0 as in ladder_wu_kernel
+template <int CODE, int WV, int IT>
+__global__ __launch_bounds__(1024, 4) void ladder_wu_shortest_kernel(const LadderArgs a)
+{
+    constexpr bool STATS = false, CONV = true, QUEUE = true, ALPHA = true, SHORT = true;
 #include "ladder_wu_body.inc"
 }
 // (the transfer macros of wu_run's general tail, which the kernels' epilogue shares)
@@ -1043,6 +1071,15 @@ struct WaveStatsSet {
     static const void *find(const KernelKey &k)
     {
         return k == wave_stats_key(CODE, WV, ALPHA) ? (const void *)ladder_wu_stats_kernel<CODE, WV, ALPHA> : nullptr;
+    }
+};
+
+template <int CODE, int WV>
+struct WaveShortestSet {
+    static const void *find(const KernelKey &k)
+    {
+        if (!(k == wave_short_key(CODE, WV, k.it))) return nullptr;
+        return k.it == 10 ? (const void *)ladder_wu_shortest_kernel<CODE, WV, 10> : k.it == 0 ? (const void *)ladder_wu_shortest_kernel<CODE, WV, 0> : nullptr;
     }
 };
 

@@ -1,13 +1,13 @@
 // The body of the scan = 3 kernels (ladder_wu.hpp), included as text into ladder_wu_kernel and into ladder_wu_stats_kernel: the two are one program
 // under two names, told apart by the compile-time STATS alone (wrapped in a force-inlined function the body compiles to other code in the
-// kernels that sit at their register budget, DESIGN.md 7).  The includer provides CODE, WV, CONV, QUEUE, IT, ALPHA, STATS and the argument `a`.
+// kernels that sit at their register budget, DESIGN.md 7).  The includer provides CODE, WV, CONV, QUEUE, IT, ALPHA, STATS, SHORT and the argument `a`.
     typedef typename WuVec<WV>::type vec_t;
     extern __shared__ uint32_t lds[];
     const int NC = a.Nc, W = a.W, L = a.L, nq = a.nq, ncls = a.ncls;
     const int nthreads = NC * 64;
     const int tid = (int)threadIdx.x, lane = tid & 63;
     const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);      // this wave's rung (fixed: states move)
-    const WuLds o = wu_lds(NC, W, ncls, L, CONV, ALPHA);
+    const WuLds o = wu_lds(NC, W, ncls, L, CONV, ALPHA, SHORT);
     uint32_t *xbuf = lds + o.xbuf, *rec = lds + o.rec, *hist = lds + o.hist, *thrT = lds + o.thr;
     uint32_t *swapT = lds + o.swapT, *lml = lds + o.lml;
     volatile uint32_t *stopf = lds + o.stop;
@@ -30,6 +30,9 @@
             bk[i] = row == 9 ? (l < cnt ? 8u : 0u) : row == 12 ? (uint32_t)s0 + (uint32_t)l : 0u;                   // state: has; the lane's ladder
         }
         for (int i = tid; i < 128; i += nthreads) mail[i] = kWuKeep;
+    }
+    if constexpr (SHORT) {
+        for (int i = tid; i < kShortRows * 64; i += nthreads) lds[o.sst + i] = short_init_word(i >> 6);
     }
     if constexpr (ALPHA) {
         // (D_xy, D_z) of a proposal as two fp16 integers, at byte offset 4 ((D_z + 4) + 9 (D_xy + 4)); ln(pz_i / pz_i+1) of the rung pairs
@@ -95,8 +98,8 @@
     ev.lad = live ? (uint32_t)ladder : kWuDead;
     ev.lane = lane; ev.chunk_hi = s1;
     // (the two roles are separate loops: they meet at the step's barriers)
-    if (top) wu_run<CODE, WV, CONV, QUEUE, true, IT, ALPHA, STATS>(a, st, cx, ev);
-    else wu_run<CODE, WV, CONV, QUEUE, false, IT, ALPHA, STATS>(a, st, cx, ev);
+    if (top) wu_run<CODE, WV, CONV, QUEUE, true, IT, ALPHA, STATS, SHORT>(a, st, cx, ev);
+    else wu_run<CODE, WV, CONV, QUEUE, false, IT, ALPHA, STATS, SHORT>(a, st, cx, ev);
     if constexpr (QUEUE) return;                                      // (every ladder wrote its results when it ended)
     if constexpr (STATS) {
         // qecmc_plan_set_stats: this wave's two counters of the lane's ladder -- pair slot - 1 (mcmc.py:97-99) and the slot's summed error counts

@@ -93,7 +93,7 @@ inline KernelShape kernel_shape(const LadderArgs &a)
     const uint32_t lower = (1u << (a.Nc - 1)) - 1u;      // rungs below the top
     return {a.code, a.noise, a.scan, a.L, a.Nc, a.W, a.nq, a.ncls, (int)a.n_gen, a.n_types, a.gen_type != nullptr, (int)((a.acc_all_mask >> (a.Nc - 1)) & 1u),
             (a.acc_all_mask & lower) != 0, a.thr_logical != 0, a.conv_mode != 0, a.queue != nullptr, a.uset_tab != nullptr, a.xyz_thr != nullptr,
-            a.swap_acc != nullptr, a.resume != 0, a.neff != nullptr, (a.bias_f32ok & lower) == lower, a.swap_fast_ok != 0,
+            a.swap_acc != nullptr ? 1 : a.short_neff != nullptr ? 2 : 0, a.resume != 0, a.neff != nullptr, (a.bias_f32ok & lower) == lower, a.swap_fast_ok != 0,
             a.iters > 0x7FFFFFFFu ? 0x7FFFFFFF : (int)a.iters, (int)a.tune};
 }
 inline bool same_shape(const KernelShape &a, const KernelShape &b) { return std::memcmp(&a, &b, sizeof a) == 0; }   // (ints only: no padding)
@@ -290,6 +290,28 @@ inline qecmc_params plan_key(const qecmc_params &p)
     k.iters = p.iters; k.tops_burn = p.tops_burn; k.TOPS = p.TOPS; k.SEQ = p.SEQ; k.replicas = p.replicas; k.eps = p.eps; k.p = p.p; k.eta = p.eta;
     k.alpha = p.alpha; k.p_logical = p.p_logical; k.flags = p.flags;
     return k;
+}
+
+// The shortest-chain statistics (qecmc_plan_set_shortest): slots of a ladder's set of `set_capacity` distinct keys -- the smallest power of two that is at
+// least twice as many --, THE formula of the set workspace, and what the statistics refuse of a plan before they look at a buffer (the chooser's text).
+inline uint64_t shortest_set_slots(uint64_t set_capacity) { uint64_t s = 2; while (s < 2 * set_capacity) s <<= 1; return s; }
+constexpr uint64_t kShortMaxCapacity = uint64_t(1) << 26;
+inline uint64_t shortest_set_need(uint64_t N, uint64_t set_capacity) { return N * shortest_set_slots(set_capacity) * sizeof(uint64_t); }
+inline Refusal shortest_check(const qecmc_params &prm, const KernelShape &plan_shape)
+{
+    KernelShape s = plan_shape;
+    s.stats = 2;
+    if (const KernelKey k = choose_kernel(s); !k.ok()) return refuse_params(QECMC_ERR_UNSUPPORTED, "qecmc_plan_set_shortest: %s", k.why);
+    if (prm.replicas > 1) return refuse_params(QECMC_ERR_UNSUPPORTED, "qecmc_plan_set_shortest: the statistics are per ladder: not with replicas > 1");
+    return {};
+}
+
+// LDS bytes of a workgroup of the shortest-chain kernels (the plan's args: scan = wave or colour under the alpha rule): what launch_ladder asks for, what
+// qecmc_plan_set_shortest holds against the 160 KiB of a workgroup and qecmc_plan_info reports while the statistics are set
+inline size_t shortest_lds_bytes(const LadderArgs &a)
+{
+    if (a.scan == QECMC_SCAN_WAVE) return wu_lds_bytes(a.Nc, a.W, a.ncls, a.L, true, true, true);
+    return sizeof(uint32_t) * colour_lds_dwords(a.Nc, a.W, a.ncls, a.n_phases, a.n_gen, a.L, a.nq, a.swap_fast_ok != 0, a.noise, true);
 }
 
 // a criterion launch of `steps` ladder steps runs on the plan's persistent grid unless it asks for final states or statistics

@@ -44,6 +44,14 @@ __device__ __forceinline__ void window_update(uint32_t v0, uint32_t vc, uint32_t
     }
 }
 
+// n_eff = n_z + alpha (n_x + n_y) of a record n_z | n_xy << 16 as Chain_alpha forms it (mcmc_alpha.py:22,58; alpha_flip rebuilds it the same way): the one
+// spelling every layout uses (product and sum rounded separately, as the reference's and the oracle's double arithmetic does)
+__device__ __forceinline__ double alpha_neff(uint32_t rec, double alpha)
+{
+#pragma clang fp contract(off)
+    return (double)(rec & 0xFFFFu) + alpha * (double)(rec >> 16);
+}
+
 // conv_crit_error_based_PT_alpha, decoders_biasednoise.py:229-238: |mean Q2 - mean Q4| < eps on the n_eff series, each mean
 // formed as (sum n_z + alpha sum n_xy) / len from exact integer sums
 __device__ inline bool alpha_series_close(uint64_t z2, uint64_t xy2, uint32_t den2, uint64_t z4, uint64_t xy4, uint32_t den4,

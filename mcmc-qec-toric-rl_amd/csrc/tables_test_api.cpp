@@ -159,5 +159,29 @@ int qt_resume_conv_check(const qecmc_params *p, char *msg, int msg_cap)
     if (msg && msg_cap > 0) std::snprintf(msg, (size_t)msg_cap, "%s", r.msg.c_str());
     return r.code;
 }
+// the shortest-chain statistics (qecmc_plan_set_shortest): what they refuse of a parameter block before a buffer is looked at, and the set workspace
+int qt_shortest_check(const qecmc_params *p, char *msg, int msg_cap)
+{
+    Refusal r = validate_params(p);
+    HostPlan hp;
+    if (!r.code) r = plan_host(*p, hp);
+    if (!r.code) r = shortest_check(*p, hp.shape);
+    snprintf(msg, (size_t)msg_cap, "%s", r.msg.c_str());
+    return r.code;
+}
+// LDS of an accepted plan's shortest-chain kernels: the bytes a launch asks for, the plan's plain figure, and -- scan = colour -- the dword at which the
+// kernel keeps the kShortRows words of the statistics (0 otherwise); -1: the block is refused
+int qt_shortest_lds(const qecmc_params *p, uint64_t *short_bytes, uint64_t *plain_bytes, uint32_t *colour_at, uint32_t *rows)
+{
+    HostPlan hp;
+    if (validate_params(p).code || plan_host(*p, hp).code || shortest_check(*p, hp.shape).code) return -1;
+    const LadderArgs &a = hp.args;
+    *short_bytes = shortest_lds_bytes(a);
+    *plain_bytes = hp.lds_bytes;
+    *colour_at = p->scan == QECMC_SCAN_COLOUR ? colour_short_at(a.Nc, a.W, a.ncls, a.n_phases, a.n_gen, a.L, a.nq, a.swap_fast_ok != 0) : 0u;
+    *rows = (uint32_t)kShortRows;
+    return 0;
+}
+uint64_t qt_shortest_set_need(uint64_t N, uint64_t set_capacity) { return shortest_set_need(N, set_capacity); }
 int qt_launch_takes_queue(uint32_t grid, uint64_t steps, int wants_states_or_stats) { return launch_takes_queue(grid, steps, wants_states_or_stats != 0); }
 }

@@ -97,6 +97,10 @@ SIGNATURES = {
     "qecmc_pteq_batch_stats": (C.c_int, [C.POINTER(Params), _u8p, C.c_uint64, _u32p, _u32p, _u32p, _u32p, _u8p, _u8p, _u32p, _u32p,
                                          C.POINTER(Stats)]),
     "qecmc_plan_set_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qecmc_plan_shortest_set_bytes": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "qecmc_plan_set_shortest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "qecmc_pteq_batch_shortest": (C.c_int, [C.POINTER(Params), _u8p, C.c_uint64, C.c_uint64, _u32p, _u32p, _u32p, _u32p, _u8p, C.POINTER(C.c_double),
+                                            _u32p, _u32p, _u8p, C.POINTER(Stats)]),
     "qecmc_pteq_resume_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64,
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "qecmc_plan_resume_conv_bytes": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

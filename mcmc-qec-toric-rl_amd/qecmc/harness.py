@@ -184,6 +184,8 @@ def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_
     noise 'depolarizing' -> PTEQ (:136); 'biased' -> errors from the eta split (:78-83) decoded by PTEQ_alpha with
     (pz_tilde, alpha) derived from (p, eta) exactly as :142-150 does (biased_decoder="biased" decodes with PTEQ_biased
     instead); 'alpha' -> p_error is pz_tilde, errors and decoder from (pz_tilde, alpha) (:84-91,:151-160).
+    params['method'] = "PTEQ_with_shortest" (alpha noise, generate_data.py:167-173) runs pteq_shortest_batch (scan "wave" unless given) and keeps the three
+    vectors of PTEQ_alpha_with_shortest per datapoint: distr, distr_shortest, distr_shortest_n (success from the first).
     params['method'] (default "PTEQ") may also be "PTDC", "PTRC", "STDC", "STRC" or "STDC_N_n" (generate_data.py:168-196): the
     unique-chain estimators on one representative per class of every syndrome, with params['p_sampling'] (default p_error),
     params['droplets'], params['conv_mult'] and `steps` as the estimator's own `steps`; `batch` syndromes go into one launch
@@ -212,6 +214,20 @@ def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_
         eq_true = np.asarray(_class_of(code, raw), dtype=np.int32)
         init = hide_class(code, raw, rng)
     method = params.get("method", "PTEQ")
+    if method == "PTEQ_with_shortest":                                         # generate_data.py:167-173, PTEQ_alpha_with_shortest on the whole batch
+        if noise != "alpha":
+            raise ValueError("method PTEQ_with_shortest is defined for alpha noise (generate_data.py:167-173)")
+        from .decoders_biasednoise import pteq_shortest_batch, shortest_distribution
+        pteq_kw.setdefault("scan", "wave")
+        res = pteq_shortest_batch(init, p, params["alpha"], Nc=params.get("Nc") or size, steps=steps, conv_criteria=conv_criteria, seed=seed, code=code,
+                                  **pteq_kw)
+        distr, distr_shortest, distr_shortest_n = shortest_distribution(res, p)
+        out = dict(qubit_matrix=raw, eq_true=eq_true, counts=res["counts"], distr=distr, distr_shortest=distr_shortest, distr_shortest_n=distr_shortest_n,
+                   success=np.argmax(distr, axis=1) == eq_true, steps_done=res["steps_done"], converged=res["converged"], samples=res["samples"],
+                   tops0=res["tops0"], overflow=res["overflow"])
+        if file_path is not None:
+            np.savez_compressed(file_path, params=np.array([repr(params)]), **out)
+        return out
     if method != "PTEQ":
         if noise != ("alpha" if method == "STDC_N_n" else "depolarizing"):
             raise ValueError(f"method {method} is defined for {'alpha' if method == 'STDC_N_n' else 'depolarizing'} noise (generate_data.py:168-196)")

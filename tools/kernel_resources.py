@@ -30,6 +30,14 @@ def kernel_label(mangled):
     if s:   # ladder_colour_stats_kernel<CODE, RULE> -> 'colour-stats<1024,4,xzzx: rule 1>'
         code, rule = (int(x) for x in s.groups())
         return "colour-stats<1024,4,%s: rule %d>" % (CODES[code], rule)
+    # the shortest-chain kernels (qecmc_plan_set_shortest): the alpha rule's criterion kernels with the per-class minimum and the set
+    s = re.search(r"ladder_wu_shortest_kernelILi(\d+)ELi(\d+)ELi(\d+)EE", mangled)
+    if s:   # ladder_wu_shortest_kernel<CODE, WV, IT> -> 'wave-shortest<1024,4,xzzx: 8 words, iters 10>'
+        code, wv, it = (int(x) for x in s.groups())
+        return "wave-shortest<1024,4,%s: %d words%s>" % (CODES[code], wv, ", iters %d" % it if it else "")
+    s = re.search(r"ladder_colour_shortest_kernelILi(\d+)EE", mangled)
+    if s:   # ladder_colour_shortest_kernel<CODE> -> 'colour-shortest<1024,4,rotated>'
+        return "colour-shortest<1024,4,%s>" % CODES[int(s.group(1))]
     m = re.search(r"ladder_kernelILi(\d+)ELi(\d+)ELi(\d+)ELj(\d+)E", mangled)
     if not m:
         m2 = re.match(r"_ZN5qecmc\d+([A-Za-z_0-9]+?)(?:I|E)", mangled)
