@@ -124,6 +124,13 @@ typedef struct qecmc_stats {
 
 int         qecmc_abi_version(void);
 const char *qecmc_last_error(void);
+/* The kernel the calling thread's last ladder launch ran (PTEQ, PTDC, Ladder.step, ... -- every entry point that runs a ladder kernel): ten numbers,
+ * family (1 ladder_kernel, 2 the scan = wave kernels, 3 the scan = colour kernels), maxt (the launch bound in threads), minw (waves per SIMD), code,
+ * flags (ladder_kernel: its variant mask; wave / colour: 0, 1 = the statistics kernels, 2 = the shortest-chain kernels), wv (state words per rung, wave),
+ * conv, it (the unrolled iters, 0: the general loop), alpha, rule (colour).  tools/kernel_resources.py key_label() names it as the build's resource
+ * tables do.  QECMC_ERR_INVALID while the thread has launched nothing; a call of N = 0 and a refused launch leave the answer as it was.  For tests and
+ * tools: which kernel a shape runs is not part of the ABI's promises (additive: QECMC_ABI_VERSION stays). */
+int         qecmc_last_kernel(int64_t key_out[10]);
 int         qecmc_device_count(void);      /* 0 when no GPU is visible */
 
 /* ---- stencil primitives (batched; N states per call, host pointers) -------

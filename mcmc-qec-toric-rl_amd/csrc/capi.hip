@@ -198,6 +198,15 @@ extern "C" {
 
 int qecmc_abi_version(void) { return QECMC_ABI_VERSION; }
 const char *qecmc_last_error(void) { return g_err.c_str(); }
+int qecmc_last_kernel(int64_t key_out[10])
+{
+    KernelKey k;
+    if (!key_out) return fail(QECMC_ERR_INVALID, "qecmc_last_kernel: NULL key_out");
+    if (!last_launched_kernel(k)) return fail(QECMC_ERR_INVALID, "qecmc_last_kernel: this thread has launched no ladder kernel");
+    const int64_t v[10] = {k.family, k.maxt, k.minw, k.code, k.flags, k.wv, k.conv, k.it, k.alpha, k.rule};
+    memcpy(key_out, v, sizeof v);
+    return QECMC_OK;
+}
 int qecmc_device_count(void)
 {
     int n = 0;

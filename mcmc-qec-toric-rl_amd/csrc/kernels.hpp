@@ -122,6 +122,7 @@ enum ConvRecWord : int {
 __host__ __device__ constexpr int conv_record_words(int noise) { return noise == 2 ? kRecWordsAlpha : kRecWords; }
 
 hipError_t launch_ladder(const LadderArgs &a, hipStream_t stream);     // ladder_rs.hip: the kernel choose_kernel() picks for kernel_shape(a) (plan_host.hpp), on its grid
+bool last_launched_kernel(KernelKey &out);                             // ladder_rs.hip: the key of this thread's last launch_ladder() that reached the runtime (qecmc_last_kernel)
 // the instantiation units, one per kernel family (built in parallel): the kernel of `k` if the unit builds it, else nullptr -- ladder_kernel
 // (ladder_{toric,surf,biased,sweep,uset}.hip), ladder_colour_kernel (ladder_colour.hip), ladder_wu_kernel (ladder_wu{,_xzzx,_rotated,_planar,_alpha}.hip),
 // the statistics kernels ladder_wu_stats_kernel (ladder_wu_stats{,_alpha}.hip) and ladder_colour_stats_kernel (ladder_colour_stats.hip), the shortest-chain

@@ -1699,6 +1699,22 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_kernel(const LadderArgs a)
                 // of the loop: its variables start as the constants they are in a fresh run, and the load is a cold block behind a scalar test.)
                 if (wave_u == 0 && t == 0 && a.crec != nullptr && lane_t < cnt) { QECMC_LOAD_RECORD(lane_t); }
             }
+            if (a.swap_acc != nullptr && wave_u == 0) {
+                // equilibrium observables (qecmc_plan_set_stats): the cascade once more, with every rung's decision and the error
+                // count each rung ends the step with added to per-lane LDS counters (off the hot path: one scalar branch when off)
+                uint32_t *sacc = lds_all + gdw + lane_t, *nsum = sacc + NC * 64;
+                uint32_t c2 = cur[(NC - 1) * 64];
+                for (int i = NC - 2; i >= 0; --i) {
+                    const uint32_t lo = cur[i * 64], xi = sx[i * 64];
+                    const bool flip = swap_flip(i, c2, lo, xi);
+                    if (!done) {                                                   // (a converged syndrome stops counting -- behind the step that stops it: this runs ahead of the criterion)
+                        sacc[i * 64] += flip;
+                        nsum[(i + 1) * 64] += (flip ? lo : c2) & 0xFFFFu;
+                    }
+                    c2 = flip ? c2 : lo;
+                }
+                if (!done) nsum[0] += c2 & 0xFFFFu;
+            }
             if (wave_u == 0 && !done) {                                             // ladder + PTEQ bookkeeping on slot 0's new state
                 if constexpr (kLdsCounters) { tops0 = ctrT[lane_t]; samples = ctrS[lane_t]; }
                 tops0 += (NC == 1) | (car >> 31);                                   // chains[0].flag == 1, :101-102
@@ -1745,22 +1761,6 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_kernel(const LadderArgs a)
                     }
                 }
                 if constexpr (kLdsCounters) { ctrT[lane_t] = tops0; ctrS[lane_t] = samples; tops0 = 0; samples = 0; }
-            }
-            if (a.swap_acc != nullptr && wave_u == 0) {
-                // equilibrium observables (qecmc_plan_set_stats): the cascade once more, with every rung's decision and the error
-                // count each rung ends the step with added to per-lane LDS counters (off the hot path: one scalar branch when off)
-                uint32_t *sacc = lds_all + gdw + lane_t, *nsum = sacc + NC * 64;
-                uint32_t c2 = cur[(NC - 1) * 64];
-                for (int i = NC - 2; i >= 0; --i) {
-                    const uint32_t lo = cur[i * 64], xi = sx[i * 64];
-                    const bool flip = swap_flip(i, c2, lo, xi);
-                    if (!done) {                                                   // (a converged syndrome stops counting)
-                        sacc[i * 64] += flip;
-                        nsum[(i + 1) * 64] += (flip ? lo : c2) & 0xFFFFu;
-                    }
-                    c2 = flip ? c2 : lo;
-                }
-                if (!done) nsum[0] += c2 & 0xFFFFu;
             }
             if constexpr (QUEUE) {
                 if (wave_u == 0) {

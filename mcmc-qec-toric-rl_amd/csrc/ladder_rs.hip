@@ -18,6 +18,10 @@ const void *kernel_of(const KernelKey &k)
     return fn;
 }
 
+// the key of the last kernel this thread handed to the runtime (qecmc_last_kernel): one 48-byte copy per launch, nothing else
+thread_local KernelKey t_last_kernel = {kRefused, 0, 0, 0, 0u, 0, 0, 0, 0, 0, nullptr};
+inline void note_kernel(const KernelKey &k) { t_last_kernel = k; }
+
 hipError_t launch_fn(const void *fn, const LadderArgs &a, hipStream_t stream, unsigned grid, size_t lds)
 {
     if (lds > 64 * 1024) {   // beyond the default dynamic-LDS window (160 KiB per CU on gfx950)
@@ -33,13 +37,14 @@ hipError_t launch_fn(const void *fn, const LadderArgs &a, hipStream_t stream, un
 
 // ladder_kernel: one 64-syndrome group (Nc waves) per workgroup (two per workgroup measured slower at every batch size); `persistent`: fn is a
 // QUEUE instantiation -- only those run on the capped grid, and a.queue without one is an error: a plain kernel never skips ladders
-hipError_t launch_ladder_fn(const void *fn, const LadderArgs &a, hipStream_t stream, bool persistent)
+hipError_t launch_ladder_fn(const void *fn, const KernelKey &k, const LadderArgs &a, hipStream_t stream, bool persistent)
 {
     unsigned grid = (unsigned)((a.N + 63) / 64);
     if ((a.queue != nullptr) != persistent) return hipErrorInvalidValue;
     if (persistent && a.grid_cap && grid > a.grid_cap) grid = a.grid_cap;
     const size_t lds = ladder_launch_lds(kernel_shape(a));
     if (lds > 160 * 1024) return hipErrorInvalidValue;
+    note_kernel(k);
     return launch_fn(fn, a, stream, grid, lds);
 }
 
@@ -62,6 +67,7 @@ hipError_t launch_ladder(const LadderArgs &a, hipStream_t stream)
         if (a.wu_desc == nullptr || (a.first_syndrome & 63u) || a.bias_tbl == nullptr || a.alpha_lnb == nullptr || a.write_states) return hipErrorInvalidValue;
         LadderArgs b = a;
         b.wu_chunk = 64u; b.wu_once = 0u; b.queue = nullptr; b.grid_cap = 0u;
+        note_kernel(k);
         return launch_fn(fn, b, stream, (unsigned)((a.N + 63) / 64), shortest_lds_bytes(a));
     }
     if (k.family == kFamWave) {
@@ -72,6 +78,7 @@ hipError_t launch_ladder(const LadderArgs &a, hipStream_t stream)
         const uint64_t per = k.conv ? a.wu_chunk : 64u;
         LadderArgs b = a;
         b.wu_once = wave_cascade_once(kernel_shape(a)) ? 1u : 0u;
+        note_kernel(k);
         return launch_fn(fn, b, stream, (unsigned)((a.N + per - 1) / per), wu_lds_bytes(a.Nc, a.W, a.ncls, a.L, k.conv, k.alpha));
     }
     if (k.family == kFamColour) {
@@ -80,9 +87,17 @@ hipError_t launch_ladder(const LadderArgs &a, hipStream_t stream)
         if (a.noise != 0 && (a.col_thr == nullptr || a.bias_tbl == nullptr || (a.noise == 2 && a.alpha_lnb == nullptr))) return hipErrorInvalidValue;
         const size_t lds = shortest ? shortest_lds_bytes(a) : sizeof(uint32_t) * colour_lds_dwords(a.Nc, a.W, a.ncls, a.n_phases, a.n_gen, a.L, a.nq, a.swap_fast_ok != 0, a.noise);
         if (lds > 160 * 1024) return hipErrorInvalidValue;
+        note_kernel(k);
         return launch_fn(fn, a, stream, (unsigned)a.N, lds);
     }
-    return launch_ladder_fn(fn, a, stream, k.takes_queue());
+    return launch_ladder_fn(fn, k, a, stream, k.takes_queue());
+}
+
+// the key launch_ladder() last launched on this thread; false: it has launched nothing yet (an N == 0 call and a refused launch leave the key untouched)
+bool last_launched_kernel(KernelKey &out)
+{
+    out = t_last_kernel;
+    return t_last_kernel.ok();
 }
 
 }  // namespace qecmc

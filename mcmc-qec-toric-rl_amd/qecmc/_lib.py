@@ -64,6 +64,7 @@ _u16p = C.POINTER(C.c_uint16)
 SIGNATURES = {
     "qecmc_abi_version": (C.c_int, []),
     "qecmc_last_error": (C.c_char_p, []),
+    "qecmc_last_kernel": (C.c_int, [_i64p]),
     "qecmc_device_count": (C.c_int, []),
     "qecmc_apply_stabilizer": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, _u8p, _i32p, _i32p, _i32p, _i32p]),
     "qecmc_apply_logical": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, _u8p, _i32p, _i32p, _i32p, _i32p, _i32p]),
@@ -160,6 +161,28 @@ def library_path():
 def check(rc):
     if rc != 0:
         raise QecmcError(f"libqecmc error {rc}: {lib().qecmc_last_error().decode()}")
+
+
+_key_label = None
+
+
+def last_kernel():
+    """the kernel this thread's last ladder launch ran (qecmc_last_kernel), as tools/kernel_resources.py labels the build's kernels:
+    'ladder<512,8,toric: gsplit|delut|ssw>', 'wave<1024,8,xzzx: 8 words, conv, queue>', 'colour<1024,4,rotated: rule 2, conv>', 'wave-stats<...>', ..."""
+    global _key_label
+    key = (C.c_int64 * 10)()
+    check(lib().qecmc_last_kernel(key))
+    if _key_label is None:
+        import importlib.util
+        # (a helper for the tests and tools of the source tree: the one vocabulary of kernel labels lives in tools/, not in the package)
+        path = os.path.join(_HERE, "..", "..", "tools", "kernel_resources.py")
+        if not os.path.exists(path):
+            raise QecmcError("last_kernel() names kernels with tools/kernel_resources.py of the source tree, which is not at " + os.path.abspath(path))
+        spec = importlib.util.spec_from_file_location("kernel_resources", path)
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        _key_label = mod.key_label
+    return _key_label(list(key))
 
 
 def device_count():

@@ -32,7 +32,8 @@ def pteq_batch(init, p, Nc=None, steps=1000, iters=10, tops_burn=2, p_logical=0.
     counts, samples and tops0 on the device (steps_done: the slowest ladder; converged: all of them) -- the droplets
     pattern of decoders.py:215-225, which is how a call with few syndromes fills the GPU; states are then [N*R, Nc, ...].
     return_swap_stats=True adds swap_accepts uint32[N,Nc-1] (accepted swap tests per rung pair over all `steps` ladder steps)
-    and nerr_sums uint32[N,Nc] (sum over the steps of each rung's error count after the swaps), the per-batch mixing
+    and nerr_sums uint32[N,Nc] (sum over the steps of each rung's error count after the swaps; a run the criterion stops: over its
+    steps_done steps, the stopping step included), the per-batch mixing
     metrics of SURVEY.md 5 -- under every scan; scan="wave" and scan="colour" count in statistics kernels of their own (the same
     chain bit for bit; fixed-length runs, "wave" up to 16 packed state words per rung: QecmcError otherwise).  flags: qecmc_params.flags (developer switches between equivalent kernel variants, _lib.dev_flags).
     Returns dict(counts uint32[N,16], samples uint32[N], tops0 uint32[N], steps_done uint32[N],

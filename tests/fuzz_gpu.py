@@ -4,7 +4,8 @@ convergence criterion, batch sizes that leave ragged workgroups -- runs `pteq_ba
 Philox streams, and demands identical class counts, sample counts, tops0, stopping steps and (fixed-length runs) final states
 of every rung.  The oracle is the checker here, as in tests/ proper; nothing under oracle/ is on the product path.
 Writes gpurun_out/fuzz_<seed>.json.  `python tests/fuzz_gpu.py other [cases] [seed]` does the same for the other entry points
-(chain updates, Ladder.step in chunks, the unique-chain estimators' ptdc_batch).""" 
+(chain updates, Ladder.step in chunks, the unique-chain estimators' ptdc_batch).  The JSON of the PTEQ sweep names, under `kernels`, the kernels its
+cases ran (qecmc._lib.last_kernel()) and how often.""" 
 import json
 import os
 import sys
@@ -224,7 +225,7 @@ def main():
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
     rng = np.random.default_rng(seed)
     t0 = time.time()
-    failures, done, kinds = [], 0, {}
+    failures, done, kinds, kernels = [], 0, {}, {}
     for i in range(cases):
         c = draw_case(rng)
         if os.environ.get("QECMC_FUZZ_TRACE"):
@@ -244,9 +245,11 @@ def main():
             k = "%s/%s/%s%s%s%s%s" % (c["code"], c["noise"], c["scan"], "/conv" if c["conv"] else "", "/queue-grid-" + c["grid"] if c["grid"] else "",
                                       "/chunked" if c["chunks"] else "", "/replicas" if c["R"] > 1 else "")
             kinds[k] = kinds.get(k, 0) + 1
+            kern = q._lib.last_kernel()                                       # the kernel the case's (last) launch ran
+            kernels[kern] = kernels.get(kern, 0) + 1
         if i % 20 == 19:
             print("%d cases, %d compared, %d failures, %.0f s" % (i + 1, done, len(failures), time.time() - t0), flush=True)
-    out = dict(seed=seed, cases=cases, compared=done, failures=failures, kinds=kinds, seconds=time.time() - t0)
+    out = dict(seed=seed, cases=cases, compared=done, failures=failures, kinds=kinds, kernels=kernels, seconds=time.time() - t0)
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     json.dump(out, open(os.path.join(ROOT, "gpurun_out", "fuzz_%d.json" % seed), "w"), indent=1)
     print(json.dumps({k: v for k, v in out.items() if k != "failures"}))

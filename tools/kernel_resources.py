@@ -38,6 +38,10 @@ def kernel_label(mangled):
     s = re.search(r"ladder_colour_shortest_kernelILi(\d+)EE", mangled)
     if s:   # ladder_colour_shortest_kernel<CODE> -> 'colour-shortest<1024,4,rotated>'
         return "colour-shortest<1024,4,%s>" % CODES[int(s.group(1))]
+    s = re.search(r"ladder_colour_kernelILi(\d+)ELb([01])ELi(\d+)ELi(\d+)ELi(\d+)E", mangled)
+    if s:   # ladder_colour_kernel<CODE, CONV, RULE, MAXT, MINW> -> 'colour<1024,4,xzzx: rule 1, conv>'
+        code, conv, rule, maxt, minw = (int(x) for x in s.groups())
+        return "colour<%d,%d,%s: rule %d%s>" % (maxt, minw, CODES[code], rule, ", conv" if conv else "")
     m = re.search(r"ladder_kernelILi(\d+)ELi(\d+)ELi(\d+)ELj(\d+)E", mangled)
     if not m:
         m2 = re.match(r"_ZN5qecmc\d+([A-Za-z_0-9]+?)(?:I|E)", mangled)
@@ -45,6 +49,29 @@ def kernel_label(mangled):
     maxt, minw, code, fl = (int(x) for x in m.groups())
     names = [n for i, n in enumerate(FLAGS) if fl >> i & 1]
     return "ladder<%d,%d,%s: %s>" % (maxt, minw, CODES[code], "|".join(names) or "plain")
+
+
+def key_label(key):
+    """the key of a launch (qecmc_last_kernel; kernel_choice.hpp KernelKey: family, maxt, minw, code, flags, wv, conv, it, alpha, rule) in the labels
+    kernel_label() gives the build's kernels.  The criterion kernels of scan = wave are built with their work queue (QUEUE = CONV)."""
+    family, maxt, minw, code, flags, wv, conv, it, alpha, rule = (int(x) for x in list(key)[:10])
+    head = "<%d,%d,%s" % (maxt, minw, CODES[code])
+    iters = ", iters %d" % it if it else ""
+    if family == 1:
+        return "ladder%s: %s>" % (head, "|".join(n for i, n in enumerate(FLAGS) if flags >> i & 1) or "plain")
+    if family == 2 and flags == 0:
+        return "wave%s: %d words%s%s%s>" % (head, wv, ", conv, queue" if conv else "", ", alpha" if alpha else "", iters)
+    if family == 2 and flags == 1:
+        return "wave-stats%s: %d words%s>" % (head, wv, ", alpha" if alpha else "")
+    if family == 2 and flags == 2:
+        return "wave-shortest%s: %d words%s>" % (head, wv, iters)
+    if family == 3 and flags == 0:
+        return "colour%s: rule %d%s>" % (head, rule, ", conv" if conv else "")
+    if family == 3 and flags == 1:
+        return "colour-stats%s: rule %d>" % (head, rule)
+    if family == 3 and flags == 2:
+        return "colour-shortest%s>" % head
+    raise ValueError("not the key of a kernel: %r" % (list(key),))
 
 
 def parse(path):
