@@ -172,6 +172,28 @@ int qecmc_generate_syndromes_dev(int code, int L, uint64_t N, double p_x, double
                                  uint64_t seed, uint32_t first_syndrome, void *d_init_out, void *d_raw_out,
                                  void *d_eq_true_out, void *hip_stream);
 
+/* ---- start chains from bare syndromes (no counterpart in the reference, whose entry points all start from an error chain) ------
+ * defects uint8[N][cells] in the layout qecmc_syndrome writes (a non-zero byte = a defect) -> chains_out uint8[N][nq], a Pauli
+ * configuration with exactly that syndrome: what qecmc_pteq_batch takes as `init`.  chain = XOR, over the set cells, of the rows of
+ * the code's lift table (one Pauli string per check whose syndrome is that check alone -- on the torus plus its component's root
+ * check; built by breadth-first search over the single-qubit X / Z errors, csrc/syndrome_lift.hpp); descend != 0 then sweeps the
+ * stabilizer generators in table order, applying one iff it lowers the error count, until a whole sweep applies nothing (at most
+ * nq + 1 sweeps).  No matching: the chain is a local minimum of the weight, in an arbitrary equivalence class.
+ * status_out uint8[N] (nullable): 0 lifted; 1 not a syndrome of this code (a set cell that is no check, or an odd number of defects in
+ * a component without boundary) -- that chain is all zero.  weight_out int32[N] (nullable): count_errors of the chain, -1 with status 1.
+ * Additive: QECMC_ABI_VERSION stays.  A NULL buffer or a (code, L) the library does not know is refused (QECMC_ERR_INVALID) before a
+ * device is looked for.
+ * qecmc_lift: the uploaded table of one (code, L), on the device current when it was created.  The _dev form takes device pointers and
+ * a hipStream_t, allocates nothing and does not synchronise (it composes with qecmc_generate_syndromes_dev / qecmc_pteq_launch_dev);
+ * the lift must outlive the launches enqueued with it. */
+int qecmc_chains_from_syndromes(int code, int L, uint64_t N, const uint8_t *defects, int descend, uint8_t *chains_out,
+                                uint8_t *status_out, int32_t *weight_out);
+typedef struct qecmc_lift qecmc_lift;
+int qecmc_lift_create(int code, int L, qecmc_lift **out);
+int qecmc_lift_destroy(qecmc_lift *lift);
+int qecmc_chains_from_syndromes_dev(qecmc_lift *lift, const void *d_defects, uint64_t N, int descend, void *d_chains_out,
+                                    void *d_status_out /*nullable*/, void *d_weight_out /*nullable*/, void *hip_stream);
+
 /* ---- chain / ladder on caller-owned state (host pointers) ----------------- */
 
 /* Chain.update_chain(iters), src/mcmc.py:19-43, on N independent chains.

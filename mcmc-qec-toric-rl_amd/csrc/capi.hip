@@ -20,6 +20,7 @@
 #include "kernels.hpp"
 #include "plan_host.hpp"
 #include "stencil_bytes.hpp"
+#include "syndrome_lift.hpp"
 #include "tables.hpp"
 
 using namespace qecmc;
@@ -153,6 +154,12 @@ struct qecmc_plan {
     // (plan_host.hpp: whether a launch runs on the persistent grid, and THE workspace formula of the criterion runs)
     bool takes_queue(bool wants_states_or_stats) const { return launch_takes_queue(queue_grid, prm.steps, wants_states_or_stats); }
     uint64_t workspace(uint64_t N, bool queue) const { return workspace_need(prm, queue_grid, N, queue); }
+};
+
+// the lift table of one (code, L) on the device (syndrome_lift.hpp): rows [cells][W + 1], the generator table, the launch's dimensions
+struct qecmc_lift {
+    LiftArgs args = {};
+    DevBuf rows, gen;
 };
 
 namespace {
@@ -371,6 +378,79 @@ int qecmc_generate_syndromes(int code, int L, uint64_t N, double p_x, double p_y
     HIP_TRY(hipMemcpy(init_out, dout.p, N * nq, hipMemcpyDeviceToHost));
     if (raw_out) HIP_TRY(hipMemcpy(raw_out, draw.p, N * nq, hipMemcpyDeviceToHost));
     if (eq_true_out) HIP_TRY(hipMemcpy(eq_true_out, deq.p, N * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---------------------------------------------------------------- start chains from bare syndromes (syndrome_lift.hpp)
+static int lift_upload(int code, int L, qecmc_lift *lf)
+{
+    const lift::Table t = lift::build_table(code, L);
+    if (t.rows.empty()) return fail(QECMC_ERR_UNSUPPORTED, "internal: no lift table for code %d, L=%d", code, L);
+    lf->args.N = 0; lf->args.n_cells = t.n_cells; lf->args.W = t.W; lf->args.nq = t.nq; lf->args.n_gen = t.n_gen; lf->args.descend = 0;
+    HIP_TRY(lf->rows.alloc(t.rows.size() * sizeof(uint32_t)));
+    HIP_TRY(lf->gen.alloc(t.gen.size() * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpy(lf->rows.p, t.rows.data(), t.rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(lf->gen.p, t.gen.data(), t.gen.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return 0;
+}
+
+static int lift_launch(const qecmc_lift *lf, const void *d_defects, uint64_t N, int descend, void *d_chains, void *d_status, void *d_weight, hipStream_t s)
+{
+    LiftArgs a = lf->args;
+    a.N = N; a.descend = descend != 0;
+    HIP_TRY(launch_syndrome_lift(a, lf->rows.as<uint32_t>(), lf->gen.as<uint32_t>(), static_cast<const uint8_t *>(d_defects), static_cast<uint8_t *>(d_chains),
+                                 static_cast<uint8_t *>(d_status), static_cast<int32_t *>(d_weight), s));
+    return 0;
+}
+
+int qecmc_lift_create(int code, int L, qecmc_lift **out)
+{
+    if (!out) return fail(QECMC_ERR_INVALID, "qecmc_lift_create: NULL out");
+    *out = nullptr;
+    if (int rc = report(check_code_L(code, L))) return rc;
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(QECMC_ERR_NO_DEVICE, "no HIP device visible: libqecmc has no CPU fallback");
+    std::unique_ptr<qecmc_lift> lf(new (std::nothrow) qecmc_lift);
+    if (!lf) return fail(QECMC_ERR_INVALID, "out of host memory");
+    if (int rc = lift_upload(code, L, lf.get())) return rc;
+    *out = lf.release();
+    return 0;
+}
+
+int qecmc_lift_destroy(qecmc_lift *lift)
+{
+    delete lift;
+    return 0;
+}
+
+int qecmc_chains_from_syndromes_dev(qecmc_lift *lift, const void *d_defects, uint64_t N, int descend, void *d_chains_out, void *d_status_out,
+                                    void *d_weight_out, void *hip_stream)
+{
+    if (!lift) return fail(QECMC_ERR_INVALID, "qecmc_chains_from_syndromes_dev: NULL lift");
+    if (N > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "N=%llu syndromes exceed 32 bits", (unsigned long long)N);
+    if (N == 0) return 0;
+    if (!d_defects || !d_chains_out) return fail(QECMC_ERR_INVALID, "NULL device buffer");
+    return lift_launch(lift, d_defects, N, descend, d_chains_out, d_status_out, d_weight_out, static_cast<hipStream_t>(hip_stream));
+}
+
+int qecmc_chains_from_syndromes(int code, int L, uint64_t N, const uint8_t *defects, int descend, uint8_t *chains_out, uint8_t *status_out,
+                                int32_t *weight_out)
+{
+    if (!defects || !chains_out) return fail(QECMC_ERR_INVALID, "qecmc_chains_from_syndromes: NULL buffer");
+    if (int rc = report(check_code_L(code, L))) return rc;
+    if (N > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "N=%llu syndromes exceed 32 bits", (unsigned long long)N);
+    if (int rc = use_device(0)) return rc;
+    if (N == 0) return 0;
+    qecmc_lift lf;
+    if (int rc = lift_upload(code, L, &lf)) return rc;
+    const size_t nq = (size_t)lf.args.nq, nd = (size_t)lf.args.n_cells;
+    DevBuf din, dout, dst, dw;
+    HIP_TRY(din.alloc(N * nd)); HIP_TRY(dout.alloc(N * nq)); HIP_TRY(dst.alloc(N)); HIP_TRY(dw.alloc(N * 4));
+    HIP_TRY(hipMemcpy(din.p, defects, N * nd, hipMemcpyHostToDevice));
+    if (int rc = lift_launch(&lf, din.p, N, descend, dout.p, dst.p, dw.p, 0)) return rc;
+    HIP_TRY(hipMemcpy(chains_out, dout.p, N * nq, hipMemcpyDeviceToHost));
+    if (status_out) HIP_TRY(hipMemcpy(status_out, dst.p, N, hipMemcpyDeviceToHost));
+    if (weight_out) HIP_TRY(hipMemcpy(weight_out, dw.p, N * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 

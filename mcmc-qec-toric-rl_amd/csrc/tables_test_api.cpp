@@ -5,6 +5,7 @@
 // Not part of libqecmc.so.
 #include "kernel_choice.hpp"
 #include "plan_host.hpp"
+#include "syndrome_lift.hpp"
 #include "tables.hpp"
 
 #include <cstdio>
@@ -184,4 +185,21 @@ int qt_shortest_lds(const qecmc_params *p, uint64_t *short_bytes, uint64_t *plai
 }
 uint64_t qt_shortest_set_need(uint64_t N, uint64_t set_capacity) { return shortest_set_need(N, set_capacity); }
 int qt_launch_takes_queue(uint32_t grid, uint64_t steps, int wants_states_or_stats) { return launch_takes_queue(grid, steps, wants_states_or_stats != 0); }
+// the lift table of a code (syndrome_lift.hpp): uint32[cells][W + 1], W packed state words then the flag word (0: the cell is no check); the number of
+// words, -1 for a (code, L) check_code_L() refuses.  qt_chains_from_syndromes: the host twin of qecmc_chains_from_syndromes -- lift_body(), the body the
+// kernel runs, on a plain array; the QECMC_ERR_* code of the same host checks
+int qt_lift_table(int code, int L, uint32_t *out, int cap)
+{
+    if (check_code_L(code, L).code) return -1;
+    return put(lift::build_table(code, L).rows, out, cap);
+}
+int qt_chains_from_syndromes(int code, int L, uint64_t N, const uint8_t *defects, int descend, uint8_t *chains, uint8_t *status, int32_t *weight)
+{
+    if (!defects || !chains) return QECMC_ERR_INVALID;
+    if (const Refusal r = check_code_L(code, L); r.code) return r.code;
+    const lift::Table t = lift::build_table(code, L);
+    if (t.rows.empty()) return QECMC_ERR_UNSUPPORTED;
+    lift::chains_from_syndromes_host(t, N, defects, descend != 0, chains, status, weight);
+    return 0;
+}
 }

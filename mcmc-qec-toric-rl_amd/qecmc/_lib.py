@@ -76,6 +76,10 @@ SIGNATURES = {
                                            C.c_uint32, _u8p, _u8p, _i32p]),
     "qecmc_generate_syndromes_dev": (C.c_int, [C.c_int, C.c_int, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_int,
                                                C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qecmc_chains_from_syndromes": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, C.c_int, _u8p, _u8p, _i32p]),
+    "qecmc_lift_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "qecmc_lift_destroy": (C.c_int, [C.c_void_p]),
+    "qecmc_chains_from_syndromes_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qecmc_chain_update": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, C.c_double, C.c_double, C.c_uint64,
                                      C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64]),
     "qecmc_chain_update_biased": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, C.c_double, C.c_double, C.c_double,

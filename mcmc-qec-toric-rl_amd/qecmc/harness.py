@@ -178,8 +178,67 @@ def _estimate(method, code, reps, p_error, p_sampling, Nc, steps, droplets, conv
     raise ValueError(f"method={method!r}")
 
 
+def syndrome_of(code, m):
+    """the defects of a batch of configurations in the flat layout qecmc_syndrome writes: uint8[n, cells]"""
+    from . import _surf, planar_model, toric_model
+    code = _CODES.get(code, code)
+    m = np.ascontiguousarray(m, dtype=np.uint8)
+    if code == L_.PLANAR:
+        v, q = planar_model.syndrome(m)
+        return np.concatenate([v.reshape(len(m), -1), q.reshape(len(m), -1)], axis=1).astype(np.uint8)
+    d = toric_model.syndrome(m) if code == L_.TORIC else _surf.syndrome(code, m)
+    return d.reshape(len(m), -1)
+
+
+def _pteq_decode(params, init, seed, steps, conv_criteria, biased_decoder, metrics, pteq_kw):
+    """generate's PTEQ call on a batch of start chains (generate_data.py:136-160) -> (pteq_batch's result, wall seconds, Nc)"""
+    import time
+    code, size, p = _CODES[params["code"]], params["size"], params["p_error"]
+    noise = params.get("noise", "depolarizing")
+    eta = params.get("eta") if noise == "biased" else None
+    dec = dict(eta=eta)
+    p_dec = p
+    if noise == "alpha":
+        dec = dict(alpha=params["alpha"])
+    elif noise == "biased" and biased_decoder == "alpha":
+        p_dec, a = biased_as_alpha(p, eta)
+        dec = dict(alpha=float(a))
+    Nc = params.get("Nc") or size
+    t0 = time.perf_counter()
+    if metrics not in ("basic", "full"):
+        raise ValueError(f"metrics={metrics!r}")
+    nq = int(np.prod(init.shape[1:]))
+    swap_stats = metrics == "full" and Nc > 1 and int(pteq_kw.get("replicas", 1)) <= 1 and nq * int(steps) < 2 ** 32
+    res = pteq_batch(init, p_dec, Nc=Nc, steps=steps, conv_criteria=conv_criteria, seed=seed, code=code, return_stats=True,
+                     return_swap_stats=swap_stats, **dec, **pteq_kw)
+    return res, time.perf_counter() - t0, Nc
+
+
+def decode_syndromes(params, defects, seed=0, steps=100000, conv_criteria="error_based", biased_decoder="alpha", metrics="basic", **pteq_kw):
+    """Decode BARE SYNDROMES: `defects` (as qecmc.chains_from_syndromes takes them, for params['code'] / params['size']) are lifted to start
+    chains on the device and decoded exactly as `generate` decodes its seed configurations for params['method'] == "PTEQ" -- the same
+    decoder routing by params['noise'], the same keywords.  The start chain is a local minimum of the weight in an arbitrary class: the
+    class law does not depend on it, only the burn-in does.
+    Returns dict(distr, counts, steps_done, converged, samples, tops0, chains, status, weight); raises if a syndrome is none of the code."""
+    from .syndrome_lift import chains_from_syndromes
+    if params.get("method", "PTEQ") != "PTEQ":
+        raise ValueError("decode_syndromes decodes with PTEQ (params['method'])")
+    noise = params.get("noise", "depolarizing")
+    if noise not in ("depolarizing", "biased", "alpha"):
+        raise ValueError(f"noise={noise!r}")
+    lifted = chains_from_syndromes(params["code"], defects, device=int(pteq_kw.get("device", 0)), size=params["size"])
+    chains, status, weight = lifted["chains"], np.atleast_1d(lifted["status"]), np.atleast_1d(lifted["weight"])
+    if chains.ndim == (3 if _CODES[params["code"]] in (L_.TORIC, L_.PLANAR) else 2):
+        chains = chains[None]
+    if status.any():
+        raise ValueError("not syndromes of the %s code: rows %s" % (params["code"], np.flatnonzero(status)[:8].tolist()))
+    res, _, _ = _pteq_decode(params, chains, seed, steps, conv_criteria, biased_decoder, metrics, pteq_kw)
+    return dict(distr=res["percent"], counts=res["counts"], steps_done=res["steps_done"], converged=res["converged"], samples=res["samples"],
+                tops0=res["tops0"], chains=chains, status=status, weight=weight)
+
+
 def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_criteria="error_based", biased_decoder="alpha",
-             rng=None, device_generation=False, metrics="basic", **pteq_kw):
+             rng=None, device_generation=False, metrics="basic", start="error", **pteq_kw):
     """params: dict like generate_data.py:276-296 ({'code','size','p_error','noise'[,'eta','alpha']}), method PTEQ.
     noise 'depolarizing' -> PTEQ (:136); 'biased' -> errors from the eta split (:78-83) decoded by PTEQ_alpha with
     (pz_tilde, alpha) derived from (p, eta) exactly as :142-150 does (biased_decoder="biased" decodes with PTEQ_biased
@@ -191,6 +250,9 @@ def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_
     params['droplets'], params['conv_mult'] and `steps` as the estimator's own `steps`; `batch` syndromes go into one launch
     (default 256: the sets of visited chains live in HBM).  They return distr float64[n, ncls] and no counts.
     device_generation=True draws the errors and the hiding logical operator on the GPU (`generate_syndromes`) instead of NumPy.
+    start="error" (default) is the reference's recipe: the decoder starts from the error with a random logical operator on top.  start="syndrome"
+    (method PTEQ only) lets nothing but syndrome(raw) reach the decoder: the start chains are qecmc.chains_from_syndromes of it and no logical
+    operator is drawn; eq_true and the success rule are the same.
     metrics="basic" (default) costs nothing: throughput, convergence, burn-in and success figures.  metrics="full" also attaches the
     mixing counters (swap acceptance per rung pair, mean error count per rung) -- which rule out the work-queue kernels
     (their lanes run several ladders) and need nq * steps < 2^32, so they are dropped, not failed on, where they do not fit.
@@ -205,15 +267,22 @@ def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_
     eta = params.get("eta") if noise == "biased" else None
     rng = np.random.default_rng(seed) if rng is None else rng         # (shards pass a generator keyed by (seed, shard id))
     rates = alpha_rates(p, params["alpha"]) if noise == "alpha" else None
+    method = params.get("method", "PTEQ")
+    if start not in ("error", "syndrome"):
+        raise ValueError(f"start={start!r}")
+    if start == "syndrome" and method != "PTEQ":
+        raise ValueError(f"start='syndrome' is built for method PTEQ, not {method}")
     if device_generation:
         # errors, true class and the hiding logical operator drawn on the GPU (Philox keyed by the global syndrome index: the data
         # set does not depend on how it is cut into shards)
-        init, raw, eq_true = generate_syndromes(code, size, nbr_datapoints, p, eta, rates, True, seed, int(pteq_kw.get("first_syndrome", 0)))
+        init, raw, eq_true = generate_syndromes(code, size, nbr_datapoints, p, eta, rates, start == "error", seed, int(pteq_kw.get("first_syndrome", 0)))
     else:
         raw = draw_errors(code, size, nbr_datapoints, p, rng, eta, rates=rates)
         eq_true = np.asarray(_class_of(code, raw), dtype=np.int32)
-        init = hide_class(code, raw, rng)
-    method = params.get("method", "PTEQ")
+        init = hide_class(code, raw, rng) if start == "error" else raw
+    if start == "syndrome":
+        from .syndrome_lift import chains_from_syndromes
+        init = chains_from_syndromes(code, syndrome_of(code, raw), device=int(pteq_kw.get("device", 0)), size=size)["chains"]
     if method == "PTEQ_with_shortest":                                         # generate_data.py:167-173, PTEQ_alpha_with_shortest on the whole batch
         if noise != "alpha":
             raise ValueError("method PTEQ_with_shortest is defined for alpha noise (generate_data.py:167-173)")
@@ -244,23 +313,7 @@ def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_
         if file_path is not None:
             np.savez_compressed(file_path, params=np.array([repr(params)]), **out)
         return out
-    dec = dict(eta=eta)
-    p_dec = p
-    if noise == "alpha":
-        dec = dict(alpha=params["alpha"])
-    elif noise == "biased" and biased_decoder == "alpha":
-        p_dec, a = biased_as_alpha(p, eta)
-        dec = dict(alpha=float(a))
-    import time
-    Nc = params.get("Nc") or size
-    t0 = time.perf_counter()
-    if metrics not in ("basic", "full"):
-        raise ValueError(f"metrics={metrics!r}")
-    nq = int(np.prod(init.shape[1:]))
-    swap_stats = metrics == "full" and Nc > 1 and int(pteq_kw.get("replicas", 1)) <= 1 and nq * int(steps) < 2 ** 32
-    res = pteq_batch(init, p_dec, Nc=Nc, steps=steps, conv_criteria=conv_criteria, seed=seed, code=code, return_stats=True,
-                     return_swap_stats=swap_stats, **dec, **pteq_kw)
-    wall = time.perf_counter() - t0
+    res, wall, Nc = _pteq_decode(params, init, seed, steps, conv_criteria, biased_decoder, metrics, pteq_kw)
     out = dict(qubit_matrix=raw, eq_true=eq_true, counts=res["counts"], distr=res["percent"],
                success=np.argmax(res["percent"], axis=1) == eq_true, steps_done=res["steps_done"],
                converged=res["converged"], samples=res["samples"], tops0=res["tops0"])
