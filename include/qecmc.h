@@ -194,6 +194,33 @@ int qecmc_lift_destroy(qecmc_lift *lift);
 int qecmc_chains_from_syndromes_dev(qecmc_lift *lift, const void *d_defects, uint64_t N, int descend, void *d_chains_out,
                                     void *d_status_out /*nullable*/, void *d_weight_out /*nullable*/, void *hip_stream);
 
+/* ---- corrections from decoded syndromes (no counterpart in the reference, which returns a class histogram) -----------------------
+ * candidates uint8[N][K][nq]: K >= 1 chains per syndrome that all have that syndrome (not checked: e.g. the lifted chain, final rung
+ * states); target int32[N]: the class the correction shall lie in, in the convention of qecmc_eq_class (the column order of counts /
+ * distr: argmax of a row).  corrections_out uint8[N][nq]: a chain with the candidates' syndrome in class target -- the lightest
+ * candidate already in that class (lowest index on ties; moved 0), else the lightest of all (moved 1) multiplied by the logical
+ * operators a host-derived class-move table names (csrc/corrections.hpp), each at position 0 (place == 0) or at the position in
+ * [0, L) that gives the lowest error count (place != 0, ties to the lowest position); descend != 0 then runs the greedy descent of
+ * qecmc_chains_from_syndromes.  weight_out int32[N]: count_errors of the correction; source_out int32[N]: the candidate it came
+ * from; moved_out uint8[N]; status_out uint8[N]: 0 corrected, 1 target outside [0, ncls) -- that chain is all zero, weight -1,
+ * source -1, moved 0.  The last four are nullable.
+ * Additive: QECMC_ABI_VERSION stays.  A NULL required buffer, K == 0 or a (code, L) the library does not know is refused
+ * (QECMC_ERR_INVALID), a (code, L) without a class move -- the toric code at even L, whose parity class does not see a logical
+ * line -- with QECMC_ERR_UNSUPPORTED, both before a device is looked for.  N == 0 succeeds.
+ * qecmc_corrector: the uploaded mask rows, class-move table and generator table of one (code, L), on the device current when it was
+ * created.  The _dev form takes device pointers and a hipStream_t, allocates nothing and does not synchronise (it composes on one
+ * stream with qecmc_generate_syndromes_dev, qecmc_chains_from_syndromes_dev and qecmc_pteq_launch_dev); the corrector must outlive
+ * the launches enqueued with it. */
+int qecmc_corrections(int code, int L, uint64_t N, uint32_t K, const uint8_t *candidates, const int32_t *target, int place,
+                      int descend, uint8_t *corrections_out, int32_t *weight_out, int32_t *source_out, uint8_t *moved_out,
+                      uint8_t *status_out);
+typedef struct qecmc_corrector qecmc_corrector;
+int qecmc_corrector_create(int code, int L, qecmc_corrector **out);
+int qecmc_corrector_destroy(qecmc_corrector *c);
+int qecmc_corrections_dev(qecmc_corrector *c, const void *d_candidates, const void *d_target, uint64_t N, uint32_t K, int place,
+                          int descend, void *d_corrections_out, void *d_weight_out /*nullable*/, void *d_source_out /*nullable*/,
+                          void *d_moved_out /*nullable*/, void *d_status_out /*nullable*/, void *hip_stream);
+
 /* ---- chain / ladder on caller-owned state (host pointers) ----------------- */
 
 /* Chain.update_chain(iters), src/mcmc.py:19-43, on N independent chains.

@@ -20,6 +20,7 @@
 #include "kernels.hpp"
 #include "plan_host.hpp"
 #include "stencil_bytes.hpp"
+#include "corrections.hpp"
 #include "syndrome_lift.hpp"
 #include "tables.hpp"
 
@@ -160,6 +161,12 @@ struct qecmc_plan {
 struct qecmc_lift {
     LiftArgs args = {};
     DevBuf rows, gen;
+};
+
+// the correction tables of one (code, L) on the device (corrections.hpp): the logical masks [4][L+1][W], the class-move table, the generator table
+struct qecmc_corrector {
+    CorrectArgs args = {};
+    DevBuf masks, need, gen;
 };
 
 namespace {
@@ -451,6 +458,109 @@ int qecmc_chains_from_syndromes(int code, int L, uint64_t N, const uint8_t *defe
     HIP_TRY(hipMemcpy(chains_out, dout.p, N * nq, hipMemcpyDeviceToHost));
     if (status_out) HIP_TRY(hipMemcpy(status_out, dst.p, N, hipMemcpyDeviceToHost));
     if (weight_out) HIP_TRY(hipMemcpy(weight_out, dw.p, N * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---------------------------------------------------------------- corrections from decoded syndromes (corrections.hpp)
+// the host half: INVALID for a (code, L) the library does not know, UNSUPPORTED where the logical operators do not reach every class
+static int corrector_table(int code, int L, correct::Table &t)
+{
+    if (int rc = report(check_code_L(code, L))) return rc;
+    t = correct::build_table(code, L);
+    if (t.need.empty())
+        return fail(QECMC_ERR_UNSUPPORTED, "no class move for code %d at L=%d: its logical operators do not reach every equivalence class (the toric code's "
+                                           "parity class does not see a logical line of even length)", code, L);
+    return 0;
+}
+
+static int corrector_upload(const correct::Table &t, qecmc_corrector *c)
+{
+    CorrectArgs &a = c->args;
+    a.N = 0; a.code = t.code; a.L = t.L; a.W = t.W; a.nq = t.nq; a.n_gen = t.n_gen; a.ncls = t.ncls; a.kinds = t.kinds; a.K = 1; a.place = 0; a.descend = 0;
+    HIP_TRY(c->masks.alloc(t.masks.size() * sizeof(uint32_t)));
+    HIP_TRY(c->need.alloc(t.need.size() * sizeof(uint32_t)));
+    HIP_TRY(c->gen.alloc(t.gen.size() * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpy(c->masks.p, t.masks.data(), t.masks.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->need.p, t.need.data(), t.need.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->gen.p, t.gen.data(), t.gen.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return 0;
+}
+
+static int corrector_launch(const qecmc_corrector *c, const void *d_candidates, const void *d_target, uint64_t N, uint32_t K, int place, int descend,
+                            void *d_out, void *d_weight, void *d_source, void *d_moved, void *d_status, hipStream_t s)
+{
+    CorrectArgs a = c->args;
+    a.N = N; a.K = (int)K; a.place = place != 0; a.descend = descend != 0;
+    HIP_TRY(launch_corrections(a, c->masks.as<uint32_t>(), c->need.as<uint32_t>(), c->gen.as<uint32_t>(), static_cast<const uint8_t *>(d_candidates),
+                               static_cast<const int32_t *>(d_target), static_cast<uint8_t *>(d_out), static_cast<int32_t *>(d_weight),
+                               static_cast<int32_t *>(d_source), static_cast<uint8_t *>(d_moved), static_cast<uint8_t *>(d_status), s));
+    return 0;
+}
+
+// (K candidates of nq <= 8192 bytes per syndrome: K * nq stays below 2^31)
+static int check_corrections_size(uint64_t N, uint32_t K)
+{
+    if (K == 0) return fail(QECMC_ERR_INVALID, "K=0: a correction needs at least one candidate chain");
+    if (K > 0xFFFFu) return fail(QECMC_ERR_INVALID, "K=%u candidates per syndrome exceed 65535", K);
+    if (N > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "N=%llu syndromes exceed 32 bits", (unsigned long long)N);
+    return 0;
+}
+
+int qecmc_corrector_create(int code, int L, qecmc_corrector **out)
+{
+    if (!out) return fail(QECMC_ERR_INVALID, "qecmc_corrector_create: NULL out");
+    *out = nullptr;
+    correct::Table t;
+    if (int rc = corrector_table(code, L, t)) return rc;
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(QECMC_ERR_NO_DEVICE, "no HIP device visible: libqecmc has no CPU fallback");
+    std::unique_ptr<qecmc_corrector> c(new (std::nothrow) qecmc_corrector);
+    if (!c) return fail(QECMC_ERR_INVALID, "out of host memory");
+    if (int rc = corrector_upload(t, c.get())) return rc;
+    *out = c.release();
+    return 0;
+}
+
+int qecmc_corrector_destroy(qecmc_corrector *c)
+{
+    delete c;
+    return 0;
+}
+
+int qecmc_corrections_dev(qecmc_corrector *c, const void *d_candidates, const void *d_target, uint64_t N, uint32_t K, int place, int descend,
+                          void *d_corrections_out, void *d_weight_out, void *d_source_out, void *d_moved_out, void *d_status_out, void *hip_stream)
+{
+    if (!c) return fail(QECMC_ERR_INVALID, "qecmc_corrections_dev: NULL corrector");
+    if (int rc = check_corrections_size(N, K)) return rc;
+    if (N == 0) return 0;
+    if (!d_candidates || !d_target || !d_corrections_out) return fail(QECMC_ERR_INVALID, "NULL device buffer");
+    return corrector_launch(c, d_candidates, d_target, N, K, place, descend, d_corrections_out, d_weight_out, d_source_out, d_moved_out, d_status_out,
+                            static_cast<hipStream_t>(hip_stream));
+}
+
+int qecmc_corrections(int code, int L, uint64_t N, uint32_t K, const uint8_t *candidates, const int32_t *target, int place, int descend,
+                      uint8_t *corrections_out, int32_t *weight_out, int32_t *source_out, uint8_t *moved_out, uint8_t *status_out)
+{
+    if (!candidates || !target || !corrections_out) return fail(QECMC_ERR_INVALID, "qecmc_corrections: NULL buffer");
+    if (int rc = check_corrections_size(N, K)) return rc;
+    correct::Table t;
+    if (int rc = corrector_table(code, L, t)) return rc;
+    if (int rc = use_device(0)) return rc;
+    if (N == 0) return 0;
+    qecmc_corrector c;
+    if (int rc = corrector_upload(t, &c)) return rc;
+    const size_t nq = (size_t)t.nq;
+    DevBuf din, dt, dout, dw, ds, dm, dst;
+    HIP_TRY(din.alloc(N * K * nq)); HIP_TRY(dt.alloc(N * 4)); HIP_TRY(dout.alloc(N * nq));
+    HIP_TRY(dw.alloc(N * 4)); HIP_TRY(ds.alloc(N * 4)); HIP_TRY(dm.alloc(N)); HIP_TRY(dst.alloc(N));
+    HIP_TRY(hipMemcpy(din.p, candidates, N * K * nq, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dt.p, target, N * 4, hipMemcpyHostToDevice));
+    if (int rc = corrector_launch(&c, din.p, dt.p, N, K, place, descend, dout.p, dw.p, ds.p, dm.p, dst.p, 0)) return rc;
+    HIP_TRY(hipMemcpy(corrections_out, dout.p, N * nq, hipMemcpyDeviceToHost));
+    if (weight_out) HIP_TRY(hipMemcpy(weight_out, dw.p, N * 4, hipMemcpyDeviceToHost));
+    if (source_out) HIP_TRY(hipMemcpy(source_out, ds.p, N * 4, hipMemcpyDeviceToHost));
+    if (moved_out) HIP_TRY(hipMemcpy(moved_out, dm.p, N, hipMemcpyDeviceToHost));
+    if (status_out) HIP_TRY(hipMemcpy(status_out, dst.p, N, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -133,6 +133,34 @@ __host__ __device__ inline int count_fields(uint32_t v)
 #endif
 }
 
+// The greedy descent of lift_body() (and of correct_body(), corrections.hpp) on the state st holds: generators in table order, one applied iff it lowers
+// the error count, whole sweeps until one applies nothing.  Every application lowers the count by >= 1: at most nq of them, nq + 1 sweeps.
+template <class St>
+__host__ __device__ inline void greedy_descent(St &st, const uint32_t *__restrict__ gen, int nq, int n_gen)
+{
+    for (int sweep = 0; sweep <= nq; ++sweep) {
+        bool changed = false;
+        for (int g = 0; g < n_gen; ++g) {
+            const uint32_t e01 = gen[2 * (size_t)g], e23 = gen[2 * (size_t)g + 1];
+            int dE = 0;
+            for (int u = 0; u < 4; ++u) {
+                const uint32_t e = (u < 2 ? e01 >> (16 * u) : e23 >> (16 * (u - 2))) & 0xFFFFu, P = e & 3u, q = e >> 2;
+                if (P == 0u) continue;
+                const uint32_t f = (st.get((int)(q >> 4)) >> ((q & 15u) * 2u)) & 3u;
+                dE += f == 0u ? 1 : f == P ? -1 : 0;
+            }
+            const bool apply = dE < 0;
+            for (int u = 0; u < 4; ++u) {
+                const uint32_t e = (u < 2 ? e01 >> (16 * u) : e23 >> (16 * (u - 2))) & 0xFFFFu, P = e & 3u, q = e >> 2;
+                if (P == 0u) continue;
+                if (apply) st.set((int)(q >> 4), st.get((int)(q >> 4)) ^ (P << ((q & 15u) * 2u)));
+            }
+            changed |= apply;
+        }
+        if (!st.any(changed)) break;
+    }
+}
+
 // One syndrome.  St holds W state words: get(w), set(w, v), and any(b) -- true iff b holds for some syndrome that walks the loops together with this
 // one (the 64 lanes of a wavefront on the device; on the host, this one alone: a syndrome whose sweep applied nothing is at a fixed point, so the
 // extra sweeps a wavefront makes for its neighbours change nothing).  Every table address depends on the loop counters only.
@@ -160,29 +188,7 @@ __host__ __device__ inline void lift_body(St &st, const uint32_t *__restrict__ r
     status = (stray || (parity >> 1) != 0u) ? 1 : 0;
     if (status)
         for (int w = 0; w < W; ++w) st.set(w, 0u);
-    if (descend) {
-        for (int sweep = 0; sweep <= nq; ++sweep) {                   // every application lowers the count by >= 1: at most nq of them, nq + 1 sweeps
-            bool changed = false;
-            for (int g = 0; g < n_gen; ++g) {
-                const uint32_t e01 = gen[2 * (size_t)g], e23 = gen[2 * (size_t)g + 1];
-                int dE = 0;
-                for (int u = 0; u < 4; ++u) {
-                    const uint32_t e = (u < 2 ? e01 >> (16 * u) : e23 >> (16 * (u - 2))) & 0xFFFFu, P = e & 3u, q = e >> 2;
-                    if (P == 0u) continue;
-                    const uint32_t f = (st.get((int)(q >> 4)) >> ((q & 15u) * 2u)) & 3u;
-                    dE += f == 0u ? 1 : f == P ? -1 : 0;
-                }
-                const bool apply = dE < 0;
-                for (int u = 0; u < 4; ++u) {
-                    const uint32_t e = (u < 2 ? e01 >> (16 * u) : e23 >> (16 * (u - 2))) & 0xFFFFu, P = e & 3u, q = e >> 2;
-                    if (P == 0u) continue;
-                    if (apply) st.set((int)(q >> 4), st.get((int)(q >> 4)) ^ (P << ((q & 15u) * 2u)));
-                }
-                changed |= apply;
-            }
-            if (!st.any(changed)) break;
-        }
-    }
+    if (descend) greedy_descent(st, gen, nq, n_gen);
     weight = 0;
     for (int w = 0; w < W; ++w) weight += count_fields(st.get(w));
     if (status) weight = -1;

@@ -3,6 +3,7 @@
 // plan precomputes for the kernels against values the CPU oracle computes; tests/test_kernel_choice.py asks choose_kernel()
 // (kernel_choice.hpp) which kernel every shape runs, and plan_host() (plan_host.hpp) which plan -- or which refusal -- a parameter block gets.
 // Not part of libqecmc.so.
+#include "corrections.hpp"
 #include "kernel_choice.hpp"
 #include "plan_host.hpp"
 #include "syndrome_lift.hpp"
@@ -200,6 +201,24 @@ int qt_chains_from_syndromes(int code, int L, uint64_t N, const uint8_t *defects
     const lift::Table t = lift::build_table(code, L);
     if (t.rows.empty()) return QECMC_ERR_UNSUPPORTED;
     lift::chains_from_syndromes_host(t, N, defects, descend != 0, chains, status, weight);
+    return 0;
+}
+// the class-move table of a code (corrections.hpp): uint32[ncls][ncls] bit masks over the logical kinds; the number of entries, 0 where the code's
+// logical operators do not reach every class, -1 for a (code, L) check_code_L() refuses.  qt_corrections: the host twin of qecmc_corrections --
+// correct_body(), the body the kernel runs, on a plain array; the QECMC_ERR_* code of the same host checks
+int qt_class_moves(int code, int L, uint32_t *out, int cap)
+{
+    if (check_code_L(code, L).code) return -1;
+    return put(correct::build_table(code, L).need, out, cap);
+}
+int qt_corrections(int code, int L, uint64_t N, uint32_t K, const uint8_t *candidates, const int32_t *target, int place, int descend, uint8_t *corrections,
+                   int32_t *weight, int32_t *source, uint8_t *moved, uint8_t *status)
+{
+    if (!candidates || !target || !corrections || K == 0) return QECMC_ERR_INVALID;
+    if (const Refusal r = check_code_L(code, L); r.code) return r.code;
+    const correct::Table t = correct::build_table(code, L);
+    if (t.need.empty()) return QECMC_ERR_UNSUPPORTED;
+    correct::corrections_host(t, N, K, candidates, target, place != 0, descend != 0, corrections, weight, source, moved, status);
     return 0;
 }
 }

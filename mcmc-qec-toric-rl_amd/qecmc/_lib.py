@@ -80,6 +80,11 @@ SIGNATURES = {
     "qecmc_lift_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "qecmc_lift_destroy": (C.c_int, [C.c_void_p]),
     "qecmc_chains_from_syndromes_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qecmc_corrections": (C.c_int, [C.c_int, C.c_int, C.c_uint64, C.c_uint32, _u8p, _i32p, C.c_int, C.c_int, _u8p, _i32p, _i32p, _u8p, _u8p]),
+    "qecmc_corrector_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "qecmc_corrector_destroy": (C.c_int, [C.c_void_p]),
+    "qecmc_corrections_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "qecmc_chain_update": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, C.c_double, C.c_double, C.c_uint64,
                                      C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64]),
     "qecmc_chain_update_biased": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, C.c_double, C.c_double, C.c_double,

@@ -214,12 +214,24 @@ def _pteq_decode(params, init, seed, steps, conv_criteria, biased_decoder, metri
     return res, time.perf_counter() - t0, Nc
 
 
-def decode_syndromes(params, defects, seed=0, steps=100000, conv_criteria="error_based", biased_decoder="alpha", metrics="basic", **pteq_kw):
+def _corrections_for(code, size, candidates, distr, device):
+    """the correction of every row towards target = argmax(distr) -- the very expression `success` uses -- from candidates [n, K, ...] or [n, ...]"""
+    from .syndrome_corrections import corrections as correct
+    target = np.argmax(distr, axis=1).astype(np.int32)
+    return target, correct(code, candidates, target, device=device, size=size)
+
+
+def decode_syndromes(params, defects, seed=0, steps=100000, conv_criteria="error_based", biased_decoder="alpha", metrics="basic", corrections=False,
+                     correction_candidates="lift", **pteq_kw):
     """Decode BARE SYNDROMES: `defects` (as qecmc.chains_from_syndromes takes them, for params['code'] / params['size']) are lifted to start
     chains on the device and decoded exactly as `generate` decodes its seed configurations for params['method'] == "PTEQ" -- the same
     decoder routing by params['noise'], the same keywords.  The start chain is a local minimum of the weight in an arbitrary class: the
     class law does not depend on it, only the burn-in does.
-    Returns dict(distr, counts, steps_done, converged, samples, tops0, chains, status, weight); raises if a syndrome is none of the code."""
+    Returns dict(distr, counts, steps_done, converged, samples, tops0, chains, status, weight); raises if a syndrome is none of the code.
+    corrections=True adds what a user who measured a syndrome wants (qecmc.corrections): target = argmax(distr) per row, correction -- a
+    chain with the syndrome in that class --, correction_weight, correction_source and correction_moved.  The candidate is the lifted chain;
+    correction_candidates="states" adds the Nc final rung states of every ladder as candidates 1 ..., where the route returns them: a fixed-length
+    run (conv_criteria=None).  A run the convergence criterion stops may go to the work-queue kernels, which write no final states: ValueError."""
     from .syndrome_lift import chains_from_syndromes
     if params.get("method", "PTEQ") != "PTEQ":
         raise ValueError("decode_syndromes decodes with PTEQ (params['method'])")
@@ -232,13 +244,30 @@ def decode_syndromes(params, defects, seed=0, steps=100000, conv_criteria="error
         chains = chains[None]
     if status.any():
         raise ValueError("not syndromes of the %s code: rows %s" % (params["code"], np.flatnonzero(status)[:8].tolist()))
+    if correction_candidates not in ("lift", "states"):
+        raise ValueError(f"correction_candidates={correction_candidates!r}")
+    with_states = bool(corrections) and correction_candidates == "states"
+    if with_states:
+        if conv_criteria is not None:
+            raise ValueError(f"correction_candidates='states': the route conv_criteria={conv_criteria!r} (a run stopped by the convergence criterion, which may "
+                             "take the work-queue kernels) returns no final states; decode with conv_criteria=None or keep the lifted chain")
+        pteq_kw = dict(pteq_kw, return_states=True)
     res, _, _ = _pteq_decode(params, chains, seed, steps, conv_criteria, biased_decoder, metrics, pteq_kw)
-    return dict(distr=res["percent"], counts=res["counts"], steps_done=res["steps_done"], converged=res["converged"], samples=res["samples"],
-                tops0=res["tops0"], chains=chains, status=status, weight=weight)
+    out = dict(distr=res["percent"], counts=res["counts"], steps_done=res["steps_done"], converged=res["converged"], samples=res["samples"],
+               tops0=res["tops0"], chains=chains, status=status, weight=weight)
+    if corrections:
+        cand = chains
+        if with_states:                                            # [n * replicas, Nc, ...] -> the lifted chain, then every final rung state of the row
+            n = chains.shape[0]
+            cand = np.concatenate([chains[:, None], res["states"].reshape((n, -1) + chains.shape[1:])], axis=1)
+        target, cor = _corrections_for(_CODES[params["code"]], params["size"], cand, out["distr"], int(pteq_kw.get("device", 0)))
+        out.update(target=target, correction=cor["corrections"], correction_weight=cor["weight"], correction_source=cor["source"],
+                   correction_moved=cor["moved"])
+    return out
 
 
 def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_criteria="error_based", biased_decoder="alpha",
-             rng=None, device_generation=False, metrics="basic", start="error", **pteq_kw):
+             rng=None, device_generation=False, metrics="basic", start="error", corrections=False, **pteq_kw):
     """params: dict like generate_data.py:276-296 ({'code','size','p_error','noise'[,'eta','alpha']}), method PTEQ.
     noise 'depolarizing' -> PTEQ (:136); 'biased' -> errors from the eta split (:78-83) decoded by PTEQ_alpha with
     (pz_tilde, alpha) derived from (p, eta) exactly as :142-150 does (biased_decoder="biased" decodes with PTEQ_biased
@@ -256,6 +285,9 @@ def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_
     metrics="basic" (default) costs nothing: throughput, convergence, burn-in and success figures.  metrics="full" also attaches the
     mixing counters (swap acceptance per rung pair, mean error count per rung) -- which rule out the work-queue kernels
     (their lanes run several ladders) and need nq * steps < 2^32, so they are dropped, not failed on, where they do not fit.
+    corrections=True (method PTEQ) closes the loop: correction uint8[n,...] is qecmc.corrections of the start chain -- the seed configuration, or the
+    lifted chain of start="syndrome" -- towards argmax(distr), correction_weight its error count, and success_correction[s] is true iff
+    raw[s] ^ correction[s] (byte values XOR as the Pauli product) is a stabilizer: an all-zero syndrome and the class of the zero chain.
     Returns (and optionally saves as npz) qubit_matrix uint8[n,...] (the raw errors, generate_data.py:120),
     eq_true int32[n], counts uint32[n,ncls], distr uint8[n,ncls] (what PTEQ returns), success bool[n]
     (argmax(distr) == eq_true, generate_data.py:139), steps_done, converged."""
@@ -272,6 +304,8 @@ def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_
         raise ValueError(f"start={start!r}")
     if start == "syndrome" and method != "PTEQ":
         raise ValueError(f"start='syndrome' is built for method PTEQ, not {method}")
+    if corrections and method != "PTEQ":
+        raise ValueError(f"corrections=True is built for method PTEQ, not {method}")
     if device_generation:
         # errors, true class and the hiding logical operator drawn on the GPU (Philox keyed by the global syndrome index: the data
         # set does not depend on how it is cut into shards)
@@ -317,6 +351,12 @@ def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_
     out = dict(qubit_matrix=raw, eq_true=eq_true, counts=res["counts"], distr=res["percent"],
                success=np.argmax(res["percent"], axis=1) == eq_true, steps_done=res["steps_done"],
                converged=res["converged"], samples=res["samples"], tops0=res["tops0"])
+    if corrections:
+        _, cor = _corrections_for(code, size, init, out["distr"], int(pteq_kw.get("device", 0)))
+        residual = raw ^ cor["corrections"]
+        stabilizer_class = int(np.asarray(_class_of(code, np.zeros_like(raw[:1])))[0])
+        out.update(correction=cor["corrections"], correction_weight=cor["weight"],
+                   success_correction=~syndrome_of(code, residual).any(axis=1) & (np.asarray(_class_of(code, residual)) == stabilizer_class))
     if file_path is not None:
         np.savez_compressed(file_path, params=np.array([repr(params)]), **out)
     out["metrics"] = batch_metrics(code, size, Nc, int(pteq_kw.get("iters", 10)), res, wall, out["success"],
