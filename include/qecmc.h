@@ -223,6 +223,12 @@ int qecmc_corrections_dev(qecmc_corrector *c, const void *d_candidates, const vo
 
 /* ---- chain / ladder on caller-owned state (host pointers) ----------------- */
 
+/* The supported range of a start index.  A Philox counter holds a proposal index (the swap stream: a ladder-step index) in 48 bits,
+ * so the entry points that take one -- k0 of qecmc_chain_update*, step0 / prop0 of qecmc_ladder_step*, step0 of qecmc_pteq_resume_dev
+ * and qecmc_pteq_resume_conv_dev (whose first proposal is step0 * iters) -- return QECMC_ERR_INVALID, before anything is enqueued, when
+ * the index of the call's last proposal (or ladder step) plus 64 is not below 2^48, or when step0 * iters or
+ * prop0 + nsteps * iters overflows 64 bits: indices there would draw the blocks of index - 2^48 again (DESIGN.md "RNG addressing"). */
+
 /* Chain.update_chain(iters), src/mcmc.py:19-43, on N independent chains.
  * Chain i draws from Philox stream (syndrome = first_syndrome+i, slot, proposals
  * k0 .. k0+iters-1).  p_logical != 0 selects the top-chain branch (mcmc.py:20). */

@@ -592,6 +592,7 @@ static int chain_update_impl(int code, int L, uint64_t N, uint8_t *states_inout,
     } else if (!(p > 0.0) || !(p <= 0.75)) return fail(QECMC_ERR_INVALID, "p=%g must be in (0, 0.75]", p);
     if (!(p_logical >= 0.0) || !(p_logical <= 1.0)) return fail(QECMC_ERR_INVALID, "p_logical=%g must be in [0,1]", p_logical);
     if (slot >= 0x100u) return fail(QECMC_ERR_INVALID, "slot %u collides with the swap stream id", slot);
+    if (int rc = report(rng_range_check("qecmc_chain_update", 0, 1, k0, iters))) return rc;
     ChainArgs a;
     std::memset(&a, 0, sizeof a);
     const double f = noise ? 0.0 : chain_factor(p);
@@ -658,6 +659,7 @@ int qecmc_chain_update_xyz(int code, int L, uint64_t N, uint8_t *states_inout, c
     const double tot = (p_xyz[0] + p_xyz[1]) + p_xyz[2];
     if (!(p_xyz[0] > 0) || !(p_xyz[1] > 0) || !(p_xyz[2] > 0) || !(tot < 1.0)) return fail(QECMC_ERR_INVALID, "p_xyz=(%g,%g,%g) must be positive with a sum below 1", p_xyz[0], p_xyz[1], p_xyz[2]);
     if (slot >= 0x100u) return fail(QECMC_ERR_INVALID, "slot %u collides with the swap stream id", slot);
+    if (int rc = report(rng_range_check("qecmc_chain_update_xyz", 0, 1, k0, iters))) return rc;
     const std::vector<uint64_t> thr = xyz_thresholds(p_xyz);          // mcmc.py:110,170
     ChainArgs a;
     std::memset(&a, 0, sizeof a);
@@ -717,6 +719,7 @@ static int ladder_step_impl(const qecmc_params *params, uint64_t N, uint8_t *sta
     if (!states_inout || !flags_inout || !tops0_inout) return fail(QECMC_ERR_INVALID, "NULL buffer");
     if ((p.noise == QECMC_NOISE_ALPHA) != (neff_inout != nullptr))
         return fail(QECMC_ERR_INVALID, "alpha-noise ladders step through qecmc_ladder_step_alpha (which carries the slots' n_eff), the others through qecmc_ladder_step");
+    if (int rc = report(rng_range_check(neff_inout ? "qecmc_ladder_step_alpha" : "qecmc_ladder_step", step0, nsteps, prop0, iters))) return rc;
     if (int rc = use_device(p.device)) return rc;
     if (N == 0) return 0;
     // a Python loop over Ladder.step presents the same parameters every call: the tables of the last few plans are kept
@@ -963,6 +966,7 @@ int qecmc_pteq_resume_dev(qecmc_plan *plan, void *d_states, void *d_flags, void 
     if (N + first_syndrome > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "global syndrome index exceeds 32 bits");
     if (plan->args.scan == QECMC_SCAN_WAVE && (first_syndrome & 63u))
         return fail(QECMC_ERR_INVALID, "scan = wave: first_syndrome=%u must be a multiple of 64 (a wavefront shares its generator picks)", first_syndrome);
+    if (int rc = report(rng_range_check_resume("qecmc_pteq_resume_dev", step0, plan->prm.steps, plan->prm.iters))) return rc;
     LadderArgs a = plan->args;
     a.states = static_cast<uint8_t *>(d_states); a.flags = static_cast<uint8_t *>(d_flags); a.tops0 = static_cast<uint32_t *>(d_tops0);
     a.counts = static_cast<uint32_t *>(d_counts); a.samples = static_cast<uint32_t *>(d_samples);
@@ -1001,6 +1005,7 @@ int qecmc_pteq_resume_conv_dev(qecmc_plan *plan, void *d_states, void *d_flags, 
         return fail(QECMC_ERR_INVALID, "step0 + steps = %llu + %llu exceeds the log's %llu rows (row = absolute ladder step: grow the log by appending rows)",
                     (unsigned long long)step0, (unsigned long long)steps, (unsigned long long)log_rows);
     if (step0 + steps > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "step0 + steps exceeds the 32-bit step count of steps_done");
+    if (int rc = report(rng_range_check_resume("qecmc_pteq_resume_conv_dev", step0, steps, plan->prm.iters))) return rc;
     const ResumeConvBytes need = resume_conv_need(plan->prm, N, log_rows);
     if (workspace_bytes < need.log)
         return fail(QECMC_ERR_INVALID, "workspace of %llu bytes, a log of %llu rows takes %llu (qecmc_plan_resume_conv_bytes)",

@@ -368,4 +368,37 @@ inline Refusal resume_conv_check(const qecmc_params &prm)
     return {};
 }
 
+// THE range of the Philox addresses (philox.hpp, DESIGN.md "RNG addressing"): a counter holds a proposal index -- or a ladder-step index, swap stream --
+// in 48 bits, c0 = k[31:0], c1[15:0] = k[47:32], so index 2^48 + k would draw the blocks of index k again.  The entry points that take a start
+// index (step0 / prop0 / k0) refuse a call whose last index, plus kRngIndexSlack, is not below 2^48 (the slack: the colour kernels address the top
+// rung's block of phase K as K + lane), or whose step0 * iters / prop0 + nsteps * iters does not fit 64 bits -- before anything is enqueued.
+// The call runs ladder steps [step0, step0 + nsteps) and proposals [prop0, prop0 + nsteps * iters) (a single chain: nsteps = 1, prop0 = k0).
+constexpr uint64_t kRngIndexLimit = 1ull << 48;
+constexpr uint64_t kRngIndexSlack = 64;
+inline Refusal rng_range_check(const char *who, uint64_t step0, uint64_t nsteps, uint64_t prop0, uint64_t iters)
+{
+    constexpr uint64_t kEndMax = kRngIndexLimit - kRngIndexSlack;         // the largest accepted one-past-the-last index
+    uint64_t props = 0, prop_end = 0, step_end = 0;
+    if (__builtin_mul_overflow(nsteps, iters, &props) || __builtin_add_overflow(prop0, props, &prop_end))
+        return refuse_params(QECMC_ERR_INVALID, "%s: proposals %llu + %llu steps x %llu iters overflow 64 bits (the Philox counter holds 48: last index + %llu < 2^48)", who,
+                             (unsigned long long)prop0, (unsigned long long)nsteps, (unsigned long long)iters, (unsigned long long)kRngIndexSlack);
+    if (prop_end > kEndMax)
+        return refuse_params(QECMC_ERR_INVALID, "%s: proposals %llu .. %llu (start %llu, %llu steps x %llu iters) leave the 48-bit Philox counter: the last index + %llu must be below 2^48 = %llu",
+                             who, (unsigned long long)prop0, (unsigned long long)(prop_end - (props ? 1 : 0)), (unsigned long long)prop0, (unsigned long long)nsteps,
+                             (unsigned long long)iters, (unsigned long long)kRngIndexSlack, (unsigned long long)kRngIndexLimit);
+    if (__builtin_add_overflow(step0, nsteps, &step_end) || step_end > kEndMax)
+        return refuse_params(QECMC_ERR_INVALID, "%s: ladder steps %llu + %llu leave the 48-bit Philox counter of the swap stream: the last index + %llu must be below 2^48 = %llu", who,
+                             (unsigned long long)step0, (unsigned long long)nsteps, (unsigned long long)kRngIndexSlack, (unsigned long long)kRngIndexLimit);
+    return {};
+}
+// ... of a run continued at ladder step step0, whose first proposal is step0 * iters (qecmc_pteq_resume_dev, qecmc_pteq_resume_conv_dev)
+inline Refusal rng_range_check_resume(const char *who, uint64_t step0, uint64_t nsteps, uint64_t iters)
+{
+    uint64_t prop0 = 0;
+    if (__builtin_mul_overflow(step0, iters, &prop0))
+        return refuse_params(QECMC_ERR_INVALID, "%s: step0 * iters = %llu * %llu overflows 64 bits (the Philox counter holds 48: last proposal index + %llu < 2^48)", who,
+                             (unsigned long long)step0, (unsigned long long)iters, (unsigned long long)kRngIndexSlack);
+    return rng_range_check(who, step0, nsteps, prop0, iters);
+}
+
 }  // namespace qecmc

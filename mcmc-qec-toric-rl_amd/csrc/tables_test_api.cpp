@@ -161,6 +161,14 @@ int qt_resume_conv_check(const qecmc_params *p, char *msg, int msg_cap)
     if (msg && msg_cap > 0) std::snprintf(msg, (size_t)msg_cap, "%s", r.msg.c_str());
     return r.code;
 }
+// rng_range_check(): the QECMC_ERR_* code with which the entry points that take step0 / prop0 / k0 refuse indices beyond the 48-bit Philox counter (0: accepted);
+// resume != 0: prop0 is step0 * iters, as qecmc_pteq_resume_dev / qecmc_pteq_resume_conv_dev derive it (the argument is ignored)
+int qt_rng_range_check(int resume, uint64_t step0, uint64_t nsteps, uint64_t prop0, uint64_t iters, char *msg, int msg_cap)
+{
+    const Refusal r = resume ? rng_range_check_resume("resume", step0, nsteps, iters) : rng_range_check("step", step0, nsteps, prop0, iters);
+    if (msg && msg_cap > 0) std::snprintf(msg, (size_t)msg_cap, "%s", r.msg.c_str());
+    return r.code;
+}
 // the shortest-chain statistics (qecmc_plan_set_shortest): what they refuse of a parameter block before a buffer is looked at, and the set workspace
 int qt_shortest_check(const qecmc_params *p, char *msg, int msg_cap)
 {
