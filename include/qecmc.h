@@ -221,6 +221,27 @@ int qecmc_corrections_dev(qecmc_corrector *c, const void *d_candidates, const vo
                           int descend, void *d_corrections_out, void *d_weight_out /*nullable*/, void *d_source_out /*nullable*/,
                           void *d_moved_out /*nullable*/, void *d_status_out /*nullable*/, void *hip_stream);
 
+/* ---- the exact class law by coset enumeration (no counterpart in the reference: every decoder there estimates this) --------------
+ * chains uint8[N][nq]: one chain per syndrome (e.g. the lifted chain).  hist_out uint64[N][ncls][nq+1][nq+1]:
+ * hist[s][c][n_xy][n_z] = the number of chains with the syndrome of chain s, in class c (the convention of qecmc_eq_class: the column
+ * order of counts / distr), that have n_xy X or Y errors and n_z Z errors -- counted over the elements of the stabilizer group the call
+ * covers.  Every weight the library knows is a function of (n_xy, n_z): Z_c = sum hist[s][c] * w(n_xy, n_z) is the EXACT weight of
+ * class c, and a whole class sums to 2^rank.  class_out int32[N] (nullable): the class of the input chain.
+ * Element e in [0, 2^rank) of the group is the product of the basis generators whose bit is set in e, the basis being the generators
+ * greedy GF(2) elimination keeps in table order (csrc/enumerate.hpp); chunk k of width chunk_bits (0: the default, at most 24; a value
+ * beyond the rank means the rank) is e in [k << chunk_bits, (k + 1) << chunk_bits).  The call covers chunks
+ * [chunk_first, chunk_first + chunk_count), chunk_count == 0 meaning all from chunk_first: histograms over disjoint ranges add up to
+ * the whole, one launch covers one chunk of a bounded group of syndromes, and hist_out is overwritten, not added to.
+ * qecmc_coset_enumerate_info: the sizes of one (code, L) -- every pointer nullable --, on the host alone.
+ * Additive: QECMC_ABI_VERSION stays.  Refused before a device is looked for: a NULL chains / hist_out, a (code, L) the library does not
+ * know (xzzx / rotated at even L among them), chunk_bits outside {0} and [8, 30] or a chunk range past 2^(rank - chunk_bits) with
+ * QECMC_ERR_INVALID; more than 32 qubits, a rank above 36 or below 8, a (code, L) without a class move (the toric code at even L) or
+ * a histogram beyond the kernel's LDS with QECMC_ERR_UNSUPPORTED -- which leaves toric L = 3, planar L = 3, 4 and xzzx / rotated
+ * L = 3, 5.  N == 0 succeeds.  Host pointers only. */
+int qecmc_coset_enumerate_info(int code, int L, int32_t *rank, int32_t *ncls, int32_t *nq, int32_t *default_chunk_bits);
+int qecmc_coset_enumerate(int code, int L, uint64_t N, const uint8_t *chains, int chunk_bits, uint64_t chunk_first,
+                          uint64_t chunk_count, uint64_t *hist_out, int32_t *class_out);
+
 /* ---- chain / ladder on caller-owned state (host pointers) ----------------- */
 
 /* The supported range of a start index.  A Philox counter holds a proposal index (the swap stream: a ladder-step index) in 48 bits,

@@ -21,6 +21,7 @@
 #include "plan_host.hpp"
 #include "stencil_bytes.hpp"
 #include "corrections.hpp"
+#include "enumerate.hpp"
 #include "syndrome_lift.hpp"
 #include "tables.hpp"
 
@@ -561,6 +562,62 @@ int qecmc_corrections(int code, int L, uint64_t N, uint32_t K, const uint8_t *ca
     if (source_out) HIP_TRY(hipMemcpy(source_out, ds.p, N * 4, hipMemcpyDeviceToHost));
     if (moved_out) HIP_TRY(hipMemcpy(moved_out, dm.p, N, hipMemcpyDeviceToHost));
     if (status_out) HIP_TRY(hipMemcpy(status_out, dst.p, N, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---------------------------------------------------------------- the exact class law by coset enumeration (enumerate.hpp)
+int qecmc_coset_enumerate_info(int code, int L, int32_t *rank, int32_t *ncls, int32_t *nq, int32_t *default_chunk_bits)
+{
+    const enumr::Table t = enumr::build_table(code, L);
+    if (int rc = report(t.refusal)) return rc;
+    int bits = 0;
+    uint64_t count = 0;
+    if (int rc = report(enumr::resolve_range(t, bits, 0, count))) return rc;
+    if (rank) *rank = t.rank;
+    if (ncls) *ncls = t.ncls;
+    if (nq) *nq = t.nq;
+    if (default_chunk_bits) *default_chunk_bits = bits;
+    return 0;
+}
+
+int qecmc_coset_enumerate(int code, int L, uint64_t N, const uint8_t *chains, int chunk_bits, uint64_t chunk_first, uint64_t chunk_count,
+                          uint64_t *hist_out, int32_t *class_out)
+{
+    if (!chains || !hist_out) return fail(QECMC_ERR_INVALID, "qecmc_coset_enumerate: NULL buffer");
+    if (N > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "N=%llu syndromes exceed 32 bits", (unsigned long long)N);
+    const enumr::Table t = enumr::build_table(code, L);
+    if (int rc = report(t.refusal)) return rc;
+    if (int rc = report(enumr::resolve_range(t, chunk_bits, chunk_first, chunk_count))) return rc;
+    if (int rc = use_device(0)) return rc;
+    if (N == 0) return 0;
+    const enumr::Shape shape = enumr::launch_shape(t.ncls, chunk_bits, N);
+    const size_t per = (size_t)t.carve.copy_words;                              // counters of one syndrome
+    std::vector<uint32_t> gen((size_t)2 * t.rank), reps((size_t)shape.group * t.ncls * 2);
+    for (int b = 0; b < t.rank; ++b) { gen[(size_t)2 * b] = t.gx[(size_t)b]; gen[(size_t)2 * b + 1] = t.gz[(size_t)b]; }
+    DevBuf dgen, dreps, dhist;
+    HIP_TRY(dgen.alloc(gen.size() * sizeof(uint32_t)));
+    HIP_TRY(dreps.alloc(reps.size() * sizeof(uint32_t)));
+    HIP_TRY(dhist.alloc((size_t)shape.group * per * sizeof(uint64_t)));
+    HIP_TRY(hipMemcpy(dgen.p, gen.data(), gen.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    EnumArgs a = {};
+    a.nq1 = (uint32_t)t.nq + 1u; a.bins = t.carve.bins; a.copies = t.carve.copies; a.ncls = t.ncls;
+    a.chunk_bits = chunk_bits; a.slice_bits = shape.slice_bits; a.blocks = shape.blocks;
+    // the host loops over groups of syndromes and over chunks: no launch, and no device block, grows with the batch
+    for (uint64_t first = 0; first < N; first += shape.group) {
+        const uint64_t here = N - first < shape.group ? N - first : shape.group;
+        for (uint64_t s = 0; s < here; ++s) {
+            const int cls = enumr::class_representatives(t, chains + (first + s) * (uint64_t)t.nq, reps.data() + s * (uint64_t)t.ncls * 2);
+            if (class_out) class_out[first + s] = cls;
+        }
+        HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * t.ncls * 2 * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemsetAsync(dhist.p, 0, (size_t)here * per * sizeof(uint64_t), 0));   // (a block from the pool comes back dirty)
+        a.S = (uint32_t)here;
+        for (uint64_t k = chunk_first; k < chunk_first + chunk_count; ++k) {
+            enumr::product_planes(t, chunk_bits, k, a.cx, a.cz);
+            HIP_TRY(launch_enumerate(a, dgen.as<uint32_t>(), dreps.as<uint32_t>(), dhist.as<unsigned long long>(), 0));
+        }
+        HIP_TRY(hipMemcpy(hist_out + first * per, dhist.p, (size_t)here * per * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    }
     return 0;
 }
 

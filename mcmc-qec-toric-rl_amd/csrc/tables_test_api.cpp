@@ -4,6 +4,7 @@
 // (kernel_choice.hpp) which kernel every shape runs, and plan_host() (plan_host.hpp) which plan -- or which refusal -- a parameter block gets.
 // Not part of libqecmc.so.
 #include "corrections.hpp"
+#include "enumerate.hpp"
 #include "kernel_choice.hpp"
 #include "plan_host.hpp"
 #include "syndrome_lift.hpp"
@@ -227,6 +228,44 @@ int qt_corrections(int code, int L, uint64_t N, uint32_t K, const uint8_t *candi
     const correct::Table t = correct::build_table(code, L);
     if (t.need.empty()) return QECMC_ERR_UNSUPPORTED;
     correct::corrections_host(t, N, K, candidates, target, place != 0, descend != 0, corrections, weight, source, moved, status);
+    return 0;
+}
+// the coset enumeration (enumerate.hpp).  qt_enumerate_info: rank, ncls, nq, the default chunk_bits, the LDS bytes and histogram copies of a
+// workgroup -- the QECMC_ERR_* code of build_table()'s refusal; qt_enumerate_basis: the basis planes uint32[rank][2] (x, z), -1 where refused;
+// qt_enumerate_shape: group, blocks and slice_bits of a launch; qt_coset_enumerate: the host twin of qecmc_coset_enumerate behind the same host checks
+int qt_enumerate_info(int code, int L, int32_t *out6, char *msg, int msg_cap)
+{
+    const enumr::Table t = enumr::build_table(code, L);
+    if (msg && msg_cap > 0) std::snprintf(msg, (size_t)msg_cap, "%s", t.refusal.msg.c_str());
+    if (t.refusal.code) return t.refusal.code;
+    int bits = 0;
+    uint64_t count = 0;
+    (void)enumr::resolve_range(t, bits, 0, count);
+    const int32_t v[6] = {t.rank, t.ncls, t.nq, bits, (int32_t)t.carve.bytes, (int32_t)t.carve.copies};
+    std::memcpy(out6, v, sizeof v);
+    return 0;
+}
+int qt_enumerate_basis(int code, int L, uint32_t *out, int cap)
+{
+    const enumr::Table t = enumr::build_table(code, L);
+    if (t.refusal.code) return -1;
+    std::vector<uint32_t> v;
+    for (int b = 0; b < t.rank; ++b) { v.push_back(t.gx[(size_t)b]); v.push_back(t.gz[(size_t)b]); }
+    return put(v, out, cap);
+}
+void qt_enumerate_shape(int ncls, int chunk_bits, uint64_t N, uint32_t *group, uint32_t *blocks, int32_t *slice_bits)
+{
+    const enumr::Shape s = enumr::launch_shape(ncls, chunk_bits, N);
+    *group = s.group; *blocks = s.blocks; *slice_bits = s.slice_bits;
+}
+int qt_coset_enumerate(int code, int L, uint64_t N, const uint8_t *chains, int chunk_bits, uint64_t chunk_first, uint64_t chunk_count, uint64_t *hist,
+                       int32_t *cls)
+{
+    if (!chains || !hist) return QECMC_ERR_INVALID;
+    const enumr::Table t = enumr::build_table(code, L);
+    if (t.refusal.code) return t.refusal.code;
+    if (const Refusal r = enumr::resolve_range(t, chunk_bits, chunk_first, chunk_count); r.code) return r.code;
+    enumr::enumerate_host(t, N, chains, chunk_bits, chunk_first, chunk_count, hist, cls);
     return 0;
 }
 }

@@ -59,6 +59,7 @@ _i32p = C.POINTER(C.c_int32)
 _u32p = C.POINTER(C.c_uint32)
 _i64p = C.POINTER(C.c_int64)
 _u16p = C.POINTER(C.c_uint16)
+_u64p = C.POINTER(C.c_uint64)
 
 # every symbol include/qecmc.h declares, with its signature
 SIGNATURES = {
@@ -85,6 +86,8 @@ SIGNATURES = {
     "qecmc_corrector_destroy": (C.c_int, [C.c_void_p]),
     "qecmc_corrections_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qecmc_coset_enumerate_info": (C.c_int, [C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p]),
+    "qecmc_coset_enumerate": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, C.c_int, C.c_uint64, C.c_uint64, _u64p, _i32p]),
     "qecmc_chain_update": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, C.c_double, C.c_double, C.c_uint64,
                                      C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64]),
     "qecmc_chain_update_biased": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, C.c_double, C.c_double, C.c_double,

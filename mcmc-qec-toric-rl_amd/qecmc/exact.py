@@ -1,0 +1,104 @@
+"""The exact class law by coset enumeration on the device (qecmc_coset_enumerate; no counterpart in the reference, whose decoders all estimate
+this quantity): for every syndrome the integer histogram hist[c, n_xy, n_z] of the chains of class c over their X-or-Y and Z counts, summed over
+the whole stabilizer group, and from it the class weights Z_c = sum hist[c] * w(n_xy, n_z) of any noise model whose weight is a function of the two
+counts -- the maximum-likelihood decoder of the small codes (toric L = 3, planar L = 3, 4, xzzx / rotated L = 3, 5)."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L_
+
+_CODES = {"toric": L_.TORIC, "xzzx": L_.XZZX, "rotated": L_.ROTATED, "planar": L_.PLANAR}
+
+
+def enumerator_info(code, size):
+    """dict(rank, ncls, nq, chunk_bits: the default) of one (code, size), from the host half of the library alone; raises QecmcError where the
+    enumeration refuses the code"""
+    v = [C.c_int32() for _ in range(4)]
+    L_.check(L_.lib().qecmc_coset_enumerate_info(_CODES.get(code, code), int(size), *[C.byref(x) for x in v]))
+    return dict(zip(("rank", "ncls", "nq", "chunk_bits"), (int(x.value) for x in v)))
+
+
+def _as_chains(code, chains, size):
+    """chains -> (uint8[N, nq], L).  [N, ...] or one [...] with ... the code's qubit_matrix shape; with `size` given also the flat [N, nq]."""
+    a = np.ascontiguousarray(chains, dtype=np.uint8)
+    sd = 3 if code in (L_.TORIC, L_.PLANAR) else 2
+    if size is not None and a.ndim == 2 and a.shape[-1] == (2 if sd == 3 else 1) * size * size:
+        return a, int(size)
+    if a.ndim == sd:
+        a = a[None]
+    if a.ndim != sd + 1 or a.shape[-1] != a.shape[-2] or (sd == 3 and a.shape[-3] != 2) or (size is not None and size != a.shape[-1]):
+        raise ValueError(f"chains of shape {a.shape} are not [N, ...] configurations of this code" + ("" if size is None else f" at size {size}"))
+    return a.reshape(a.shape[0], -1), a.shape[-1]
+
+
+def coset_enumerator(code, chains, size=None, chunk_bits=0, chunks=None, device=0):
+    """The histogram of every syndrome, on the GPU.  code: "toric" / "xzzx" / "rotated" / "planar" (or the qecmc code number); chains uint8[N, ...]:
+    one chain per syndrome (any chain with it: hist depends on the syndrome alone).  chunk_bits (0: the
+    default) cuts the 2^rank group elements into chunks of 2^chunk_bits; chunks=(first, count) enumerates that range only -- partial histograms over
+    disjoint ranges add up to the whole.
+    Returns dict(hist uint64[N, ncls, nq+1, nq+1], cls int32[N]: the class of each input chain, rank)."""
+    code = _CODES.get(code, code)
+    if int(device) != 0:
+        raise ValueError("coset_enumerator runs on device 0: the library has no device-pointer form of it yet")
+    flat, L = _as_chains(code, chains, size)
+    info = enumerator_info(code, L)
+    n, nq1 = flat.shape[0], info["nq"] + 1
+    first, count = (0, 0) if chunks is None else (int(chunks[0]), int(chunks[1]))
+    if chunks is not None and count < 1:
+        raise ValueError(f"chunks={chunks!r}: (first, count) with count >= 1")
+    hist = np.zeros((n, info["ncls"], nq1, nq1), dtype=np.uint64)
+    cls = np.zeros(n, dtype=np.int32)
+    L_.check(L_.lib().qecmc_coset_enumerate(code, L, n, L_.u8(flat), int(chunk_bits), first, count, hist.ctypes.data_as(L_._u64p), L_.i32(cls)))
+    return dict(hist=hist, cls=cls, rank=info["rank"])
+
+
+def class_weights(hist, weight):
+    """Z[..., c] = sum over (n_xy, n_z) of hist[..., c, n_xy, n_z] * weight(n_xy, n_z): weight is broadcast over the grid of counts, float64"""
+    hist = np.asarray(hist)
+    n = np.arange(hist.shape[-1], dtype=np.float64)
+    w = np.broadcast_to(np.asarray(weight(n[:, None], n[None, :]), dtype=np.float64), hist.shape[-2:])
+    return np.einsum("...ij,ij->...", hist.astype(np.float64), w)
+
+
+def depolarizing_weight(p):
+    """f^(n_xy + n_z), f = (p / 3) / (1 - p)"""
+    f = (p / 3.0) / (1.0 - p)
+    return lambda nxy, nz: f ** (nxy + nz)
+
+
+def biased_weight(p, eta):
+    """(p_x / p_I)^n_xy (p_z / p_I)^n_z with p_z = p eta / (eta + 1), p_x = p_y = p / (2 (eta + 1)), p_I = 1 - p: the ratio form, so a cell that holds
+    no qubit (the planar code's) does not enter"""
+    rz, rx = p * eta / (eta + 1.0) / (1.0 - p), p / (2.0 * (eta + 1.0)) / (1.0 - p)
+    return lambda nxy, nz: rx ** nxy * rz ** nz
+
+
+def alpha_weight(pz_tilde, alpha):
+    """pz_tilde^(n_z + alpha n_xy)"""
+    return lambda nxy, nz: pz_tilde ** (nz + alpha * nxy)
+
+
+def exact_class_probabilities(code, chains, p, eta=None, alpha=None, hist=None, **enumerator_kw):
+    """float64[N, ncls]: the exact class law of every syndrome under depolarizing noise p, Z-biased noise (p, eta) or the alpha model (p is pz_tilde).
+    hist: a histogram already enumerated (coset_enumerator(...)['hist']) -- chains is then not looked at; otherwise the keywords go to coset_enumerator."""
+    if eta is not None and alpha is not None:
+        raise ValueError("eta and alpha name two noise models")
+    if hist is None:
+        hist = coset_enumerator(code, chains, **enumerator_kw)["hist"]
+    weight = alpha_weight(p, alpha) if alpha is not None else biased_weight(p, eta) if eta is not None else depolarizing_weight(p)
+    z = class_weights(hist, weight)
+    return z / z.sum(axis=-1, keepdims=True)
+
+
+def exact_rung_observables(hist, p_ladder):
+    """float64[N, Nc]: the exact mean error count of every rung of a depolarizing ladder (np.linspace(p, 0.75, Nc) in the decoders).  A rung samples
+    f_rung^n over the union of the classes: the truth of nerr_sums / steps."""
+    tot = np.asarray(hist).sum(axis=-3).astype(np.float64)                     # [N, n_xy, n_z]
+    n = np.arange(tot.shape[-1], dtype=np.float64)
+    errs = n[:, None] + n[None, :]
+    out = []
+    for p in np.atleast_1d(np.asarray(p_ladder, dtype=np.float64)):
+        w = ((p / 3.0) / (1.0 - p)) ** errs
+        out.append(np.einsum("...ij,ij->...", tot, w * errs) / np.einsum("...ij,ij->...", tot, w))
+    return np.stack(out, axis=-1)

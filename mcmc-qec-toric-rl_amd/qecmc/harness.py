@@ -214,11 +214,32 @@ def _pteq_decode(params, init, seed, steps, conv_criteria, biased_decoder, metri
     return res, time.perf_counter() - t0, Nc
 
 
+def _exact_distr(params, chains, device):
+    """params['method'] == "exact": the exact class law of every row (qecmc.exact_class_probabilities) under the weight of
+    params['noise'] itself -- biased noise with the biased weight, whatever biased_decoder says"""
+    from .exact import exact_class_probabilities
+    noise = params.get("noise", "depolarizing")
+    if _CODES[params["code"]] == L_.TORIC and noise != "depolarizing":
+        raise ValueError(f"method exact on the toric code is defined for depolarizing noise, not {noise} (its errors are drawn without a bias)")
+    kw = dict(eta=params["eta"]) if noise == "biased" else dict(alpha=params["alpha"]) if noise == "alpha" else {}
+    return exact_class_probabilities(params["code"], chains, params["p_error"], size=params["size"], chunk_bits=int(params.get("chunk_bits", 0)),
+                                     device=device, **kw)
+
+
 def _corrections_for(code, size, candidates, distr, device):
     """the correction of every row towards target = argmax(distr) -- the very expression `success` uses -- from candidates [n, K, ...] or [n, ...]"""
     from .syndrome_corrections import corrections as correct
     target = np.argmax(distr, axis=1).astype(np.int32)
     return target, correct(code, candidates, target, device=device, size=size)
+
+
+def _correction_outputs(code, size, raw, init, distr, device):
+    """generate's corrections=True: the correction of every start chain towards argmax(distr), its weight, and whether raw ^ correction is a stabilizer"""
+    _, cor = _corrections_for(code, size, init, distr, device)
+    residual = raw ^ cor["corrections"]
+    stabilizer_class = int(np.asarray(_class_of(code, np.zeros_like(raw[:1])))[0])
+    return dict(correction=cor["corrections"], correction_weight=cor["weight"],
+                success_correction=~syndrome_of(code, residual).any(axis=1) & (np.asarray(_class_of(code, residual)) == stabilizer_class))
 
 
 def decode_syndromes(params, defects, seed=0, steps=100000, conv_criteria="error_based", biased_decoder="alpha", metrics="basic", corrections=False,
@@ -228,13 +249,16 @@ def decode_syndromes(params, defects, seed=0, steps=100000, conv_criteria="error
     decoder routing by params['noise'], the same keywords.  The start chain is a local minimum of the weight in an arbitrary class: the
     class law does not depend on it, only the burn-in does.
     Returns dict(distr, counts, steps_done, converged, samples, tops0, chains, status, weight); raises if a syndrome is none of the code.
+    params['method'] = "exact" decodes by coset enumeration instead (qecmc.exact_class_probabilities under the weight of params['noise'] itself;
+    params['chunk_bits'] optional): distr float64[n, ncls], chains, status, weight -- no counts, no run.
     corrections=True adds what a user who measured a syndrome wants (qecmc.corrections): target = argmax(distr) per row, correction -- a
     chain with the syndrome in that class --, correction_weight, correction_source and correction_moved.  The candidate is the lifted chain;
     correction_candidates="states" adds the Nc final rung states of every ladder as candidates 1 ..., where the route returns them: a fixed-length
     run (conv_criteria=None).  A run the convergence criterion stops may go to the work-queue kernels, which write no final states: ValueError."""
     from .syndrome_lift import chains_from_syndromes
-    if params.get("method", "PTEQ") != "PTEQ":
-        raise ValueError("decode_syndromes decodes with PTEQ (params['method'])")
+    method = params.get("method", "PTEQ")
+    if method not in ("PTEQ", "exact"):
+        raise ValueError("decode_syndromes decodes with PTEQ or exact (params['method'])")
     noise = params.get("noise", "depolarizing")
     if noise not in ("depolarizing", "biased", "alpha"):
         raise ValueError(f"noise={noise!r}")
@@ -247,6 +271,15 @@ def decode_syndromes(params, defects, seed=0, steps=100000, conv_criteria="error
     if correction_candidates not in ("lift", "states"):
         raise ValueError(f"correction_candidates={correction_candidates!r}")
     with_states = bool(corrections) and correction_candidates == "states"
+    if method == "exact":
+        if with_states:
+            raise ValueError("correction_candidates='states': method exact runs no ladder; keep the lifted chain")
+        out = dict(distr=_exact_distr(params, chains, int(pteq_kw.get("device", 0))), chains=chains, status=status, weight=weight)
+        if corrections:
+            target, cor = _corrections_for(_CODES[params["code"]], params["size"], chains, out["distr"], int(pteq_kw.get("device", 0)))
+            out.update(target=target, correction=cor["corrections"], correction_weight=cor["weight"], correction_source=cor["source"],
+                       correction_moved=cor["moved"])
+        return out
     if with_states:
         if conv_criteria is not None:
             raise ValueError(f"correction_candidates='states': the route conv_criteria={conv_criteria!r} (a run stopped by the convergence criterion, which may "
@@ -278,14 +311,18 @@ def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_
     unique-chain estimators on one representative per class of every syndrome, with params['p_sampling'] (default p_error),
     params['droplets'], params['conv_mult'] and `steps` as the estimator's own `steps`; `batch` syndromes go into one launch
     (default 256: the sets of visited chains live in HBM).  They return distr float64[n, ncls] and no counts.
+    params['method'] = "exact" is the maximum-likelihood decoder of the small codes: distr float64[n, ncls] is the exact class law of every
+    syndrome by coset enumeration on the device (qecmc.exact_class_probabilities) under the weight of params['noise'] itself --
+    biased noise with the biased weight, whatever biased_decoder says --, with success and no counts; start="syndrome" and corrections=True work
+    on top of it; `steps` and the sampler keywords are not looked at.
     device_generation=True draws the errors and the hiding logical operator on the GPU (`generate_syndromes`) instead of NumPy.
     start="error" (default) is the reference's recipe: the decoder starts from the error with a random logical operator on top.  start="syndrome"
-    (method PTEQ only) lets nothing but syndrome(raw) reach the decoder: the start chains are qecmc.chains_from_syndromes of it and no logical
+    (methods PTEQ and exact) lets nothing but syndrome(raw) reach the decoder: the start chains are qecmc.chains_from_syndromes of it and no logical
     operator is drawn; eq_true and the success rule are the same.
     metrics="basic" (default) costs nothing: throughput, convergence, burn-in and success figures.  metrics="full" also attaches the
     mixing counters (swap acceptance per rung pair, mean error count per rung) -- which rule out the work-queue kernels
     (their lanes run several ladders) and need nq * steps < 2^32, so they are dropped, not failed on, where they do not fit.
-    corrections=True (method PTEQ) closes the loop: correction uint8[n,...] is qecmc.corrections of the start chain -- the seed configuration, or the
+    corrections=True (methods PTEQ and exact) closes the loop: correction uint8[n,...] is qecmc.corrections of the start chain -- the seed configuration, or the
     lifted chain of start="syndrome" -- towards argmax(distr), correction_weight its error count, and success_correction[s] is true iff
     raw[s] ^ correction[s] (byte values XOR as the Pauli product) is a stabilizer: an all-zero syndrome and the class of the zero chain.
     Returns (and optionally saves as npz) qubit_matrix uint8[n,...] (the raw errors, generate_data.py:120),
@@ -302,10 +339,10 @@ def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_
     method = params.get("method", "PTEQ")
     if start not in ("error", "syndrome"):
         raise ValueError(f"start={start!r}")
-    if start == "syndrome" and method != "PTEQ":
-        raise ValueError(f"start='syndrome' is built for method PTEQ, not {method}")
-    if corrections and method != "PTEQ":
-        raise ValueError(f"corrections=True is built for method PTEQ, not {method}")
+    if start == "syndrome" and method not in ("PTEQ", "exact"):
+        raise ValueError(f"start='syndrome' is built for methods PTEQ and exact, not {method}")
+    if corrections and method not in ("PTEQ", "exact"):
+        raise ValueError(f"corrections=True is built for methods PTEQ and exact, not {method}")
     if device_generation:
         # errors, true class and the hiding logical operator drawn on the GPU (Philox keyed by the global syndrome index: the data
         # set does not depend on how it is cut into shards)
@@ -331,6 +368,14 @@ def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_
         if file_path is not None:
             np.savez_compressed(file_path, params=np.array([repr(params)]), **out)
         return out
+    if method == "exact":
+        distr = _exact_distr(params, init, int(pteq_kw.get("device", 0)))
+        out = dict(qubit_matrix=raw, eq_true=eq_true, distr=distr, success=np.argmax(distr, axis=1) == eq_true)
+        if corrections:
+            out.update(_correction_outputs(code, size, raw, init, distr, int(pteq_kw.get("device", 0))))
+        if file_path is not None:
+            np.savez_compressed(file_path, params=np.array([repr(params)]), **out)
+        return out
     if method != "PTEQ":
         if noise != ("alpha" if method == "STDC_N_n" else "depolarizing"):
             raise ValueError(f"method {method} is defined for {'alpha' if method == 'STDC_N_n' else 'depolarizing'} noise (generate_data.py:168-196)")
@@ -352,11 +397,7 @@ def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_
                success=np.argmax(res["percent"], axis=1) == eq_true, steps_done=res["steps_done"],
                converged=res["converged"], samples=res["samples"], tops0=res["tops0"])
     if corrections:
-        _, cor = _corrections_for(code, size, init, out["distr"], int(pteq_kw.get("device", 0)))
-        residual = raw ^ cor["corrections"]
-        stabilizer_class = int(np.asarray(_class_of(code, np.zeros_like(raw[:1])))[0])
-        out.update(correction=cor["corrections"], correction_weight=cor["weight"],
-                   success_correction=~syndrome_of(code, residual).any(axis=1) & (np.asarray(_class_of(code, residual)) == stabilizer_class))
+        out.update(_correction_outputs(code, size, raw, init, out["distr"], int(pteq_kw.get("device", 0))))
     if file_path is not None:
         np.savez_compressed(file_path, params=np.array([repr(params)]), **out)
     out["metrics"] = batch_metrics(code, size, Nc, int(pteq_kw.get("iters", 10)), res, wall, out["success"],
