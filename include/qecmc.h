@@ -242,6 +242,21 @@ int qecmc_coset_enumerate_info(int code, int L, int32_t *rank, int32_t *ncls, in
 int qecmc_coset_enumerate(int code, int L, uint64_t N, const uint8_t *chains, int chunk_bits, uint64_t chunk_first,
                           uint64_t chunk_count, uint64_t *hist_out, int32_t *class_out);
 
+/* ---- the exact class law by a frontier sweep: the same law where 2^rank elements are out of reach -----------------------------------
+ * chains uint8[N][nq]: one chain per syndrome.  w[4]: the weight of I, X, Y and Z at one qubit (any positive scale; the library's noise
+ * models in ratio form have w[0] = 1), finite and > 0.  z_out double[N][ncls]:
+ * z_out[s][c] = the sum over the chains of class c (the convention of qecmc_eq_class) with the syndrome of chain s of prod_q w[Pauli at q]
+ * -- the product over the qubits of the code: a cell of the state layout that holds no qubit (the planar code's) does not enter.
+ * class_out int32[N] (nullable): the class of the input chain.  The sum is carried out by variable elimination across the lattice
+ * (csrc/class_sweep.hpp): (2 G + nq) 2^width operations per class, width the widest frontier of the plan, on a state vector in LDS.
+ * qecmc_class_sweep_info: width, ncls, nq and the number of ops of the plan of one (code, L) -- every pointer nullable --, on the host alone.
+ * Additive: QECMC_ABI_VERSION stays.  Refused before a device is looked for: a NULL chains / w / z_out, a weight that is not finite and
+ * > 0 or a (code, L) the library does not know with QECMC_ERR_INVALID; a (code, L) without a class move (the toric code at even L) or a
+ * plan wider than 13 with QECMC_ERR_UNSUPPORTED -- which leaves toric L = 3, planar L = 3 .. 6 and xzzx / rotated L = 3, 5, 7, 9.
+ * N == 0 succeeds.  Host pointers only. */
+int qecmc_class_sweep_info(int code, int L, int32_t *width, int32_t *ncls, int32_t *nq, int32_t *n_ops);
+int qecmc_class_sweep(int code, int L, uint64_t N, const uint8_t *chains, const double *w, double *z_out, int32_t *class_out);
+
 /* ---- chain / ladder on caller-owned state (host pointers) ----------------- */
 
 /* The supported range of a start index.  A Philox counter holds a proposal index (the swap stream: a ladder-step index) in 48 bits,

@@ -21,6 +21,7 @@
 #include "plan_host.hpp"
 #include "stencil_bytes.hpp"
 #include "corrections.hpp"
+#include "class_sweep.hpp"
 #include "enumerate.hpp"
 #include "syndrome_lift.hpp"
 #include "tables.hpp"
@@ -617,6 +618,53 @@ int qecmc_coset_enumerate(int code, int L, uint64_t N, const uint8_t *chains, in
             HIP_TRY(launch_enumerate(a, dgen.as<uint32_t>(), dreps.as<uint32_t>(), dhist.as<unsigned long long>(), 0));
         }
         HIP_TRY(hipMemcpy(hist_out + first * per, dhist.p, (size_t)here * per * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- the exact class law by a frontier sweep (class_sweep.hpp)
+int qecmc_class_sweep_info(int code, int L, int32_t *width, int32_t *ncls, int32_t *nq, int32_t *n_ops)
+{
+    const sweep::Plan p = sweep::build_plan(code, L);
+    if (int rc = report(p.refusal)) return rc;
+    if (width) *width = p.width;
+    if (ncls) *ncls = p.ncls;
+    if (nq) *nq = p.nq;
+    if (n_ops) *n_ops = p.n_ops;
+    return 0;
+}
+
+int qecmc_class_sweep(int code, int L, uint64_t N, const uint8_t *chains, const double *w, double *z_out, int32_t *class_out)
+{
+    if (!chains || !w || !z_out) return fail(QECMC_ERR_INVALID, "qecmc_class_sweep: NULL buffer");
+    if (N > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "N=%llu syndromes exceed 32 bits", (unsigned long long)N);
+    if (int rc = report(sweep::check_weights(w))) return rc;
+    const sweep::Plan p = sweep::build_plan(code, L);
+    if (int rc = report(p.refusal)) return rc;
+    if (int rc = use_device(0)) return rc;
+    if (N == 0) return 0;
+    const uint32_t group = sweep::launch_group(N);
+    const size_t rep_words = (size_t)p.ncls * p.W;                              // words of one syndrome's representatives
+    std::vector<uint32_t> reps((size_t)group * rep_words);
+    DevBuf dops, dreps, dz;
+    HIP_TRY(dops.alloc(p.ops.size() * sizeof(uint32_t)));
+    HIP_TRY(dreps.alloc(reps.size() * sizeof(uint32_t)));
+    HIP_TRY(dz.alloc((size_t)group * p.ncls * sizeof(double)));
+    HIP_TRY(hipMemcpy(dops.p, p.ops.data(), p.ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    SweepArgs a = {};
+    a.ncls = p.ncls; a.W = p.W; a.width = p.width; a.n_ops = p.n_ops; a.scale = p.scale;
+    sweep::weights_xz(w, a.wxz);
+    // the host loops over groups of syndromes: no launch, and no device block, grows with the batch; every z of a group is written by its workgroup
+    for (uint64_t first = 0; first < N; first += group) {
+        const uint64_t here = N - first < group ? N - first : group;
+        for (uint64_t s = 0; s < here; ++s) {
+            const int cls = sweep::class_representatives(p, chains + (first + s) * (uint64_t)p.nq, reps.data() + s * rep_words);
+            if (class_out) class_out[first + s] = cls;
+        }
+        HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * rep_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+        a.S = (uint32_t)here;
+        HIP_TRY(launch_class_sweep(a, dops.as<uint32_t>(), dreps.as<uint32_t>(), dz.as<double>(), 0));
+        HIP_TRY(hipMemcpy(z_out + first * (uint64_t)p.ncls, dz.p, (size_t)here * p.ncls * sizeof(double), hipMemcpyDeviceToHost));
     }
     return 0;
 }

@@ -3,6 +3,7 @@
 // plan precomputes for the kernels against values the CPU oracle computes; tests/test_kernel_choice.py asks choose_kernel()
 // (kernel_choice.hpp) which kernel every shape runs, and plan_host() (plan_host.hpp) which plan -- or which refusal -- a parameter block gets.
 // Not part of libqecmc.so.
+#include "class_sweep.hpp"
 #include "corrections.hpp"
 #include "enumerate.hpp"
 #include "kernel_choice.hpp"
@@ -266,6 +267,32 @@ int qt_coset_enumerate(int code, int L, uint64_t N, const uint8_t *chains, int c
     if (t.refusal.code) return t.refusal.code;
     if (const Refusal r = enumr::resolve_range(t, chunk_bits, chunk_first, chunk_count); r.code) return r.code;
     enumr::enumerate_host(t, N, chains, chunk_bits, chunk_first, chunk_count, hist, cls);
+    return 0;
+}
+// the frontier sweep (class_sweep.hpp).  qt_class_sweep_info: width, ncls, nq, n_ops, rank, n_gen, the LDS bytes of a workgroup and kMaxWidth -- the
+// QECMC_ERR_* code of build_plan()'s refusal (width and n_ops are the planner's even where it refuses the width); qt_class_sweep_ops: the op stream
+// uint32[n_ops][4], -1 where refused; qt_class_sweep: the host twin of qecmc_class_sweep behind the same host checks
+int qt_class_sweep_info(int code, int L, int32_t *out8, char *msg, int msg_cap)
+{
+    const sweep::Plan p = sweep::build_plan(code, L);
+    if (msg && msg_cap > 0) std::snprintf(msg, (size_t)msg_cap, "%s", p.refusal.msg.c_str());
+    const int32_t v[8] = {p.width, p.ncls, p.nq, p.n_ops, p.rank, p.n_gen, (int32_t)sweep::lds_carve(p.width).bytes, sweep::kMaxWidth};
+    if (out8) std::memcpy(out8, v, sizeof v);
+    return p.refusal.code;
+}
+int qt_class_sweep_ops(int code, int L, uint32_t *out, int cap)
+{
+    const sweep::Plan p = sweep::build_plan(code, L);
+    if (p.refusal.code) return -1;
+    return put(p.ops, out, cap);
+}
+int qt_class_sweep(int code, int L, uint64_t N, const uint8_t *chains, const double *w, double *z, int32_t *cls)
+{
+    if (!chains || !w || !z) return QECMC_ERR_INVALID;
+    if (const Refusal r = sweep::check_weights(w); r.code) return r.code;
+    const sweep::Plan p = sweep::build_plan(code, L);
+    if (p.refusal.code) return p.refusal.code;
+    sweep::sweep_host(p, N, chains, w, z, cls);
     return 0;
 }
 }

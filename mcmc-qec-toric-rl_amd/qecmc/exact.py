@@ -1,7 +1,10 @@
 """The exact class law by coset enumeration on the device (qecmc_coset_enumerate; no counterpart in the reference, whose decoders all estimate
 this quantity): for every syndrome the integer histogram hist[c, n_xy, n_z] of the chains of class c over their X-or-Y and Z counts, summed over
 the whole stabilizer group, and from it the class weights Z_c = sum hist[c] * w(n_xy, n_z) of any noise model whose weight is a function of the two
-counts -- the maximum-likelihood decoder of the small codes (toric L = 3, planar L = 3, 4, xzzx / rotated L = 3, 5)."""
+counts -- the maximum-likelihood decoder of the small codes (toric L = 3, planar L = 3, 4, xzzx / rotated L = 3, 5).
+
+The same law by a frontier sweep (qecmc_class_sweep): the class weights themselves, float64, for four per-qubit weights of I, X, Y
+and Z, by variable elimination across the lattice -- which reaches xzzx / rotated L = 9 and planar L = 6."""
 import ctypes as C
 
 import numpy as np
@@ -53,6 +56,35 @@ def coset_enumerator(code, chains, size=None, chunk_bits=0, chunks=None, device=
     return dict(hist=hist, cls=cls, rank=info["rank"])
 
 
+def sweep_info(code, size):
+    """dict(width, ncls, nq, n_ops) of the sweep plan of one (code, size), from the host half of the library alone; raises QecmcError where the
+    sweep refuses the code"""
+    v = [C.c_int32() for _ in range(4)]
+    L_.check(L_.lib().qecmc_class_sweep_info(_CODES.get(code, code), int(size), *[C.byref(x) for x in v]))
+    return dict(zip(("width", "ncls", "nq", "n_ops"), (int(x.value) for x in v)))
+
+
+def class_sweep(code, chains, weights, size=None, device=0):
+    """The class weights of every syndrome, on the GPU.  code and chains as coset_enumerator takes them; weights: the four weights of I, X, Y and Z
+    at one qubit, finite and > 0 (depolarizing_w4 / biased_w4 / alpha_w4, or any other).
+    Returns dict(Z float64[N, ncls]: Z[s, c] = the sum over the chains of class c with the syndrome of chain s of the product of the weights of their
+    Paulis, cls int32[N]: the class of each input chain, width: the widest frontier of the plan)."""
+    code = _CODES.get(code, code)
+    if int(device) != 0:
+        raise ValueError("class_sweep runs on device 0: the library has no device-pointer form of it yet")
+    flat, L = _as_chains(code, chains, size)
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.shape != (4,):
+        raise ValueError(f"weights of shape {w.shape}: the four weights of I, X, Y and Z")
+    info = sweep_info(code, L)
+    n = flat.shape[0]
+    z = np.zeros((n, info["ncls"]), dtype=np.float64)
+    cls = np.zeros(n, dtype=np.int32)
+    f64p = C.POINTER(C.c_double)
+    L_.check(L_.lib().qecmc_class_sweep(code, L, n, L_.u8(flat), w.ctypes.data_as(f64p), z.ctypes.data_as(f64p), L_.i32(cls)))
+    return dict(Z=z, cls=cls, width=info["width"])
+
+
 def class_weights(hist, weight):
     """Z[..., c] = sum over (n_xy, n_z) of hist[..., c, n_xy, n_z] * weight(n_xy, n_z): weight is broadcast over the grid of counts, float64"""
     hist = np.asarray(hist)
@@ -79,16 +111,60 @@ def alpha_weight(pz_tilde, alpha):
     return lambda nxy, nz: pz_tilde ** (nz + alpha * nxy)
 
 
-def exact_class_probabilities(code, chains, p, eta=None, alpha=None, hist=None, **enumerator_kw):
+def depolarizing_w4(p):
+    """depolarizing_weight per qubit: (1, f, f, f), f = (p / 3) / (1 - p)"""
+    f = (p / 3.0) / (1.0 - p)
+    return np.array([1.0, f, f, f])
+
+
+def biased_w4(p, eta):
+    """biased_weight per qubit: (1, p_x / p_I, p_y / p_I, p_z / p_I)"""
+    rz, rx = p * eta / (eta + 1.0) / (1.0 - p), p / (2.0 * (eta + 1.0)) / (1.0 - p)
+    return np.array([1.0, rx, rx, rz])
+
+
+def alpha_w4(pz_tilde, alpha):
+    """alpha_weight per qubit: (1, pz_tilde^alpha, pz_tilde^alpha, pz_tilde)"""
+    return np.array([1.0, pz_tilde ** alpha, pz_tilde ** alpha, pz_tilde])
+
+
+def resolve_method(code, size, method="auto"):
+    """what exact_class_probabilities runs at one (code, size): "auto" is the enumerator wherever it accepts the shape -- so a call that worked
+    before the sweep existed returns what it returned -- and the sweep where the enumerator answers QECMC_ERR_UNSUPPORTED; any other answer is the
+    enumerator's to report.  From the host half of the library alone."""
+    if method not in ("auto", "enumerate", "sweep"):
+        raise ValueError(f"method={method!r}")
+    if method != "auto":
+        return method
+    rc = L_.lib().qecmc_coset_enumerate_info(_CODES.get(code, code), int(size), None, None, None, None)
+    return "sweep" if rc == -4 else "enumerate"
+
+
+def exact_class_probabilities(code, chains, p, eta=None, alpha=None, hist=None, method="auto", **enumerator_kw):
     """float64[N, ncls]: the exact class law of every syndrome under depolarizing noise p, Z-biased noise (p, eta) or the alpha model (p is pz_tilde).
-    hist: a histogram already enumerated (coset_enumerator(...)['hist']) -- chains is then not looked at; otherwise the keywords go to coset_enumerator."""
+    method "enumerate": by coset_enumerator, which takes the keywords; "sweep": by class_sweep (of the keywords it takes size and device; chunk_bits
+    means nothing to it); "auto" (default): the enumerator wherever it accepts the (code, size), the sweep elsewhere.
+    hist: a histogram already enumerated (coset_enumerator(...)['hist']) -- chains is then not looked at, and the method is the enumerator's."""
     if eta is not None and alpha is not None:
         raise ValueError("eta and alpha name two noise models")
+    if method not in ("auto", "enumerate", "sweep"):
+        raise ValueError(f"method={method!r}")
     if hist is None:
-        hist = coset_enumerator(code, chains, **enumerator_kw)["hist"]
-    weight = alpha_weight(p, alpha) if alpha is not None else biased_weight(p, eta) if eta is not None else depolarizing_weight(p)
-    z = class_weights(hist, weight)
-    return z / z.sum(axis=-1, keepdims=True)
+        method = resolve_method(code, _as_chains(_CODES.get(code, code), chains, enumerator_kw.get("size"))[1], method)
+    if hist is None and method == "sweep":
+        if "chunks" in enumerator_kw:
+            raise ValueError("chunks= is the enumerator's: the sweep has no partial sums")
+        w4 = alpha_w4(p, alpha) if alpha is not None else biased_w4(p, eta) if eta is not None else depolarizing_w4(p)
+        z = class_sweep(code, chains, w4, size=enumerator_kw.get("size"), device=enumerator_kw.get("device", 0))["Z"]
+    else:
+        if hist is None:
+            hist = coset_enumerator(code, chains, **enumerator_kw)["hist"]
+        weight = alpha_weight(p, alpha) if alpha is not None else biased_weight(p, eta) if eta is not None else depolarizing_weight(p)
+        z = class_weights(hist, weight)
+    tot = z.sum(axis=-1, keepdims=True)
+    if not np.all(tot > 0.0):
+        raise FloatingPointError("every class weight of a syndrome underflows to 0 in float64: the law of that row is not representable")
+    return z / tot
 
 
 def exact_rung_observables(hist, p_ladder):

@@ -215,15 +215,16 @@ def _pteq_decode(params, init, seed, steps, conv_criteria, biased_decoder, metri
 
 
 def _exact_distr(params, chains, device):
-    """params['method'] == "exact": the exact class law of every row (qecmc.exact_class_probabilities, DESIGN.md 4.1j) under the weight of
-    params['noise'] itself -- biased noise with the biased weight, whatever biased_decoder says"""
+    """params['method'] == "exact": the exact class law of every row (qecmc.exact_class_probabilities, DESIGN.md 4.1j, 4.1k) under the weight of
+    params['noise'] itself -- biased noise with the biased weight, whatever biased_decoder says; params['exact_method']: "auto" (default: coset
+    enumeration where it takes the shape, the frontier sweep elsewhere), "enumerate" or "sweep" (qecmc.exact)"""
     from .exact import exact_class_probabilities
     noise = params.get("noise", "depolarizing")
     if _CODES[params["code"]] == L_.TORIC and noise != "depolarizing":
         raise ValueError(f"method exact on the toric code is defined for depolarizing noise, not {noise} (its errors are drawn without a bias)")
     kw = dict(eta=params["eta"]) if noise == "biased" else dict(alpha=params["alpha"]) if noise == "alpha" else {}
     return exact_class_probabilities(params["code"], chains, params["p_error"], size=params["size"], chunk_bits=int(params.get("chunk_bits", 0)),
-                                     device=device, **kw)
+                                     device=device, method=params.get("exact_method", "auto"), **kw)
 
 
 def _corrections_for(code, size, candidates, distr, device):
