@@ -79,7 +79,7 @@ __host__ __device__ inline uint32_t colour_short_at(int Nc, int W, int ncls, uin
 // ladder_wu_kernel: LDS carve-up of one workgroup (dwords): the exchange buffer (W words per rung), records, swap uniforms, histogram, acceptance
 // rows, swap rows, logical masks (rows padded to WV words, + 64: the frame reads a row with all 64 lanes), stop / refill flags, and -- the
 // criterion kernels -- wave 0's per-ladder bookkeeping [kWuBk][64] and the refill mailbox [2][64]
-struct WuLds { int xbuf, rec, swd, hist, thr, swapT, lml, stop, bk, mail, bot, cht, nef, lnb, bot2, skey, sst, total; };
+struct WuLds { int xbuf, rec, swd, hist, thr, swapT, lml, stop, bk, mail, bot, cht, nef, lnb, bot2, skey, sst, frm, total; };
 constexpr int kWuBk = 13;      // tops0, samples, burn, conv_start, conv_streak, sumA lo / hi, sumB lo / hi, state (done | pending << 1 | has << 3),
                                // steps_done, converged, the lane's ladder (QUEUE)
 constexpr int kWuBkAlpha = 17; // ... and the alpha rule's second pair of window sums (n_x + n_y): sumAxy lo / hi, sumBxy lo / hi
@@ -90,10 +90,14 @@ constexpr int kWuHalf = 16;                                                     
 // kernels (-30 tests per step at 29 words).  The criterion kernels keep the tight layout -- W rows, a transfer of a word at or beyond wu_words_min
 // tests the width --: padded rows cost the headline shape's criterion kernel its fourth workgroup per CU (42 KB instead of 39.9) and the route 11 %.
 __host__ __device__ inline int wu_rows(int W, bool conv) { return W > 16 ? kWuHalf : conv ? W : wu_words(W); }
+// The fixed-length kernels of up to 16 words under the depolarizing rule with the unrolled proposal loop (it = 10) keep the top rung's moves of a pick
+// window as frames (wu_frames.hpp): [steps][WV + 1] words behind everything else, private to the top rung's wave, steps = 128 / 10 ladder steps per
+// window.  wu_frame_steps: that number for a kernel of these properties (`it` as in the kernel key: 10 or 0), 0 for a kernel without the buffer.
+__host__ __device__ constexpr int wu_frame_steps(int wv, bool conv, bool alpha, int it) { return !conv && !alpha && wv <= 16 && it == 10 ? 128 / 10 : 0; }
 // (alpha rule: the 9 x 9 table of a proposal's count change as two fp16 numbers, the slots' n_eff attributes as doubles [Nc][64], ln(pz_i / pz_i+1),
 // and -- criterion runs -- slot 0's n_eff record by step parity; shortest: the key of rung 0's new state by step parity [2][2][64] beside it, and the
 // booking wave's per-lane state of the shortest-chain statistics [kShortRows][64])
-__host__ __device__ inline WuLds wu_lds(int Nc, int W, int ncls, int L, bool conv, bool alpha = false, bool shortest = false)
+__host__ __device__ inline WuLds wu_lds(int Nc, int W, int ncls, int L, bool conv, bool alpha = false, bool shortest = false, int frame_steps = 0)
 {
     const int WV = wu_words(W);
     WuLds o;
@@ -114,12 +118,18 @@ __host__ __device__ inline WuLds wu_lds(int Nc, int W, int ncls, int L, bool con
     o.bot2 = o.lnb + (alpha ? 2 * Nc : 0);
     o.skey = o.bot2 + (alpha && conv ? 2 * 64 : 0);
     o.sst = o.skey + (shortest ? 4 * 64 : 0);
-    o.total = o.sst + (shortest ? kShortRows * 64 : 0);
+    o.frm = o.sst + (shortest ? kShortRows * 64 : 0);
+    o.total = o.frm + frame_steps * (WV + 1);
     return o;
 }
-inline size_t wu_lds_bytes(int Nc, int W, int ncls, int L, bool conv, bool alpha, bool shortest = false)
+inline size_t wu_lds_bytes(int Nc, int W, int ncls, int L, bool conv, bool alpha, bool shortest = false, int frame_steps = 0)
 {
-    return sizeof(uint32_t) * (size_t)wu_lds(Nc, W, ncls, L, conv, alpha, shortest).total;
+    return sizeof(uint32_t) * (size_t)wu_lds(Nc, W, ncls, L, conv, alpha, shortest, frame_steps).total;
+}
+// ... of the kernel choose_wave picks for a launch of `iters` proposals per step (statistics launches run the general loop and ask for less: ladder_rs.hip)
+inline size_t wu_plan_lds_bytes(int Nc, int W, int ncls, int L, bool conv, bool alpha, int iters)
+{
+    return wu_lds_bytes(Nc, W, ncls, L, conv, alpha, false, wu_frame_steps(wu_words(W), conv, alpha, iters == 10 ? 10 : 0));
 }
 
 // What the choice reads of a launch (kernel_shape(LadderArgs), plan_host.hpp).  top_acc / lower_acc: the top rung / some rung below it accepts every
@@ -289,9 +299,9 @@ inline bool wu_supported(const KernelShape &s)
 {
     if (s.noise == 2)
         return (s.code == kCodeXzzx || s.code == kCodeRotated) && s.Nc >= 2 && s.Nc <= 16 && s.W <= 8 && s.n_gen <= 1023 && s.iters >= 1 && s.iters <= 128 &&
-               s.f32ok && !s.uset && !s.resume && !s.neff && wu_lds_bytes(s.Nc, s.W, s.ncls, s.L, s.conv, true) <= 160 * 1024;
+               s.f32ok && !s.uset && !s.resume && !s.neff && wu_plan_lds_bytes(s.Nc, s.W, s.ncls, s.L, s.conv, true, s.iters) <= 160 * 1024;
     return s.noise == 0 && s.Nc >= 2 && s.top_acc && !s.lower_acc && (s.W <= 16 || (s.W <= 32 && !s.conv && s.Nc <= 8 && s.code != kCodePlanar)) &&
-           s.n_gen <= 1023 && s.iters >= 1 && s.iters <= 128 && s.swap_fast_ok && !s.uset && wu_lds_bytes(s.Nc, s.W, s.ncls, s.L, s.conv, false) <= 160 * 1024;
+           s.n_gen <= 1023 && s.iters >= 1 && s.iters <= 128 && s.swap_fast_ok && !s.uset && wu_plan_lds_bytes(s.Nc, s.W, s.ncls, s.L, s.conv, false, s.iters) <= 160 * 1024;
 }
 // the padded state width (wu_words); 8 waves per SIMD up to 12 words, 6 at 16 and 32 words and for the alpha rule's criterion kernels (scratch
 // reloaded every step at 8: profiles/r04_crit_occupancy_ab.json); 9 .. 16 rungs: the same code under a launch bound of 1 024 threads; IT = 10: the
@@ -320,7 +330,7 @@ inline bool wave_cascade_once(const KernelShape &s)
 {
     const KernelKey k = choose_wave(s);
     return s.scan == 3 && k.ok() && k.flags == 0 && !k.conv && !k.alpha && k.wv <= 16 && s.Nc >= 5 && s.Nc <= 7 && !(s.tune & 8) &&
-           4 * wu_lds_bytes(s.Nc, s.W, s.ncls, s.L, false, false) <= 160 * 1024;
+           4 * wu_plan_lds_bytes(s.Nc, s.W, s.ncls, s.L, false, false, s.iters) <= 160 * 1024;
 }
 
 // stats = 2, the shortest-chain statistics of PTEQ_alpha_with_shortest: a chooser of their own (no shape the sweeps of stats = 0 / 1 present comes here).

@@ -79,7 +79,7 @@ hipError_t launch_ladder(const LadderArgs &a, hipStream_t stream)
         LadderArgs b = a;
         b.wu_once = wave_cascade_once(kernel_shape(a)) ? 1u : 0u;
         note_kernel(k);
-        return launch_fn(fn, b, stream, (unsigned)((a.N + per - 1) / per), wu_lds_bytes(a.Nc, a.W, a.ncls, a.L, k.conv, k.alpha));
+        return launch_fn(fn, b, stream, (unsigned)((a.N + per - 1) / per), wu_lds_bytes(a.Nc, a.W, a.ncls, a.L, k.conv, k.alpha, false, wu_frame_steps(k.wv, k.conv, k.alpha, k.it)));
     }
     if (k.family == kFamColour) {
         // scan = 2: one ladder per workgroup

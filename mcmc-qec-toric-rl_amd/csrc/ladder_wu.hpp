@@ -17,7 +17,8 @@
 //     window of up to 128 proposals), the per-ladder acceptance uniform 12 bits: one block per TEN proposals per lane; the 44-bit
 //     uniform is completed (a 32-bit refinement word) only when a lane's 12 bits tie with its threshold's;
 //   * the top rung (p = 0.75: every move is accepted, mcmc.py:30) applies its stabilizers blindly and collects its logical
-//     operators -- wave-uniform now -- in one frame that is applied once per step.
+//     operators -- wave-uniform now -- in one frame that is applied once per step.  The lean kernels with iters = 10 build all ten moves
+//     of a step as one frame when the pick window is drawn (wu_frames.hpp): a step of the top rung's wave is one row read and the flush.
 // States move through LDS once per ladder step, when the swap sweep (mcmc.py:94-103) has decided who goes where: every wave
 // writes its rung's W words, and after the cascade reads the W words of the rung whose state it receives.
 //
@@ -35,6 +36,7 @@
 #pragma once
 #include "ladder_kernel.hpp"
 #include "shortest_book.hpp"
+#include "wu_frames.hpp"
 
 namespace qecmc {
 
@@ -64,6 +66,13 @@ template <int WV> constexpr int wu_base() { return WV == 32 ? 48 : 64 - WV; }
 template <int WV> __device__ __forceinline__ void wu_def(typename WuVec<WV>::type &st)
 {
 #define M(PIN) asm volatile("" : "=" PIN(st));
+    WU_BY_WV(M)
+#undef M
+}
+// (the tuple is in its pinned registers here: a value that only passes through -- a join of two paths -- has no other place to be)
+template <int WV> __device__ __forceinline__ void wu_pin(typename WuVec<WV>::type &st)
+{
+#define M(PIN) asm volatile("" : "+" PIN(st));
     WU_BY_WV(M)
 #undef M
 }
@@ -251,7 +260,7 @@ struct WuCtx {
     uint32_t swapc = 0, nsum = 0;      // STATS: the steps in which the pair below this wave's slot traded states, the summed error counts the slot held
 };
 struct WuEnv {
-    uint32_t lds0, thr_off, lml_off, cht_off, slot, grp, lad;    // lad: the lane's first ladder of this launch (kWuDead: none)
+    uint32_t lds0, thr_off, lml_off, cht_off, frm_off, slot, grp, lad;    // frm_off: the top rung's frames (wu_frames.hpp); lad: the lane's first ladder of this launch (kWuDead: none)
     int lane;
     uint64_t chunk_hi;                                  // QUEUE: end of the workgroup's share of the batch
 };
@@ -493,6 +502,10 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
     const int lane = ev.lane;
     constexpr bool top = TOP;
     constexpr bool LEAN = !CONV && !ALPHA && WV <= 16;                            // the kernels whose step tail is the lean one below
+    // the top rung's role of the lean kernels with the unrolled loop: its ten moves of a step are one row of frames built with the pick window
+    // (wu_frames.hpp; the buffer: wu_lds's frm, private to this wave) -- no proposal loop, no picks held across steps
+    constexpr bool FRAME = TOP && wu_frame_steps(WV, CONV, ALPHA, IT) != 0;
+    constexpr uint32_t FW = (uint32_t)WV + 1u;                                    // words of a row: the mask of the WV state words, the class change
     const uint32_t G = a.n_gen;
     const uint32_t m55 = 0x55555555u;
     uint32_t n4 = cx.n4, cls = cx.cls, flag = cx.flag;
@@ -519,9 +532,32 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
     auto refresh = [&]() {
         // lane l: the picks of proposals 2l, 2l + 1 of the window (one Philox block), as descriptor offsets
         const u32x4 b = wu_philox(wi * 64u + (uint64_t)lane, kSubWuPick, grp, kWuPickStream + slot, a.seed_lo, a.seed_hi);
+        if constexpr (FRAME) {
+            // ... and what they do, added to the row of their step (both in one: a step's first proposal is an even one).  A run that starts inside a
+            // window builds the rows in front of its first step too.  Only this wave touches the buffer: its LDS operations execute in program order,
+            // the fences keep the compiler from moving one lane's stores, atomics and loads across another lane's.
+            constexpr uint32_t FS = (uint32_t)wu_frame_steps(WV, CONV, ALPHA, IT);
+            wu_lds_rw const frm = (wu_lds_rw)(uintptr_t)(lds0 + ev.frm_off);
+#pragma unroll
+            for (uint32_t i = 0; i < (FS * FW + 63u) / 64u; ++i) {
+                const uint32_t at = i * 64u + (uint32_t)lane;
+                if (at < FS * FW) frm[at] = 0u;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            if ((uint32_t)lane < FS * (uint32_t)IT / 2u) {
+                wu_lds_rw const row = frm + ((uint32_t)lane / ((uint32_t)IT / 2u)) * FW;
+                auto desc_word = [&](uint32_t g, int i) { return a.wu_desc[(size_t)g * (CODE == kCodeToric ? 8u : 16u) + (uint32_t)i]; };
+                auto lml_word = [&](uint32_t kind, uint32_t pos, int w) { return lml[(kind * (uint32_t)(L + 1) + pos) * (uint32_t)WV + (uint32_t)w]; };
+                auto xor_word = [&](uint32_t w, uint32_t v) { __hip_atomic_fetch_xor(row + w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); };
+                wu_frame_add<CODE, WV>(b.x, b.y, thr16, G, L, desc_word, lml_word, xor_word);
+                wu_frame_add<CODE, WV>(b.z, b.w, thr16, G, L, desc_word, lml_word, xor_word);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        } else {
         const uint32_t g0 = scale_u32(b.y, G), g1 = scale_u32(b.w, G);
         pk = CODE == kCodeToric ? (g0 << 5) | (g1 << 21) : (g0 << 6) | (g1 << 22);
         if (top) { pa0 = b.x; pb0 = b.y; pa1 = b.z; pb1 = b.w; }
+        }
     };
     refresh();
 
@@ -533,6 +569,12 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
         const uint32_t pbase = ws * iters;                                         // the step's first proposal within the window
         [[maybe_unused]] WuAl al{0u, 0u, 0u};
         if constexpr (ALPHA && !top) al.Nb = wu_counts_packed<WV>(st, m55, a.W);   // p_b's counts (mcmc_alpha.py:38-41)
+        if constexpr (FRAME) {
+            // the step's row: lane w < WV takes the mask of word w, the lanes from WV on the class change
+            const uint32_t fv = ((wu_lds_ptr)(uintptr_t)(lds0 + ev.frm_off))[ws * FW + (uint32_t)(lane < WV ? lane : WV)];
+            maskv = fv;
+            cdelta = (uint32_t)__builtin_amdgcn_readlane((int)fv, WV);
+        } else
         for (uint32_t c = 0; c < nch; ++c) {
             [[maybe_unused]] u32x4 ab{0, 0, 0, 0};                                 // this ladder's block of ten 12-bit acceptance uniforms
             if (!top) ab = wu_philox(T * nch + c, kSubWuAcc, syn, slot, a.seed_lo, a.seed_hi);
@@ -553,27 +595,11 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
                 if constexpr (top) {
                     const uint32_t A = (uint32_t)__builtin_amdgcn_readlane((int)((P & 1u) ? pa1 : pa0), (int)(P >> 1));
                     // a logical operator (mcmc.py:23-24; toric_model.py:228-253, xzzx_model.py:340-357) goes into the frame; a stabilizer is applied
-                    // unseen (mcmc.py:30)
+                    // unseen (mcmc.py:30); wu_logical (wu_frames.hpp): the operators that act and what they change of the class
 #define QECMC_WU_LOGICAL()                                                                                                       \
                         const uint32_t B = (uint32_t)__builtin_amdgcn_readlane((int)((P & 1u) ? pb1 : pb0), (int)(P >> 1)); \
                         const int LW = (L + 1) * WV; \
-                        if constexpr (CODE == kCodeToric) { \
-                            const uint32_t op0 = (A >> 14) & 3u, op1 = (A >> 12) & 3u; \
-                            const uint32_t dx0 = (op0 ^ (op0 >> 1)) & 1u, dz0 = op0 >> 1, dx1 = (op1 ^ (op1 >> 1)) & 1u, dz1 = op1 >> 1; \
-                            if (dx0) maskv ^= lml[(((A & 0xFFFu) * (uint32_t)L) >> 12) * WV + lane]; \
-                            if (dz0) maskv ^= lml[LW + (((B >> 21) * (uint32_t)L) >> 11) * WV + lane]; \
-                            if (dx1) maskv ^= lml[2 * LW + ((((B >> 10) & 0x7FFu) * (uint32_t)L) >> 11) * WV + lane]; \
-                            if (dz1) maskv ^= lml[3 * LW + (((B & 0x3FFu) * (uint32_t)L) >> 10) * WV + lane]; \
-                            if (L & 1) cdelta ^= dx0 | (dz0 << 1) | (dx1 << 2) | (dz1 << 3); \
-                        } else { \
-                            const uint32_t op = (A >> 14) & 3u; \
-                            const uint32_t hx = (op ^ (op >> 1)) & 1u, hz = op >> 1; \
-                            const uint32_t xp = hx ? ((A & 0x3FFFu) * (uint32_t)L) >> 14 : 0u, zp = hz ? ((B >> 16) * (uint32_t)L) >> 16 : 0u; \
-                            const uint32_t ax = CODE == kCodeXzzx ? hx : (op & 1u), az = hz; \
-                            if (ax) maskv ^= lml[xp * WV + lane]; \
-                            if (az) maskv ^= lml[LW + zp * WV + lane]; \
-                            cdelta ^= ax | (az << 1); \
-                        }
+                        cdelta ^= wu_logical<CODE>(A, B, L, [&](uint32_t kind, uint32_t pos) { maskv ^= lml[kind * LW + pos * WV + lane]; });
                     if constexpr (WV == 32) {
                         // (32 words: a logical proposal passes through the stabilizer's XOR too, with zeros, so that the state tuple has ONE path
                         // through the loop body -- a branch around an asm statement that updates the tuple makes the compiler merge two copies of it
@@ -719,7 +745,7 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
         __syncthreads();
         uint32_t mine;
         if (once) {
-            // the cascade once per workgroup: the top rung's wave -- its step is the shortest -- walks the pairs top-down and leaves in rec[i] the
+            // the cascade once per workgroup: the top rung's wave walks the pairs top-down and leaves in rec[i] the
             // record slot i now holds (rec[i + 1] is dead once pair i is decided: `car` has it); behind a third barrier a wave reads its slot's
             if constexpr (TOP) {
                 wu_lds_rw pr = recl + (NC - 2) * 64, px = swdl + (NC - 2) * 64;
@@ -883,8 +909,8 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
                 }
             }
             if constexpr (CONV && TOP) {
-                // ---- ladder + PTEQ bookkeeping with the error_based criterion (decoders.py:60-82,93-105), by the wave of the TOP rung -- the
-                // one with the shortest step -- and one step behind: rung 0's wave leaves the record that landed in rung 0 at step tb in LDS
+                // ---- ladder + PTEQ bookkeeping with the error_based criterion (decoders.py:60-82,93-105), by the wave of the TOP rung
+                // and one step behind: rung 0's wave leaves the record that landed in rung 0 at step tb in LDS
                 // (by step parity), and this wave books it behind the barrier of step tb + 1, off the critical path of the workgroup.  The
                 // per-ladder state lives in LDS between steps.
                 auto book = [&](uint64_t tb, uint64_t Tb) {

@@ -7,7 +7,7 @@
     const int nthreads = NC * 64;
     const int tid = (int)threadIdx.x, lane = tid & 63;
     const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);      // this wave's rung (fixed: states move)
-    const WuLds o = wu_lds(NC, W, ncls, L, CONV, ALPHA, SHORT);
+    const WuLds o = wu_lds(NC, W, ncls, L, CONV, ALPHA, SHORT, wu_frame_steps(WV, CONV, ALPHA, IT));
     uint32_t *xbuf = lds + o.xbuf, *rec = lds + o.rec, *hist = lds + o.hist, *thrT = lds + o.thr;
     uint32_t *swapT = lds + o.swapT, *lml = lds + o.lml;
     volatile uint32_t *stopf = lds + o.stop;
@@ -93,13 +93,15 @@
     if constexpr (ALPHA) { const uint32_t c3 = wu_counts_packed<WV>(st, 0x55555555u); nef0 = ((c3 >> 10) & 1023u) | ((c3 >> 20) << 16); }   // Chain_alpha.__init__, mcmc_alpha.py:18-22
     WuCtx cx{n4, cls, flag, tops0, 0u, 0u, 0u, 0u, nef0};
     WuEnv ev;
-    ev.lds0 = lds0; ev.thr_off = (uint32_t)((o.thr + (int)slot * 18) * 4); ev.lml_off = (uint32_t)(o.lml * 4); ev.cht_off = (uint32_t)(o.cht * 4); ev.slot = slot;
+    ev.lds0 = lds0; ev.thr_off = (uint32_t)((o.thr + (int)slot * 18) * 4); ev.lml_off = (uint32_t)(o.lml * 4); ev.cht_off = (uint32_t)(o.cht * 4); ev.frm_off = (uint32_t)(o.frm * 4); ev.slot = slot;
     ev.grp = (a.first_syndrome >> 6) + (uint32_t)blockIdx.x;         // the wavefront's shared picks: its position in the grid
     ev.lad = live ? (uint32_t)ladder : kWuDead;
     ev.lane = lane; ev.chunk_hi = s1;
     // (the two roles are separate loops: they meet at the step's barriers)
+    if constexpr (wu_frame_steps(WV, CONV, ALPHA, IT) != 0) wu_pin<WV>(st);
     if (top) wu_run<CODE, WV, CONV, QUEUE, true, IT, ALPHA, STATS, SHORT>(a, st, cx, ev);
     else wu_run<CODE, WV, CONV, QUEUE, false, IT, ALPHA, STATS, SHORT>(a, st, cx, ev);
+    if constexpr (wu_frame_steps(WV, CONV, ALPHA, IT) != 0) wu_pin<WV>(st);
     if constexpr (QUEUE) return;                                      // (every ladder wrote its results when it ended)
     if constexpr (STATS) {
         // qecmc_plan_set_stats: this wave's two counters of the lane's ladder -- pair slot - 1 (mcmc.py:97-99) and the slot's summed error counts

@@ -163,7 +163,7 @@ inline Refusal plan_host(const qecmc_params &p, HostPlan &hp)
         hp.xyz_lut = count_change_table(patterns);
     }
     if (p.scan != QECMC_SCAN_COLOUR) {     // (scan = colour: its LDS holds the swap thresholds, known further down)
-        hp.lds_bytes = p.scan == QECMC_SCAN_WAVE ? wu_lds_bytes(Nc, W, ncls, L, p.conv_mode != 0, alpha)
+        hp.lds_bytes = p.scan == QECMC_SCAN_WAVE ? wu_plan_lds_bytes(Nc, W, ncls, L, p.conv_mode != 0, alpha, p.iters)
                                                  : ladder_lds_bytes(Nc, W, ncls, ladder_gen_dwords(p.code, p.noise, p.scan, a.n_gen, Nc, nq, a.n_types));
         if (hp.lds_bytes > 160 * 1024)
             return refuse_params(QECMC_ERR_UNSUPPORTED, "L=%d Nc=%d needs %zu B of LDS per workgroup (> 160 KiB)", L, Nc, hp.lds_bytes);

@@ -10,6 +10,7 @@
 #include "plan_host.hpp"
 #include "syndrome_lift.hpp"
 #include "tables.hpp"
+#include "wu_frames.hpp"
 
 #include <cstdio>
 #include <cstring>
@@ -294,5 +295,26 @@ int qt_class_sweep(int code, int L, uint64_t N, const uint8_t *chains, const dou
     if (p.refusal.code) return p.refusal.code;
     sweep::sweep_host(p, N, chains, w, z, cls);
     return 0;
+}
+// the top rung's frames of a pick window (wu_frames.hpp) for an accepted scan = wave block, from the window's 64 pick blocks picks[64][4]: the plan's
+// descriptors and logical masks (rows padded to the kernel's WV words, as the kernel stages them), thr16 from the plan's thr_logical as wu_run forms it.
+// Writes frames[128 / iters][WV + 1] and returns WV; -1: refused, an unsupported width, or too small a buffer
+int qt_wave_frames(const qecmc_params *p, const uint32_t *picks, uint32_t *frames, int cap)
+{
+    HostPlan hp;
+    if (validate_params(p).code || plan_host(*p, hp).code || p->scan != QECMC_SCAN_WAVE) return -1;
+    const LadderArgs &a = hp.args;
+    const int L = a.L, W = a.W, WV = wu_words(W);
+    const uint32_t steps = 128u / a.iters, thr16 = (uint32_t)((a.thr_logical + 65535u) >> 16);
+    if (WV > 16 || (int)(steps * (uint32_t)(WV + 1)) > cap) return -1;
+    std::vector<uint32_t> lml((size_t)4 * (L + 1) * WV, 0u);
+    for (int row = 0; row < 4 * (L + 1); ++row)
+        for (int w = 0; w < W; ++w) lml[(size_t)row * WV + w] = hp.lmask[(size_t)row * W + w];
+#define QT_FRAMES(CODE, WVC) if (a.code == CODE && WV == WVC) wu_build_frames<CODE, WVC>(picks, a.iters, thr16, a.n_gen, L, hp.wu_desc.data(), lml.data(), frames);
+#define QT_FRAMES_W(CODE) QT_FRAMES(CODE, 4) QT_FRAMES(CODE, 8) QT_FRAMES(CODE, 12) QT_FRAMES(CODE, 16)
+    QT_FRAMES_W(kCodeToric) QT_FRAMES_W(kCodeXzzx) QT_FRAMES_W(kCodeRotated) QT_FRAMES_W(kCodePlanar)
+#undef QT_FRAMES_W
+#undef QT_FRAMES
+    return WV;
 }
 }
