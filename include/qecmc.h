@@ -253,9 +253,29 @@ int qecmc_coset_enumerate(int code, int L, uint64_t N, const uint8_t *chains, in
  * Additive: QECMC_ABI_VERSION stays.  Refused before a device is looked for: a NULL chains / w / z_out, a weight that is not finite and
  * > 0 or a (code, L) the library does not know with QECMC_ERR_INVALID; a (code, L) without a class move (the toric code at even L) or a
  * plan wider than 13 with QECMC_ERR_UNSUPPORTED -- which leaves toric L = 3, planar L = 3 .. 6 and xzzx / rotated L = 3, 5, 7, 9.
- * N == 0 succeeds.  Host pointers only. */
+ * N == 0 succeeds.  Host pointers only.  (qecmc_class_sweep_cut below takes the next shapes.) */
 int qecmc_class_sweep_info(int code, int L, int32_t *width, int32_t *ncls, int32_t *nq, int32_t *n_ops);
 int qecmc_class_sweep(int code, int L, uint64_t N, const uint8_t *chains, const double *w, double *z_out, int32_t *class_out);
+
+/* ---- the frontier sweep past one LDS state vector: cut-set conditioning (csrc/class_sweep_cut.hpp) ------------------------------------
+ * The arguments and the result of qecmc_class_sweep, for plans it refuses as too wide.  n_held generators are held out of the elimination:
+ * for every assignment h of them the class representative is multiplied by the held generators h names and the rest is swept as before,
+ * over a frontier of `width` <= lds_width; z = 2^-(G - rank) * the sum of the 2^n_held partial sweeps, taken in a fixed order.  One (class,
+ * syndrome) is 2^n_held workgroups and one workgroup that sums them; a launch covers a bounded group of syndromes, whatever N.
+ * lds_width: the widest state vector a workgroup may hold, 2 .. 14 (2^lds_width doubles of LDS; 14 is 128 KiB, one workgroup per CU), or
+ * 0 for the default: 13 where nothing is held then, 14 where that holds nothing, else 13.
+ * qecmc_class_sweep_cut_info: the frontier of the uncut plan, the cut plan's width, held generators, classes, qubits and ops -- every
+ * pointer nullable --, on the host alone.
+ * Additive: QECMC_ABI_VERSION stays.  Refused before a device is looked for: what qecmc_class_sweep refuses with QECMC_ERR_INVALID, and an
+ * lds_width outside {0} and [2, 14]; a (code, L) without a class move (the toric code at even L) or a plan that would hold more than 12
+ * generators with QECMC_ERR_UNSUPPORTED -- which adds toric L = 5, planar L = 7 and xzzx / rotated L = 11 to qecmc_class_sweep's shapes;
+ * toric L >= 7, planar L >= 8 and xzzx / rotated L >= 13 stay refused.  A device that does not grant 128 KiB of LDS to a workgroup
+ * answers QECMC_ERR_UNSUPPORTED at width 14.  Where n_held is 0 and width <= 13 the result is qecmc_class_sweep's, bit for bit.
+ * N == 0 succeeds.  Host pointers only. */
+int qecmc_class_sweep_cut_info(int code, int L, int lds_width, int32_t *full_width, int32_t *width, int32_t *n_held, int32_t *ncls,
+                               int32_t *nq, int32_t *n_ops);
+int qecmc_class_sweep_cut(int code, int L, uint64_t N, const uint8_t *chains, const double *w, int lds_width, double *z_out,
+                          int32_t *class_out);
 
 /* ---- chain / ladder on caller-owned state (host pointers) ----------------- */
 

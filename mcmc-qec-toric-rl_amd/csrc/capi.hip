@@ -22,6 +22,7 @@
 #include "stencil_bytes.hpp"
 #include "corrections.hpp"
 #include "class_sweep.hpp"
+#include "class_sweep_cut.hpp"
 #include "enumerate.hpp"
 #include "syndrome_lift.hpp"
 #include "tables.hpp"
@@ -664,6 +665,62 @@ int qecmc_class_sweep(int code, int L, uint64_t N, const uint8_t *chains, const 
         HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * rep_words * sizeof(uint32_t), hipMemcpyHostToDevice));
         a.S = (uint32_t)here;
         HIP_TRY(launch_class_sweep(a, dops.as<uint32_t>(), dreps.as<uint32_t>(), dz.as<double>(), 0));
+        HIP_TRY(hipMemcpy(z_out + first * (uint64_t)p.ncls, dz.p, (size_t)here * p.ncls * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- the frontier sweep past one LDS state vector (class_sweep_cut.hpp)
+int qecmc_class_sweep_cut_info(int code, int L, int lds_width, int32_t *full_width, int32_t *width, int32_t *n_held, int32_t *ncls, int32_t *nq,
+                               int32_t *n_ops)
+{
+    const sweep::CutPlan cp = sweep::build_cut_plan(code, L, lds_width);
+    if (int rc = report(cp.plan.refusal)) return rc;
+    if (full_width) *full_width = cp.full_width;
+    if (width) *width = cp.plan.width;
+    if (n_held) *n_held = cp.n_held;
+    if (ncls) *ncls = cp.plan.ncls;
+    if (nq) *nq = cp.plan.nq;
+    if (n_ops) *n_ops = cp.plan.n_ops;
+    return 0;
+}
+
+int qecmc_class_sweep_cut(int code, int L, uint64_t N, const uint8_t *chains, const double *w, int lds_width, double *z_out, int32_t *class_out)
+{
+    if (!chains || !w || !z_out) return fail(QECMC_ERR_INVALID, "qecmc_class_sweep_cut: NULL buffer");
+    if (N > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "N=%llu syndromes exceed 32 bits", (unsigned long long)N);
+    if (int rc = report(sweep::check_weights(w))) return rc;
+    const sweep::CutPlan cp = sweep::build_cut_plan(code, L, lds_width);
+    const sweep::Plan &p = cp.plan;
+    if (int rc = report(p.refusal)) return rc;
+    if (int rc = use_device(0)) return rc;
+    if (N == 0) return 0;
+    if (class_sweep_cut_allow_lds(p.width) != hipSuccess)
+        return fail(QECMC_ERR_UNSUPPORTED, "this device does not grant a workgroup the %u bytes of LDS a state vector of width %d takes", p.carve.bytes, p.width);
+    const uint32_t group = sweep::cut_launch_group(N, p.ncls, cp.n_held);
+    const size_t rep_words = (size_t)p.ncls * p.W, partials = (size_t)p.ncls << cp.n_held;   // of one syndrome
+    std::vector<uint32_t> reps((size_t)group * rep_words);
+    DevBuf dops, dheld, dreps, dpart, dz;
+    HIP_TRY(dops.alloc(p.ops.size() * sizeof(uint32_t)));
+    HIP_TRY(dheld.alloc(cp.held_words.size() * sizeof(uint32_t)));
+    HIP_TRY(dreps.alloc(reps.size() * sizeof(uint32_t)));
+    HIP_TRY(dpart.alloc((size_t)group * partials * sizeof(double)));            // kCutGridMax doubles at most; dirty: every partial is written before it is read
+    HIP_TRY(dz.alloc((size_t)group * p.ncls * sizeof(double)));
+    HIP_TRY(hipMemcpy(dops.p, p.ops.data(), p.ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (cp.n_held) HIP_TRY(hipMemcpy(dheld.p, cp.held_words.data(), cp.held_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    SweepCutArgs a = {};
+    a.ncls = p.ncls; a.W = p.W; a.width = p.width; a.n_ops = p.n_ops; a.n_held = cp.n_held; a.scale = p.scale;
+    sweep::weights_xz(w, a.wxz);
+    // the host loops over groups of syndromes: no launch, and no device block, grows with the batch
+    for (uint64_t first = 0; first < N; first += group) {
+        const uint64_t here = N - first < group ? N - first : group;
+        for (uint64_t s = 0; s < here; ++s) {
+            const int cls = sweep::class_representatives(p, chains + (first + s) * (uint64_t)p.nq, reps.data() + s * rep_words);
+            if (class_out) class_out[first + s] = cls;
+        }
+        HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * rep_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+        a.S = (uint32_t)here;
+        HIP_TRY(launch_class_sweep_cut(a, dops.as<uint32_t>(), dheld.as<uint32_t>(), dreps.as<uint32_t>(), dpart.as<double>(), dz.as<double>(), 0));
         HIP_TRY(hipMemcpy(z_out + first * (uint64_t)p.ncls, dz.p, (size_t)here * p.ncls * sizeof(double), hipMemcpyDeviceToHost));
     }
     return 0;

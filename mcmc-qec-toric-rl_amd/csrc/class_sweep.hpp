@@ -22,7 +22,7 @@
 // Refused, before a device is looked for: QECMC_ERR_INVALID for a (code, L) check_code_L() does not know; QECMC_ERR_UNSUPPORTED for a (code, L) without
 // a class move (the toric code at even L) and for a plan wider than kMaxWidth -- what lds_carve(), which the launch calls too, fits into the LDS of
 // one workgroup.  Accepted today: toric L = 3; planar L = 3 .. 6; xzzx / rotated L = 3, 5, 7, 9.  Width 14 (xzzx / rotated L = 11, planar L = 7) would
-// need 128 KiB in place and is refused by name.
+// need 128 KiB in place and is refused by name here; class_sweep_cut.hpp takes it, and the toric code at L = 5, through build_plan_held().
 #pragma once
 #include "../../include/qecmc.h"
 
@@ -106,7 +106,16 @@ inline int generator_rank(const correct::Table &ct)
     return (int)rows.size();
 }
 
-inline Plan build_plan(int code, int L)
+// What build_plan_held() saw on the way, for a planner that holds generators out (class_sweep_cut.hpp): where in the stream every generator is
+// introduced and forgotten (-1: held, or never met), and the first op at which the number of live slots reaches its peak.
+struct Trace {
+    std::vector<int> intro_at, forget_at;
+    int first_peak_op = -1;
+};
+
+// build_plan() with the generators g that have held[g] != 0 left out of the elimination: they get no INTRO and no FORGET and no CLOSE names them; a
+// qubit they alone touch is still closed, with no pair.  `held` empty: nothing held.  A plan wider than max_width is refused by name and not encoded.
+inline Plan build_plan_held(int code, int L, const std::vector<char> &held, int max_width, Trace *trace)
 {
     Plan p;
     p.code = code; p.L = L;
@@ -122,24 +131,28 @@ inline Plan build_plan(int code, int L)
     struct Touch { int gen; uint32_t xz; };
     std::vector<std::vector<Touch>> touch((size_t)p.nq);
     std::vector<int> open((size_t)p.n_gen, 0);
+    std::vector<char> is_qubit((size_t)p.nq, 0);
     for (int g = 0; g < p.n_gen; ++g)
         for (int i = 0; i < 4; ++i) {
             const uint32_t e = (ct.gen[(size_t)(2 * g + (i >> 1))] >> ((i & 1) * 16)) & 0xFFFFu, pauli = e & 3u, site = e >> 2;
             if (pauli == 0u) continue;
             if ((int)site >= p.nq) { p.refusal = refuse_params(QECMC_ERR_UNSUPPORTED, "internal: generator %d of code %d at L=%d leaves the state", g, code, L); return p; }
+            is_qubit[site] = 1;
+            if ((size_t)g < held.size() && held[(size_t)g]) continue;
             touch[site].push_back({g, pauli_to_xz(pauli)});
             ++open[(size_t)g];
         }
     std::vector<int> order;
     for (int q = 0; q < p.nq; ++q) {
         if (touch[(size_t)q].size() > 4) { p.refusal = refuse_params(QECMC_ERR_UNSUPPORTED, "internal: qubit %d of code %d at L=%d is touched by more than four generators", q, code, L); return p; }
-        if (!touch[(size_t)q].empty()) order.push_back(q);                      // (a cell no generator touches holds no qubit)
+        if (is_qubit[(size_t)q]) order.push_back(q);                            // (a cell no generator touches holds no qubit)
     }
     for (size_t i = 1; i < order.size(); ++i)                                   // insertion sort by the cell's key
         for (size_t j = i; j > 0 && cell_key(code, L, order[j - 1]) > cell_key(code, L, order[j]); --j) { const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
     p.n_qubits = (int)order.size();
     // ---- the stream.  Slots beyond kMaxWidth are still handed out, so a refusal can name the width; such a plan is not encoded.
     struct Op { uint32_t kind, slot, qubit, pairs, pair[4]; std::vector<char> live; };
+    if (trace) { trace->intro_at.assign((size_t)p.n_gen, -1); trace->forget_at.assign((size_t)p.n_gen, -1); trace->first_peak_op = -1; }
     std::vector<int> slot_of((size_t)p.n_gen, -1);
     std::vector<char> used;
     std::vector<Op> stream;
@@ -150,9 +163,10 @@ inline Plan build_plan(int code, int L)
             size_t s = 0;
             while (s < used.size() && used[s]) ++s;                             // the lowest free slot
             if (s == used.size()) used.push_back(0);
+            if (trace) trace->intro_at[(size_t)t.gen] = (int)stream.size();
             stream.push_back({kIntro, (uint32_t)s, 0u, 0u, {0u, 0u, 0u, 0u}, used});
             used[s] = 1; slot_of[(size_t)t.gen] = (int)s;
-            if (++live > p.width) p.width = live;
+            if (++live > p.width) { p.width = live; if (trace) trace->first_peak_op = (int)stream.size() - 1; }
         }
         Op close = {kClose, 0u, (uint32_t)q, 0u, {0u, 0u, 0u, 0u}, used};
         for (const Touch &t : touch[(size_t)q]) close.pair[close.pairs++] = ((uint32_t)slot_of[(size_t)t.gen] & 15u) | (t.xz << 4);
@@ -161,13 +175,14 @@ inline Plan build_plan(int code, int L)
             if (--open[(size_t)t.gen]) continue;
             const uint32_t s = (uint32_t)slot_of[(size_t)t.gen];
             used[s] = 0; --live;
+            if (trace) trace->forget_at[(size_t)t.gen] = (int)stream.size();
             stream.push_back({kForget, s, 0u, 0u, {0u, 0u, 0u, 0u}, used});
         }
     }
     p.n_ops = (int)stream.size();
-    if (p.width > kMaxWidth) {
+    if (p.width > max_width) {
         p.refusal = refuse_params(QECMC_ERR_UNSUPPORTED, "the frontier of code %d at L=%d is %d generators wide: a state vector of 2^%d doubles does not fit the %u bytes of "
-                                                         "LDS a workgroup sweeps in (width %d at most)", code, L, p.width, p.width, kLdsBudget, kMaxWidth);
+                                                         "LDS a workgroup sweeps in (width %d at most)", code, L, p.width, p.width, lds_carve(max_width).bytes, max_width);
         return p;
     }
     if (live != 0) { p.refusal = refuse_params(QECMC_ERR_UNSUPPORTED, "internal: the plan of code %d at L=%d ends with %d live slots", code, L, live); return p; }
@@ -189,6 +204,9 @@ inline Plan build_plan(int code, int L)
     p.carve = lds_carve(p.width);
     return p;
 }
+
+inline Plan build_plan(int code, int L) { return build_plan_held(code, L, {}, kMaxWidth, nullptr); }
+static_assert(lds_carve(kMaxWidth).bytes == kLdsBudget, "build_plan's refusal names the budget");
 
 // the four weights: finite and > 0
 inline Refusal check_weights(const double *w)

@@ -4,6 +4,7 @@
 // (kernel_choice.hpp) which kernel every shape runs, and plan_host() (plan_host.hpp) which plan -- or which refusal -- a parameter block gets.
 // Not part of libqecmc.so.
 #include "class_sweep.hpp"
+#include "class_sweep_cut.hpp"
 #include "corrections.hpp"
 #include "enumerate.hpp"
 #include "kernel_choice.hpp"
@@ -294,6 +295,44 @@ int qt_class_sweep(int code, int L, uint64_t N, const uint8_t *chains, const dou
     const sweep::Plan p = sweep::build_plan(code, L);
     if (p.refusal.code) return p.refusal.code;
     sweep::sweep_host(p, N, chains, w, z, cls);
+    return 0;
+}
+// the cut-set sweep (class_sweep_cut.hpp).  qt_class_sweep_cut_info: full_width, width, n_held, ncls, nq, n_ops, rank, n_gen, the LDS bytes of a
+// workgroup, kMaxHeld, kCutMaxWidth, the lds_width the plan was built for -- the QECMC_ERR_* code of build_cut_plan()'s refusal;
+// qt_class_sweep_cut_ops: the op stream, -1 where refused; qt_class_sweep_cut_held: the held generators' table indices int32[n_held] and packed words
+// uint32[n_held][W] -> n_held, -1 where refused or too small a buffer; qt_class_sweep_cut_group: the syndromes of one launch; qt_class_sweep_cut: the
+// host twin of qecmc_class_sweep_cut behind the same host checks
+int qt_class_sweep_cut_info(int code, int L, int lds_width, int32_t *out12, char *msg, int msg_cap)
+{
+    const sweep::CutPlan cp = sweep::build_cut_plan(code, L, lds_width);
+    if (msg && msg_cap > 0) std::snprintf(msg, (size_t)msg_cap, "%s", cp.plan.refusal.msg.c_str());
+    const int32_t v[12] = {cp.full_width, cp.plan.width, cp.n_held, cp.plan.ncls, cp.plan.nq, cp.plan.n_ops, cp.plan.rank, cp.plan.n_gen,
+                           (int32_t)sweep::lds_carve(cp.plan.width).bytes, sweep::kMaxHeld, sweep::kCutMaxWidth, cp.lds_width};
+    if (out12) std::memcpy(out12, v, sizeof v);
+    return cp.plan.refusal.code;
+}
+int qt_class_sweep_cut_ops(int code, int L, int lds_width, uint32_t *out, int cap)
+{
+    const sweep::CutPlan cp = sweep::build_cut_plan(code, L, lds_width);
+    if (cp.plan.refusal.code) return -1;
+    return put(cp.plan.ops, out, cap);
+}
+int qt_class_sweep_cut_held(int code, int L, int lds_width, int32_t *index, uint32_t *words, int cap_words)
+{
+    const sweep::CutPlan cp = sweep::build_cut_plan(code, L, lds_width);
+    if (cp.plan.refusal.code || (int)cp.held_words.size() > cap_words) return -1;
+    for (int j = 0; j < cp.n_held; ++j) index[j] = cp.held[(size_t)j];
+    if (!cp.held_words.empty()) std::memcpy(words, cp.held_words.data(), cp.held_words.size() * sizeof(uint32_t));
+    return cp.n_held;
+}
+uint32_t qt_class_sweep_cut_group(uint64_t N, int ncls, int n_held) { return sweep::cut_launch_group(N, ncls, n_held); }
+int qt_class_sweep_cut(int code, int L, uint64_t N, const uint8_t *chains, const double *w, int lds_width, double *z, int32_t *cls)
+{
+    if (!chains || !w || !z) return QECMC_ERR_INVALID;
+    if (const Refusal r = sweep::check_weights(w); r.code) return r.code;
+    const sweep::CutPlan cp = sweep::build_cut_plan(code, L, lds_width);
+    if (cp.plan.refusal.code) return cp.plan.refusal.code;
+    sweep::sweep_cut_host(cp, N, chains, w, z, cls);
     return 0;
 }
 // the top rung's frames of a pick window (wu_frames.hpp) for an accepted scan = wave block, from the window's 64 pick blocks picks[64][4]: the plan's

@@ -4,7 +4,10 @@ the whole stabilizer group, and from it the class weights Z_c = sum hist[c] * w(
 counts -- the maximum-likelihood decoder of the small codes (toric L = 3, planar L = 3, 4, xzzx / rotated L = 3, 5).
 
 The same law by a frontier sweep (qecmc_class_sweep): the class weights themselves, float64, for four per-qubit weights of I, X, Y
-and Z, by variable elimination across the lattice -- which reaches xzzx / rotated L = 9 and planar L = 6."""
+and Z, by variable elimination across the lattice -- which reaches xzzx / rotated L = 9 and planar L = 6.
+
+The sweep past one LDS state vector (qecmc_class_sweep_cut): generators held out of the elimination and summed over by workgroups --
+which reaches the toric code at L = 5, and with a 128 KiB state vector xzzx / rotated L = 11 and planar L = 7."""
 import ctypes as C
 
 import numpy as np
@@ -85,6 +88,33 @@ def class_sweep(code, chains, weights, size=None, device=0):
     return dict(Z=z, cls=cls, width=info["width"])
 
 
+def sweep_cut_info(code, size, lds_width=0):
+    """dict(full_width, width, held, ncls, nq, n_ops) of the cut-set plan of one (code, size) for a state vector of at most 2^lds_width doubles in LDS
+    (0: the library's default), from the host half of the library alone; raises QecmcError where the plan is refused"""
+    v = [C.c_int32() for _ in range(6)]
+    L_.check(L_.lib().qecmc_class_sweep_cut_info(_CODES.get(code, code), int(size), int(lds_width), *[C.byref(x) for x in v]))
+    return dict(zip(("full_width", "width", "held", "ncls", "nq", "n_ops"), (int(x.value) for x in v)))
+
+
+def class_sweep_cut(code, chains, weights, size=None, lds_width=0):
+    """class_sweep past one LDS state vector (qecmc_class_sweep_cut): `held` generators are held out of the elimination and summed over
+    by 2^held workgroups per (class, syndrome) -- the toric code at L = 5, and with nothing held xzzx / rotated L = 11 and planar L = 7 at width 14.
+    lds_width: the widest state vector a workgroup may hold, 2 .. 14, 0: the default.
+    Returns dict(Z float64[N, ncls], cls int32[N], width: the widest frontier of the cut plan, held: the number of held generators)."""
+    code = _CODES.get(code, code)
+    flat, L = _as_chains(code, chains, size)
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.shape != (4,):
+        raise ValueError(f"weights of shape {w.shape}: the four weights of I, X, Y and Z")
+    info = sweep_cut_info(code, L, lds_width)
+    n = flat.shape[0]
+    z = np.zeros((n, info["ncls"]), dtype=np.float64)
+    cls = np.zeros(n, dtype=np.int32)
+    f64p = C.POINTER(C.c_double)
+    L_.check(L_.lib().qecmc_class_sweep_cut(code, L, n, L_.u8(flat), w.ctypes.data_as(f64p), int(lds_width), z.ctypes.data_as(f64p), L_.i32(cls)))
+    return dict(Z=z, cls=cls, width=info["width"], held=info["held"])
+
+
 def class_weights(hist, weight):
     """Z[..., c] = sum over (n_xy, n_z) of hist[..., c, n_xy, n_z] * weight(n_xy, n_z): weight is broadcast over the grid of counts, float64"""
     hist = np.asarray(hist)
@@ -128,34 +158,49 @@ def alpha_w4(pz_tilde, alpha):
     return np.array([1.0, pz_tilde ** alpha, pz_tilde ** alpha, pz_tilde])
 
 
+_METHODS = ("auto", "enumerate", "sweep", "cut")
+
+
 def resolve_method(code, size, method="auto"):
     """what exact_class_probabilities runs at one (code, size): "auto" is the enumerator wherever it accepts the shape -- so a call that worked
-    before the sweep existed returns what it returned -- and the sweep where the enumerator answers QECMC_ERR_UNSUPPORTED; any other answer is the
-    enumerator's to report.  From the host half of the library alone."""
-    if method not in ("auto", "enumerate", "sweep"):
+    before the sweep existed returns what it returned --, the sweep where the enumerator answers QECMC_ERR_UNSUPPORTED, and the cut-set sweep where
+    the sweep answers QECMC_ERR_UNSUPPORTED too and the cut plan is accepted; any other answer is the enumerator's to report.  From the host half of
+    the library alone."""
+    if method not in _METHODS:
         raise ValueError(f"method={method!r}")
     if method != "auto":
         return method
-    rc = L_.lib().qecmc_coset_enumerate_info(_CODES.get(code, code), int(size), None, None, None, None)
-    return "sweep" if rc == -4 else "enumerate"
+    code = _CODES.get(code, code)
+    if L_.lib().qecmc_coset_enumerate_info(code, int(size), None, None, None, None) != -4:
+        return "enumerate"
+    if L_.lib().qecmc_class_sweep_info(code, int(size), None, None, None, None) == -4 and \
+            L_.lib().qecmc_class_sweep_cut_info(code, int(size), 0, None, None, None, None, None, None) == 0:
+        return "cut"
+    return "sweep"
 
 
 def exact_class_probabilities(code, chains, p, eta=None, alpha=None, hist=None, method="auto", **enumerator_kw):
     """float64[N, ncls]: the exact class law of every syndrome under depolarizing noise p, Z-biased noise (p, eta) or the alpha model (p is pz_tilde).
     method "enumerate": by coset_enumerator, which takes the keywords; "sweep": by class_sweep (of the keywords it takes size and device; chunk_bits
-    means nothing to it); "auto" (default): the enumerator wherever it accepts the (code, size), the sweep elsewhere.
+    means nothing to it); "cut": by class_sweep_cut (size, and lds_width); "auto" (default): the enumerator wherever it accepts the (code, size), the
+    sweep where it does not, the cut-set sweep where neither does.
     hist: a histogram already enumerated (coset_enumerator(...)['hist']) -- chains is then not looked at, and the method is the enumerator's."""
     if eta is not None and alpha is not None:
         raise ValueError("eta and alpha name two noise models")
-    if method not in ("auto", "enumerate", "sweep"):
+    if method not in _METHODS:
         raise ValueError(f"method={method!r}")
     if hist is None:
         method = resolve_method(code, _as_chains(_CODES.get(code, code), chains, enumerator_kw.get("size"))[1], method)
-    if hist is None and method == "sweep":
+    if hist is None and method in ("sweep", "cut"):
         if "chunks" in enumerator_kw:
             raise ValueError("chunks= is the enumerator's: the sweep has no partial sums")
         w4 = alpha_w4(p, alpha) if alpha is not None else biased_w4(p, eta) if eta is not None else depolarizing_w4(p)
-        z = class_sweep(code, chains, w4, size=enumerator_kw.get("size"), device=enumerator_kw.get("device", 0))["Z"]
+        if method == "cut":
+            if int(enumerator_kw.get("device", 0)) != 0:
+                raise ValueError("class_sweep_cut runs on device 0: the library has no device-pointer form of it yet")
+            z = class_sweep_cut(code, chains, w4, size=enumerator_kw.get("size"), lds_width=enumerator_kw.get("lds_width", 0))["Z"]
+        else:
+            z = class_sweep(code, chains, w4, size=enumerator_kw.get("size"), device=enumerator_kw.get("device", 0))["Z"]
     else:
         if hist is None:
             hist = coset_enumerator(code, chains, **enumerator_kw)["hist"]

@@ -215,9 +215,9 @@ def _pteq_decode(params, init, seed, steps, conv_criteria, biased_decoder, metri
 
 
 def _exact_distr(params, chains, device):
-    """params['method'] == "exact": the exact class law of every row (qecmc.exact_class_probabilities, DESIGN.md 4.1j, 4.1k) under the weight of
+    """params['method'] == "exact": the exact class law of every row (qecmc.exact_class_probabilities, DESIGN.md 4.1j, 4.1k, 4.1l) under the weight of
     params['noise'] itself -- biased noise with the biased weight, whatever biased_decoder says; params['exact_method']: "auto" (default: coset
-    enumeration where it takes the shape, the frontier sweep elsewhere), "enumerate" or "sweep" (qecmc.exact)"""
+    enumeration where it takes the shape, the frontier sweep elsewhere, the cut-set sweep where both refuse), "enumerate", "sweep" or "cut" (qecmc.exact)"""
     from .exact import exact_class_probabilities
     noise = params.get("noise", "depolarizing")
     if _CODES[params["code"]] == L_.TORIC and noise != "depolarizing":
