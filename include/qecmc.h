@@ -277,6 +277,26 @@ int qecmc_class_sweep_cut_info(int code, int L, int lds_width, int32_t *full_wid
 int qecmc_class_sweep_cut(int code, int L, uint64_t N, const uint8_t *chains, const double *w, int lds_width, double *z_out,
                           int32_t *class_out);
 
+/* ---- the frontier sweep on a state vector tiled over HBM (csrc/class_sweep_tiled.hpp) -------------------------------------------------
+ * The arguments and the result of qecmc_class_sweep_cut, for frontiers no LDS state vector holds.  The state vector of one (syndrome, class,
+ * assignment) is 2^width doubles in a device workspace (1 GiB at most, whatever N), width <= hbm_width; the op stream is cut into segments
+ * whose INTRO / FORGET slots fit tile_width index bits, and one launch per segment moves every live tile of 2^tile_width doubles through
+ * LDS.  Where the frontier is wider than hbm_width, n_held generators are held out by qecmc_class_sweep_cut's rule and summed over in its
+ * order.  hbm_width: tile_width .. 24 (128 MiB per state vector), 0 for the default, 24.  tile_width: 4 .. 13, 0 for the default, 11 (the fastest measured).
+ * qecmc_class_sweep_tiled_info: the frontier of the plan with nothing held, the plan's width, held generators, classes, qubits, ops and
+ * segments -- every pointer nullable --, on the host alone.
+ * Additive: QECMC_ABI_VERSION stays.  Refused before a device is looked for: what qecmc_class_sweep refuses with QECMC_ERR_INVALID, and an
+ * hbm_width or tile_width out of range; a (code, L) without a class move (the toric code at even L) or a frontier that 12 held generators
+ * do not bring down to hbm_width with QECMC_ERR_UNSUPPORTED, by name with its widths -- which adds planar L = 8 .. 12, xzzx / rotated
+ * L = 13 .. 21 and toric L = 7 to qecmc_class_sweep_cut's shapes; toric L >= 9 (37 wide), planar L >= 13 and xzzx / rotated L >= 23 (26
+ * wide) stay refused.  The result is the same bits for every tile_width;
+ * where nothing is held and width <= 13 it is qecmc_class_sweep's, and where the held generators are qecmc_class_sweep_cut's (hbm_width =
+ * its lds_width) it is that one's, bit for bit.  Denormal entries are kept on either side.  N == 0 succeeds.  Host pointers only. */
+int qecmc_class_sweep_tiled_info(int code, int L, int hbm_width, int tile_width, int32_t *full_width, int32_t *width, int32_t *n_held,
+                                 int32_t *ncls, int32_t *nq, int32_t *n_ops, int32_t *n_segments);
+int qecmc_class_sweep_tiled(int code, int L, uint64_t N, const uint8_t *chains, const double *w, int hbm_width, int tile_width,
+                            double *z_out, int32_t *class_out);
+
 /* ---- chain / ladder on caller-owned state (host pointers) ----------------- */
 
 /* The supported range of a start index.  A Philox counter holds a proposal index (the swap stream: a ladder-step index) in 48 bits,

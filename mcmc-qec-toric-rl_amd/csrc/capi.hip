@@ -23,6 +23,7 @@
 #include "corrections.hpp"
 #include "class_sweep.hpp"
 #include "class_sweep_cut.hpp"
+#include "class_sweep_tiled.hpp"
 #include "enumerate.hpp"
 #include "syndrome_lift.hpp"
 #include "tables.hpp"
@@ -721,6 +722,95 @@ int qecmc_class_sweep_cut(int code, int L, uint64_t N, const uint8_t *chains, co
         HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * rep_words * sizeof(uint32_t), hipMemcpyHostToDevice));
         a.S = (uint32_t)here;
         HIP_TRY(launch_class_sweep_cut(a, dops.as<uint32_t>(), dheld.as<uint32_t>(), dreps.as<uint32_t>(), dpart.as<double>(), dz.as<double>(), 0));
+        HIP_TRY(hipMemcpy(z_out + first * (uint64_t)p.ncls, dz.p, (size_t)here * p.ncls * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- the frontier sweep on a state vector tiled over HBM (class_sweep_tiled.hpp)
+int qecmc_class_sweep_tiled_info(int code, int L, int hbm_width, int tile_width, int32_t *full_width, int32_t *width, int32_t *n_held, int32_t *ncls, int32_t *nq,
+                                 int32_t *n_ops, int32_t *n_segments)
+{
+    const sweep::TiledPlan tp = sweep::build_tiled_plan(code, L, hbm_width, tile_width);
+    if (int rc = report(tp.plan.refusal)) return rc;
+    if (full_width) *full_width = tp.full_width;
+    if (width) *width = tp.plan.width;
+    if (n_held) *n_held = tp.n_held;
+    if (ncls) *ncls = tp.plan.ncls;
+    if (nq) *nq = tp.plan.nq;
+    if (n_ops) *n_ops = tp.plan.n_ops;
+    if (n_segments) *n_segments = (int32_t)tp.segments.size();
+    return 0;
+}
+
+namespace {
+// The state vectors of the tiled sweep: one block per device, taken with one hipMalloc when a call first needs more than is there and kept -- it is
+// kTiledWorkspaceBytes at most, and never cleared.  A call holds the lock from its first launch to its last copy.
+struct TiledWorkspace {
+    static constexpr int kDevices = 64;
+    std::mutex mu;
+    void *p[kDevices] = {};
+    size_t bytes[kDevices] = {};
+    static TiledWorkspace &get() { static TiledWorkspace *w = new TiledWorkspace; return *w; }      // (never destroyed, as DevPool)
+    hipError_t take(size_t want, double **out)                                    // under mu
+    {
+        int dev = 0;
+        if (hipError_t e = hipGetDevice(&dev)) return e;
+        if (dev < 0 || dev >= kDevices || want > sweep::kTiledWorkspaceBytes) return hipErrorInvalidValue;
+        if (bytes[dev] < want) {
+            if (p[dev]) { (void)hipFree(p[dev]); p[dev] = nullptr; bytes[dev] = 0; }
+            if (hipError_t e = hipMalloc(&p[dev], want)) return e;
+            bytes[dev] = want;
+        }
+        *out = static_cast<double *>(p[dev]);
+        return hipSuccess;
+    }
+};
+}  // namespace
+
+int qecmc_class_sweep_tiled(int code, int L, uint64_t N, const uint8_t *chains, const double *w, int hbm_width, int tile_width, double *z_out, int32_t *class_out)
+{
+    if (!chains || !w || !z_out) return fail(QECMC_ERR_INVALID, "qecmc_class_sweep_tiled: NULL buffer");
+    if (N > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "N=%llu syndromes exceed 32 bits", (unsigned long long)N);
+    if (int rc = report(sweep::check_weights(w))) return rc;
+    const sweep::TiledPlan tp = sweep::build_tiled_plan(code, L, hbm_width, tile_width);
+    const sweep::Plan &p = tp.plan;
+    if (int rc = report(p.refusal)) return rc;
+    if (int rc = use_device(0)) return rc;
+    if (N == 0) return 0;
+    const uint32_t group = sweep::cut_launch_group(N, p.ncls, tp.n_held), pass = sweep::tiled_pass_units(tp.state_bits);
+    const size_t rep_words = (size_t)p.ncls * p.W, partials = (size_t)p.ncls << tp.n_held;   // of one syndrome
+    const uint64_t group_units = (uint64_t)group * partials;
+    std::vector<uint32_t> reps((size_t)group * rep_words);
+    DevBuf dops, dheld, dreps, dpart, dz;
+    HIP_TRY(dops.alloc(tp.dev_ops.size() * sizeof(uint32_t)));
+    HIP_TRY(dheld.alloc(tp.held_words.size() * sizeof(uint32_t)));
+    HIP_TRY(dreps.alloc(reps.size() * sizeof(uint32_t)));
+    HIP_TRY(dpart.alloc((size_t)group * partials * sizeof(double)));            // kCutGridMax doubles at most; dirty: every partial is written before it is read
+    HIP_TRY(dz.alloc((size_t)group * p.ncls * sizeof(double)));
+    HIP_TRY(hipMemcpy(dops.p, tp.dev_ops.data(), tp.dev_ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (tp.n_held) HIP_TRY(hipMemcpy(dheld.p, tp.held_words.data(), tp.held_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    TiledWorkspace &ws = TiledWorkspace::get();
+    std::lock_guard<std::mutex> hold(ws.mu);
+    double *work = nullptr;
+    HIP_TRY(ws.take((size_t)(group_units < pass ? group_units : pass) * (sizeof(double) << tp.state_bits), &work));
+    SweepCutArgs ra = {};
+    ra.ncls = p.ncls; ra.W = p.W; ra.width = p.width; ra.n_ops = p.n_ops; ra.n_held = tp.n_held; ra.scale = p.scale;
+    double wxz[4];
+    sweep::weights_xz(w, wxz);
+    // the host loops over groups of syndromes and, within a group, over passes of units: no launch, and no device block, grows with the batch
+    for (uint64_t first = 0; first < N; first += group) {
+        const uint64_t here = N - first < group ? N - first : group, units = here * partials;
+        for (uint64_t s = 0; s < here; ++s) {
+            const int cls = sweep::class_representatives(p, chains + (first + s) * (uint64_t)p.nq, reps.data() + s * rep_words);
+            if (class_out) class_out[first + s] = cls;
+        }
+        HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * rep_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+        for (uint64_t u = 0; u < units; u += pass)
+            HIP_TRY(launch_class_sweep_tiled(tp, wxz, (uint32_t)u, (uint32_t)(units - u < pass ? units - u : pass), dops.as<uint32_t>(), dheld.as<uint32_t>(),
+                                             dreps.as<uint32_t>(), work, dpart.as<double>(), 0));
+        ra.S = (uint32_t)here;
+        HIP_TRY(launch_class_sweep_reduce(ra, dpart.as<double>(), dz.as<double>(), 0));
         HIP_TRY(hipMemcpy(z_out + first * (uint64_t)p.ncls, dz.p, (size_t)here * p.ncls * sizeof(double), hipMemcpyDeviceToHost));
     }
     return 0;

@@ -113,19 +113,35 @@ struct Trace {
     int first_peak_op = -1;
 };
 
-// build_plan() with the generators g that have held[g] != 0 left out of the elimination: they get no INTRO and no FORGET and no CLOSE names them; a
-// qubit they alone touch is still closed, with no pair.  `held` empty: nothing held.  A plan wider than max_width is refused by name and not encoded.
-inline Plan build_plan_held(int code, int L, const std::vector<char> &held, int max_width, Trace *trace)
+// The op stream before it is encoded: what build_plan_held() and the wide encoder of class_sweep_tiled.hpp both read.  `live`: the occupied slots
+// -- INTRO before it, CLOSE as they are, FORGET after it.  A pair is (slot, xz) of a generator's Pauli at the CLOSE's qubit.
+struct StreamOp {
+    uint32_t kind, slot, qubit, pairs, pair_slot[4], pair_xz[4];
+    std::vector<char> live;
+};
+struct Stream {
+    Plan head;                         // code .. n_ops and width, ops empty; refusal: not a (code, L), no class move, or an internal one
+    std::vector<StreamOp> ops;
+    int live_at_end = 0;
+    correct::Table table;
+};
+
+// The stream of build_plan() with the generators g that have held[g] != 0 left out of the elimination: they get no INTRO and no FORGET and no CLOSE
+// names them; a qubit they alone touch is still closed, with no pair.  `held` empty: nothing held.  Slots are handed out without a bound, so a
+// refusal can name the width.
+inline Stream build_stream(int code, int L, const std::vector<char> &held, Trace *trace)
 {
-    Plan p;
+    Stream st;
+    Plan &p = st.head;
     p.code = code; p.L = L;
-    if ((p.refusal = check_code_L(code, L)).code) return p;
-    const correct::Table ct = correct::build_table(code, L);
+    if ((p.refusal = check_code_L(code, L)).code) return st;
+    st.table = correct::build_table(code, L);
+    const correct::Table &ct = st.table;
     p.nq = ct.nq; p.W = ct.W; p.ncls = ct.ncls; p.kinds = ct.kinds; p.n_gen = ct.n_gen;
     if (ct.need.empty()) {
         p.refusal = refuse_params(QECMC_ERR_UNSUPPORTED, "no class move for code %d at L=%d: its logical operators do not reach every equivalence class (the toric code's "
                                                          "parity class does not see a logical line of even length)", code, L);
-        return p;
+        return st;
     }
     // ---- the supports: which generators touch a qubit, with which Pauli; how many of a generator's qubits are still open
     struct Touch { int gen; uint32_t xz; };
@@ -136,7 +152,7 @@ inline Plan build_plan_held(int code, int L, const std::vector<char> &held, int 
         for (int i = 0; i < 4; ++i) {
             const uint32_t e = (ct.gen[(size_t)(2 * g + (i >> 1))] >> ((i & 1) * 16)) & 0xFFFFu, pauli = e & 3u, site = e >> 2;
             if (pauli == 0u) continue;
-            if ((int)site >= p.nq) { p.refusal = refuse_params(QECMC_ERR_UNSUPPORTED, "internal: generator %d of code %d at L=%d leaves the state", g, code, L); return p; }
+            if ((int)site >= p.nq) { p.refusal = refuse_params(QECMC_ERR_UNSUPPORTED, "internal: generator %d of code %d at L=%d leaves the state", g, code, L); return st; }
             is_qubit[site] = 1;
             if ((size_t)g < held.size() && held[(size_t)g]) continue;
             touch[site].push_back({g, pauli_to_xz(pauli)});
@@ -144,18 +160,17 @@ inline Plan build_plan_held(int code, int L, const std::vector<char> &held, int 
         }
     std::vector<int> order;
     for (int q = 0; q < p.nq; ++q) {
-        if (touch[(size_t)q].size() > 4) { p.refusal = refuse_params(QECMC_ERR_UNSUPPORTED, "internal: qubit %d of code %d at L=%d is touched by more than four generators", q, code, L); return p; }
+        if (touch[(size_t)q].size() > 4) { p.refusal = refuse_params(QECMC_ERR_UNSUPPORTED, "internal: qubit %d of code %d at L=%d is touched by more than four generators", q, code, L); return st; }
         if (is_qubit[(size_t)q]) order.push_back(q);                            // (a cell no generator touches holds no qubit)
     }
     for (size_t i = 1; i < order.size(); ++i)                                   // insertion sort by the cell's key
         for (size_t j = i; j > 0 && cell_key(code, L, order[j - 1]) > cell_key(code, L, order[j]); --j) { const int t = order[j]; order[j] = order[j - 1]; order[j - 1] = t; }
     p.n_qubits = (int)order.size();
-    // ---- the stream.  Slots beyond kMaxWidth are still handed out, so a refusal can name the width; such a plan is not encoded.
-    struct Op { uint32_t kind, slot, qubit, pairs, pair[4]; std::vector<char> live; };
+    // ---- the stream
     if (trace) { trace->intro_at.assign((size_t)p.n_gen, -1); trace->forget_at.assign((size_t)p.n_gen, -1); trace->first_peak_op = -1; }
     std::vector<int> slot_of((size_t)p.n_gen, -1);
     std::vector<char> used;
-    std::vector<Op> stream;
+    std::vector<StreamOp> &stream = st.ops;
     int live = 0;
     for (const int q : order) {
         for (const Touch &t : touch[(size_t)q]) {
@@ -164,44 +179,61 @@ inline Plan build_plan_held(int code, int L, const std::vector<char> &held, int 
             while (s < used.size() && used[s]) ++s;                             // the lowest free slot
             if (s == used.size()) used.push_back(0);
             if (trace) trace->intro_at[(size_t)t.gen] = (int)stream.size();
-            stream.push_back({kIntro, (uint32_t)s, 0u, 0u, {0u, 0u, 0u, 0u}, used});
+            stream.push_back({kIntro, (uint32_t)s, 0u, 0u, {0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}, used});
             used[s] = 1; slot_of[(size_t)t.gen] = (int)s;
             if (++live > p.width) { p.width = live; if (trace) trace->first_peak_op = (int)stream.size() - 1; }
         }
-        Op close = {kClose, 0u, (uint32_t)q, 0u, {0u, 0u, 0u, 0u}, used};
-        for (const Touch &t : touch[(size_t)q]) close.pair[close.pairs++] = ((uint32_t)slot_of[(size_t)t.gen] & 15u) | (t.xz << 4);
+        StreamOp close = {kClose, 0u, (uint32_t)q, 0u, {0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}, used};
+        for (const Touch &t : touch[(size_t)q]) { close.pair_slot[close.pairs] = (uint32_t)slot_of[(size_t)t.gen]; close.pair_xz[close.pairs++] = t.xz; }
         stream.push_back(close);
         for (const Touch &t : touch[(size_t)q]) {
             if (--open[(size_t)t.gen]) continue;
             const uint32_t s = (uint32_t)slot_of[(size_t)t.gen];
             used[s] = 0; --live;
             if (trace) trace->forget_at[(size_t)t.gen] = (int)stream.size();
-            stream.push_back({kForget, s, 0u, 0u, {0u, 0u, 0u, 0u}, used});
+            stream.push_back({kForget, s, 0u, 0u, {0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}, used});
         }
     }
     p.n_ops = (int)stream.size();
+    st.live_at_end = live;
+    return st;
+}
+
+// what every encoder fills in after its op words: the rank and the scale, the class-move table, the LDS of a state vector of the plan's width
+inline void finish_plan(Plan &p, const correct::Table &ct)
+{
+    p.rank = generator_rank(ct);
+    p.scale = std::ldexp(1.0, -(p.n_gen - p.rank));
+    p.masks = ct.masks; p.need = ct.need;
+    p.carve = lds_carve(p.width);
+}
+
+// build_stream() in the four-word encoding above.  A plan wider than max_width is refused by name and not encoded.
+inline Plan build_plan_held(int code, int L, const std::vector<char> &held, int max_width, Trace *trace)
+{
+    const Stream st = build_stream(code, L, held, trace);
+    Plan p = st.head;
+    if (p.refusal.code) return p;
     if (p.width > max_width) {
         p.refusal = refuse_params(QECMC_ERR_UNSUPPORTED, "the frontier of code %d at L=%d is %d generators wide: a state vector of 2^%d doubles does not fit the %u bytes of "
                                                          "LDS a workgroup sweeps in (width %d at most)", code, L, p.width, p.width, lds_carve(max_width).bytes, max_width);
         return p;
     }
-    if (live != 0) { p.refusal = refuse_params(QECMC_ERR_UNSUPPORTED, "internal: the plan of code %d at L=%d ends with %d live slots", code, L, live); return p; }
-    for (const Op &o : stream) {
-        uint32_t mask = 0, top = 0;
+    if (st.live_at_end != 0) { p.refusal = refuse_params(QECMC_ERR_UNSUPPORTED, "internal: the plan of code %d at L=%d ends with %d live slots", code, L, st.live_at_end); return p; }
+    for (const StreamOp &o : st.ops) {
+        uint32_t mask = 0, top = 0, pair[4];
         for (size_t s = 0; s < o.live.size(); ++s)
             if (o.live[s]) mask |= 1u << s;
         const uint32_t reach = o.kind == kClose ? mask : mask | (1u << o.slot);
         while (top < 32u && (reach >> top)) ++top;
         if ((int)top > p.width || (int)o.qubit >= p.nq) { p.refusal = refuse_params(QECMC_ERR_UNSUPPORTED, "internal: an op of code %d at L=%d leaves its state vector", code, L); return p; }
+        for (int j = 0; j < 4; ++j) pair[j] = (uint32_t)j < o.pairs ? (o.pair_slot[j] & 15u) | (o.pair_xz[j] << 4) : 0u;
         p.ops.push_back(o.kind | (o.slot << 4) | (o.pairs << 8) | (top << 12));
         p.ops.push_back(mask);
-        p.ops.push_back(o.pair[0] | (o.pair[1] << 8) | (o.pair[2] << 16) | (o.pair[3] << 24));
+        p.ops.push_back(pair[0] | (pair[1] << 8) | (pair[2] << 16) | (pair[3] << 24));
         p.ops.push_back(o.qubit);
     }
-    p.rank = generator_rank(ct);
-    p.scale = std::ldexp(1.0, -(p.n_gen - p.rank));
-    p.masks = ct.masks; p.need = ct.need;
-    p.carve = lds_carve(p.width);
+    finish_plan(p, st.table);
     return p;
 }
 

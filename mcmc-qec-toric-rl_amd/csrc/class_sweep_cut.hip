@@ -103,7 +103,14 @@ hipError_t launch_class_sweep_cut(const SweepCutArgs &a, const uint32_t *ops, co
     const uint32_t pairs = a.S * (uint32_t)a.ncls;
     hipLaunchKernelGGL(k_class_sweep_cut, dim3(pairs << a.n_held), dim3(sweep::cut_threads(a.width)), carve.bytes, stream, a, ops, held, reps, P);
     if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL(k_class_sweep_reduce, dim3(pairs), dim3(sweep::kThreads), 0, stream, a, P, z);
+    return launch_class_sweep_reduce(a, P, z, stream);
+}
+
+hipError_t launch_class_sweep_reduce(const SweepCutArgs &a, double *P, double *z, hipStream_t stream)
+{
+    if (a.S == 0) return hipSuccess;
+    if ((a.ncls != 4 && a.ncls != 16) || a.n_held < 0 || a.n_held > sweep::kMaxHeld || a.S > sweep::cut_launch_group(a.S, a.ncls, a.n_held)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_class_sweep_reduce, dim3(a.S * (uint32_t)a.ncls), dim3(sweep::kThreads), 0, stream, a, P, z);
     return hipGetLastError();
 }
 

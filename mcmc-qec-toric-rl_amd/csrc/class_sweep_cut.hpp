@@ -66,6 +66,34 @@ struct CutPlan {
 // lds_width = 0: kMaxWidth where nothing is held then; kCutMaxWidth where that holds nothing; kDefaultHeldWidth elsewhere
 inline int default_width(int full_width) { return full_width <= kMaxWidth ? kMaxWidth : full_width <= kCutMaxWidth ? kCutMaxWidth : kDefaultHeldWidth; }
 
+// the hold rule: of the generators live at the first op at which the stream reaches its peak, the one with the longest lifetime, ties to the lowest
+// table index; -1: none is live there
+inline int pick_hold(const Trace &tr, int n_gen)
+{
+    int pick = -1, longest = -1;
+    for (int g = 0; g < n_gen; ++g) {
+        if (tr.intro_at[(size_t)g] < 0 || tr.intro_at[(size_t)g] > tr.first_peak_op || tr.forget_at[(size_t)g] < tr.first_peak_op) continue;   // not live there
+        const int life = tr.forget_at[(size_t)g] - tr.intro_at[(size_t)g];
+        if (life > longest) { longest = life; pick = g; }
+    }
+    return pick;
+}
+
+// the held generators of a plan: their table indices, ascending, and each as packed state words [W], 2 bits per qubit
+inline void held_generator_words(const correct::Table &ct, const std::vector<char> &held, std::vector<int> &index, std::vector<uint32_t> &words_out)
+{
+    for (int g = 0; g < ct.n_gen; ++g) {
+        if (!held[(size_t)g]) continue;
+        index.push_back(g);
+        std::vector<uint32_t> words((size_t)ct.W, 0u);
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t e = (ct.gen[(size_t)(2 * g + (i >> 1))] >> ((i & 1) * 16)) & 0xFFFFu, pauli = e & 3u, site = e >> 2;
+            words[site >> 4] ^= pauli << ((site & 15u) * 2u);                   // (Pauli values XOR as the Pauli product)
+        }
+        words_out.insert(words_out.end(), words.begin(), words.end());
+    }
+}
+
 inline CutPlan build_cut_plan(int code, int L, int lds_width)
 {
     CutPlan cp;
@@ -83,21 +111,16 @@ inline CutPlan build_cut_plan(int code, int L, int lds_width)
     cp.lds_width = lds_width;
     if (cp.full_width - kMaxHeld > lds_width) {
         cp.plan.refusal = refuse_params(QECMC_ERR_UNSUPPORTED, "the frontier of code %d at L=%d is %d generators wide: a state vector of width %d needs more than the %d held "
-                                                               "generators a cut plan takes (an HBM-tiled state is not built)", code, L, cp.full_width, lds_width, kMaxHeld);
+                                                               "generators a cut plan takes (qecmc_class_sweep_tiled keeps a wider state vector in HBM)", code, L, cp.full_width, lds_width, kMaxHeld);
         return cp;
     }
     held.assign((size_t)cp.plan.n_gen, 0);
     while (cp.plan.width > lds_width) {
-        int pick = -1, longest = -1;
-        for (int g = 0; g < cp.plan.n_gen; ++g) {
-            if (tr.intro_at[(size_t)g] < 0 || tr.intro_at[(size_t)g] > tr.first_peak_op || tr.forget_at[(size_t)g] < tr.first_peak_op) continue;   // not live there
-            const int life = tr.forget_at[(size_t)g] - tr.intro_at[(size_t)g];
-            if (life > longest) { longest = life; pick = g; }
-        }
+        const int pick = pick_hold(tr, cp.plan.n_gen);
         if (pick < 0) { cp.plan.refusal = refuse_params(QECMC_ERR_UNSUPPORTED, "internal: no generator is live at the peak of code %d at L=%d", code, L); return cp; }
         if (cp.n_held == kMaxHeld) {
             cp.plan.refusal = refuse_params(QECMC_ERR_UNSUPPORTED, "the frontier of code %d at L=%d is %d generators wide: %d held generators leave width %d, a state vector of "
-                                                                   "width %d needs more than that (an HBM-tiled state is not built)", code, L, cp.full_width, kMaxHeld,
+                                                                   "width %d needs more than that (qecmc_class_sweep_tiled keeps a wider state vector in HBM)", code, L, cp.full_width, kMaxHeld,
                                             cp.plan.width, lds_width);
             return cp;
         }
@@ -106,17 +129,7 @@ inline CutPlan build_cut_plan(int code, int L, int lds_width)
         if (cp.plan.refusal.code && cp.plan.width <= lds_width) return cp;      // (an internal refusal)
     }
     if (cp.plan.refusal.code) return cp;
-    const correct::Table ct = correct::build_table(code, L);
-    for (int g = 0; g < cp.plan.n_gen; ++g) {
-        if (!held[(size_t)g]) continue;
-        cp.held.push_back(g);
-        std::vector<uint32_t> words((size_t)cp.plan.W, 0u);
-        for (int i = 0; i < 4; ++i) {
-            const uint32_t e = (ct.gen[(size_t)(2 * g + (i >> 1))] >> ((i & 1) * 16)) & 0xFFFFu, pauli = e & 3u, site = e >> 2;
-            words[site >> 4] ^= pauli << ((site & 15u) * 2u);                   // (Pauli values XOR as the Pauli product)
-        }
-        cp.held_words.insert(cp.held_words.end(), words.begin(), words.end());
-    }
+    held_generator_words(correct::build_table(code, L), held, cp.held, cp.held_words);
     return cp;
 }
 
@@ -200,5 +213,7 @@ struct SweepCutArgs {
 };
 hipError_t class_sweep_cut_allow_lds(int width);      // hipSuccess: a state vector of this width can be launched on the current device
 hipError_t launch_class_sweep_cut(const SweepCutArgs &a, const uint32_t *ops, const uint32_t *held, const uint32_t *reps, double *P, double *z, hipStream_t stream);
+// k_class_sweep_reduce alone, on the partials of a.S syndromes (n_held, ncls and scale are read): class_sweep_tiled.hip forms its partials itself
+hipError_t launch_class_sweep_reduce(const SweepCutArgs &a, double *P, double *z, hipStream_t stream);
 
 }  // namespace qecmc

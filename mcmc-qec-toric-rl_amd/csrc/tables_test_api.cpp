@@ -5,6 +5,7 @@
 // Not part of libqecmc.so.
 #include "class_sweep.hpp"
 #include "class_sweep_cut.hpp"
+#include "class_sweep_tiled.hpp"
 #include "corrections.hpp"
 #include "enumerate.hpp"
 #include "kernel_choice.hpp"
@@ -333,6 +334,55 @@ int qt_class_sweep_cut(int code, int L, uint64_t N, const uint8_t *chains, const
     const sweep::CutPlan cp = sweep::build_cut_plan(code, L, lds_width);
     if (cp.plan.refusal.code) return cp.plan.refusal.code;
     sweep::sweep_cut_host(cp, N, chains, w, z, cls);
+    return 0;
+}
+// the tiled sweep (class_sweep_tiled.hpp).  qt_class_sweep_tiled_info: full_width, width, n_held, ncls, nq, n_ops, rank, n_gen, n_segments, state_bits,
+// the hbm_width and tile_width the plan was built for, kMaxHeld, kTiledMaxWidth, the units of one pass and the threads of a workgroup -- the
+// QECMC_ERR_* code of build_tiled_plan()'s refusal; qt_class_sweep_tiled_ops: the wide op stream uint32[n_ops][4]; qt_class_sweep_tiled_segments: the
+// segment table uint32[n_segments][8] (op_first, op_count, tile, live, live_in, live_out, n_tiles, 0); qt_class_sweep_tiled_held: as the cut sweep's;
+// qt_class_sweep_tiled: the host twin of qecmc_class_sweep_tiled behind the same host checks.  -1 where refused or too small a buffer
+int qt_class_sweep_tiled_info(int code, int L, int hbm_width, int tile_width, int32_t *out16, char *msg, int msg_cap)
+{
+    const sweep::TiledPlan tp = sweep::build_tiled_plan(code, L, hbm_width, tile_width);
+    if (msg && msg_cap > 0) std::snprintf(msg, (size_t)msg_cap, "%s", tp.plan.refusal.msg.c_str());
+    const int32_t v[16] = {tp.full_width, tp.plan.width, tp.n_held, tp.plan.ncls, tp.plan.nq, tp.plan.n_ops, tp.plan.rank, tp.plan.n_gen, (int32_t)tp.segments.size(),
+                           tp.state_bits, tp.hbm_width, tp.tile_width, sweep::kMaxHeld, sweep::kTiledMaxWidth,
+                           tp.state_bits ? (int32_t)sweep::tiled_pass_units(tp.state_bits) : 0, tp.tile_width ? (int32_t)sweep::tiled_threads(tp.tile_width) : 0};
+    if (out16) std::memcpy(out16, v, sizeof v);
+    return tp.plan.refusal.code;
+}
+int qt_class_sweep_tiled_ops(int code, int L, int hbm_width, int tile_width, uint32_t *out, int cap)
+{
+    const sweep::TiledPlan tp = sweep::build_tiled_plan(code, L, hbm_width, tile_width);
+    if (tp.plan.refusal.code) return -1;
+    return put(tp.ops, out, cap);
+}
+int qt_class_sweep_tiled_segments(int code, int L, int hbm_width, int tile_width, uint32_t *out, int cap)
+{
+    const sweep::TiledPlan tp = sweep::build_tiled_plan(code, L, hbm_width, tile_width);
+    if (tp.plan.refusal.code) return -1;
+    std::vector<uint32_t> v;
+    for (const sweep::Segment &sg : tp.segments) {
+        const uint32_t w[sweep::kSegmentWords] = {sg.op_first, sg.op_count, sg.tile, sg.live, sg.live_in, sg.live_out, sg.n_tiles, 0u};
+        v.insert(v.end(), w, w + sweep::kSegmentWords);
+    }
+    return put(v, out, cap);
+}
+int qt_class_sweep_tiled_held(int code, int L, int hbm_width, int tile_width, int32_t *index, uint32_t *words, int cap_words)
+{
+    const sweep::TiledPlan tp = sweep::build_tiled_plan(code, L, hbm_width, tile_width);
+    if (tp.plan.refusal.code || (int)tp.held_words.size() > cap_words) return -1;
+    for (int j = 0; j < tp.n_held; ++j) index[j] = tp.held[(size_t)j];
+    if (!tp.held_words.empty()) std::memcpy(words, tp.held_words.data(), tp.held_words.size() * sizeof(uint32_t));
+    return tp.n_held;
+}
+int qt_class_sweep_tiled(int code, int L, uint64_t N, const uint8_t *chains, const double *w, int hbm_width, int tile_width, double *z, int32_t *cls)
+{
+    if (!chains || !w || !z) return QECMC_ERR_INVALID;
+    if (const Refusal r = sweep::check_weights(w); r.code) return r.code;
+    const sweep::TiledPlan tp = sweep::build_tiled_plan(code, L, hbm_width, tile_width);
+    if (tp.plan.refusal.code) return tp.plan.refusal.code;
+    sweep::sweep_tiled_host(tp, N, chains, w, z, cls);
     return 0;
 }
 // the top rung's frames of a pick window (wu_frames.hpp) for an accepted scan = wave block, from the window's 64 pick blocks picks[64][4]: the plan's

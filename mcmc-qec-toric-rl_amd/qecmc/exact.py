@@ -7,7 +7,11 @@ The same law by a frontier sweep (qecmc_class_sweep): the class 
 and Z, by variable elimination across the lattice -- which reaches xzzx / rotated L = 9 and planar L = 6.
 
 The sweep past one LDS state vector (qecmc_class_sweep_cut): generators held out of the elimination and summed over by workgroups --
-which reaches the toric code at L = 5, and with a 128 KiB state vector xzzx / rotated L = 11 and planar L = 7."""
+which reaches the toric code at L = 5, and with a 128 KiB state vector xzzx / rotated L = 11 and planar L = 7.
+
+The sweep on a state vector tiled over HBM (qecmc_class_sweep_tiled): the state vector of a (syndrome, class) lives in a device
+workspace and passes through LDS one tile per workgroup, one launch per segment of the op stream -- which reaches xzzx / rotated L = 21, planar
+L = 12 and, with five generators held, the toric code at L = 7.  It runs only where it is named (method="tiled"): "auto" routes as before."""
 import ctypes as C
 
 import numpy as np
@@ -115,6 +119,37 @@ def class_sweep_cut(code, chains, weights, size=None, lds_width=0):
     return dict(Z=z, cls=cls, width=info["width"], held=info["held"])
 
 
+def sweep_tiled_info(code, size, hbm_width=0, tile_width=0):
+    """dict(full_width, width, held, ncls, nq, n_ops, segments) of the tiled plan of one (code, size) for a state vector of at most 2^hbm_width
+    doubles in HBM and tiles of 2^tile_width doubles in LDS (0: the library's defaults, 24 and 11), from the host half of the library alone; raises
+    QecmcError where the plan is refused"""
+    v = [C.c_int32() for _ in range(7)]
+    L_.check(L_.lib().qecmc_class_sweep_tiled_info(_CODES.get(code, code), int(size), int(hbm_width), int(tile_width), *[C.byref(x) for x in v]))
+    return dict(zip(("full_width", "width", "held", "ncls", "nq", "n_ops", "segments"), (int(x.value) for x in v)))
+
+
+def class_sweep_tiled(code, chains, weights, size=None, hbm_width=0, tile_width=0):
+    """class_sweep on a state vector tiled over HBM (qecmc_class_sweep_tiled): xzzx / rotated L = 13 .. 21, planar L = 8 .. 12 and,
+    with `held` generators held out as class_sweep_cut holds them, the toric code at L = 7.  hbm_width: the widest state vector, tile_width .. 24
+    (2^24 doubles are 128 MiB per class and assignment), 0: the default; tile_width: the index bits of a tile in LDS, 4 .. 13, 0: the default.  The
+    result does not depend on tile_width, bit for bit.
+    Returns dict(Z float64[N, ncls], cls int32[N], width: the widest frontier of the plan, held: the number of held generators, segments: the launches
+    one pass of state vectors takes)."""
+    code = _CODES.get(code, code)
+    flat, L = _as_chains(code, chains, size)
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.shape != (4,):
+        raise ValueError(f"weights of shape {w.shape}: the four weights of I, X, Y and Z")
+    info = sweep_tiled_info(code, L, hbm_width, tile_width)
+    n = flat.shape[0]
+    z = np.zeros((n, info["ncls"]), dtype=np.float64)
+    cls = np.zeros(n, dtype=np.int32)
+    f64p = C.POINTER(C.c_double)
+    L_.check(L_.lib().qecmc_class_sweep_tiled(code, L, n, L_.u8(flat), w.ctypes.data_as(f64p), int(hbm_width), int(tile_width), z.ctypes.data_as(f64p),
+                                              L_.i32(cls)))
+    return dict(Z=z, cls=cls, width=info["width"], held=info["held"], segments=info["segments"])
+
+
 def class_weights(hist, weight):
     """Z[..., c] = sum over (n_xy, n_z) of hist[..., c, n_xy, n_z] * weight(n_xy, n_z): weight is broadcast over the grid of counts, float64"""
     hist = np.asarray(hist)
@@ -158,14 +193,15 @@ def alpha_w4(pz_tilde, alpha):
     return np.array([1.0, pz_tilde ** alpha, pz_tilde ** alpha, pz_tilde])
 
 
-_METHODS = ("auto", "enumerate", "sweep", "cut")
+_METHODS = ("auto", "enumerate", "sweep", "cut", "tiled")
 
 
 def resolve_method(code, size, method="auto"):
     """what exact_class_probabilities runs at one (code, size): "auto" is the enumerator wherever it accepts the shape -- so a call that worked
     before the sweep existed returns what it returned --, the sweep where the enumerator answers QECMC_ERR_UNSUPPORTED, and the cut-set sweep where
-    the sweep answers QECMC_ERR_UNSUPPORTED too and the cut plan is accepted; any other answer is the enumerator's to report.  From the host half of
-    the library alone."""
+    the sweep answers QECMC_ERR_UNSUPPORTED too and the cut plan is accepted; any other answer is the enumerator's to report.  "auto" never answers
+    "tiled": the sweep tiled over HBM runs only where it is named, and where all three refuse the refusal a caller sees is still the sweep's.  From
+    the host half of the library alone."""
     if method not in _METHODS:
         raise ValueError(f"method={method!r}")
     if method != "auto":
@@ -183,7 +219,8 @@ def exact_class_probabilities(code, chains, p, eta=None, alpha=None, hist=None, 
     """float64[N, ncls]: the exact class law of every syndrome under depolarizing noise p, Z-biased noise (p, eta) or the alpha model (p is pz_tilde).
     method "enumerate": by coset_enumerator, which takes the keywords; "sweep": by class_sweep (of the keywords it takes size and device; chunk_bits
     means nothing to it); "cut": by class_sweep_cut (size, and lds_width); "auto" (default): the enumerator wherever it accepts the (code, size), the
-    sweep where it does not, the cut-set sweep where neither does.
+    sweep where it does not, the cut-set sweep where neither does; "tiled": by class_sweep_tiled (size, hbm_width and tile_width), which "auto"
+    never picks.
     hist: a histogram already enumerated (coset_enumerator(...)['hist']) -- chains is then not looked at, and the method is the enumerator's."""
     if eta is not None and alpha is not None:
         raise ValueError("eta and alpha name two noise models")
@@ -191,13 +228,16 @@ def exact_class_probabilities(code, chains, p, eta=None, alpha=None, hist=None, 
         raise ValueError(f"method={method!r}")
     if hist is None:
         method = resolve_method(code, _as_chains(_CODES.get(code, code), chains, enumerator_kw.get("size"))[1], method)
-    if hist is None and method in ("sweep", "cut"):
+    if hist is None and method in ("sweep", "cut", "tiled"):
         if "chunks" in enumerator_kw:
             raise ValueError("chunks= is the enumerator's: the sweep has no partial sums")
         w4 = alpha_w4(p, alpha) if alpha is not None else biased_w4(p, eta) if eta is not None else depolarizing_w4(p)
-        if method == "cut":
-            if int(enumerator_kw.get("device", 0)) != 0:
-                raise ValueError("class_sweep_cut runs on device 0: the library has no device-pointer form of it yet")
+        if method in ("cut", "tiled") and int(enumerator_kw.get("device", 0)) != 0:
+            raise ValueError(f"class_sweep_{method} runs on device 0: the library has no device-pointer form of it yet")
+        if method == "tiled":
+            z = class_sweep_tiled(code, chains, w4, size=enumerator_kw.get("size"), hbm_width=enumerator_kw.get("hbm_width", 0),
+                                  tile_width=enumerator_kw.get("tile_width", 0))["Z"]
+        elif method == "cut":
             z = class_sweep_cut(code, chains, w4, size=enumerator_kw.get("size"), lds_width=enumerator_kw.get("lds_width", 0))["Z"]
         else:
             z = class_sweep(code, chains, w4, size=enumerator_kw.get("size"), device=enumerator_kw.get("device", 0))["Z"]

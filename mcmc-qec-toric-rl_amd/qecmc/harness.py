@@ -215,14 +215,17 @@ def _pteq_decode(params, init, seed, steps, conv_criteria, biased_decoder, metri
 
 
 def _exact_distr(params, chains, device):
-    """params['method'] == "exact": the exact class law of every row (qecmc.exact_class_probabilities) under the weight of
+    """params['method'] == "exact": the exact class law of every row (qecmc.exact_class_probabilities, DESIGN.md 4.1j .. 4.1m) under the weight of
     params['noise'] itself -- biased noise with the biased weight, whatever biased_decoder says; params['exact_method']: "auto" (default: coset
-    enumeration where it takes the shape, the frontier sweep elsewhere, the cut-set sweep where both refuse), "enumerate", "sweep" or "cut" (qecmc.exact)"""
+    enumeration where it takes the shape, the frontier sweep elsewhere, the cut-set sweep where both refuse), "enumerate", "sweep", "cut" or "tiled" (qecmc.exact) -- the sweep tiled
+    over HBM only where it is named, with params['hbm_width'] and params['tile_width'] (0: the defaults)"""
     from .exact import exact_class_probabilities
     noise = params.get("noise", "depolarizing")
     if _CODES[params["code"]] == L_.TORIC and noise != "depolarizing":
         raise ValueError(f"method exact on the toric code is defined for depolarizing noise, not {noise} (its errors are drawn without a bias)")
     kw = dict(eta=params["eta"]) if noise == "biased" else dict(alpha=params["alpha"]) if noise == "alpha" else {}
+    if params.get("exact_method", "auto") == "tiled":
+        kw.update(hbm_width=int(params.get("hbm_width", 0)), tile_width=int(params.get("tile_width", 0)))
     return exact_class_probabilities(params["code"], chains, params["p_error"], size=params["size"], chunk_bits=int(params.get("chunk_bits", 0)),
                                      device=device, method=params.get("exact_method", "auto"), **kw)
 
