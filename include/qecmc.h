@@ -297,6 +297,26 @@ int qecmc_class_sweep_tiled_info(int code, int L, int hbm_width, int tile_width,
 int qecmc_class_sweep_tiled(int code, int L, uint64_t N, const uint8_t *chains, const double *w, int hbm_width, int tile_width,
                             double *z_out, int32_t *class_out);
 
+/* ---- the three sweeps under a weight per (syndrome, qubit): erasures, inhomogeneous noise, soft priors (csrc/class_sweep_site.hpp) ------
+ * The arguments and the result of qecmc_class_sweep, qecmc_class_sweep_cut and qecmc_class_sweep_tiled with the four weights w replaced by a
+ * table: wq double[wq_rows][nq][4], the weights of I, X, Y and Z at every cell of the state layout (any non-negative scale per qubit; in
+ * ratio form w_I = 1).  wq_rows is 1 -- one table for every syndrome -- or N -- row s belongs to syndrome s: a shot's own erased qubits carry
+ * (1, 1, 1, 1).  z_out[s][c] = the sum over the chains of class c with the syndrome of chain s of prod_q wq[row(s)][q][Pauli at q].
+ * Plans, widths, holds, segments and launch groups are the sibling's -- its _info call reports them, and what it accepts and refuses is what
+ * the site entry point accepts and refuses, with the same code and message.  The device holds the weight rows of one launch group at a time.
+ * Weights are finite and >= 0: zero is allowed (off an erased set the pure-erasure limit is (1, 0, 0, 0)), the arithmetic stays copies,
+ * multiplies and adds of finite non-negative numbers.  Only the rows of qubits the plan closes are read: a cell that holds no qubit (the planar
+ * code's unused cells) is neither read nor validated.  With constant rows the result is the uniform sibling's, bit for bit.
+ * Additive: QECMC_ABI_VERSION stays.  Refused before a device is looked for, with QECMC_ERR_INVALID: everything the sibling refuses so, a
+ * NULL wq, a wq_rows that is neither 1 nor N (N > 0), a weight that is negative, NaN or infinite -- by row, qubit and Pauli --, a qubit whose
+ * four weights are all zero; with QECMC_ERR_UNSUPPORTED: the sibling's (code, L) and width refusals.  N == 0 succeeds.  Host pointers only. */
+int qecmc_class_sweep_site(int code, int L, uint64_t N, const uint8_t *chains, const double *wq, uint64_t wq_rows, double *z_out,
+                           int32_t *class_out);
+int qecmc_class_sweep_cut_site(int code, int L, uint64_t N, const uint8_t *chains, const double *wq, uint64_t wq_rows, int lds_width,
+                               double *z_out, int32_t *class_out);
+int qecmc_class_sweep_tiled_site(int code, int L, uint64_t N, const uint8_t *chains, const double *wq, uint64_t wq_rows, int hbm_width,
+                                 int tile_width, double *z_out, int32_t *class_out);
+
 /* ---- chain / ladder on caller-owned state (host pointers) ----------------- */
 
 /* The supported range of a start index.  A Philox counter holds a proposal index (the swap stream: a ladder-step index) in 48 bits,

@@ -24,6 +24,7 @@
 #include "class_sweep.hpp"
 #include "class_sweep_cut.hpp"
 #include "class_sweep_tiled.hpp"
+#include "class_sweep_site.hpp"
 #include "enumerate.hpp"
 #include "syndrome_lift.hpp"
 #include "tables.hpp"
@@ -809,6 +810,168 @@ int qecmc_class_sweep_tiled(int code, int L, uint64_t N, const uint8_t *chains, 
         for (uint64_t u = 0; u < units; u += pass)
             HIP_TRY(launch_class_sweep_tiled(tp, wxz, (uint32_t)u, (uint32_t)(units - u < pass ? units - u : pass), dops.as<uint32_t>(), dheld.as<uint32_t>(),
                                              dreps.as<uint32_t>(), work, dpart.as<double>(), 0));
+        ra.S = (uint32_t)here;
+        HIP_TRY(launch_class_sweep_reduce(ra, dpart.as<double>(), dz.as<double>(), 0));
+        HIP_TRY(hipMemcpy(z_out + first * (uint64_t)p.ncls, dz.p, (size_t)here * p.ncls * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- the three sweeps under a weight per (syndrome, qubit) (class_sweep_site.hpp)
+namespace {
+// the host checks every site entry point makes once its sibling's plan is accepted: the rows, then every weight of a qubit some CLOSE names
+int check_site(uint64_t N, const double *wq, uint64_t wq_rows, int nq, const std::vector<uint32_t> &ops)
+{
+    if (int rc = report(sweep::check_site_rows(N, wq_rows))) return rc;
+    return N ? report(sweep::check_site_weights(wq, wq_rows, nq, sweep::closed_qubits(ops, nq))) : 0;
+}
+
+// The weight rows on the device, in (x, z) order: the one table once, or the rows of a launch group at a time -- `group` rows at most, whatever N.
+struct SiteRows {
+    DevBuf d;
+    std::vector<double> host;
+    const double *wq;
+    size_t row;                                                                 // doubles of one row
+    int nq, per_syndrome;
+    int open(const double *wq_in, uint64_t wq_rows, int nq_in, uint32_t group)
+    {
+        wq = wq_in; nq = nq_in; row = (size_t)nq * 4u; per_syndrome = wq_rows != 1;
+        host.resize((per_syndrome ? (size_t)group : 1u) * row);
+        HIP_TRY(d.alloc(host.size() * sizeof(double)));
+        if ((reinterpret_cast<uintptr_t>(d.p) & 31u) != 0) return fail(QECMC_ERR_HIP, "internal: the device block of the site weights is not 32-byte aligned");
+        return per_syndrome ? 0 : upload(0, 1);
+    }
+    int upload(uint64_t first, uint64_t rows)
+    {
+        sweep::site_rows_xz(wq + first * row, rows, nq, host.data());
+        HIP_TRY(hipMemcpy(d.p, host.data(), (size_t)rows * row * sizeof(double), hipMemcpyHostToDevice));
+        return 0;
+    }
+    int group(uint64_t first, uint64_t here) { return per_syndrome ? upload(first, here) : 0; }
+};
+}  // namespace
+
+int qecmc_class_sweep_site(int code, int L, uint64_t N, const uint8_t *chains, const double *wq, uint64_t wq_rows, double *z_out, int32_t *class_out)
+{
+    if (!chains || !wq || !z_out) return fail(QECMC_ERR_INVALID, "qecmc_class_sweep_site: NULL buffer");
+    if (N > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "N=%llu syndromes exceed 32 bits", (unsigned long long)N);
+    const sweep::Plan p = sweep::build_plan(code, L);
+    if (int rc = report(p.refusal)) return rc;
+    if (int rc = check_site(N, wq, wq_rows, p.nq, p.ops)) return rc;
+    if (int rc = use_device(0)) return rc;
+    if (N == 0) return 0;
+    const uint32_t group = sweep::launch_group(N);
+    const size_t rep_words = (size_t)p.ncls * p.W;                              // words of one syndrome's representatives
+    std::vector<uint32_t> reps((size_t)group * rep_words);
+    DevBuf dops, dreps, dz;
+    SiteRows rows;
+    HIP_TRY(dops.alloc(p.ops.size() * sizeof(uint32_t)));
+    HIP_TRY(dreps.alloc(reps.size() * sizeof(uint32_t)));
+    HIP_TRY(dz.alloc((size_t)group * p.ncls * sizeof(double)));
+    HIP_TRY(hipMemcpy(dops.p, p.ops.data(), p.ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (int rc = rows.open(wq, wq_rows, p.nq, group)) return rc;
+    SweepSiteArgs a = {};
+    a.ncls = p.ncls; a.W = p.W; a.width = p.width; a.n_ops = p.n_ops; a.nq = p.nq; a.per_syndrome = rows.per_syndrome; a.scale = p.scale;
+    // the host loops over groups of syndromes: no launch, and no device block -- the weight rows among them -- grows with the batch
+    for (uint64_t first = 0; first < N; first += group) {
+        const uint64_t here = N - first < group ? N - first : group;
+        for (uint64_t s = 0; s < here; ++s) {
+            const int cls = sweep::class_representatives(p, chains + (first + s) * (uint64_t)p.nq, reps.data() + s * rep_words);
+            if (class_out) class_out[first + s] = cls;
+        }
+        HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * rep_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (int rc = rows.group(first, here)) return rc;
+        a.S = (uint32_t)here;
+        HIP_TRY(launch_class_sweep_site(a, dops.as<uint32_t>(), dreps.as<uint32_t>(), rows.d.as<double>(), dz.as<double>(), 0));
+        HIP_TRY(hipMemcpy(z_out + first * (uint64_t)p.ncls, dz.p, (size_t)here * p.ncls * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+int qecmc_class_sweep_cut_site(int code, int L, uint64_t N, const uint8_t *chains, const double *wq, uint64_t wq_rows, int lds_width, double *z_out, int32_t *class_out)
+{
+    if (!chains || !wq || !z_out) return fail(QECMC_ERR_INVALID, "qecmc_class_sweep_cut_site: NULL buffer");
+    if (N > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "N=%llu syndromes exceed 32 bits", (unsigned long long)N);
+    const sweep::CutPlan cp = sweep::build_cut_plan(code, L, lds_width);
+    const sweep::Plan &p = cp.plan;
+    if (int rc = report(p.refusal)) return rc;
+    if (int rc = check_site(N, wq, wq_rows, p.nq, p.ops)) return rc;
+    if (int rc = use_device(0)) return rc;
+    if (N == 0) return 0;
+    if (class_sweep_cut_site_allow_lds(p.width) != hipSuccess)
+        return fail(QECMC_ERR_UNSUPPORTED, "this device does not grant a workgroup the %u bytes of LDS a state vector of width %d takes", p.carve.bytes, p.width);
+    const uint32_t group = sweep::cut_launch_group(N, p.ncls, cp.n_held);
+    const size_t rep_words = (size_t)p.ncls * p.W, partials = (size_t)p.ncls << cp.n_held;   // of one syndrome
+    std::vector<uint32_t> reps((size_t)group * rep_words);
+    DevBuf dops, dheld, dreps, dpart, dz;
+    SiteRows rows;
+    HIP_TRY(dops.alloc(p.ops.size() * sizeof(uint32_t)));
+    HIP_TRY(dheld.alloc(cp.held_words.size() * sizeof(uint32_t)));
+    HIP_TRY(dreps.alloc(reps.size() * sizeof(uint32_t)));
+    HIP_TRY(dpart.alloc((size_t)group * partials * sizeof(double)));            // kCutGridMax doubles at most; dirty: every partial is written before it is read
+    HIP_TRY(dz.alloc((size_t)group * p.ncls * sizeof(double)));
+    HIP_TRY(hipMemcpy(dops.p, p.ops.data(), p.ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (cp.n_held) HIP_TRY(hipMemcpy(dheld.p, cp.held_words.data(), cp.held_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (int rc = rows.open(wq, wq_rows, p.nq, group)) return rc;
+    SweepSiteArgs a = {};
+    a.ncls = p.ncls; a.W = p.W; a.width = p.width; a.n_ops = p.n_ops; a.n_held = cp.n_held; a.nq = p.nq; a.per_syndrome = rows.per_syndrome; a.scale = p.scale;
+    for (uint64_t first = 0; first < N; first += group) {
+        const uint64_t here = N - first < group ? N - first : group;
+        for (uint64_t s = 0; s < here; ++s) {
+            const int cls = sweep::class_representatives(p, chains + (first + s) * (uint64_t)p.nq, reps.data() + s * rep_words);
+            if (class_out) class_out[first + s] = cls;
+        }
+        HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * rep_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (int rc = rows.group(first, here)) return rc;
+        a.S = (uint32_t)here;
+        HIP_TRY(launch_class_sweep_cut_site(a, dops.as<uint32_t>(), dheld.as<uint32_t>(), dreps.as<uint32_t>(), rows.d.as<double>(), dpart.as<double>(), dz.as<double>(), 0));
+        HIP_TRY(hipMemcpy(z_out + first * (uint64_t)p.ncls, dz.p, (size_t)here * p.ncls * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+int qecmc_class_sweep_tiled_site(int code, int L, uint64_t N, const uint8_t *chains, const double *wq, uint64_t wq_rows, int hbm_width, int tile_width, double *z_out,
+                                 int32_t *class_out)
+{
+    if (!chains || !wq || !z_out) return fail(QECMC_ERR_INVALID, "qecmc_class_sweep_tiled_site: NULL buffer");
+    if (N > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "N=%llu syndromes exceed 32 bits", (unsigned long long)N);
+    const sweep::TiledPlan tp = sweep::build_tiled_plan(code, L, hbm_width, tile_width);
+    const sweep::Plan &p = tp.plan;
+    if (int rc = report(p.refusal)) return rc;
+    if (int rc = check_site(N, wq, wq_rows, p.nq, tp.ops)) return rc;
+    if (int rc = use_device(0)) return rc;
+    if (N == 0) return 0;
+    const uint32_t group = sweep::cut_launch_group(N, p.ncls, tp.n_held), pass = sweep::tiled_pass_units(tp.state_bits);
+    const size_t rep_words = (size_t)p.ncls * p.W, partials = (size_t)p.ncls << tp.n_held;   // of one syndrome
+    const uint64_t group_units = (uint64_t)group * partials;
+    std::vector<uint32_t> reps((size_t)group * rep_words);
+    DevBuf dops, dheld, dreps, dpart, dz;
+    SiteRows rows;
+    HIP_TRY(dops.alloc(tp.dev_ops.size() * sizeof(uint32_t)));
+    HIP_TRY(dheld.alloc(tp.held_words.size() * sizeof(uint32_t)));
+    HIP_TRY(dreps.alloc(reps.size() * sizeof(uint32_t)));
+    HIP_TRY(dpart.alloc((size_t)group * partials * sizeof(double)));            // kCutGridMax doubles at most; dirty: every partial is written before it is read
+    HIP_TRY(dz.alloc((size_t)group * p.ncls * sizeof(double)));
+    HIP_TRY(hipMemcpy(dops.p, tp.dev_ops.data(), tp.dev_ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (tp.n_held) HIP_TRY(hipMemcpy(dheld.p, tp.held_words.data(), tp.held_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (int rc = rows.open(wq, wq_rows, p.nq, group)) return rc;
+    TiledWorkspace &ws = TiledWorkspace::get();                                 // the uniform sweep's block, its cap of kTiledWorkspaceBytes and its lock
+    std::lock_guard<std::mutex> hold(ws.mu);
+    double *work = nullptr;
+    HIP_TRY(ws.take((size_t)(group_units < pass ? group_units : pass) * (sizeof(double) << tp.state_bits), &work));
+    SweepCutArgs ra = {};
+    ra.ncls = p.ncls; ra.W = p.W; ra.width = p.width; ra.n_ops = p.n_ops; ra.n_held = tp.n_held; ra.scale = p.scale;
+    for (uint64_t first = 0; first < N; first += group) {
+        const uint64_t here = N - first < group ? N - first : group, units = here * partials;
+        for (uint64_t s = 0; s < here; ++s) {
+            const int cls = sweep::class_representatives(p, chains + (first + s) * (uint64_t)p.nq, reps.data() + s * rep_words);
+            if (class_out) class_out[first + s] = cls;
+        }
+        HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * rep_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (int rc = rows.group(first, here)) return rc;
+        for (uint64_t u = 0; u < units; u += pass)
+            HIP_TRY(launch_class_sweep_tiled_site(tp, rows.per_syndrome, (uint32_t)u, (uint32_t)(units - u < pass ? units - u : pass), dops.as<uint32_t>(),
+                                                  dheld.as<uint32_t>(), dreps.as<uint32_t>(), rows.d.as<double>(), work, dpart.as<double>(), 0));
         ra.S = (uint32_t)here;
         HIP_TRY(launch_class_sweep_reduce(ra, dpart.as<double>(), dz.as<double>(), 0));
         HIP_TRY(hipMemcpy(z_out + first * (uint64_t)p.ncls, dz.p, (size_t)here * p.ncls * sizeof(double), hipMemcpyDeviceToHost));

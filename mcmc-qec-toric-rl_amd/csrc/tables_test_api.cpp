@@ -6,6 +6,7 @@
 #include "class_sweep.hpp"
 #include "class_sweep_cut.hpp"
 #include "class_sweep_tiled.hpp"
+#include "class_sweep_site.hpp"
 #include "corrections.hpp"
 #include "enumerate.hpp"
 #include "kernel_choice.hpp"
@@ -384,6 +385,47 @@ int qt_class_sweep_tiled(int code, int L, uint64_t N, const uint8_t *chains, con
     if (tp.plan.refusal.code) return tp.plan.refusal.code;
     sweep::sweep_tiled_host(tp, N, chains, w, z, cls);
     return 0;
+}
+// the sweeps under site weights (class_sweep_site.hpp): the host twins of qecmc_class_sweep_site, _cut_site and _tiled_site behind the same host checks,
+// in the same order -- the QECMC_ERR_* code of the refusal, its message in msg (nullable)
+static int site_answer(const Refusal &r, char *msg, int msg_cap)
+{
+    if (msg && msg_cap > 0) std::snprintf(msg, (size_t)msg_cap, "%s", r.msg.c_str());
+    return r.code;
+}
+static Refusal site_checks(uint64_t N, const double *wq, uint64_t wq_rows, int nq, const std::vector<uint32_t> &ops)
+{
+    if (const Refusal r = sweep::check_site_rows(N, wq_rows); r.code) return r;
+    return N ? sweep::check_site_weights(wq, wq_rows, nq, sweep::closed_qubits(ops, nq)) : Refusal{};
+}
+int qt_class_sweep_site(int code, int L, uint64_t N, const uint8_t *chains, const double *wq, uint64_t wq_rows, double *z, int32_t *cls, char *msg, int msg_cap)
+{
+    if (!chains || !wq || !z) return site_answer(refuse_params(QECMC_ERR_INVALID, "qecmc_class_sweep_site: NULL buffer"), msg, msg_cap);
+    const sweep::Plan p = sweep::build_plan(code, L);
+    if (p.refusal.code) return site_answer(p.refusal, msg, msg_cap);
+    if (const Refusal r = site_checks(N, wq, wq_rows, p.nq, p.ops); r.code) return site_answer(r, msg, msg_cap);
+    sweep::sweep_site_host(p, N, chains, wq, wq_rows, z, cls);
+    return site_answer({}, msg, msg_cap);
+}
+int qt_class_sweep_cut_site(int code, int L, uint64_t N, const uint8_t *chains, const double *wq, uint64_t wq_rows, int lds_width, double *z, int32_t *cls, char *msg,
+                            int msg_cap)
+{
+    if (!chains || !wq || !z) return site_answer(refuse_params(QECMC_ERR_INVALID, "qecmc_class_sweep_cut_site: NULL buffer"), msg, msg_cap);
+    const sweep::CutPlan cp = sweep::build_cut_plan(code, L, lds_width);
+    if (cp.plan.refusal.code) return site_answer(cp.plan.refusal, msg, msg_cap);
+    if (const Refusal r = site_checks(N, wq, wq_rows, cp.plan.nq, cp.plan.ops); r.code) return site_answer(r, msg, msg_cap);
+    sweep::sweep_cut_site_host(cp, N, chains, wq, wq_rows, z, cls);
+    return site_answer({}, msg, msg_cap);
+}
+int qt_class_sweep_tiled_site(int code, int L, uint64_t N, const uint8_t *chains, const double *wq, uint64_t wq_rows, int hbm_width, int tile_width, double *z, int32_t *cls,
+                              char *msg, int msg_cap)
+{
+    if (!chains || !wq || !z) return site_answer(refuse_params(QECMC_ERR_INVALID, "qecmc_class_sweep_tiled_site: NULL buffer"), msg, msg_cap);
+    const sweep::TiledPlan tp = sweep::build_tiled_plan(code, L, hbm_width, tile_width);
+    if (tp.plan.refusal.code) return site_answer(tp.plan.refusal, msg, msg_cap);
+    if (const Refusal r = site_checks(N, wq, wq_rows, tp.plan.nq, tp.ops); r.code) return site_answer(r, msg, msg_cap);
+    sweep::sweep_tiled_site_host(tp, N, chains, wq, wq_rows, z, cls);
+    return site_answer({}, msg, msg_cap);
 }
 // the top rung's frames of a pick window (wu_frames.hpp) for an accepted scan = wave block, from the window's 64 pick blocks picks[64][4]: the plan's
 // descriptors and logical masks (rows padded to the kernel's WV words, as the kernel stages them), thr16 from the plan's thr_logical as wu_run forms it.

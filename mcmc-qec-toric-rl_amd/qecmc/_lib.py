@@ -94,6 +94,10 @@ SIGNATURES = {
     "qecmc_class_sweep_cut": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), _i32p]),
     "qecmc_class_sweep_tiled_info": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p]),
     "qecmc_class_sweep_tiled": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, C.POINTER(C.c_double), C.c_int, C.c_int, C.POINTER(C.c_double), _i32p]),
+    "qecmc_class_sweep_site": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, C.POINTER(C.c_double), C.c_uint64, C.POINTER(C.c_double), _i32p]),
+    "qecmc_class_sweep_cut_site": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, C.POINTER(C.c_double), C.c_uint64, C.c_int, C.POINTER(C.c_double), _i32p]),
+    "qecmc_class_sweep_tiled_site": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, C.POINTER(C.c_double), C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                               _i32p]),
     "qecmc_chain_update": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, C.c_double, C.c_double, C.c_uint64,
                                      C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64]),
     "qecmc_chain_update_biased": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, C.c_double, C.c_double, C.c_double,

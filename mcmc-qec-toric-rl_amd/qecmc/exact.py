@@ -11,7 +11,11 @@ which reaches the toric code at L = 5, and with a 128 KiB state vector xzzx / ro
 
 The sweep on a state vector tiled over HBM (qecmc_class_sweep_tiled): the state vector of a (syndrome, class) lives in a device
 workspace and passes through LDS one tile per workgroup, one launch per segment of the op stream -- which reaches xzzx / rotated L = 21, planar
-L = 12 and, with five generators held, the toric code at L = 7.  It runs only where it is named (method="tiled"): "auto" routes as before."""
+L = 12 and, with five generators held, the toric code at L = 7.  It runs only where it is named (method="tiled"): "auto" routes as before.
+
+The three sweeps under a weight per (syndrome, qubit) (qecmc_class_sweep_site, _cut_site, _tiled_site): class_sweep_site and
+exact_site_probabilities take a table of weights in place of the four numbers -- erasures (erasure_site_w4), a map of error rates
+(depolarizing_site_w4, biased_site_w4), any per-shot prior -- at every shape the uniform sweeps reach."""
 import ctypes as C
 
 import numpy as np
@@ -191,6 +195,108 @@ def biased_w4(p, eta):
 def alpha_w4(pz_tilde, alpha):
     """alpha_weight per qubit: (1, pz_tilde^alpha, pz_tilde^alpha, pz_tilde)"""
     return np.array([1.0, pz_tilde ** alpha, pz_tilde ** alpha, pz_tilde])
+
+
+_SITE_METHODS = ("auto", "sweep", "cut", "tiled")
+
+
+def _as_site_weights(code, site_weights, L, n):
+    """site_weights -> (float64[rows, nq, 4], rows): [..., 4] with ... the code's qubit_matrix shape or the flat nq, with or without a leading N"""
+    a = np.ascontiguousarray(site_weights, dtype=np.float64)
+    matrix = (2, L, L) if code in (L_.TORIC, L_.PLANAR) else (L, L)
+    nq = int(np.prod(matrix))
+    if a.ndim >= 2 and a.shape[-1] == 4:
+        if a.shape[:-1] in (matrix, (nq,)):
+            return a.reshape(1, nq, 4), 1
+        if a.shape[0] in (1, n) and a.shape[1:-1] in (matrix, (nq,)):           # (a leading 1 is one table for every syndrome)
+            return a.reshape(a.shape[0], nq, 4), a.shape[0]
+    raise ValueError(f"site_weights of shape {a.shape}: [..., 4] with ... = {matrix} or ({nq},), alone or after a leading 1 or N = {n}")
+
+
+def resolve_site_method(code, size, method="auto", lds_width=0, hbm_width=0, tile_width=0):
+    """(method, info) class_sweep_site runs at one (code, size): the method named, or for "auto" the first of "sweep", "cut", "tiled" whose _info call
+    accepts the shape, with that plan's dict(width, held, ncls, nq, ...).  Unlike resolve_method, "auto" does reach "tiled": class_sweep_site has no
+    earlier answer to preserve.  Where every route refuses, the QecmcError raised is the last one's -- the tiled sweep's, which reaches furthest.
+    From the host half of the library alone."""
+    if method not in _SITE_METHODS:
+        raise ValueError(f"method={method!r}: class_sweep_site runs {_SITE_METHODS[1:]} or 'auto'")
+    code = _CODES.get(code, code)
+    infos = {"sweep": lambda: dict(sweep_info(code, size), held=0), "cut": lambda: sweep_cut_info(code, size, lds_width),
+             "tiled": lambda: sweep_tiled_info(code, size, hbm_width, tile_width)}
+    for m in (_SITE_METHODS[1:] if method == "auto" else (method,)):
+        try:
+            return m, infos[m]()
+        except L_.QecmcError as e:
+            refusal = e
+    raise refusal
+
+
+def class_sweep_site(code, chains, site_weights, size=None, method="auto", lds_width=0, hbm_width=0, tile_width=0):
+    """The class weights of every syndrome under a weight per qubit, or per (syndrome, qubit), on the GPU (qecmc_class_sweep_site, _cut_site,
+    _tiled_site).  code and chains as class_sweep takes them.  site_weights: float [..., 4], the weights of I, X, Y and Z at every cell
+    of the state layout, ... being the code's qubit_matrix shape or the flat nq; one table for all syndromes, or with a leading N one per syndrome.
+    Weights are finite and >= 0 -- zero is allowed, a qubit whose four weights are all zero is not; the planar code's unused cells are not read.
+    method: "sweep", "cut" (lds_width), "tiled" (hbm_width, tile_width) or "auto": the first of sweep, cut, tiled whose plan is accepted
+    (resolve_site_method).  This "auto" does reach the tiled sweep -- unlike exact_class_probabilities, whose routing is kept as it was: there is no
+    earlier answer to preserve here.
+    Returns dict(Z float64[N, ncls]: Z[s, c] = the sum over the chains of class c with the syndrome of chain s of the product over the qubits of the
+    weight of their Pauli there, cls int32[N], method: the one that ran, width, held)."""
+    code = _CODES.get(code, code)
+    if method not in _SITE_METHODS:
+        raise ValueError(f"method={method!r}: class_sweep_site runs {_SITE_METHODS[1:]} or 'auto'")
+    flat, L = _as_chains(code, chains, size)
+    n = flat.shape[0]
+    wq, rows = _as_site_weights(code, site_weights, L, n)
+    ran, info = resolve_site_method(code, L, method, lds_width, hbm_width, tile_width)
+    z = np.zeros((n, info["ncls"]), dtype=np.float64)
+    cls = np.zeros(n, dtype=np.int32)
+    f64p = C.POINTER(C.c_double)
+    head = (code, L, n, L_.u8(flat), wq.ctypes.data_as(f64p), rows)
+    tail = (z.ctypes.data_as(f64p), L_.i32(cls))
+    if ran == "sweep":
+        L_.check(L_.lib().qecmc_class_sweep_site(*head, *tail))
+    elif ran == "cut":
+        L_.check(L_.lib().qecmc_class_sweep_cut_site(*head, int(lds_width), *tail))
+    else:
+        L_.check(L_.lib().qecmc_class_sweep_tiled_site(*head, int(hbm_width), int(tile_width), *tail))
+    return dict(Z=z, cls=cls, method=ran, width=info["width"], held=info["held"])
+
+
+def exact_site_probabilities(code, chains, site_weights, **kw):
+    """float64[N, ncls]: the exact class law of every syndrome under site weights -- class_sweep_site's Z, which takes the keywords, normalised per
+    row.  Raises FloatingPointError where every class weight of a row is 0, as exact_class_probabilities does."""
+    z = class_sweep_site(code, chains, site_weights, **kw)["Z"]
+    tot = z.sum(axis=-1, keepdims=True)
+    if not np.all(tot > 0.0):
+        raise FloatingPointError("every class weight of a syndrome underflows to 0 in float64: the law of that row is not representable")
+    return z / tot
+
+
+def depolarizing_site_w4(p_map):
+    """depolarizing_w4 per cell of a map of error rates p_map [...]: float64[..., 4] = (1, f, f, f), f = (p / 3) / (1 - p).  Ratio form: Z differs from
+    the Z of the probabilities (1 - p, p / 3, p / 3, p / 3) by the factor prod_q (1 - p_q), common to all classes, so the law is unaffected."""
+    p = np.asarray(p_map, dtype=np.float64)
+    f = (p / 3.0) / (1.0 - p)
+    return np.stack([np.ones_like(f), f, f, f], axis=-1)
+
+
+def biased_site_w4(p_map, eta):
+    """biased_w4 per cell of a map of error rates p_map [...] (eta a number or a map): float64[..., 4] = (1, p_x / p_I, p_y / p_I, p_z / p_I).  Ratio
+    form: Z differs from the probability-form Z by the factor prod_q (1 - p_q), common to all classes, so the law is unaffected."""
+    p, eta = np.broadcast_arrays(np.asarray(p_map, dtype=np.float64), np.asarray(eta, dtype=np.float64))
+    rz, rx = p * eta / (eta + 1.0) / (1.0 - p), p / (2.0 * (eta + 1.0)) / (1.0 - p)
+    return np.stack([np.ones_like(rx), rx, rx, rz], axis=-1)
+
+
+def erasure_site_w4(base_w4, erased):
+    """site weights of a batch of shots with erasures: float64[erased.shape + (4,)].  base_w4: the weights off the erased sets, [4] (one for all
+    cells) or [..., 4]; erased: a bool mask [N, ...] or [...].  An erased cell carries a uniform Pauli and gets (1, 1, 1, 1).  Ratio form, as
+    the builders above: Z differs from the probability-form Z (1 / 4 each on an erased cell) by a factor common to all classes, so the law is
+    unaffected."""
+    erased = np.asarray(erased, dtype=bool)
+    out = np.array(np.broadcast_to(np.asarray(base_w4, dtype=np.float64), erased.shape + (4,)))
+    out[erased] = 1.0
+    return out
 
 
 _METHODS = ("auto", "enumerate", "sweep", "cut", "tiled")

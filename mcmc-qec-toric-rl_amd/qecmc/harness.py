@@ -218,8 +218,17 @@ def _exact_distr(params, chains, device):
     """params['method'] == "exact": the exact class law of every row (qecmc.exact_class_probabilities, DESIGN.md 4.1j .. 4.1m) under the weight of
     params['noise'] itself -- biased noise with the biased weight, whatever biased_decoder says; params['exact_method']: "auto" (default: coset
     enumeration where it takes the shape, the frontier sweep elsewhere, the cut-set sweep where both refuse), "enumerate", "sweep", "cut" or "tiled" (qecmc.exact) -- the sweep tiled
-    over HBM only where it is named, with params['hbm_width'] and params['tile_width'] (0: the defaults)"""
-    from .exact import exact_class_probabilities
+    over HBM only where it is named, with params['hbm_width'] and params['tile_width'] (0: the defaults).
+    params['site_weights'] (an array as qecmc.class_sweep_site takes it: [..., 4] per cell, with or without a leading n) replaces the weight of
+    params['noise'] by a weight per (row, qubit) -- erasures, a map of error rates, soft priors: the law is qecmc.exact_site_probabilities', with
+    params['exact_method'] "auto" (default: the first of sweep, cut, tiled that takes the shape), "sweep", "cut" or "tiled" and the widths above."""
+    from .exact import exact_class_probabilities, exact_site_probabilities
+    if params.get("site_weights") is not None:
+        if device != 0:
+            raise ValueError("method exact under site weights runs on device 0: the library has no device-pointer form of it yet")
+        return exact_site_probabilities(params["code"], chains, params["site_weights"], size=params["size"], method=params.get("exact_method", "auto"),
+                                        lds_width=int(params.get("lds_width", 0)), hbm_width=int(params.get("hbm_width", 0)),
+                                        tile_width=int(params.get("tile_width", 0)))
     noise = params.get("noise", "depolarizing")
     if _CODES[params["code"]] == L_.TORIC and noise != "depolarizing":
         raise ValueError(f"method exact on the toric code is defined for depolarizing noise, not {noise} (its errors are drawn without a bias)")
@@ -254,7 +263,8 @@ def decode_syndromes(params, defects, seed=0, steps=100000, conv_criteria="error
     class law does not depend on it, only the burn-in does.
     Returns dict(distr, counts, steps_done, converged, samples, tops0, chains, status, weight); raises if a syndrome is none of the code.
     params['method'] = "exact" decodes by coset enumeration instead (qecmc.exact_class_probabilities under the weight of params['noise'] itself;
-    params['chunk_bits'] optional): distr float64[n, ncls], chains, status, weight -- no counts, no run.
+    params['chunk_bits'] optional): distr float64[n, ncls], chains, status, weight -- no counts, no run.  params['site_weights'] is passed through:
+    the exact law under a weight per (row, qubit) (_exact_distr).
     corrections=True adds what a user who measured a syndrome wants (qecmc.corrections): target = argmax(distr) per row, correction -- a
     chain with the syndrome in that class --, correction_weight, correction_source and correction_moved.  The candidate is the lifted chain;
     correction_candidates="states" adds the Nc final rung states of every ladder as candidates 1 ..., where the route returns them: a fixed-length
@@ -301,6 +311,59 @@ def decode_syndromes(params, defects, seed=0, steps=100000, conv_criteria="error
         out.update(target=target, correction=cor["corrections"], correction_weight=cor["weight"], correction_source=cor["source"],
                    correction_moved=cor["moved"])
     return out
+
+
+def _qubit_cells(code, size):
+    """bool[...]: the cells of the state layout that hold a qubit -- all of them, but for the planar code's layer 1, which lives on its first
+    size - 1 rows and columns (planar_model.py:38-39)"""
+    code = _CODES.get(code, code)
+    cells = np.ones((2, size, size) if code in (L_.TORIC, L_.PLANAR) else (size, size), dtype=bool)
+    if code == L_.PLANAR:
+        cells[1, -1, :] = False
+        cells[1, :, -1] = False
+    return cells
+
+
+def draw_erasures(code, size, n, p_erase, rng):
+    """bool[n, ...]: every qubit of every shot erased independently with probability p_erase; the planar code's unused cells are never erased"""
+    cells = _qubit_cells(code, size)
+    return (rng.random((n,) + cells.shape) < p_erase) & cells
+
+
+def apply_erasures(m, erased, rng):
+    """the error chains m uint8[n, ...] with a uniform one of I, X, Y, Z put on every erased cell (whatever was there: an erased qubit is lost)"""
+    m = np.array(m, dtype=np.uint8)
+    erased = np.asarray(erased, dtype=bool)
+    m[erased] = rng.integers(0, 4, size=int(erased.sum()), dtype=np.uint8)
+    return m
+
+
+def erasure_experiment(params, n, seed=0):
+    """n shots of params['code'] at params['size'] under the noise of params (p_error, noise, eta as draw_errors takes them) AND erasures: every qubit
+    erased with probability params['p_erase'], an erased qubit carrying a uniform Pauli.  Decoded from the BARE syndromes by the maximum-likelihood
+    decoder that knows each shot's erased set: decode_syndromes, method exact, under qecmc.erasure_site_w4 of the noise's weights
+    (params['exact_method'] and the widths as _exact_distr takes them; p_error = 0 is the pure-erasure channel, weights (1, 0, 0, 0) off the set).
+    Returns dict(distr float64[n, ncls], eq_true: the class of the true error, success: argmax(distr) == eq_true, erased bool[n, ...], chains: the
+    start chains the syndromes were lifted to)."""
+    from .exact import alpha_w4, biased_w4, depolarizing_w4, erasure_site_w4
+    code, size, p = _CODES[params["code"]], params["size"], params["p_error"]
+    noise = params.get("noise", "depolarizing")
+    if noise not in ("depolarizing", "biased", "alpha"):
+        raise ValueError(f"noise={noise!r}")
+    rng = np.random.default_rng(seed)
+    if noise == "alpha":
+        errors = draw_errors(code, size, n, p, rng, rates=alpha_rates(p, params["alpha"]))
+        base = alpha_w4(p, params["alpha"])
+    else:
+        eta = params.get("eta") if noise == "biased" and code != L_.TORIC else None
+        errors = draw_errors(code, size, n, p, rng, eta=eta)
+        base = depolarizing_w4(p) if eta is None else biased_w4(p, eta)
+    erased = draw_erasures(code, size, n, params["p_erase"], rng)
+    errors = apply_erasures(errors, erased, rng)
+    decode = dict(params, method="exact", site_weights=erasure_site_w4(base, erased))
+    out = decode_syndromes(decode, syndrome_of(code, errors))
+    eq_true = np.asarray(_class_of(code, errors)).astype(np.int32)
+    return dict(distr=out["distr"], eq_true=eq_true, success=np.argmax(out["distr"], axis=1) == eq_true, erased=erased, chains=out["chains"])
 
 
 def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_criteria="error_based", biased_decoder="alpha",
