@@ -324,7 +324,9 @@ inline KernelKey choose_wave(const KernelShape &s)
 // SSW variant would be eligible (choose_ladder_toric: fixed length, depolarizing rule, at most 16 words, workgroups of up to 512 threads of which four fit
 // a CU -- the serial section is covered by the CU's other workgroups) the measurement decides, and it turns on the ladder's length alone, whatever the code
 // and the state width: once per workgroup gains 2.6 - 5.2 % at 5, 6 and 7 rungs and loses 0.5 - 3.8 % at 2, 3, 4 -- too few replays to pay
-// for the barrier -- and at 8, where a workgroup's waves fall on the same SIMDs in every workgroup of the CU.  QECMC_FLAG_NO_SSW (tune & 8): the replay.
+// for the barrier -- and at 8.  (Not because a workgroup's waves fall on the same SIMDs in every workgroup of a CU, as this comment once guessed: the starting
+// SIMD moves on by one from each workgroup of a CU to the next at 8 waves as at 5 - 7, profiles/r11_wave_placement.json; the loss at 8 is unexplained.)
+// QECMC_FLAG_NO_SSW (tune & 8): the replay.
 // A statistics launch (flags = kKeyStats) always replays: its waves count the pair each of them decides.
 inline bool wave_cascade_once(const KernelShape &s)
 {

@@ -485,10 +485,11 @@ __device__ __forceinline__ bool wu_pair_flips(const LadderArgs &a, uint32_t car,
 // a slot here, so its attribute is a register --, the floating-point swap test, the criterion on the logged count pairs.
 // STATS (ladder_wu_stats_kernel): the equilibrium observables of qecmc_plan_set_stats.  The wave of slot s >= 1 itself decides pair s - 1 when it
 // replays the cascade and ends the step holding its slot's record: two counters per lane, in registers (cx.swapc, cx.nsum), no LDS, no atomics.
+// LONG: the ladder may have more than 8 rungs (the kernels under the launch bound of 1 024 threads): up to four blocks of swap uniforms, one per wave.
 // SHORT (ladder_wu_shortest_kernel): the shortest-chain statistics of qecmc_plan_set_shortest (shortest_book.hpp) on the alpha rule's queue kernel, run with
 // one ladder per lane (wu_chunk = 64: no refill).  Wave 0, which ends a step holding rung 0's new state in registers, leaves that state's 64-bit key beside
 // bot / bot2; the booking wave, a step behind, applies the reference's rule to its lane's rows in LDS.  conv_mode NONE: the criterion is never consulted.
-template <int CODE, int WV, bool CONV, bool QUEUE, bool TOP, int IT, bool ALPHA, bool STATS = false, bool SHORT = false>
+template <int CODE, int WV, bool CONV, bool QUEUE, bool TOP, int IT, bool ALPHA, bool STATS = false, bool SHORT = false, bool LONG = true>
 __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::type &st, WuCtx &cx, const WuEnv &ev)
 {
     static_assert(!QUEUE || CONV, "the work queue serves the runs that stop by the criterion");
@@ -727,19 +728,37 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
         wu_lds_rw const recl = (wu_lds_rw)(uintptr_t)(xaddr + (uint32_t)ol.rec * 4u), swdl = recl + NC * 64;   // rec[lane], swd[lane]
         const uint32_t tb0 = lds0l + (uint32_t)ol.swapT * 4u;
         const int swb = NC - 1 - (int)slot;                 // the top rungs draw the swap uniforms: block swb = pairs 4 swb .. 4 swb + 3
+        // (the kernels of up to 8 rungs whose top role is the frame role: that role is the lightest of the workgroup by a third, so its wave draws both
+        // blocks such a ladder has -- the words are addressed by (T, block, ladder), the same in every wave -- and the waves below it carry neither the
+        // test nor the call: -1.7 % at 8 rungs, -2.8 % at 6.  LONG, the 1 024-thread kernels, keep a block per wave: +1.5 % at 12 rungs with the top
+        // wave drawing two)
+        constexpr bool TOPDRAWS = !LONG && wu_frame_steps(WV, CONV, ALPHA, IT) != 0;
         u32x4 sb{0, 0, 0, 0};
-        const bool duty = swb >= 0 && swb < 4 && swb * 4 < NC - 1;
-        if (duty) sb = wu_philox(T, (uint32_t)swb, syn, kSwapStream, a.seed_lo, a.seed_hi);
+        [[maybe_unused]] u32x4 sb1{0, 0, 0, 0};
+        [[maybe_unused]] bool duty = false;
+        if constexpr (TOPDRAWS && TOP) {
+            sb = wu_philox(T, 0u, syn, kSwapStream, a.seed_lo, a.seed_hi);
+            if (NC > 5) sb1 = wu_philox(T, 1u, syn, kSwapStream, a.seed_lo, a.seed_hi);
+        } else if constexpr (!TOPDRAWS) {
+            duty = swb >= 0 && swb < 4 && swb * 4 < NC - 1;
+            if (duty) sb = wu_philox(T, (uint32_t)swb, syn, kSwapStream, a.seed_lo, a.seed_hi);
+        }
+        auto put_block = [&](int blk, const u32x4 &v) {
+            wu_lds_rw p = swdl + (uint32_t)(blk * 4) * 64u;
+            const int left = NC - 1 - blk * 4;
+            p[0] = v.x;
+            if (left > 1) p[64] = v.y;
+            if (left > 2) p[128] = v.z;
+            if (left > 3) p[192] = v.w;
+        };
         __syncthreads();                                   // (everybody has read the exchange buffer, the records and the swap uniforms of the step before)
         wu_put_all<WV>(st, xaddr + slot * xstride);
         recl[slot * 64u] = pack_info(n4 >> 2, slot, cls, flag);
-        if (duty) {
-            wu_lds_rw p = swdl + (uint32_t)(swb * 4) * 64u;
-            const int left = NC - 1 - swb * 4;
-            p[0] = sb.x;
-            if (left > 1) p[64] = sb.y;
-            if (left > 2) p[128] = sb.z;
-            if (left > 3) p[192] = sb.w;
+        if constexpr (TOPDRAWS && TOP) {
+            put_block(0, sb);
+            if (NC > 5) put_block(1, sb1);
+        } else if constexpr (!TOPDRAWS) {
+            if (duty) put_block(swb, sb);
         }
         wu_ds_wait<WV>(st);                                 // (the asm stores of the exchange are not in the compiler's count)
         __syncthreads();
@@ -1065,7 +1084,7 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
 template <int MAXT, int MINW, int CODE, int WV, bool CONV, bool QUEUE, int IT, bool ALPHA = false>
 __global__ __launch_bounds__(MAXT, MINW) void ladder_wu_kernel(const LadderArgs a)
 {
-    constexpr bool STATS = false, SHORT = false;
+    constexpr bool STATS = false, SHORT = false, LONG = MAXT > 512;
 #include "ladder_wu_body.inc"
 }
 
@@ -1074,7 +1093,7 @@ __global__ __launch_bounds__(MAXT, MINW) void ladder_wu_kernel(const LadderArgs 
 template <int CODE, int WV, bool ALPHA>
 __global__ __launch_bounds__(1024, 4) void ladder_wu_stats_kernel(const LadderArgs a)
 {
-    constexpr bool STATS = true, CONV = false, QUEUE = false, SHORT = false;
+    constexpr bool STATS = true, CONV = false, QUEUE = false, SHORT = false, LONG = true;
     constexpr int IT = 0;
 #include "ladder_wu_body.inc"
 }
@@ -1084,7 +1103,7 @@ __global__ __launch_bounds__(1024, 4) void ladder_wu_stats_kernel(const LadderAr
 template <int CODE, int WV, int IT>
 __global__ __launch_bounds__(1024, 4) void ladder_wu_shortest_kernel(const LadderArgs a)
 {
-    constexpr bool STATS = false, CONV = true, QUEUE = true, ALPHA = true, SHORT = true;
+    constexpr bool STATS = false, CONV = true, QUEUE = true, ALPHA = true, SHORT = true, LONG = true;
 #include "ladder_wu_body.inc"
 }
 // (the transfer macros of wu_run's general tail, which the kernels' epilogue shares)

@@ -1,6 +1,6 @@
 // The body of the scan = 3 kernels (ladder_wu.hpp), included as text into ladder_wu_kernel and into ladder_wu_stats_kernel: the two are one program
 // under two names, told apart by the compile-time STATS alone (wrapped in a force-inlined function the body compiles to other code in the
-// kernels that sit at their register budget, DESIGN.md 7).  The includer provides CODE, WV, CONV, QUEUE, IT, ALPHA, STATS, SHORT and the argument `a`.
+// kernels that sit at their register budget, DESIGN.md 7).  The includer provides CODE, WV, CONV, QUEUE, IT, ALPHA, STATS, SHORT, LONG and the argument `a`.
     typedef typename WuVec<WV>::type vec_t;
     extern __shared__ uint32_t lds[];
     const int NC = a.Nc, W = a.W, L = a.L, nq = a.nq, ncls = a.ncls;
@@ -99,8 +99,8 @@
     ev.lane = lane; ev.chunk_hi = s1;
     // (the two roles are separate loops: they meet at the step's barriers)
     if constexpr (wu_frame_steps(WV, CONV, ALPHA, IT) != 0) wu_pin<WV>(st);
-    if (top) wu_run<CODE, WV, CONV, QUEUE, true, IT, ALPHA, STATS, SHORT>(a, st, cx, ev);
-    else wu_run<CODE, WV, CONV, QUEUE, false, IT, ALPHA, STATS, SHORT>(a, st, cx, ev);
+    if (top) wu_run<CODE, WV, CONV, QUEUE, true, IT, ALPHA, STATS, SHORT, LONG>(a, st, cx, ev);
+    else wu_run<CODE, WV, CONV, QUEUE, false, IT, ALPHA, STATS, SHORT, LONG>(a, st, cx, ev);
     if constexpr (wu_frame_steps(WV, CONV, ALPHA, IT) != 0) wu_pin<WV>(st);
     if constexpr (QUEUE) return;                                      // (every ladder wrote its results when it ended)
     if constexpr (STATS) {
