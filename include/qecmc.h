@@ -317,6 +317,22 @@ int qecmc_class_sweep_cut_site(int code, int L, uint64_t N, const uint8_t *chain
 int qecmc_class_sweep_tiled_site(int code, int L, uint64_t N, const uint8_t *chains, const double *wq, uint64_t wq_rows, int hbm_width,
                                  int tile_width, double *z_out, int32_t *class_out);
 
+/* ---- the shortest chain of every class and its multiplicity: the sweep in the (min, +, count) semiring (csrc/class_minplus.hpp) --------
+ * chains, N, lds_width and class_out as qecmc_class_sweep_cut takes them; the plans are that entry point's, unchanged, and
+ * qecmc_class_sweep_cut_info reports them.  cost[4]: the integer cost of I, X, Y and Z at one qubit, 0 .. 255 each; zero is allowed anywhere
+ * and so is a non-zero cost of I.  cost_out uint32[N][ncls]: cost_out[s][c] = the least sum over the qubits of cost[Pauli at q] among the
+ * chains of class c with the syndrome of chain s -- a cell that holds no qubit (the planar code's) does not enter; count_out uint64[N][ncls]:
+ * the number of chains of that class that reach it.  Integer arithmetic throughout: the result is exact and depends on the syndrome alone.
+ * A count is kept in 48 bits while the generator table is swept (every chain is met 2^(G - rank) times there: 4 on the torus); one that
+ * reaches 2^48 - 1 saturates, stays saturated and is reported as count_out = 0 -- a true count is never 0.
+ * At cost = (0, 1, 1, 1) the class of least cost is the minimum-weight decoder of depolarizing noise over Pauli chains (a Y costs 1).
+ * Additive: QECMC_ABI_VERSION stays.  Refused before a device is looked for, the message prefixed "qecmc_class_minplus:": a NULL chains /
+ * cost / cost_out / count_out or a cost above 255 with QECMC_ERR_INVALID, and whatever qecmc_class_sweep_cut refuses, with its code -- which
+ * leaves toric L = 3, 5, planar L = 3 .. 7 and xzzx / rotated L = 3 .. 11.  A device that does not grant 128 KiB of LDS to a workgroup answers
+ * QECMC_ERR_UNSUPPORTED at width 14.  N == 0 succeeds.  Host pointers only. */
+int qecmc_class_minplus(int code, int L, uint64_t N, const uint8_t *chains, const uint32_t cost[4], int lds_width, uint32_t *cost_out,
+                        uint64_t *count_out, int32_t *class_out);
+
 /* ---- chain / ladder on caller-owned state (host pointers) ----------------- */
 
 /* The supported range of a start index.  A Philox counter holds a proposal index (the swap stream: a ladder-step index) in 48 bits,

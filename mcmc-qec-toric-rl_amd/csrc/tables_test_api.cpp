@@ -7,6 +7,7 @@
 #include "class_sweep_cut.hpp"
 #include "class_sweep_tiled.hpp"
 #include "class_sweep_site.hpp"
+#include "class_minplus.hpp"
 #include "corrections.hpp"
 #include "enumerate.hpp"
 #include "kernel_choice.hpp"
@@ -426,6 +427,25 @@ int qt_class_sweep_tiled_site(int code, int L, uint64_t N, const uint8_t *chains
     if (const Refusal r = site_checks(N, wq, wq_rows, tp.plan.nq, tp.ops); r.code) return site_answer(r, msg, msg_cap);
     sweep::sweep_tiled_site_host(tp, N, chains, wq, wq_rows, z, cls);
     return site_answer({}, msg, msg_cap);
+}
+// the (min, +, count) sweep (class_minplus.hpp).  qt_class_minplus: the host twin of qecmc_class_minplus behind the same host checks, in the same
+// order -- the QECMC_ERR_* code of the refusal, its message in msg (nullable); qt_minplus_combine: mp_combine on two packed entries, and through out3
+// (nullable) kSat, the bits of a count and the largest cost
+int qt_class_minplus(int code, int L, uint64_t N, const uint8_t *chains, const uint32_t *cost, int lds_width, uint32_t *cost_out, uint64_t *count_out, int32_t *cls,
+                     char *msg, int msg_cap)
+{
+    if (!chains || !cost || !cost_out || !count_out) return site_answer(refuse_params(QECMC_ERR_INVALID, "qecmc_class_minplus: NULL buffer"), msg, msg_cap);
+    if (N > 0xFFFFFFFFull) return site_answer(refuse_params(QECMC_ERR_INVALID, "qecmc_class_minplus: N=%llu syndromes exceed 32 bits", (unsigned long long)N), msg, msg_cap);
+    if (const Refusal r = minplus::check_costs(cost); r.code) return site_answer(r, msg, msg_cap);
+    const sweep::CutPlan cp = minplus::build_minplus_plan(code, L, lds_width);
+    if (cp.plan.refusal.code) return site_answer(cp.plan.refusal, msg, msg_cap);
+    minplus::minplus_cut_host(cp, N, chains, cost, cost_out, count_out, cls);
+    return site_answer({}, msg, msg_cap);
+}
+uint64_t qt_minplus_combine(uint64_t a, uint64_t b, uint64_t *out3)
+{
+    if (out3) { out3[0] = minplus::kSat; out3[1] = (uint64_t)minplus::kCountBits; out3[2] = minplus::kMaxCost; }
+    return minplus::mp_combine(a, b);
 }
 // the top rung's frames of a pick window (wu_frames.hpp) for an accepted scan = wave block, from the window's 64 pick blocks picks[64][4]: the plan's
 // descriptors and logical masks (rows padded to the kernel's WV words, as the kernel stages them), thr16 from the plan's thr_logical as wu_run forms it.

@@ -15,7 +15,11 @@ L = 12 and, with five generators held, the toric code at L = 7.  It runs only wh
 
 The three sweeps under a weight per (syndrome, qubit) (qecmc_class_sweep_site, _cut_site, _tiled_site): class_sweep_site and
 exact_site_probabilities take a table of weights in place of the four numbers -- erasures (erasure_site_w4), a map of error rates
-(depolarizing_site_w4, biased_site_w4), any per-shot prior -- at every shape the uniform sweeps reach."""
+(depolarizing_site_w4, biased_site_w4), any per-shot prior -- at every shape the uniform sweeps reach.
+
+The shortest chain of every class and its multiplicity (qecmc_class_minplus): the cut-set sweep's plans in the semiring of
+(cost, count) pairs under (min, +), integer and exact -- class_minplus, the minimum-weight decoder min_weight_classes, and shortest_class_law, the
+exact value of what the shortest-chain estimators converge to."""
 import ctypes as C
 
 import numpy as np
@@ -121,6 +125,75 @@ def class_sweep_cut(code, chains, weights, size=None, lds_width=0):
     f64p = C.POINTER(C.c_double)
     L_.check(L_.lib().qecmc_class_sweep_cut(code, L, n, L_.u8(flat), w.ctypes.data_as(f64p), int(lds_width), z.ctypes.data_as(f64p), L_.i32(cls)))
     return dict(Z=z, cls=cls, width=info["width"], held=info["held"])
+
+
+def class_minplus(code, chains, costs=(0, 1, 1, 1), size=None, lds_width=0):
+    """The least cost of every class of every syndrome and the number of chains that reach it, on the GPU (qecmc_class_minplus):
+    class_sweep_cut's plans run in the semiring of (cost, count) pairs under (min, +), in integers.  code and chains as class_sweep_cut takes them;
+    costs: the integer costs of I, X, Y and Z at one qubit, 0 .. 255 each (the default counts the errors of a chain); lds_width as
+    class_sweep_cut's.  Shapes: toric L = 3, 5, planar L = 3 .. 7, xzzx / rotated L = 3 .. 11.
+    Returns dict(cost uint32[N, ncls]: the least sum of costs over the chains of class c with the syndrome of chain s, count uint64[N, ncls]: how many
+    chains of the class reach it -- 0 where saturated --, saturated bool[N, ncls]: the count passed 2^48 - 1 on the way (on the torus 2^46 - 1: the
+    generator table meets every chain four times) and is not known, cls int32[N]: the class of each input chain, width, held: the cut plan's)."""
+    code = _CODES.get(code, code)
+    flat, L = _as_chains(code, chains, size)
+    c = np.asarray(costs, dtype=np.float64)
+    if c.shape != (4,) or not np.all((c >= 0) & (c <= 0xFFFFFFFF) & (c == np.floor(c))):
+        raise ValueError(f"costs={costs!r}: the four integer costs of I, X, Y and Z, each >= 0")
+    c = c.astype(np.uint32)
+    n, ncls = flat.shape[0], 16 if code == L_.TORIC else 4
+    cost = np.zeros((n, ncls), dtype=np.uint32)
+    count = np.zeros((n, ncls), dtype=np.uint64)
+    cls = np.zeros(n, dtype=np.int32)
+    L_.check(L_.lib().qecmc_class_minplus(code, L, n, L_.u8(flat), c.ctypes.data_as(L_._u32p), int(lds_width), cost.ctypes.data_as(L_._u32p),
+                                          count.ctypes.data_as(L_._u64p), L_.i32(cls)))
+    info = sweep_cut_info(code, L, lds_width)
+    return dict(cost=cost, count=count, saturated=count == 0, cls=cls, width=info["width"], held=info["held"])
+
+
+def _rank_classes(cost, count):
+    """int32[N]: the class of least cost, ties broken by the larger count, then by the lower class index (a saturated count, reported as 0, counts as the
+    largest)"""
+    cost = np.asarray(cost, dtype=np.int64)
+    count = np.asarray(count, dtype=np.uint64)
+    ncls = cost.shape[1]
+    big = np.where(count == 0, np.uint64(1) << np.uint64(48), count)
+    order = np.lexsort((np.broadcast_to(np.arange(ncls), cost.shape), -big.astype(np.int64), cost), axis=1)     # (last key first: cost, then count, then index)
+    return order[:, 0].astype(np.int32)
+
+
+def min_weight_classes(code, chains, costs=(0, 1, 1, 1), size=None, lds_width=0):
+    """int32[N]: the class class_minplus gives the least cost -- ties broken by the larger count, then by the lower class index.  At the default costs
+    this is the minimum-weight decoder of depolarizing noise over Pauli chains: a Y costs 1, which matching on separate X and Z graphs cannot say."""
+    r = class_minplus(code, chains, costs, size=size, lds_width=lds_width)
+    return _rank_classes(r["cost"], r["count"])
+
+
+def _law_from_minplus(cost, count, saturated, base):
+    """count * base^(cost - the row's least cost), normalised per row; OverflowError naming the first saturated row"""
+    if np.any(saturated):
+        row = int(np.flatnonzero(np.any(saturated, axis=1))[0])
+        raise OverflowError(f"row {row}: a count of shortest chains passed 2^48 - 1 and is not known (class_minplus reports it as saturated)")
+    rel = (cost.astype(np.int64) - cost.astype(np.int64).min(axis=1, keepdims=True)).astype(np.float64)
+    z = count.astype(np.float64) * np.power(float(base), rel)
+    return z / z.sum(axis=1, keepdims=True)
+
+
+def shortest_class_law(code, chains, p, alpha=None, **kw):
+    """float64[N, ncls]: the class law carried by the shortest chains alone, count_c * base^cost_c normalised per row (class_minplus, which takes the
+    keywords size and lds_width) -- computed relative to the row's least cost, so nothing underflows.  Depolarizing noise p: unit costs,
+    base = (p / 3) / (1 - p).  The alpha model (p is pz_tilde) with an integer-valued alpha: costs (0, alpha, alpha, 1), base = pz_tilde; a
+    non-integer alpha raises ValueError.  A row with a saturated count raises OverflowError naming it.
+    This is the exact value of the second vector of shortest_distribution (unique_n * exp(-beta * shortest), there in percent) once its ladder has
+    seen every shortest chain of every class, and the low-p limit of exact_class_probabilities."""
+    if alpha is None:
+        costs, base = (0, 1, 1, 1), (p / 3.0) / (1.0 - p)
+    else:
+        if float(alpha) != np.floor(float(alpha)) or not 0 <= float(alpha) <= 255:
+            raise ValueError(f"alpha={alpha!r}: shortest_class_law takes integer costs, so an integer-valued alpha in 0 .. 255 (non-integer costs are out of scope)")
+        costs, base = (0, int(alpha), int(alpha), 1), float(p)
+    r = class_minplus(code, chains, costs, **kw)
+    return _law_from_minplus(r["cost"], r["count"], r["saturated"], base)
 
 
 def sweep_tiled_info(code, size, hbm_width=0, tile_width=0):

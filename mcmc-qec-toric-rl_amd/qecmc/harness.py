@@ -239,6 +239,24 @@ def _exact_distr(params, chains, device):
                                      device=device, method=params.get("exact_method", "auto"), **kw)
 
 
+def _min_weight_distr(params, chains, device):
+    """params['method'] == "min_weight": the class law carried by the shortest chains alone (qecmc.shortest_class_law) -- exact, by the
+    (min, +, count) sweep: under depolarizing noise count * ((p / 3) / (1 - p))^(errors of the shortest chain), under the alpha model (an
+    integer-valued params['alpha']) count * pz_tilde^(n_z + alpha n_xy).  Its argmax weighs a class's shortest chains by their number; as p -> 0 it is
+    qecmc.min_weight_classes, the minimum-weight decoder.  params['lds_width'] (0: the default) as qecmc.class_minplus takes it.  Biased noise is
+    refused: its weights are no integer powers of one base."""
+    from .exact import shortest_class_law
+    noise = params.get("noise", "depolarizing")
+    if noise == "biased":
+        raise ValueError("method min_weight is defined for depolarizing and alpha noise, not biased: the biased weights are no integer powers of one base")
+    if _CODES[params["code"]] == L_.TORIC and noise != "depolarizing":
+        raise ValueError(f"method min_weight on the toric code is defined for depolarizing noise, not {noise} (its errors are drawn without a bias)")
+    if device != 0:
+        raise ValueError("method min_weight runs on device 0: the library has no device-pointer form of it yet")
+    return shortest_class_law(params["code"], chains, params["p_error"], alpha=params["alpha"] if noise == "alpha" else None, size=params["size"],
+                              lds_width=int(params.get("lds_width", 0)))
+
+
 def _corrections_for(code, size, candidates, distr, device):
     """the correction of every row towards target = argmax(distr) -- the very expression `success` uses -- from candidates [n, K, ...] or [n, ...]"""
     from .syndrome_corrections import corrections as correct
@@ -264,15 +282,16 @@ def decode_syndromes(params, defects, seed=0, steps=100000, conv_criteria="error
     Returns dict(distr, counts, steps_done, converged, samples, tops0, chains, status, weight); raises if a syndrome is none of the code.
     params['method'] = "exact" decodes by coset enumeration instead (qecmc.exact_class_probabilities under the weight of params['noise'] itself;
     params['chunk_bits'] optional): distr float64[n, ncls], chains, status, weight -- no counts, no run.  params['site_weights'] is passed through:
-    the exact law under a weight per (row, qubit) (_exact_distr).
+    the exact law under a weight per (row, qubit) (_exact_distr).  params['method'] = "min_weight" returns the same keys with distr the law of the
+    shortest chains alone (_min_weight_distr).
     corrections=True adds what a user who measured a syndrome wants (qecmc.corrections): target = argmax(distr) per row, correction -- a
     chain with the syndrome in that class --, correction_weight, correction_source and correction_moved.  The candidate is the lifted chain;
     correction_candidates="states" adds the Nc final rung states of every ladder as candidates 1 ..., where the route returns them: a fixed-length
     run (conv_criteria=None).  A run the convergence criterion stops may go to the work-queue kernels, which write no final states: ValueError."""
     from .syndrome_lift import chains_from_syndromes
     method = params.get("method", "PTEQ")
-    if method not in ("PTEQ", "exact"):
-        raise ValueError("decode_syndromes decodes with PTEQ or exact (params['method'])")
+    if method not in ("PTEQ", "exact", "min_weight"):
+        raise ValueError("decode_syndromes decodes with PTEQ, exact or min_weight (params['method'])")
     noise = params.get("noise", "depolarizing")
     if noise not in ("depolarizing", "biased", "alpha"):
         raise ValueError(f"noise={noise!r}")
@@ -285,10 +304,11 @@ def decode_syndromes(params, defects, seed=0, steps=100000, conv_criteria="error
     if correction_candidates not in ("lift", "states"):
         raise ValueError(f"correction_candidates={correction_candidates!r}")
     with_states = bool(corrections) and correction_candidates == "states"
-    if method == "exact":
+    if method in ("exact", "min_weight"):
         if with_states:
-            raise ValueError("correction_candidates='states': method exact runs no ladder; keep the lifted chain")
-        out = dict(distr=_exact_distr(params, chains, int(pteq_kw.get("device", 0))), chains=chains, status=status, weight=weight)
+            raise ValueError(f"correction_candidates='states': method {method} runs no ladder; keep the lifted chain")
+        distr_of = _exact_distr if method == "exact" else _min_weight_distr
+        out = dict(distr=distr_of(params, chains, int(pteq_kw.get("device", 0))), chains=chains, status=status, weight=weight)
         if corrections:
             target, cor = _corrections_for(_CODES[params["code"]], params["size"], chains, out["distr"], int(pteq_kw.get("device", 0)))
             out.update(target=target, correction=cor["corrections"], correction_weight=cor["weight"], correction_source=cor["source"],
@@ -382,14 +402,17 @@ def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_
     syndrome by coset enumeration on the device (qecmc.exact_class_probabilities) under the weight of params['noise'] itself --
     biased noise with the biased weight, whatever biased_decoder says --, with success and no counts; start="syndrome" and corrections=True work
     on top of it; `steps` and the sampler keywords are not looked at.
+    params['method'] = "min_weight" decodes by the shortest chains: distr float64[n, ncls] is the law carried by the shortest chains of every class
+    alone, exact (qecmc.shortest_class_law; depolarizing noise, or alpha noise with an integer alpha; biased noise is refused), with
+    success and no counts; start="syndrome" and corrections=True work as they do for "exact".
     device_generation=True draws the errors and the hiding logical operator on the GPU (`generate_syndromes`) instead of NumPy.
     start="error" (default) is the reference's recipe: the decoder starts from the error with a random logical operator on top.  start="syndrome"
-    (methods PTEQ and exact) lets nothing but syndrome(raw) reach the decoder: the start chains are qecmc.chains_from_syndromes of it and no logical
+    (methods PTEQ, exact and min_weight) lets nothing but syndrome(raw) reach the decoder: the start chains are qecmc.chains_from_syndromes of it and no logical
     operator is drawn; eq_true and the success rule are the same.
     metrics="basic" (default) costs nothing: throughput, convergence, burn-in and success figures.  metrics="full" also attaches the
     mixing counters (swap acceptance per rung pair, mean error count per rung) -- which rule out the work-queue kernels
     (their lanes run several ladders) and need nq * steps < 2^32, so they are dropped, not failed on, where they do not fit.
-    corrections=True (methods PTEQ and exact) closes the loop: correction uint8[n,...] is qecmc.corrections of the start chain -- the seed configuration, or the
+    corrections=True (methods PTEQ, exact and min_weight) closes the loop: correction uint8[n,...] is qecmc.corrections of the start chain -- the seed configuration, or the
     lifted chain of start="syndrome" -- towards argmax(distr), correction_weight its error count, and success_correction[s] is true iff
     raw[s] ^ correction[s] (byte values XOR as the Pauli product) is a stabilizer: an all-zero syndrome and the class of the zero chain.
     Returns (and optionally saves as npz) qubit_matrix uint8[n,...] (the raw errors, generate_data.py:120),
@@ -406,10 +429,12 @@ def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_
     method = params.get("method", "PTEQ")
     if start not in ("error", "syndrome"):
         raise ValueError(f"start={start!r}")
-    if start == "syndrome" and method not in ("PTEQ", "exact"):
-        raise ValueError(f"start='syndrome' is built for methods PTEQ and exact, not {method}")
-    if corrections and method not in ("PTEQ", "exact"):
-        raise ValueError(f"corrections=True is built for methods PTEQ and exact, not {method}")
+    if start == "syndrome" and method not in ("PTEQ", "exact", "min_weight"):
+        raise ValueError(f"start='syndrome' is built for methods PTEQ, exact and min_weight, not {method}")
+    if corrections and method not in ("PTEQ", "exact", "min_weight"):
+        raise ValueError(f"corrections=True is built for methods PTEQ, exact and min_weight, not {method}")
+    if method == "min_weight" and noise == "biased":
+        raise ValueError("method min_weight is defined for depolarizing and alpha noise, not biased: the biased weights are no integer powers of one base")
     if device_generation:
         # errors, true class and the hiding logical operator drawn on the GPU (Philox keyed by the global syndrome index: the data
         # set does not depend on how it is cut into shards)
@@ -435,8 +460,8 @@ def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_
         if file_path is not None:
             np.savez_compressed(file_path, params=np.array([repr(params)]), **out)
         return out
-    if method == "exact":
-        distr = _exact_distr(params, init, int(pteq_kw.get("device", 0)))
+    if method in ("exact", "min_weight"):
+        distr = (_exact_distr if method == "exact" else _min_weight_distr)(params, init, int(pteq_kw.get("device", 0)))
         out = dict(qubit_matrix=raw, eq_true=eq_true, distr=distr, success=np.argmax(distr, axis=1) == eq_true)
         if corrections:
             out.update(_correction_outputs(code, size, raw, init, distr, int(pteq_kw.get("device", 0))))
