@@ -333,6 +333,20 @@ int qecmc_class_sweep_tiled_site(int code, int L, uint64_t N, const uint8_t *cha
 int qecmc_class_minplus(int code, int L, uint64_t N, const uint8_t *chains, const uint32_t cost[4], int lds_width, uint32_t *cost_out,
                         uint64_t *count_out, int32_t *class_out);
 
+/* ---- a shortest chain of every class: the (min, +) sweep traced back (csrc/class_minplus_trace.hpp) --------
+ * The arguments and shapes of qecmc_class_minplus, and one more output: chain_out uint8[N][ncls][nq], chain_out[s][c] a chain with the
+ * syndrome of chain s, in class c, whose cost is cost_out[s][c] -- bytes 0 .. 3 for I, X, Y, Z, the format of the input; a cell no
+ * generator touches keeps the byte of the class representative.  cost_out and count_out are qecmc_class_minplus's, exactly; they and
+ * class_out may be NULL.  The chain is a function of (plan, input chain, cost) alone.  Where count_out == 1 it is the one shortest chain
+ * of the class and depends on the syndrome alone; where several chains tie, the one returned is selected by a fixed rule (of the
+ * assignments of the held generators the lowest that reaches the least cost; a generator is applied only where that is strictly
+ * cheaper) FROM THE INPUT CHAIN: another chain with the same syndrome may select another of the tied chains.  A saturated count does not
+ * touch the chain.  Additive: QECMC_ABI_VERSION stays.  Refused before a device is looked for, the message prefixed
+ * "qecmc_class_minplus_chains:": what qecmc_class_minplus refuses, with its codes (a NULL chains / cost / chain_out here).  N == 0
+ * succeeds.  Host pointers only; device 0. */
+int qecmc_class_minplus_chains(int code, int L, uint64_t N, const uint8_t *chains, const uint32_t cost[4], int lds_width, uint8_t *chain_out,
+                               uint32_t *cost_out, uint64_t *count_out, int32_t *class_out);
+
 /* ---- chain / ladder on caller-owned state (host pointers) ----------------- */
 
 /* The supported range of a start index.  A Philox counter holds a proposal index (the swap stream: a ladder-step index) in 48 bits,

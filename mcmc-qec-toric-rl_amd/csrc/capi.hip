@@ -26,6 +26,7 @@
 #include "class_sweep_tiled.hpp"
 #include "class_sweep_site.hpp"
 #include "class_minplus.hpp"
+#include "class_minplus_trace.hpp"
 #include "enumerate.hpp"
 #include "syndrome_lift.hpp"
 #include "tables.hpp"
@@ -771,6 +772,66 @@ int qecmc_class_minplus(int code, int L, uint64_t N, const uint8_t *chains, cons
         HIP_TRY(launch_class_minplus(a, dops.as<uint32_t>(), dheld.as<uint32_t>(), dreps.as<uint32_t>(), dpart.as<uint64_t>(), dcost.as<uint32_t>(), dcount.as<uint64_t>(), 0));
         HIP_TRY(hipMemcpy(cost_out + first * (uint64_t)p.ncls, dcost.p, (size_t)here * p.ncls * sizeof(uint32_t), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(count_out + first * (uint64_t)p.ncls, dcount.p, (size_t)here * p.ncls * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- a shortest chain per class: the (min, +) sweep traced back (class_minplus_trace.hpp)
+int qecmc_class_minplus_chains(int code, int L, uint64_t N, const uint8_t *chains, const uint32_t cost[4], int lds_width, uint8_t *chain_out, uint32_t *cost_out,
+                               uint64_t *count_out, int32_t *class_out)
+{
+    if (!chains || !cost || !chain_out) return fail(QECMC_ERR_INVALID, "qecmc_class_minplus_chains: NULL buffer");
+    if (N > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "qecmc_class_minplus_chains: N=%llu syndromes exceed 32 bits", (unsigned long long)N);
+    if (int rc = report(minplus::check_chain_costs(cost))) return rc;
+    const minplus::TracePlan tp = minplus::build_trace_plan(code, L, lds_width);
+    const sweep::CutPlan &cp = tp.cut;
+    const sweep::Plan &p = cp.plan;
+    if (int rc = report(p.refusal)) return rc;
+    if (int rc = use_device(0)) return rc;
+    if (N == 0) return 0;
+    if (class_minplus_allow_lds(p.width) != hipSuccess || class_minplus_trace_allow_lds(p.width) != hipSuccess)
+        return fail(QECMC_ERR_UNSUPPORTED, "qecmc_class_minplus_chains: this device does not grant a workgroup the %u bytes of LDS a state vector of width %d takes",
+                    p.carve.bytes, p.width);
+    const uint64_t pair_bytes = minplus::trace_bytes_per_pair(tp);
+    const uint32_t group = minplus::trace_launch_group(N, p.ncls, cp.n_held, pair_bytes);
+    const size_t rep_words = (size_t)p.ncls * p.W, partials = (size_t)p.ncls << cp.n_held;   // of one syndrome
+    std::vector<uint32_t> reps((size_t)group * rep_words);
+    DevBuf dops, dheld, dreps, dforget, dpart, dpick, ddec, dchain, dcost, dcount;
+    HIP_TRY(dops.alloc(p.ops.size() * sizeof(uint32_t)));
+    HIP_TRY(dheld.alloc(cp.held_words.size() * sizeof(uint32_t)));
+    HIP_TRY(dreps.alloc(reps.size() * sizeof(uint32_t)));
+    HIP_TRY(dforget.alloc(tp.forget_words.size() * sizeof(uint32_t)));
+    HIP_TRY(dpart.alloc((size_t)group * partials * sizeof(uint64_t)));          // dirty: every partial is written before it is read
+    HIP_TRY(dpick.alloc((size_t)group * p.ncls * sizeof(uint32_t)));
+    HIP_TRY(ddec.alloc((size_t)group * p.ncls * (size_t)pair_bytes));           // kTraceWorkspaceBytes at most; dirty: the walk reads what the trace wrote
+    HIP_TRY(dchain.alloc((size_t)group * p.ncls * p.nq));
+    HIP_TRY(dcost.alloc((size_t)group * p.ncls * sizeof(uint32_t)));
+    HIP_TRY(dcount.alloc((size_t)group * p.ncls * sizeof(uint64_t)));
+    HIP_TRY(hipMemcpy(dops.p, p.ops.data(), p.ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (cp.n_held) HIP_TRY(hipMemcpy(dheld.p, cp.held_words.data(), cp.held_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dforget.p, tp.forget_words.data(), tp.forget_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    MinplusTraceArgs t = {};
+    MinplusArgs &a = t.m;
+    a.ncls = p.ncls; a.W = p.W; a.width = p.width; a.n_ops = p.n_ops; a.n_held = cp.n_held; a.shift = p.n_gen - p.rank;
+    minplus::costs_xz(cost, a.cxz);
+    t.n_forget = tp.n_forget; t.words_per_forget = tp.words_per_forget; t.nq = p.nq;
+    // the host loops over groups of syndromes: no launch, and no device block, grows with the batch
+    for (uint64_t first = 0; first < N; first += group) {
+        const uint64_t here = N - first < group ? N - first : group;
+        for (uint64_t s = 0; s < here; ++s) {
+            const int cls = sweep::class_representatives(p, chains + (first + s) * (uint64_t)p.nq, reps.data() + s * rep_words);
+            if (class_out) class_out[first + s] = cls;
+        }
+        HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * rep_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+        a.S = (uint32_t)here;
+        HIP_TRY(launch_class_minplus_sweep(a, dops.as<uint32_t>(), dheld.as<uint32_t>(), dreps.as<uint32_t>(), dpart.as<uint64_t>(), 0));
+        HIP_TRY(launch_minplus_pick(a, dpart.as<uint64_t>(), dpick.as<uint32_t>(), 0));            // (before the reduce folds the partials in place)
+        HIP_TRY(launch_class_minplus_reduce(a, dpart.as<uint64_t>(), dcost.as<uint32_t>(), dcount.as<uint64_t>(), 0));
+        HIP_TRY(launch_minplus_trace(t, dops.as<uint32_t>(), dheld.as<uint32_t>(), dreps.as<uint32_t>(), dforget.as<uint32_t>(), dpick.as<uint32_t>(), ddec.as<uint64_t>(),
+                                     dchain.as<uint8_t>(), 0));
+        HIP_TRY(hipMemcpy(chain_out + first * (uint64_t)p.ncls * (uint64_t)p.nq, dchain.p, (size_t)here * p.ncls * p.nq, hipMemcpyDeviceToHost));
+        if (cost_out) HIP_TRY(hipMemcpy(cost_out + first * (uint64_t)p.ncls, dcost.p, (size_t)here * p.ncls * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (count_out) HIP_TRY(hipMemcpy(count_out + first * (uint64_t)p.ncls, dcount.p, (size_t)here * p.ncls * sizeof(uint64_t), hipMemcpyDeviceToHost));
     }
     return 0;
 }

@@ -10,7 +10,9 @@
 // k_class_minplus_reduce: workgroup blockIdx.x = syndrome * ncls + class combines its 2^n_held partials in place with mp_combine -- associative and
 // commutative, so the order is free; it folds the held bits in ascending order, one barrier per bit --, then unpacks, shifts the count by
 // n_gen - rank, reports a saturated count as 0 and writes cost_out and count_out.  It also runs when n_held = 0.  It is launched on the same stream
-// after the sweep kernel: stream order is the only synchronisation, there are no flags and no atomics.
+// after the sweep kernel: stream order is the only synchronisation, there are no flags and no atomics.  Either kernel has a host function of its own
+// (launch_class_minplus_sweep, launch_class_minplus_reduce; launch_class_minplus calls both): the traceback (class_minplus_trace.hip) reads the partials
+// between the two.
 //
 // A state vector beyond 64 KiB (width 14: 128 KiB, one workgroup per CU) needs the kernel's dynamic-LDS limit raised.  That limit is an attribute of
 // each kernel: class_sweep_cut_allow_lds raises it for k_class_sweep_cut only, so this unit asks for its own kernel, once per device, and answers
@@ -101,20 +103,35 @@ hipError_t class_minplus_allow_lds(int width)
     return state[dev] == 1 ? hipSuccess : hipErrorInvalidValue;
 }
 
+static bool minplus_args_ok(const MinplusArgs &a)
+{
+    return (a.ncls == 4 || a.ncls == 16) && sweep::cut_fits(a.width) && a.W >= 1 && a.n_ops >= 1 && a.n_held >= 0 && a.n_held <= sweep::kMaxHeld && a.shift >= 0 &&
+           a.shift < minplus::kCountBits && a.S <= sweep::cut_launch_group(a.S, a.ncls, a.n_held);
+}
+
+hipError_t launch_class_minplus_sweep(const MinplusArgs &a, const uint32_t *ops, const uint32_t *held, const uint32_t *reps, uint64_t *P, hipStream_t stream)
+{
+    if (a.S == 0) return hipSuccess;
+    if (!minplus_args_ok(a)) return hipErrorInvalidValue;
+    const sweep::Carve carve = sweep::lds_carve(a.width);
+    if (hipError_t e = class_minplus_allow_lds(a.width)) return e;
+    hipLaunchKernelGGL(k_class_minplus, dim3((a.S * (uint32_t)a.ncls) << a.n_held), dim3(sweep::cut_threads(a.width)), carve.bytes, stream, a, ops, held, reps, P);
+    return hipGetLastError();
+}
+
+hipError_t launch_class_minplus_reduce(const MinplusArgs &a, uint64_t *P, uint32_t *cost_out, uint64_t *count_out, hipStream_t stream)
+{
+    if (a.S == 0) return hipSuccess;
+    if (!minplus_args_ok(a)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_class_minplus_reduce, dim3(a.S * (uint32_t)a.ncls), dim3(sweep::kThreads), 0, stream, a, P, cost_out, count_out);
+    return hipGetLastError();
+}
+
 hipError_t launch_class_minplus(const MinplusArgs &a, const uint32_t *ops, const uint32_t *held, const uint32_t *reps, uint64_t *P, uint32_t *cost_out, uint64_t *count_out,
                                 hipStream_t stream)
 {
-    if (a.S == 0) return hipSuccess;
-    if ((a.ncls != 4 && a.ncls != 16) || !sweep::cut_fits(a.width) || a.W < 1 || a.n_ops < 1 || a.n_held < 0 || a.n_held > sweep::kMaxHeld || a.shift < 0 ||
-        a.shift >= minplus::kCountBits || a.S > sweep::cut_launch_group(a.S, a.ncls, a.n_held))
-        return hipErrorInvalidValue;
-    const sweep::Carve carve = sweep::lds_carve(a.width);
-    if (hipError_t e = class_minplus_allow_lds(a.width)) return e;
-    const uint32_t pairs = a.S * (uint32_t)a.ncls;
-    hipLaunchKernelGGL(k_class_minplus, dim3(pairs << a.n_held), dim3(sweep::cut_threads(a.width)), carve.bytes, stream, a, ops, held, reps, P);
-    if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL(k_class_minplus_reduce, dim3(pairs), dim3(sweep::kThreads), 0, stream, a, P, cost_out, count_out);
-    return hipGetLastError();
+    if (hipError_t e = launch_class_minplus_sweep(a, ops, held, reps, P, stream)) return e;
+    return launch_class_minplus_reduce(a, P, cost_out, count_out, stream);
 }
 
 }  // namespace qecmc

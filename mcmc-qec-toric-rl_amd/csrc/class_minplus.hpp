@@ -168,5 +168,8 @@ struct MinplusArgs {
 hipError_t class_minplus_allow_lds(int width);         // hipSuccess: a state vector of this width can be launched on the current device
 hipError_t launch_class_minplus(const MinplusArgs &a, const uint32_t *ops, const uint32_t *held, const uint32_t *reps, uint64_t *P, uint32_t *cost_out, uint64_t *count_out,
                                 hipStream_t stream);
+// its two launches, one each: class_minplus_trace.hip reads the partials between them (the reduce folds them in place)
+hipError_t launch_class_minplus_sweep(const MinplusArgs &a, const uint32_t *ops, const uint32_t *held, const uint32_t *reps, uint64_t *P, hipStream_t stream);
+hipError_t launch_class_minplus_reduce(const MinplusArgs &a, uint64_t *P, uint32_t *cost_out, uint64_t *count_out, hipStream_t stream);
 
 }  // namespace qecmc

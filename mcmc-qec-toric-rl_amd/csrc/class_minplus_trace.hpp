@@ -1,0 +1,249 @@
+// A shortest chain of every class: the (min, +) sweep of class_minplus.hpp traced back.  The sweep is integer, so which branch won at every FORGET is
+// a function of exact values, and a tie rule makes the traced chain a pure function of (plan, representative, costs): the kernels
+// (class_minplus_trace.hip) equal the twin byte for byte, whatever their order.  Counts play no part: a class whose count saturated still gets an
+// exact chain.
+//
+// For one (syndrome, class) pair, with cut plan cp and class representative rep:
+//     1. PARTIALS   P[h] = minplus_one under every assignment h of the held generators, as minplus_cut_host forms them.
+//     2. PICK       h* = the lowest h whose P[h] has the least cost.  Only costs are compared.
+//     3. FORWARD    the op loop of minplus_one under h*; at every FORGET one bit per live f with the slot bit clear,
+//                       take = cost(A[f | bit]) < cost(A[f])            -- strict: a tie leaves the generator off --
+//                   kept at (fi, h): fi the FORGET's ordinal in the stream, h the compressed index, f = insert_zero(h, slot).
+//     4. WALK       f = 0, chain = cut_representative(cp, rep, h*); through the ops in reverse: FORGET: where bit (fi, remove_bit(f, slot)) is set,
+//                   f |= bit and chain ^= forget_words[fi]; INTRO: f &= ~bit; CLOSE: nothing.  The walk ends at f == 0.
+//     5. RESULT     the chain as bytes uint8[nq]; a cell no generator touches keeps the representative's byte.
+//
+// What the chain promises: it has the input's syndrome, it lies in class c, its cost is the sweep's cost_out, and it depends on (plan,
+// representative, costs) alone.  Where count_out == 1 it is THE shortest chain of the class and so a function of the syndrome alone; where several
+// chains tie it is the one the rule above selects from this representative -- another representative of the same syndrome may select another.
+//
+// THE DECISIONS of one pair are n_forget * words_per_forget 64-bit words, words_per_forget = max(1, 2^(width - 1) / 64): bit h of FORGET fi is bit
+// h & 63 of word fi * words_per_forget + (h >> 6).  A FORGET writes every word its h reach (dead f write 0), the walk reads only bits of live f, so a
+// dirty workspace is allowed.  120 KiB per pair at rotated L = 11; trace_launch_group bounds a launch group's workspace by kTraceWorkspaceBytes.
+#pragma once
+#include "class_minplus.hpp"
+
+namespace qecmc {
+namespace minplus {
+
+constexpr uint64_t kTraceWorkspaceBytes = 256ull << 20;      // the decision words of one launch group
+
+struct TracePlan {
+    sweep::CutPlan cut;                 // refusal: cut.plan.refusal, prefixed "qecmc_class_minplus_chains:"
+    int n_forget = 0, words_per_forget = 1;
+    std::vector<int> forget_gen;        // [n_forget]: the table index of the generator FORGET fi retires, in stream order
+    std::vector<uint32_t> forget_words; // [n_forget][W]: that generator as packed state words, 2 bits per qubit (held_words' layout)
+};
+
+// a refusal of the min-plus sweep under this entry point's name
+inline Refusal chains_prefix(Refusal r)
+{
+    static const std::string from = "qecmc_class_minplus:";
+    if (r.code && r.msg.compare(0, from.size(), from) == 0) r.msg = "qecmc_class_minplus_chains:" + r.msg.substr(from.size());
+    return r;
+}
+
+inline Refusal check_chain_costs(const uint32_t *cost) { return chains_prefix(check_costs(cost)); }
+
+constexpr int trace_words_per_forget(int width) { return width - 1 > 6 ? 1 << (width - 1 - 6) : 1; }
+
+// the index f without its bit `slot`: the inverse of insert_zero on the f whose bit is clear
+__host__ __device__ inline uint32_t remove_bit(uint32_t f, uint32_t slot) { return ((f >> (slot + 1u)) << slot) | (f & ((1u << slot) - 1u)); }
+
+// build_minplus_plan, its refusals renamed, and the generator every FORGET retires: Trace::forget_at of the final stream, in stream order
+inline TracePlan build_trace_plan(int code, int L, int lds_width)
+{
+    TracePlan tp;
+    tp.cut = build_minplus_plan(code, L, lds_width);
+    sweep::Plan &p = tp.cut.plan;
+    if (p.refusal.code) { p.refusal = chains_prefix(p.refusal); return tp; }
+    std::vector<char> held((size_t)p.n_gen, 0);
+    for (const int g : tp.cut.held) held[(size_t)g] = 1;
+    sweep::Trace tr;
+    const sweep::Stream st = sweep::build_stream(code, L, held, &tr);
+    const correct::Table &ct = st.table;
+    std::vector<int> at_op((size_t)p.n_ops, -1);                                // the generator forgotten at op o
+    bool ok = st.head.refusal.code == 0 && (int)st.ops.size() == p.n_ops;
+    for (int g = 0; ok && g < p.n_gen; ++g) {
+        const int at = tr.forget_at[(size_t)g];
+        if (held[(size_t)g]) { ok = at < 0; continue; }
+        ok = at >= 0 && at < p.n_ops && at_op[(size_t)at] < 0 && (p.ops[(size_t)at * sweep::kOpWords] & 15u) == sweep::kForget;
+        if (ok) at_op[(size_t)at] = g;
+    }
+    for (int o = 0; ok && o < p.n_ops; ++o) {
+        if ((p.ops[(size_t)o * sweep::kOpWords] & 15u) != sweep::kForget) continue;
+        const int g = at_op[(size_t)o];
+        if (g < 0) { ok = false; break; }
+        tp.forget_gen.push_back(g);
+        std::vector<uint32_t> words((size_t)ct.W, 0u);
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t e = (ct.gen[(size_t)(2 * g + (i >> 1))] >> ((i & 1) * 16)) & 0xFFFFu, pauli = e & 3u, site = e >> 2;
+            words[site >> 4] ^= pauli << ((site & 15u) * 2u);                   // (Pauli values XOR as the Pauli product)
+        }
+        tp.forget_words.insert(tp.forget_words.end(), words.begin(), words.end());
+    }
+    tp.n_forget = (int)tp.forget_gen.size();
+    tp.words_per_forget = trace_words_per_forget(p.width);
+    if (!ok || tp.n_forget != p.n_gen - tp.cut.n_held)
+        p.refusal = refuse_params(QECMC_ERR_UNSUPPORTED, "qecmc_class_minplus_chains: internal: the stream of code %d at L=%d does not retire every generator once", code, L);
+    return tp;
+}
+
+// the decision words of one (syndrome, class) pair, in bytes
+inline uint64_t trace_bytes_per_pair(const TracePlan &tp) { return (uint64_t)tp.n_forget * (uint64_t)tp.words_per_forget * 8ull; }
+
+// cut_launch_group, further bounded so that the decision words of one group -- group * ncls * bytes_per_pair -- stay within kTraceWorkspaceBytes;
+// never 0: one syndrome is always launched
+inline uint32_t trace_launch_group(uint64_t N, int ncls, int n_held, uint64_t bytes_per_pair)
+{
+    uint32_t group = sweep::cut_launch_group(N, ncls, n_held);
+    const uint64_t per = (uint64_t)ncls * (bytes_per_pair ? bytes_per_pair : 1ull);
+    const uint64_t cap = kTraceWorkspaceBytes / per;
+    if (cap < group) group = cap < 1ull ? 1u : (uint32_t)cap;
+    return group;
+}
+
+// step 2: the lowest h whose partial has the least cost
+inline uint32_t pick_assignment(const uint64_t *P, int n_held)
+{
+    uint32_t best = 0;
+    for (uint32_t h = 1; h < (1u << n_held); ++h)
+        if ((P[h] >> kCountBits) < (P[best] >> kCountBits)) best = h;
+    return best;
+}
+
+// step 3: minplus_one with decisions.  A: 2^width entries of scratch, D: n_forget * words_per_forget words, both dirty allowed -> the packed partial
+inline uint64_t minplus_one_traced(const TracePlan &tp, const uint32_t *rep, const uint32_t *cxz, uint64_t *A, uint64_t *D)
+{
+    using namespace sweep;
+    const Plan &p = tp.cut.plan;
+    int fi = 0;
+    A[0] = 1ull;
+    for (int o = 0; o < p.n_ops; ++o) {
+        const uint32_t *op = &p.ops[(size_t)o * kOpWords];
+        const uint32_t kind = op[0] & 15u, slot = (op[0] >> 4) & 15u, top = (op[0] >> 12) & 31u, mask = op[1], bit = 1u << slot;
+        if (kind == kClose) {
+            const uint32_t q = op[3], cq = pauli_to_xz((rep[q >> 4] >> ((q & 15u) * 2u)) & 3u);
+            for (uint32_t f = 0; f < (1u << top); ++f) {
+                if (f & ~mask) continue;
+                uint32_t idx = cq;
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t pr = (op[2] >> (8 * j)) & 0xFFu;
+                    idx ^= (0u - ((f >> (pr & 15u)) & 1u)) & (pr >> 4);
+                }
+                A[f] = A[f] + ((uint64_t)cxz[idx] << kCountBits);
+            }
+            continue;
+        }
+        const uint32_t n_h = 1u << (top - 1u);
+        uint64_t *mine = kind == kForget ? D + (size_t)fi * (size_t)tp.words_per_forget : nullptr;
+        if (mine)
+            for (uint32_t w = 0; w < (n_h + 63u) / 64u; ++w) mine[w] = 0ull;    // (a dead f leaves a 0, as the kernel's ballot does)
+        for (uint32_t h = 0; h < n_h; ++h) {
+            const uint32_t f = insert_zero(h, slot);
+            if (f & ~mask) continue;
+            if (kind == kIntro) { A[f | bit] = A[f]; continue; }
+            if ((A[f | bit] >> kCountBits) < (A[f] >> kCountBits)) mine[h >> 6] |= 1ull << (h & 63u);
+            A[f] = mp_combine(A[f], A[f | bit]);
+        }
+        if (mine) ++fi;
+    }
+    return A[0];
+}
+
+// step 4: the walk.  chain: W packed words, cut_representative(cp, rep, h*) on entry, the traced chain on return -> the f the walk ends at (0)
+inline uint32_t trace_walk(const TracePlan &tp, const uint64_t *D, uint32_t *chain)
+{
+    using namespace sweep;
+    const Plan &p = tp.cut.plan;
+    uint32_t f = 0;
+    int fi = tp.n_forget;
+    for (int o = p.n_ops - 1; o >= 0; --o) {
+        const uint32_t w0 = p.ops[(size_t)o * kOpWords], kind = w0 & 15u, slot = (w0 >> 4) & 15u, bit = 1u << slot;
+        if (kind == kIntro) f &= ~bit;
+        else if (kind == kForget) {
+            --fi;
+            const uint32_t h = remove_bit(f, slot);
+            if ((D[(size_t)fi * (size_t)tp.words_per_forget + (h >> 6)] >> (h & 63u)) & 1ull) {
+                f |= bit;
+                for (int w = 0; w < p.W; ++w) chain[w] ^= tp.forget_words[(size_t)fi * p.W + w];
+            }
+        }
+    }
+    return f;
+}
+
+// step 5: packed words -> bytes
+inline void unpack_chain(const uint32_t *words, int nq, uint8_t *out)
+{
+    for (int q = 0; q < nq; ++q) out[q] = (uint8_t)((words[q >> 4] >> ((q & 15) * 2)) & 3u);
+}
+
+// The twin.  chains uint8[N][nq], cost4[4] (I, X, Y, Z) -> chain_out uint8[N][ncls][nq]; cost_out uint32[N][ncls], count_out uint64[N][ncls] and
+// cls int32[N] (all three nullable): minplus_cut_host's, exactly.  Threaded as minplus_cut_host: the partials of one syndrome are spread over
+// `threads` host threads; the trace of a pair is one more pass and runs on the calling thread.
+inline void minplus_trace_host(const TracePlan &tp, uint64_t N, const uint8_t *chains, const uint32_t *cost4, uint8_t *chain_out, uint32_t *cost_out, uint64_t *count_out,
+                               int32_t *cls, unsigned threads = 0)
+{
+    const sweep::CutPlan &cp = tp.cut;
+    const sweep::Plan &p = cp.plan;
+    uint32_t cxz[4];
+    costs_xz(cost4, cxz);
+    const uint32_t n_h = 1u << cp.n_held, n_work = (uint32_t)p.ncls * n_h;
+    if (threads == 0) threads = std::thread::hardware_concurrency();
+    if (threads > 16u) threads = 16u;
+    if (threads > n_work) threads = n_work;
+    if (threads < 1u || cp.n_held == 0) threads = 1u;
+    std::vector<uint32_t> reps((size_t)p.ncls * p.W), rep((size_t)p.W);
+    std::vector<uint64_t> P((size_t)n_work), A((size_t)1 << p.width), D((size_t)tp.n_forget * (size_t)tp.words_per_forget);
+    for (uint64_t s = 0; s < N; ++s) {
+        const int a = sweep::class_representatives(p, chains + s * (uint64_t)p.nq, reps.data());
+        if (cls) cls[s] = a;
+        auto work = [&](unsigned t) {
+            std::vector<uint64_t> Amine((size_t)1 << p.width);
+            std::vector<uint32_t> mine((size_t)p.W);
+            for (uint32_t i = t; i < n_work; i += threads) {
+                sweep::cut_representative(cp, &reps[(size_t)(i >> cp.n_held) * p.W], i & (n_h - 1u), mine.data());
+                P[i] = minplus_one(p, mine.data(), cxz, Amine.data());
+            }
+        };
+        if (threads == 1u) work(0);
+        else {
+            std::vector<std::thread> pool;
+            for (unsigned t = 0; t < threads; ++t) pool.emplace_back(work, t);
+            for (std::thread &t : pool) t.join();
+        }
+        for (int c = 0; c < p.ncls; ++c) {
+            const uint64_t *mine = &P[(size_t)c << cp.n_held];
+            const uint32_t pick = pick_assignment(mine, cp.n_held);
+            sweep::cut_representative(cp, &reps[(size_t)c * p.W], pick, rep.data());
+            minplus_one_traced(tp, rep.data(), cxz, A.data(), D.data());
+            trace_walk(tp, D.data(), rep.data());
+            unpack_chain(rep.data(), p.nq, chain_out + (s * (uint64_t)p.ncls + (uint64_t)c) * (uint64_t)p.nq);
+            uint64_t e = mine[0];
+            for (uint32_t h = 1; h < n_h; ++h) e = mp_combine(e, mine[h]);
+            uint32_t cost;
+            uint64_t count;
+            mp_unpack(e, p.n_gen - p.rank, &cost, &count);
+            if (cost_out) cost_out[s * (uint64_t)p.ncls + c] = cost;
+            if (count_out) count_out[s * (uint64_t)p.ncls + c] = count;
+        }
+    }
+}
+
+}  // namespace minplus
+
+// class_minplus_trace.hip: all pointers are device pointers.  ops, held, reps and P as class_minplus.hip takes them; pick uint32[S * ncls];
+// D uint64[S * ncls][n_forget][words_per_forget]: scratch, dirty allowed; forget_words uint32[n_forget][W]; chain_out uint8[S * ncls][nq]: overwritten.
+struct MinplusTraceArgs {
+    MinplusArgs m;
+    int n_forget, words_per_forget, nq;
+};
+hipError_t class_minplus_trace_allow_lds(int width);   // hipSuccess: k_minplus_trace can be launched with a state vector of this width on the current device
+// between launch_class_minplus_sweep and launch_class_minplus_reduce, on their stream: the reduce destroys the partials
+hipError_t launch_minplus_pick(const MinplusArgs &a, const uint64_t *P, uint32_t *pick, hipStream_t stream);
+// k_minplus_trace, then k_minplus_walk: stream order is the only synchronisation
+hipError_t launch_minplus_trace(const MinplusTraceArgs &a, const uint32_t *ops, const uint32_t *held, const uint32_t *reps, const uint32_t *forget_words, const uint32_t *pick,
+                                uint64_t *D, uint8_t *chain_out, hipStream_t stream);
+
+}  // namespace qecmc

@@ -8,6 +8,7 @@
 #include "class_sweep_tiled.hpp"
 #include "class_sweep_site.hpp"
 #include "class_minplus.hpp"
+#include "class_minplus_trace.hpp"
 #include "corrections.hpp"
 #include "enumerate.hpp"
 #include "kernel_choice.hpp"
@@ -446,6 +447,35 @@ uint64_t qt_minplus_combine(uint64_t a, uint64_t b, uint64_t *out3)
 {
     if (out3) { out3[0] = minplus::kSat; out3[1] = (uint64_t)minplus::kCountBits; out3[2] = minplus::kMaxCost; }
     return minplus::mp_combine(a, b);
+}
+// the traceback (class_minplus_trace.hpp).  qt_class_minplus_chains: the host twin of qecmc_class_minplus_chains behind the same host checks, in the
+// same order; qt_class_minplus_trace_plan: forget_gen int32[n_forget] and forget_words uint32[n_forget][W] -> n_forget, -1 where refused or too small
+// a buffer, and through out4 (nullable) n_forget, words_per_forget, W and the bytes of one pair's decisions; qt_class_minplus_trace_group: the
+// syndromes of one launch, and through workspace (nullable) the bound on a group's decision words
+int qt_class_minplus_chains(int code, int L, uint64_t N, const uint8_t *chains, const uint32_t *cost, int lds_width, uint8_t *chain_out, uint32_t *cost_out,
+                            uint64_t *count_out, int32_t *cls, char *msg, int msg_cap)
+{
+    if (!chains || !cost || !chain_out) return site_answer(refuse_params(QECMC_ERR_INVALID, "qecmc_class_minplus_chains: NULL buffer"), msg, msg_cap);
+    if (N > 0xFFFFFFFFull) return site_answer(refuse_params(QECMC_ERR_INVALID, "qecmc_class_minplus_chains: N=%llu syndromes exceed 32 bits", (unsigned long long)N), msg, msg_cap);
+    if (const Refusal r = minplus::check_chain_costs(cost); r.code) return site_answer(r, msg, msg_cap);
+    const minplus::TracePlan tp = minplus::build_trace_plan(code, L, lds_width);
+    if (tp.cut.plan.refusal.code) return site_answer(tp.cut.plan.refusal, msg, msg_cap);
+    minplus::minplus_trace_host(tp, N, chains, cost, chain_out, cost_out, count_out, cls);
+    return site_answer({}, msg, msg_cap);
+}
+int qt_class_minplus_trace_plan(int code, int L, int lds_width, int32_t *forget_gen, uint32_t *forget_words, int cap_words, int32_t *out4)
+{
+    const minplus::TracePlan tp = minplus::build_trace_plan(code, L, lds_width);
+    if (tp.cut.plan.refusal.code || (int)tp.forget_words.size() > cap_words) return -1;
+    for (int i = 0; i < tp.n_forget; ++i) forget_gen[i] = tp.forget_gen[(size_t)i];
+    if (!tp.forget_words.empty()) std::memcpy(forget_words, tp.forget_words.data(), tp.forget_words.size() * sizeof(uint32_t));
+    if (out4) { out4[0] = tp.n_forget; out4[1] = tp.words_per_forget; out4[2] = tp.cut.plan.W; out4[3] = (int32_t)minplus::trace_bytes_per_pair(tp); }
+    return tp.n_forget;
+}
+uint32_t qt_class_minplus_trace_group(uint64_t N, int ncls, int n_held, uint64_t bytes_per_pair, uint64_t *workspace)
+{
+    if (workspace) *workspace = minplus::kTraceWorkspaceBytes;
+    return minplus::trace_launch_group(N, ncls, n_held, bytes_per_pair);
 }
 // the top rung's frames of a pick window (wu_frames.hpp) for an accepted scan = wave block, from the window's 64 pick blocks picks[64][4]: the plan's
 // descriptors and logical masks (rows padded to the kernel's WV words, as the kernel stages them), thr16 from the plan's thr_logical as wu_run forms it.

@@ -19,7 +19,10 @@ exact_site_probabilities take a table of weights in place of the four numbers --
 
 The shortest chain of every class and its multiplicity (qecmc_class_minplus): the cut-set sweep's plans in the semiring of
 (cost, count) pairs under (min, +), integer and exact -- class_minplus, the minimum-weight decoder min_weight_classes, and shortest_class_law, the
-exact value of what the shortest-chain estimators converge to."""
+exact value of what the shortest-chain estimators converge to.
+
+That sweep traced back to a chain (qecmc_class_minplus_chains): shortest_chains returns a shortest chain of every class next to
+cost and count, min_weight_corrections the minimum-weight decoder's correction."""
 import ctypes as C
 
 import numpy as np
@@ -167,6 +170,43 @@ def min_weight_classes(code, chains, costs=(0, 1, 1, 1), size=None, lds_width=0)
     this is the minimum-weight decoder of depolarizing noise over Pauli chains: a Y costs 1, which matching on separate X and Z graphs cannot say."""
     r = class_minplus(code, chains, costs, size=size, lds_width=lds_width)
     return _rank_classes(r["cost"], r["count"])
+
+
+def shortest_chains(code, chains, costs=(0, 1, 1, 1), size=None, lds_width=0):
+    """A shortest chain of every class of every syndrome, on the GPU (qecmc_class_minplus_chains): class_minplus's sweep traced back.
+    The arguments and shapes are class_minplus's.
+    Returns dict(chains uint8[N, ncls, ...]: chains[s, c] has the syndrome of chain s, lies in class c and costs cost[s, c] -- in the layout of the
+    input, bytes 0 .. 3; cost, count, saturated, cls, width, held: class_minplus's, exactly; unique bool[N, ncls]: count == 1).  Where unique, the chain
+    is the one shortest chain of its class and depends on the syndrome alone.  Where several chains tie, the one returned is picked by a fixed rule
+    from the input chain -- a generator is applied only where that is strictly cheaper --: it is a function of (input chain, costs), and another
+    chain with the same syndrome may pick another of the tied chains.  A saturated count does not touch the chain."""
+    code = _CODES.get(code, code)
+    flat, L = _as_chains(code, chains, size)
+    c = np.asarray(costs, dtype=np.float64)
+    if c.shape != (4,) or not np.all((c >= 0) & (c <= 0xFFFFFFFF) & (c == np.floor(c))):
+        raise ValueError(f"costs={costs!r}: the four integer costs of I, X, Y and Z, each >= 0")
+    c = c.astype(np.uint32)
+    n, ncls = flat.shape[0], 16 if code == L_.TORIC else 4
+    out = np.zeros((n, ncls, flat.shape[1]), dtype=np.uint8)
+    cost = np.zeros((n, ncls), dtype=np.uint32)
+    count = np.zeros((n, ncls), dtype=np.uint64)
+    cls = np.zeros(n, dtype=np.int32)
+    L_.check(L_.lib().qecmc_class_minplus_chains(code, L, n, L_.u8(flat), c.ctypes.data_as(L_._u32p), int(lds_width), L_.u8(out), cost.ctypes.data_as(L_._u32p),
+                                                 count.ctypes.data_as(L_._u64p), L_.i32(cls)))
+    info = sweep_cut_info(code, L, lds_width)
+    state = (2, L, L) if code in (L_.TORIC, L_.PLANAR) else (L, L)
+    return dict(chains=out.reshape((n, ncls) + state), cost=cost, count=count, saturated=count == 0, unique=count == 1, cls=cls, width=info["width"],
+                held=info["held"])
+
+
+def min_weight_corrections(code, chains, costs=(0, 1, 1, 1), size=None, lds_width=0):
+    """The minimum-weight decoder's correction: dict(correction uint8[N, ...]: the traced shortest chain (shortest_chains) of target, target int32[N]:
+    the class min_weight_classes picks -- the least cost, ties by the larger count, then by the lower class index --, weight uint32[N]: the
+    correction's cost, the least of its row).  Nothing with the syndrome of the input is cheaper than the correction."""
+    r = shortest_chains(code, chains, costs, size=size, lds_width=lds_width)
+    target = _rank_classes(r["cost"], r["count"])
+    rows = np.arange(len(target))
+    return dict(correction=r["chains"][rows, target], target=target, weight=r["cost"][rows, target])
 
 
 def _law_from_minplus(cost, count, saturated, base):

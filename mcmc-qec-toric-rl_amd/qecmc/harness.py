@@ -264,9 +264,38 @@ def _corrections_for(code, size, candidates, distr, device):
     return target, correct(code, candidates, target, device=device, size=size)
 
 
-def _correction_outputs(code, size, raw, init, distr, device):
+def _correction_route(params, method):
+    """params['correction']: None (default: qecmc.corrections -- class move and greedy descent) or "shortest" (method min_weight only: the traced
+    shortest chain of the target class, qecmc.shortest_chains); refused by name under any other method"""
+    route = params.get("correction")
+    if route not in (None, "shortest"):
+        raise ValueError(f"params['correction']={route!r}: 'shortest', or absent for qecmc.corrections")
+    if route == "shortest" and method != "min_weight":
+        raise ValueError(f"params['correction']='shortest' is built for method min_weight, not {method}: only the (min, +) sweep traces a shortest chain")
+    return route
+
+
+def _shortest_corrections_for(params, chains, distr, device):
+    """_corrections_for by params['correction'] = "shortest": target = argmax(distr) and, in the keys of qecmc.corrections, the traced shortest chain of
+    that class under the costs _min_weight_distr decodes with -- weight its error count, source 0, moved: target is not the start chain's class"""
+    from .exact import shortest_chains
+    noise = params.get("noise", "depolarizing")
+    if device != 0:
+        raise ValueError("method min_weight runs on device 0: the library has no device-pointer form of it yet")
+    costs = (0, int(params["alpha"]), int(params["alpha"]), 1) if noise == "alpha" else (0, 1, 1, 1)
+    target = np.argmax(distr, axis=1).astype(np.int32)
+    r = shortest_chains(params["code"], chains, costs, size=params["size"], lds_width=int(params.get("lds_width", 0)))
+    cor = r["chains"][np.arange(len(target)), target]
+    return target, dict(corrections=cor, weight=(cor != 0).reshape(len(cor), -1).sum(axis=1).astype(np.int32), source=np.zeros(len(cor), np.int32),
+                        moved=(target != r["cls"]).astype(np.uint8))
+
+
+def _correction_outputs(code, size, raw, init, distr, device, params=None):
     """generate's corrections=True: the correction of every start chain towards argmax(distr), its weight, and whether raw ^ correction is a stabilizer"""
-    _, cor = _corrections_for(code, size, init, distr, device)
+    if params is not None and params.get("correction") == "shortest":
+        _, cor = _shortest_corrections_for(params, init, distr, device)
+    else:
+        _, cor = _corrections_for(code, size, init, distr, device)
     residual = raw ^ cor["corrections"]
     stabilizer_class = int(np.asarray(_class_of(code, np.zeros_like(raw[:1])))[0])
     return dict(correction=cor["corrections"], correction_weight=cor["weight"],
@@ -287,11 +316,15 @@ def decode_syndromes(params, defects, seed=0, steps=100000, conv_criteria="error
     corrections=True adds what a user who measured a syndrome wants (qecmc.corrections): target = argmax(distr) per row, correction -- a
     chain with the syndrome in that class --, correction_weight, correction_source and correction_moved.  The candidate is the lifted chain;
     correction_candidates="states" adds the Nc final rung states of every ladder as candidates 1 ..., where the route returns them: a fixed-length
-    run (conv_criteria=None).  A run the convergence criterion stops may go to the work-queue kernels, which write no final states: ValueError."""
+    run (conv_criteria=None).  A run the convergence criterion stops may go to the work-queue kernels, which write no final states: ValueError.
+    params['correction'] = "shortest" (method min_weight only, refused by name elsewhere): correction is the traced shortest chain of the target class
+    (qecmc.shortest_chains) instead of qecmc.corrections' class move and descent; correction_source is 0 and correction_moved says whether the target
+    is another class than the lifted chain's."""
     from .syndrome_lift import chains_from_syndromes
     method = params.get("method", "PTEQ")
     if method not in ("PTEQ", "exact", "min_weight"):
         raise ValueError("decode_syndromes decodes with PTEQ, exact or min_weight (params['method'])")
+    route = _correction_route(params, method)
     noise = params.get("noise", "depolarizing")
     if noise not in ("depolarizing", "biased", "alpha"):
         raise ValueError(f"noise={noise!r}")
@@ -310,7 +343,10 @@ def decode_syndromes(params, defects, seed=0, steps=100000, conv_criteria="error
         distr_of = _exact_distr if method == "exact" else _min_weight_distr
         out = dict(distr=distr_of(params, chains, int(pteq_kw.get("device", 0))), chains=chains, status=status, weight=weight)
         if corrections:
-            target, cor = _corrections_for(_CODES[params["code"]], params["size"], chains, out["distr"], int(pteq_kw.get("device", 0)))
+            if route == "shortest":
+                target, cor = _shortest_corrections_for(params, chains, out["distr"], int(pteq_kw.get("device", 0)))
+            else:
+                target, cor = _corrections_for(_CODES[params["code"]], params["size"], chains, out["distr"], int(pteq_kw.get("device", 0)))
             out.update(target=target, correction=cor["corrections"], correction_weight=cor["weight"], correction_source=cor["source"],
                        correction_moved=cor["moved"])
         return out
@@ -415,6 +451,9 @@ def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_
     corrections=True (methods PTEQ, exact and min_weight) closes the loop: correction uint8[n,...] is qecmc.corrections of the start chain -- the seed configuration, or the
     lifted chain of start="syndrome" -- towards argmax(distr), correction_weight its error count, and success_correction[s] is true iff
     raw[s] ^ correction[s] (byte values XOR as the Pauli product) is a stabilizer: an all-zero syndrome and the class of the zero chain.
+    params['correction'] = "shortest" (method min_weight with corrections=True; refused by name under any other method) makes correction the traced
+    shortest chain of argmax(distr) instead (qecmc.shortest_chains): no chain of that class is lighter; correction_weight and
+    success_correction keep their meaning.  The default stays the qecmc.corrections route.
     Returns (and optionally saves as npz) qubit_matrix uint8[n,...] (the raw errors, generate_data.py:120),
     eq_true int32[n], counts uint32[n,ncls], distr uint8[n,ncls] (what PTEQ returns), success bool[n]
     (argmax(distr) == eq_true, generate_data.py:139), steps_done, converged."""
@@ -435,6 +474,7 @@ def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_
         raise ValueError(f"corrections=True is built for methods PTEQ, exact and min_weight, not {method}")
     if method == "min_weight" and noise == "biased":
         raise ValueError("method min_weight is defined for depolarizing and alpha noise, not biased: the biased weights are no integer powers of one base")
+    _correction_route(params, method)
     if device_generation:
         # errors, true class and the hiding logical operator drawn on the GPU (Philox keyed by the global syndrome index: the data
         # set does not depend on how it is cut into shards)
@@ -464,7 +504,7 @@ def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_
         distr = (_exact_distr if method == "exact" else _min_weight_distr)(params, init, int(pteq_kw.get("device", 0)))
         out = dict(qubit_matrix=raw, eq_true=eq_true, distr=distr, success=np.argmax(distr, axis=1) == eq_true)
         if corrections:
-            out.update(_correction_outputs(code, size, raw, init, distr, int(pteq_kw.get("device", 0))))
+            out.update(_correction_outputs(code, size, raw, init, distr, int(pteq_kw.get("device", 0)), params))
         if file_path is not None:
             np.savez_compressed(file_path, params=np.array([repr(params)]), **out)
         return out
