@@ -6,6 +6,8 @@
 // predicate what it does.
 #include "corrections.hpp"
 
+#include <mutex>
+
 namespace qecmc {
 
 namespace {
@@ -51,6 +53,27 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8))) void k_
     }
 }
 
+// the dynamic-LDS limit of k_corrections on the current device: beyond the default 64 KiB window it is raised ONCE per device, to kServiceLdsMax (what the
+// largest accepted lattice needs), under a mutex -- never per launch with the launch's own size, which would let one host thread lower the limit
+// between another thread's request and its launch.  hipErrorInvalidValue where the runtime does not grant it
+static hipError_t corrections_allow_lds(size_t lds)
+{
+    if (lds <= 64 * 1024) return hipSuccess;
+    constexpr int kDevices = 64;
+    static std::mutex mu;
+    static signed char state[kDevices] = {};                  // 0: not asked, 1: granted, -1: refused
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev)) return e;
+    if (dev < 0 || dev >= kDevices) return hipErrorInvalidValue;
+    std::lock_guard<std::mutex> g(mu);
+    if (state[dev] == 0) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_corrections), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kServiceLdsMax);
+        if (e != hipSuccess) (void)hipGetLastError();         // (the refusal is reported by value; it is not left behind as the thread's last error)
+        state[dev] = e == hipSuccess ? 1 : -1;
+    }
+    return state[dev] == 1 ? hipSuccess : hipErrorInvalidValue;
+}
+
 hipError_t launch_corrections(const CorrectArgs &a, const uint32_t *masks, const uint32_t *need, const uint32_t *gen, const uint8_t *candidates,
                               const int32_t *target, uint8_t *corrections, int32_t *weight, int32_t *source, uint8_t *moved, uint8_t *status,
                               hipStream_t stream)
@@ -58,11 +81,8 @@ hipError_t launch_corrections(const CorrectArgs &a, const uint32_t *masks, const
     if (a.N == 0) return hipSuccess;
     const size_t lds = (size_t)a.W * 64u * sizeof(uint32_t);
     const uint64_t grid = (a.N + 63u) / 64u;
-    if (a.K < 1 || lds > 160 * 1024 || grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {   // beyond the default dynamic-LDS window (160 KiB per CU on gfx950)
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_corrections), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (a.K < 1 || lds > kServiceLdsMax || grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    if (hipError_t e = corrections_allow_lds(lds)) return e;
     hipLaunchKernelGGL(k_corrections, dim3((unsigned)grid), dim3(64), lds, stream, a, masks, need, gen, candidates, target, corrections, weight, source,
                        moved, status);
     return hipGetLastError();

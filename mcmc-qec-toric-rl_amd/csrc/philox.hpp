@@ -78,7 +78,10 @@ constexpr uint32_t kSubTopPair = 5u;
 // stays on one stream for the whole run and the words a step leaves over in its last four-proposal block (two of twelve at
 // iters = 10) are still in its registers when the next step needs them.  The top rule keeps stream c = Nc - 1.
 constexpr uint32_t kDiagStream = 0x400u;
-__host__ __device__ __forceinline__ uint32_t pick_top20(uint32_t x, uint32_t n) { return ((x >> 12) * n) >> 20; }
+__host__ __device__ __forceinline__ uint32_t pick_top20(uint32_t x, uint32_t n) { return ((x >> 12) * n) >> 20; }   // n <= 2^12: the product fits 32 bits
+// The same pick where n may pass 2^12 -- the byte-state chain of primitives.hip takes every lattice up to L = 64, 8 192 generators on the torus and
+// 8 064 on the planar code (more than 4 096 from L = 46 on): the 33-bit product in 64 bits.  The ladder, wave and colour kernels hold no such shape.
+__host__ __device__ __forceinline__ uint32_t pick_top20_wide(uint32_t x, uint32_t n) { return (uint32_t)(((uint64_t)(x >> 12) * n) >> 20); }
 
 // int(u * n) for u = x * 2^-32, exactly (toric_model.py:291 `int(random() * size)`)
 __host__ __device__ __forceinline__ uint32_t scale_u32(uint32_t x, uint32_t n)

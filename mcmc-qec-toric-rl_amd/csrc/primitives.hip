@@ -80,7 +80,7 @@ __global__ void k_syndrome(int code, int L, uint64_t N, const uint8_t *in, uint8
 __device__ __forceinline__ void surf_pick(int code, int L, uint32_t w, bool top, int &row, int &col, int &op)
 {
     const uint32_t G = (uint32_t)surf_ngen(code, L);
-    surf_gen_rco(code, L, (int)(top ? scale_u32(w, G) : pick_top20(w, G)), row, col, op);
+    surf_gen_rco(code, L, (int)(top ? scale_u32(w, G) : pick_top20_wide(w, G)), row, col, op);
 }
 
 // p_x^nx p_y^ny p_z^nz p_I^nI from the host-built power tables (mcmc_biased.py:31,43): IEEE products in the
@@ -150,7 +150,7 @@ __global__ void k_chain_update(const ChainArgs a)
             }
         } else if (code == kCodeToric) {
             // one word picks one of the 2L^2 generators (toric_model.py:291-295): X plaquettes first, row-major
-            const uint32_t g = packed ? scale_u32(pB, 2u * L * L) : pick_top20(x.x, 2u * L * L), rc = g < (uint32_t)(L * L) ? g : g - L * L;
+            const uint32_t g = packed ? scale_u32(pB, 2u * L * L) : pick_top20_wide(x.x, 2u * L * L), rc = g < (uint32_t)(L * L) ? g : g - L * L;
             row = rc / L; col = rc % L; op = g < (uint32_t)(L * L) ? 1 : 3;
             dE = toric_apply_stabilizer_b(L, m, row, col, op);
         } else {

@@ -5,6 +5,8 @@
 // A lane whose cell is clear, or whose generator does not lower its count, is predicated off.
 #include "syndrome_lift.hpp"
 
+#include <mutex>
+
 namespace qecmc {
 
 namespace {
@@ -44,17 +46,35 @@ __global__ __launch_bounds__(64) void k_syndrome_lift(const LiftArgs a, const ui
     }
 }
 
+// the dynamic-LDS limit of k_syndrome_lift on the current device: beyond the default 64 KiB window it is raised ONCE per device, to kServiceLdsMax (what the
+// largest accepted lattice needs), under a mutex -- never per launch with the launch's own size, which would let one host thread lower the limit
+// between another thread's request and its launch.  hipErrorInvalidValue where the runtime does not grant it
+static hipError_t lift_allow_lds(size_t lds)
+{
+    if (lds <= 64 * 1024) return hipSuccess;
+    constexpr int kDevices = 64;
+    static std::mutex mu;
+    static signed char state[kDevices] = {};                  // 0: not asked, 1: granted, -1: refused
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev)) return e;
+    if (dev < 0 || dev >= kDevices) return hipErrorInvalidValue;
+    std::lock_guard<std::mutex> g(mu);
+    if (state[dev] == 0) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_syndrome_lift), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kServiceLdsMax);
+        if (e != hipSuccess) (void)hipGetLastError();         // (the refusal is reported by value; it is not left behind as the thread's last error)
+        state[dev] = e == hipSuccess ? 1 : -1;
+    }
+    return state[dev] == 1 ? hipSuccess : hipErrorInvalidValue;
+}
+
 hipError_t launch_syndrome_lift(const LiftArgs &a, const uint32_t *rows, const uint32_t *gen, const uint8_t *defects, uint8_t *chains, uint8_t *status,
                                 int32_t *weight, hipStream_t stream)
 {
     if (a.N == 0) return hipSuccess;
     const size_t lds = (size_t)a.W * 64u * sizeof(uint32_t);
     const uint64_t grid = (a.N + 63u) / 64u;
-    if (lds > 160 * 1024 || grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    if (lds > 64 * 1024) {   // beyond the default dynamic-LDS window (160 KiB per CU on gfx950)
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_syndrome_lift), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (lds > kServiceLdsMax || grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    if (hipError_t e = lift_allow_lds(lds)) return e;
     hipLaunchKernelGGL(k_syndrome_lift, dim3((unsigned)grid), dim3(64), lds, stream, a, rows, gen, defects, chains, status, weight);
     return hipGetLastError();
 }

@@ -218,6 +218,10 @@ inline void chains_from_syndromes_host(const Table &t, uint64_t N, const uint8_t
 
 }  // namespace lift
 
+// the dynamic LDS of the largest lattice check_code_L accepts (toric / planar L = 64: W = 512 words of 64 lanes): what k_syndrome_lift and
+// k_corrections ask the runtime for, once per device, when a launch needs more than the default 64 KiB window
+constexpr size_t kServiceLdsMax = 512u * 64u * sizeof(uint32_t);
+
 // syndrome_lift.hip: all pointers are device pointers; status / weight nullable.  One lane per syndrome, 64-lane workgroups, W * 256 bytes of LDS.
 struct LiftArgs {
     uint64_t N;

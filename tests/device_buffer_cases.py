@@ -5,7 +5,8 @@ qecmc_plan_set_shortest.  A sampler row is a parameter block in the vocabulary o
 are reused) plus `replicas`, `chunks` (the resume calls) and `null`, the nullable parameters passed as NULL; the generator, lift and corrections rows
 name their own arguments.  The shapes are the smallest at which a write past the end or a skipped store can occur: one ladder, one full wavefront
 plus one lane (N = 65), several workgroups of scan = colour (N = 3), nq = 9 / 18 / 32 / 338 (one word of four, a ragged word, whole words, the 32-word
-wave kernel), a persistent grid of one workgroup (N = 200).
+wave kernel), a persistent grid of one workgroup (N = 200); and nq = 8192 for the lift and the corrections (L = 64: the largest state they hold,
+131 072 bytes of LDS).
 
   run_dev(q, row, poison)   the call through the device-pointer API with EVERY buffer -- inputs, outputs, workspace, set, record -- from a
                             guarded.Arena filled with `poison`, on a side stream with the fills enqueued on that same stream -> (outputs, inputs
@@ -128,6 +129,11 @@ for _code in ("toric", "xzzx", "planar"):
     for _N, _K, _null in ((65, 3, ()), (65, 1, _ALL4), (1, 3, ("d_weight_out", "d_moved_out")), (1, 1, ("d_source_out", "d_status_out"))):
         _plain("corrections", CORRECT, "corrections %s N=%d K=%d%s" % (_code, _N, _K, "".join(" no " + n[2:] for n in _null)), code=_code, L=3, N=_N,
                K=_K, null=_null, place=1, descend=1)
+# ---- the lift and the corrections at the top of the range: nq = 8192, W = 512 state words, 131 072 bytes of LDS behind the launcher's opt-in and a
+#      write-out of 64 x 8192 bytes a workgroup (the torus at L = 64 has no class move: no corrections row there)
+for _code in ("toric", "planar"):
+    _plain("lift", LIFT, "lift %s L=64 N=65 descend=1" % _code, code=_code, L=64, N=65, descend=1, null=())
+_plain("corrections", CORRECT, "corrections planar L=64 N=65 K=3", code="planar", L=64, N=65, K=3, null=(), place=1, descend=1)
 
 for _r in ROWS:
     _r.setdefault("kind", {LAUNCH: "launch", RESUME: "resume", RESUME_CONV: "resume_conv"}.get(_r["api"][0]))
