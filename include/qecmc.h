@@ -347,6 +347,23 @@ int qecmc_class_minplus(int code, int L, uint64_t N, const uint8_t *chains, cons
 int qecmc_class_minplus_chains(int code, int L, uint64_t N, const uint8_t *chains, const uint32_t cost[4], int lds_width, uint8_t *chain_out,
                                uint32_t *cost_out, uint64_t *count_out, int32_t *class_out);
 
+/* ---- both under a cost per (syndrome, qubit): erasures, inhomogeneous noise, soft priors on an integer scale (csrc/class_minplus_site.hpp) ----
+ * The arguments, shapes, nullability and results of qecmc_class_minplus and qecmc_class_minplus_chains with the four costs replaced by a
+ * table: cq uint8[cq_rows][nq][4], the costs of I, X, Y and Z at every cell of the state layout, every byte value a cost.  cq_rows is 1 -- one
+ * table for every syndrome -- or N -- row s belongs to syndrome s: a shot's own erased qubits cost (0, 0, 0, 0).  cost_out[s][c] = the least
+ * sum over the qubits of cq[row(s)][q][Pauli at q] among the chains of class c with the syndrome of chain s, count_out[s][c] the number of
+ * chains that reach it, chain_out[s][c] one of them, selected by qecmc_class_minplus_chains' rule.  With integer log-likelihood costs that is
+ * the most likely chain of the class, exactly.  Plans, widths, holds and launch groups are the siblings'; the device holds the cost rows of one
+ * launch group at a time.  Only the rows of qubits the plan closes are read: a cell that holds no qubit (the planar code's unused cells) may
+ * hold anything.  With constant rows the result is the uniform sibling's, chains included.
+ * Additive: QECMC_ABI_VERSION stays.  Refused before a device is looked for, the message prefixed "qecmc_class_minplus_site:" /
+ * "qecmc_class_minplus_chains_site:": what the sibling refuses of (code, L, N, lds_width), with its codes; a NULL chains / cq / output the
+ * sibling requires and a cq_rows that is neither 1 nor N (N > 0) with QECMC_ERR_INVALID.  N == 0 succeeds.  Host pointers only; device 0. */
+int qecmc_class_minplus_site(int code, int L, uint64_t N, const uint8_t *chains, const uint8_t *cq, uint64_t cq_rows, int lds_width,
+                             uint32_t *cost_out, uint64_t *count_out, int32_t *class_out);
+int qecmc_class_minplus_chains_site(int code, int L, uint64_t N, const uint8_t *chains, const uint8_t *cq, uint64_t cq_rows, int lds_width,
+                                    uint8_t *chain_out, uint32_t *cost_out, uint64_t *count_out, int32_t *class_out);
+
 /* ---- chain / ladder on caller-owned state (host pointers) ----------------- */
 
 /* The supported range of a start index.  A Philox counter holds a proposal index (the swap stream: a ladder-step index) in 48 bits,

@@ -27,6 +27,7 @@
 #include "class_sweep_site.hpp"
 #include "class_minplus.hpp"
 #include "class_minplus_trace.hpp"
+#include "class_minplus_site.hpp"
 #include "enumerate.hpp"
 #include "syndrome_lift.hpp"
 #include "tables.hpp"
@@ -1083,6 +1084,155 @@ int qecmc_class_sweep_tiled_site(int code, int L, uint64_t N, const uint8_t *cha
         ra.S = (uint32_t)here;
         HIP_TRY(launch_class_sweep_reduce(ra, dpart.as<double>(), dz.as<double>(), 0));
         HIP_TRY(hipMemcpy(z_out + first * (uint64_t)p.ncls, dz.p, (size_t)here * p.ncls * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- the (min, +) sweep and its traceback under a cost per (syndrome, qubit) (class_minplus_site.hpp)
+namespace {
+// The cost words on the device: the one table once, or the rows of a launch group at a time -- `group` rows at most, whatever N.
+struct CostRows {
+    DevBuf d;
+    std::vector<uint32_t> host;
+    const uint8_t *cq;
+    int nq, per_syndrome;
+    int open(const uint8_t *cq_in, uint64_t cq_rows, int nq_in, uint32_t group)
+    {
+        cq = cq_in; nq = nq_in; per_syndrome = cq_rows != 1;
+        host.resize((per_syndrome ? (size_t)group : 1u) * (size_t)nq);
+        HIP_TRY(d.alloc(host.size() * sizeof(uint32_t)));
+        return per_syndrome ? 0 : upload(0, 1);
+    }
+    int upload(uint64_t first, uint64_t rows)
+    {
+        minplus::site_cost_words(cq + first * (uint64_t)nq * 4u, rows, nq, host.data());
+        HIP_TRY(hipMemcpy(d.p, host.data(), (size_t)rows * (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice));
+        return 0;
+    }
+    int group(uint64_t first, uint64_t here) { return per_syndrome ? upload(first, here) : 0; }
+};
+
+// every CLOSE of the stream names a cell of the table: the kernels index a row of nq words by it
+bool closes_within(const std::vector<uint32_t> &ops, int nq)
+{
+    for (size_t o = 0; o + 3 < ops.size(); o += 4)
+        if ((ops[o] & 15u) == sweep::kClose && ops[o + 3] >= (uint32_t)nq) return false;
+    return true;
+}
+}  // namespace
+
+int qecmc_class_minplus_site(int code, int L, uint64_t N, const uint8_t *chains, const uint8_t *cq, uint64_t cq_rows, int lds_width, uint32_t *cost_out, uint64_t *count_out,
+                             int32_t *class_out)
+{
+    if (!chains || !cq || !cost_out || !count_out) return fail(QECMC_ERR_INVALID, "qecmc_class_minplus_site: NULL buffer");
+    if (N > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "qecmc_class_minplus_site: N=%llu syndromes exceed 32 bits", (unsigned long long)N);
+    const sweep::CutPlan cp = minplus::build_minplus_site_plan(code, L, lds_width);
+    const sweep::Plan &p = cp.plan;
+    if (int rc = report(p.refusal)) return rc;
+    if (int rc = report(minplus::check_cost_rows("qecmc_class_minplus_site", N, cq_rows))) return rc;
+    if (!closes_within(p.ops, p.nq)) return fail(QECMC_ERR_UNSUPPORTED, "qecmc_class_minplus_site: internal: a CLOSE names a cell beyond the %d of the table", p.nq);
+    if (int rc = use_device(0)) return rc;
+    if (N == 0) return 0;
+    if (class_minplus_site_allow_lds(p.width) != hipSuccess)
+        return fail(QECMC_ERR_UNSUPPORTED, "qecmc_class_minplus_site: this device does not grant a workgroup the %u bytes of LDS a state vector of width %d takes",
+                    p.carve.bytes, p.width);
+    const uint32_t group = sweep::cut_launch_group(N, p.ncls, cp.n_held);
+    const size_t rep_words = (size_t)p.ncls * p.W, partials = (size_t)p.ncls << cp.n_held;   // of one syndrome
+    std::vector<uint32_t> reps((size_t)group * rep_words);
+    DevBuf dops, dheld, dreps, dpart, dcost, dcount;
+    CostRows rows;
+    HIP_TRY(dops.alloc(p.ops.size() * sizeof(uint32_t)));
+    HIP_TRY(dheld.alloc(cp.held_words.size() * sizeof(uint32_t)));
+    HIP_TRY(dreps.alloc(reps.size() * sizeof(uint32_t)));
+    HIP_TRY(dpart.alloc((size_t)group * partials * sizeof(uint64_t)));          // kCutGridMax entries at most; dirty: every partial is written before it is read
+    HIP_TRY(dcost.alloc((size_t)group * p.ncls * sizeof(uint32_t)));
+    HIP_TRY(dcount.alloc((size_t)group * p.ncls * sizeof(uint64_t)));
+    HIP_TRY(hipMemcpy(dops.p, p.ops.data(), p.ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (cp.n_held) HIP_TRY(hipMemcpy(dheld.p, cp.held_words.data(), cp.held_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (int rc = rows.open(cq, cq_rows, p.nq, group)) return rc;
+    MinplusSiteArgs sa = {};
+    MinplusArgs &a = sa.t.m;
+    a.ncls = p.ncls; a.W = p.W; a.width = p.width; a.n_ops = p.n_ops; a.n_held = cp.n_held; a.shift = p.n_gen - p.rank;
+    sa.t.nq = p.nq; sa.per_syndrome = rows.per_syndrome;
+    // the host loops over groups of syndromes: no launch, and no device block -- the cost rows among them -- grows with the batch
+    for (uint64_t first = 0; first < N; first += group) {
+        const uint64_t here = N - first < group ? N - first : group;
+        for (uint64_t s = 0; s < here; ++s) {
+            const int cls = sweep::class_representatives(p, chains + (first + s) * (uint64_t)p.nq, reps.data() + s * rep_words);
+            if (class_out) class_out[first + s] = cls;
+        }
+        HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * rep_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (int rc = rows.group(first, here)) return rc;
+        a.S = (uint32_t)here;
+        HIP_TRY(launch_class_minplus_site_sweep(sa, dops.as<uint32_t>(), dheld.as<uint32_t>(), dreps.as<uint32_t>(), rows.d.as<uint32_t>(), dpart.as<uint64_t>(), 0));
+        HIP_TRY(launch_class_minplus_reduce(a, dpart.as<uint64_t>(), dcost.as<uint32_t>(), dcount.as<uint64_t>(), 0));
+        HIP_TRY(hipMemcpy(cost_out + first * (uint64_t)p.ncls, dcost.p, (size_t)here * p.ncls * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(count_out + first * (uint64_t)p.ncls, dcount.p, (size_t)here * p.ncls * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+int qecmc_class_minplus_chains_site(int code, int L, uint64_t N, const uint8_t *chains, const uint8_t *cq, uint64_t cq_rows, int lds_width, uint8_t *chain_out,
+                                    uint32_t *cost_out, uint64_t *count_out, int32_t *class_out)
+{
+    if (!chains || !cq || !chain_out) return fail(QECMC_ERR_INVALID, "qecmc_class_minplus_chains_site: NULL buffer");
+    if (N > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "qecmc_class_minplus_chains_site: N=%llu syndromes exceed 32 bits", (unsigned long long)N);
+    const minplus::TracePlan tp = minplus::build_trace_site_plan(code, L, lds_width);
+    const sweep::CutPlan &cp = tp.cut;
+    const sweep::Plan &p = cp.plan;
+    if (int rc = report(p.refusal)) return rc;
+    if (int rc = report(minplus::check_cost_rows("qecmc_class_minplus_chains_site", N, cq_rows))) return rc;
+    if (!closes_within(p.ops, p.nq)) return fail(QECMC_ERR_UNSUPPORTED, "qecmc_class_minplus_chains_site: internal: a CLOSE names a cell beyond the %d of the table", p.nq);
+    if (int rc = use_device(0)) return rc;
+    if (N == 0) return 0;
+    if (class_minplus_site_allow_lds(p.width) != hipSuccess || class_minplus_trace_site_allow_lds(p.width) != hipSuccess)
+        return fail(QECMC_ERR_UNSUPPORTED, "qecmc_class_minplus_chains_site: this device does not grant a workgroup the %u bytes of LDS a state vector of width %d takes",
+                    p.carve.bytes, p.width);
+    const uint64_t pair_bytes = minplus::trace_bytes_per_pair(tp);
+    const uint32_t group = minplus::trace_launch_group(N, p.ncls, cp.n_held, pair_bytes);
+    const size_t rep_words = (size_t)p.ncls * p.W, partials = (size_t)p.ncls << cp.n_held;   // of one syndrome
+    std::vector<uint32_t> reps((size_t)group * rep_words);
+    DevBuf dops, dheld, dreps, dforget, dpart, dpick, ddec, dchain, dcost, dcount;
+    CostRows rows;
+    HIP_TRY(dops.alloc(p.ops.size() * sizeof(uint32_t)));
+    HIP_TRY(dheld.alloc(cp.held_words.size() * sizeof(uint32_t)));
+    HIP_TRY(dreps.alloc(reps.size() * sizeof(uint32_t)));
+    HIP_TRY(dforget.alloc(tp.forget_words.size() * sizeof(uint32_t)));
+    HIP_TRY(dpart.alloc((size_t)group * partials * sizeof(uint64_t)));          // dirty: every partial is written before it is read
+    HIP_TRY(dpick.alloc((size_t)group * p.ncls * sizeof(uint32_t)));
+    HIP_TRY(ddec.alloc((size_t)group * p.ncls * (size_t)pair_bytes));           // kTraceWorkspaceBytes at most; dirty: the walk reads what the trace wrote
+    HIP_TRY(dchain.alloc((size_t)group * p.ncls * p.nq));
+    HIP_TRY(dcost.alloc((size_t)group * p.ncls * sizeof(uint32_t)));
+    HIP_TRY(dcount.alloc((size_t)group * p.ncls * sizeof(uint64_t)));
+    HIP_TRY(hipMemcpy(dops.p, p.ops.data(), p.ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (cp.n_held) HIP_TRY(hipMemcpy(dheld.p, cp.held_words.data(), cp.held_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dforget.p, tp.forget_words.data(), tp.forget_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (int rc = rows.open(cq, cq_rows, p.nq, group)) return rc;
+    MinplusSiteArgs sa = {};
+    MinplusTraceArgs &t = sa.t;
+    MinplusArgs &a = t.m;
+    a.ncls = p.ncls; a.W = p.W; a.width = p.width; a.n_ops = p.n_ops; a.n_held = cp.n_held; a.shift = p.n_gen - p.rank;
+    t.n_forget = tp.n_forget; t.words_per_forget = tp.words_per_forget; t.nq = p.nq;
+    sa.per_syndrome = rows.per_syndrome;
+    // the host loops over groups of syndromes: no launch, and no device block -- the cost rows among them -- grows with the batch
+    for (uint64_t first = 0; first < N; first += group) {
+        const uint64_t here = N - first < group ? N - first : group;
+        for (uint64_t s = 0; s < here; ++s) {
+            const int cls = sweep::class_representatives(p, chains + (first + s) * (uint64_t)p.nq, reps.data() + s * rep_words);
+            if (class_out) class_out[first + s] = cls;
+        }
+        HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * rep_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (int rc = rows.group(first, here)) return rc;
+        a.S = (uint32_t)here;
+        HIP_TRY(launch_class_minplus_site_sweep(sa, dops.as<uint32_t>(), dheld.as<uint32_t>(), dreps.as<uint32_t>(), rows.d.as<uint32_t>(), dpart.as<uint64_t>(), 0));
+        HIP_TRY(launch_minplus_pick(a, dpart.as<uint64_t>(), dpick.as<uint32_t>(), 0));            // (before the reduce folds the partials in place)
+        HIP_TRY(launch_class_minplus_reduce(a, dpart.as<uint64_t>(), dcost.as<uint32_t>(), dcount.as<uint64_t>(), 0));
+        HIP_TRY(launch_minplus_trace_site(sa, dops.as<uint32_t>(), dheld.as<uint32_t>(), dreps.as<uint32_t>(), rows.d.as<uint32_t>(), dpick.as<uint32_t>(), ddec.as<uint64_t>(), 0));
+        HIP_TRY(launch_minplus_walk(t, dops.as<uint32_t>(), dheld.as<uint32_t>(), dreps.as<uint32_t>(), dforget.as<uint32_t>(), dpick.as<uint32_t>(), ddec.as<uint64_t>(),
+                                    dchain.as<uint8_t>(), 0));
+        HIP_TRY(hipMemcpy(chain_out + first * (uint64_t)p.ncls * (uint64_t)p.nq, dchain.p, (size_t)here * p.ncls * p.nq, hipMemcpyDeviceToHost));
+        if (cost_out) HIP_TRY(hipMemcpy(cost_out + first * (uint64_t)p.ncls, dcost.p, (size_t)here * p.ncls * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (count_out) HIP_TRY(hipMemcpy(count_out + first * (uint64_t)p.ncls, dcount.p, (size_t)here * p.ncls * sizeof(uint64_t), hipMemcpyDeviceToHost));
     }
     return 0;
 }

@@ -167,21 +167,34 @@ hipError_t launch_minplus_pick(const MinplusArgs &a, const uint64_t *P, uint32_t
     return hipGetLastError();
 }
 
+static bool trace_shape_ok(const MinplusTraceArgs &t)
+{
+    const MinplusArgs &a = t.m;
+    return trace_args_ok(a) && t.n_forget >= 1 && t.words_per_forget == minplus::trace_words_per_forget(a.width) && t.nq >= 1 && t.nq <= 16 * a.W &&
+           (uint64_t)a.S * (uint64_t)a.ncls * (uint64_t)t.n_forget * (uint64_t)t.words_per_forget * 8ull <= minplus::kTraceWorkspaceBytes;
+}
+
+hipError_t launch_minplus_walk(const MinplusTraceArgs &t, const uint32_t *ops, const uint32_t *held, const uint32_t *reps, const uint32_t *forget_words, const uint32_t *pick,
+                               const uint64_t *D, uint8_t *chain_out, hipStream_t stream)
+{
+    const MinplusArgs &a = t.m;
+    if (a.S == 0) return hipSuccess;
+    if (!trace_shape_ok(t)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_minplus_walk, dim3(a.S * (uint32_t)a.ncls), dim3(kWave), 0, stream, t, ops, held, reps, forget_words, pick, D, chain_out);
+    return hipGetLastError();
+}
+
 hipError_t launch_minplus_trace(const MinplusTraceArgs &t, const uint32_t *ops, const uint32_t *held, const uint32_t *reps, const uint32_t *forget_words, const uint32_t *pick,
                                 uint64_t *D, uint8_t *chain_out, hipStream_t stream)
 {
     const MinplusArgs &a = t.m;
     if (a.S == 0) return hipSuccess;
-    if (!trace_args_ok(a) || t.n_forget < 1 || t.words_per_forget != minplus::trace_words_per_forget(a.width) || t.nq < 1 || t.nq > 16 * a.W ||
-        (uint64_t)a.S * (uint64_t)a.ncls * (uint64_t)t.n_forget * (uint64_t)t.words_per_forget * 8ull > minplus::kTraceWorkspaceBytes)
-        return hipErrorInvalidValue;
+    if (!trace_shape_ok(t)) return hipErrorInvalidValue;
     const sweep::Carve carve = sweep::lds_carve(a.width);
     if (hipError_t e = class_minplus_trace_allow_lds(a.width)) return e;
-    const uint32_t pairs = a.S * (uint32_t)a.ncls;
-    hipLaunchKernelGGL(k_minplus_trace, dim3(pairs), dim3(sweep::cut_threads(a.width)), carve.bytes, stream, t, ops, held, reps, pick, D);
+    hipLaunchKernelGGL(k_minplus_trace, dim3(a.S * (uint32_t)a.ncls), dim3(sweep::cut_threads(a.width)), carve.bytes, stream, t, ops, held, reps, pick, D);
     if (hipError_t e = hipGetLastError()) return e;
-    hipLaunchKernelGGL(k_minplus_walk, dim3(pairs), dim3(kWave), 0, stream, t, ops, held, reps, forget_words, pick, (const uint64_t *)D, chain_out);
-    return hipGetLastError();
+    return launch_minplus_walk(t, ops, held, reps, forget_words, pick, D, chain_out, stream);
 }
 
 }  // namespace qecmc

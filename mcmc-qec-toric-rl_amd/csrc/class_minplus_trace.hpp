@@ -242,6 +242,10 @@ struct MinplusTraceArgs {
 hipError_t class_minplus_trace_allow_lds(int width);   // hipSuccess: k_minplus_trace can be launched with a state vector of this width on the current device
 // between launch_class_minplus_sweep and launch_class_minplus_reduce, on their stream: the reduce destroys the partials
 hipError_t launch_minplus_pick(const MinplusArgs &a, const uint64_t *P, uint32_t *pick, hipStream_t stream);
+// k_minplus_walk alone, after a kernel that wrote the decision words D on the same stream (launch_minplus_trace ends with it; class_minplus_site.hip
+// runs it after its own trace kernel): the walk looks at no cost
+hipError_t launch_minplus_walk(const MinplusTraceArgs &a, const uint32_t *ops, const uint32_t *held, const uint32_t *reps, const uint32_t *forget_words, const uint32_t *pick,
+                               const uint64_t *D, uint8_t *chain_out, hipStream_t stream);
 // k_minplus_trace, then k_minplus_walk: stream order is the only synchronisation
 hipError_t launch_minplus_trace(const MinplusTraceArgs &a, const uint32_t *ops, const uint32_t *held, const uint32_t *reps, const uint32_t *forget_words, const uint32_t *pick,
                                 uint64_t *D, uint8_t *chain_out, hipStream_t stream);

@@ -9,6 +9,7 @@
 #include "class_sweep_site.hpp"
 #include "class_minplus.hpp"
 #include "class_minplus_trace.hpp"
+#include "class_minplus_site.hpp"
 #include "corrections.hpp"
 #include "enumerate.hpp"
 #include "kernel_choice.hpp"
@@ -477,6 +478,33 @@ uint32_t qt_class_minplus_trace_group(uint64_t N, int ncls, int n_held, uint64_t
     if (workspace) *workspace = minplus::kTraceWorkspaceBytes;
     return minplus::trace_launch_group(N, ncls, n_held, bytes_per_pair);
 }
+// the (min, +) sweep and its traceback under site costs (class_minplus_site.hpp): the host twins of qecmc_class_minplus_site and
+// qecmc_class_minplus_chains_site behind the same host checks, in the same order -- the QECMC_ERR_* code of the refusal, its message in msg (nullable);
+// qt_site_cost_words: rows of cq as the words host and device read, out uint32[rows][nq]
+int qt_class_minplus_site(int code, int L, uint64_t N, const uint8_t *chains, const uint8_t *cq, uint64_t cq_rows, int lds_width, uint32_t *cost_out, uint64_t *count_out,
+                          int32_t *cls, char *msg, int msg_cap)
+{
+    if (!chains || !cq || !cost_out || !count_out) return site_answer(refuse_params(QECMC_ERR_INVALID, "qecmc_class_minplus_site: NULL buffer"), msg, msg_cap);
+    if (N > 0xFFFFFFFFull) return site_answer(refuse_params(QECMC_ERR_INVALID, "qecmc_class_minplus_site: N=%llu syndromes exceed 32 bits", (unsigned long long)N), msg, msg_cap);
+    const sweep::CutPlan cp = minplus::build_minplus_site_plan(code, L, lds_width);
+    if (cp.plan.refusal.code) return site_answer(cp.plan.refusal, msg, msg_cap);
+    if (const Refusal r = minplus::check_cost_rows("qecmc_class_minplus_site", N, cq_rows); r.code) return site_answer(r, msg, msg_cap);
+    minplus::minplus_cut_site_host(cp, N, chains, cq, cq_rows, cost_out, count_out, cls);
+    return site_answer({}, msg, msg_cap);
+}
+int qt_class_minplus_chains_site(int code, int L, uint64_t N, const uint8_t *chains, const uint8_t *cq, uint64_t cq_rows, int lds_width, uint8_t *chain_out, uint32_t *cost_out,
+                                 uint64_t *count_out, int32_t *cls, char *msg, int msg_cap)
+{
+    if (!chains || !cq || !chain_out) return site_answer(refuse_params(QECMC_ERR_INVALID, "qecmc_class_minplus_chains_site: NULL buffer"), msg, msg_cap);
+    if (N > 0xFFFFFFFFull)
+        return site_answer(refuse_params(QECMC_ERR_INVALID, "qecmc_class_minplus_chains_site: N=%llu syndromes exceed 32 bits", (unsigned long long)N), msg, msg_cap);
+    const minplus::TracePlan tp = minplus::build_trace_site_plan(code, L, lds_width);
+    if (tp.cut.plan.refusal.code) return site_answer(tp.cut.plan.refusal, msg, msg_cap);
+    if (const Refusal r = minplus::check_cost_rows("qecmc_class_minplus_chains_site", N, cq_rows); r.code) return site_answer(r, msg, msg_cap);
+    minplus::minplus_trace_site_host(tp, N, chains, cq, cq_rows, chain_out, cost_out, count_out, cls);
+    return site_answer({}, msg, msg_cap);
+}
+void qt_site_cost_words(const uint8_t *cq, uint64_t rows, int nq, uint32_t *out) { minplus::site_cost_words(cq, rows, nq, out); }
 // the top rung's frames of a pick window (wu_frames.hpp) for an accepted scan = wave block, from the window's 64 pick blocks picks[64][4]: the plan's
 // descriptors and logical masks (rows padded to the kernel's WV words, as the kernel stages them), thr16 from the plan's thr_logical as wu_run forms it.
 // Writes frames[128 / iters][WV + 1] and returns WV; -1: refused, an unsupported width, or too small a buffer

@@ -22,7 +22,11 @@ The shortest chain of every class and its multiplicity (qecmc_class_minplus, DES
 exact value of what the shortest-chain estimators converge to.
 
 That sweep traced back to a chain (qecmc_class_minplus_chains): shortest_chains returns a shortest chain of every class next to
-cost and count, min_weight_corrections the minimum-weight decoder's correction."""
+cost and count, min_weight_corrections the minimum-weight decoder's correction.
+
+Both under a cost per (syndrome, qubit) (qecmc_class_minplus_site, qecmc_class_minplus_chains_site): class_minplus_site,
+shortest_chains_site, min_weight_classes_site and min_weight_corrections_site take a table of integer costs in place of the four numbers --
+erasures (erasure_site_costs), integer log-likelihoods of any site weights (llr_site_costs): the most likely chain of a class, exactly."""
 import ctypes as C
 
 import numpy as np
@@ -219,11 +223,13 @@ def _law_from_minplus(cost, count, saturated, base):
     return z / z.sum(axis=1, keepdims=True)
 
 
-def shortest_class_law(code, chains, p, alpha=None, **kw):
+def shortest_class_law(code, chains, p, alpha=None, site_costs=None, **kw):
     """float64[N, ncls]: the class law carried by the shortest chains alone, count_c * base^cost_c normalised per row (class_minplus, which takes the
     keywords size and lds_width) -- computed relative to the row's least cost, so nothing underflows.  Depolarizing noise p: unit costs,
     base = (p / 3) / (1 - p).  The alpha model (p is pz_tilde) with an integer-valued alpha: costs (0, alpha, alpha, 1), base = pz_tilde; a
     non-integer alpha raises ValueError.  A row with a saturated count raises OverflowError naming it.
+    site_costs (a table as class_minplus_site takes it): count_c * base^cost_c under those costs instead, base formed from p / alpha as above -- the
+    caller vouches that the costs are exponents of that base (erasure_site_costs of the noise's own costs are).
     This is the exact value of the second vector of shortest_distribution (unique_n * exp(-beta * shortest), there in percent) once its ladder has
     seen every shortest chain of every class, and the low-p limit of exact_class_probabilities."""
     if alpha is None:
@@ -232,8 +238,114 @@ def shortest_class_law(code, chains, p, alpha=None, **kw):
         if float(alpha) != np.floor(float(alpha)) or not 0 <= float(alpha) <= 255:
             raise ValueError(f"alpha={alpha!r}: shortest_class_law takes integer costs, so an integer-valued alpha in 0 .. 255 (non-integer costs are out of scope)")
         costs, base = (0, int(alpha), int(alpha), 1), float(p)
-    r = class_minplus(code, chains, costs, **kw)
+    r = class_minplus(code, chains, costs, **kw) if site_costs is None else class_minplus_site(code, chains, site_costs, **kw)
     return _law_from_minplus(r["cost"], r["count"], r["saturated"], base)
+
+
+def _as_site_costs(code, site_costs, L, n):
+    """site_costs -> (uint8[rows, nq, 4], rows): integers 0 .. 255 shaped as _as_site_weights takes its weights; ValueError naming the first cell that is
+    no such integer"""
+    a = np.asarray(site_costs)
+    if a.dtype.kind not in "biuf":
+        raise ValueError(f"site_costs of dtype {a.dtype}: integer costs 0 .. 255")
+    try:
+        wq, rows = _as_site_weights(code, a.astype(np.float64), L, n)
+    except ValueError as e:
+        raise ValueError(str(e).replace("site_weights", "site_costs")) from None
+    bad = ~(np.isfinite(wq) & (wq >= 0) & (wq <= 255) & (wq == np.floor(np.where(np.isfinite(wq), wq, 0.0))))
+    if bad.any():
+        r, q, i = (int(x) for x in np.argwhere(bad)[0])
+        raise ValueError(f"site_costs[row {r}][qubit {q}][{'IXYZ'[i]}]={float(wq[r, q, i])!r}: the site costs are integers 0 .. 255")
+    return np.ascontiguousarray(wq.astype(np.uint8)), rows
+
+
+def class_minplus_site(code, chains, site_costs, size=None, lds_width=0):
+    """class_minplus under a cost per qubit, or per (syndrome, qubit), on the GPU (qecmc_class_minplus_site).  code, chains, size and
+    lds_width as class_minplus takes them.  site_costs: integer [..., 4], the costs of I, X, Y and Z at every cell of the state layout, 0 .. 255 each,
+    ... being the code's qubit_matrix shape or the flat nq; one table for all syndromes (alone or after a leading 1), or with a leading N one per
+    syndrome.  The planar code's unused cells are not read.  erasure_site_costs and llr_site_costs build such tables.
+    Returns class_minplus's dict, key for key: cost[s, c] the least sum over the qubits of site_costs[row(s), q, Pauli at q]."""
+    code = _CODES.get(code, code)
+    flat, L = _as_chains(code, chains, size)
+    n, ncls = flat.shape[0], 16 if code == L_.TORIC else 4
+    cq, rows = _as_site_costs(code, site_costs, L, n)
+    cost = np.zeros((n, ncls), dtype=np.uint32)
+    count = np.zeros((n, ncls), dtype=np.uint64)
+    cls = np.zeros(n, dtype=np.int32)
+    L_.check(L_.lib().qecmc_class_minplus_site(code, L, n, L_.u8(flat), L_.u8(cq), rows, int(lds_width), cost.ctypes.data_as(L_._u32p),
+                                               count.ctypes.data_as(L_._u64p), L_.i32(cls)))
+    info = sweep_cut_info(code, L, lds_width)
+    return dict(cost=cost, count=count, saturated=count == 0, cls=cls, width=info["width"], held=info["held"])
+
+
+def shortest_chains_site(code, chains, site_costs, size=None, lds_width=0):
+    """shortest_chains under a cost per qubit, or per (syndrome, qubit), on the GPU (qecmc_class_minplus_chains_site): the arguments
+    are class_minplus_site's, the dict is shortest_chains', key for key -- chains[s, c] has the syndrome of chain s, lies in class c and costs
+    cost[s, c] under the table.  Under llr_site_costs it is a most likely chain of its class, exactly; where unique, THE most likely one."""
+    code = _CODES.get(code, code)
+    flat, L = _as_chains(code, chains, size)
+    n, ncls = flat.shape[0], 16 if code == L_.TORIC else 4
+    cq, rows = _as_site_costs(code, site_costs, L, n)
+    out = np.zeros((n, ncls, flat.shape[1]), dtype=np.uint8)
+    cost = np.zeros((n, ncls), dtype=np.uint32)
+    count = np.zeros((n, ncls), dtype=np.uint64)
+    cls = np.zeros(n, dtype=np.int32)
+    L_.check(L_.lib().qecmc_class_minplus_chains_site(code, L, n, L_.u8(flat), L_.u8(cq), rows, int(lds_width), L_.u8(out), cost.ctypes.data_as(L_._u32p),
+                                                      count.ctypes.data_as(L_._u64p), L_.i32(cls)))
+    info = sweep_cut_info(code, L, lds_width)
+    state = (2, L, L) if code in (L_.TORIC, L_.PLANAR) else (L, L)
+    return dict(chains=out.reshape((n, ncls) + state), cost=cost, count=count, saturated=count == 0, unique=count == 1, cls=cls, width=info["width"],
+                held=info["held"])
+
+
+def min_weight_classes_site(code, chains, site_costs, size=None, lds_width=0):
+    """int32[N]: min_weight_classes under site costs -- the class class_minplus_site gives the least cost, ties broken by the larger count, then by the
+    lower class index"""
+    r = class_minplus_site(code, chains, site_costs, size=size, lds_width=lds_width)
+    return _rank_classes(r["cost"], r["count"])
+
+
+def min_weight_corrections_site(code, chains, site_costs, size=None, lds_width=0):
+    """min_weight_corrections under site costs: dict(correction: the traced shortest chain (shortest_chains_site) of target, target: the class
+    min_weight_classes_site picks, weight uint32[N]: the correction's cost under the table, the least of its row)"""
+    r = shortest_chains_site(code, chains, site_costs, size=size, lds_width=lds_width)
+    target = _rank_classes(r["cost"], r["count"])
+    rows = np.arange(len(target))
+    return dict(correction=r["chains"][rows, target], target=target, weight=r["cost"][rows, target])
+
+
+def erasure_site_costs(base_costs, erased):
+    """site costs of a batch of shots with erasures: uint8[erased.shape + (4,)].  base_costs: the integer costs off the erased sets, [4] (one for all
+    cells) or [..., 4]; erased: a bool mask [N, ...] or [...].  An erased cell carries a uniform Pauli, so nothing there tells one chain from another:
+    it gets (0, 0, 0, 0)."""
+    erased = np.asarray(erased, dtype=bool)
+    base = np.asarray(base_costs)
+    if base.dtype.kind not in "biuf" or not np.all(np.isfinite(base)) or not np.all((base >= 0) & (base <= 255) & (base == np.floor(base))):
+        raise ValueError("base_costs: integer costs 0 .. 255")
+    out = np.array(np.broadcast_to(base.astype(np.uint8), erased.shape + (4,)))
+    out[erased] = 0
+    return out
+
+
+def llr_site_costs(site_w4, scale):
+    """integer log-likelihood costs of site weights: uint8[...], cost[q][P] = rint(scale * ln(max_P' w_q[P'] / w_q[P])) for site_w4 float [..., 4] (as the
+    _site_w4 builders return it), so that the likeliest Pauli of a cell costs 0 and the shortest chain under the table is the most likely one on the
+    scale's grid.  Weights that are exact powers base^k of one base give k at scale = 1 / ln(1 / base).  ValueError naming the first cell with a
+    zero, negative or non-finite weight, or whose cost passes 255: there is no silent cap."""
+    w = np.asarray(site_w4, dtype=np.float64)
+    if w.ndim < 1 or w.shape[-1] != 4:
+        raise ValueError(f"site_w4 of shape {w.shape}: [..., 4], the weights of I, X, Y and Z per cell")
+    bad = ~(np.isfinite(w) & (w > 0))
+    if bad.any():
+        cell = tuple(int(x) for x in np.argwhere(bad)[0])
+        raise ValueError(f"site_w4{list(cell[:-1])}[{'IXYZ'[cell[-1]]}]={float(w[cell])!r}: llr_site_costs takes finite weights > 0 (an erased cell is (1, 1, 1, 1), a cost of 0)")
+    if not np.isfinite(scale) or not scale > 0:
+        raise ValueError(f"scale={scale!r}: a finite number > 0")
+    cost = np.rint(float(scale) * (np.log(w.max(axis=-1, keepdims=True)) - np.log(w)))
+    if (cost > 255).any():
+        cell = tuple(int(x) for x in np.argwhere(cost > 255)[0])
+        raise ValueError(f"site_w4{list(cell[:-1])}[{'IXYZ'[cell[-1]]}]: a cost of {int(cost[cell])} at scale {scale!r} passes 255; lower the scale")
+    return cost.astype(np.uint8)
 
 
 def sweep_tiled_info(code, size, hbm_width=0, tile_width=0):

@@ -244,7 +244,10 @@ def _min_weight_distr(params, chains, device):
     (min, +, count) sweep: under depolarizing noise count * ((p / 3) / (1 - p))^(errors of the shortest chain), under the alpha model (an
     integer-valued params['alpha']) count * pz_tilde^(n_z + alpha n_xy).  Its argmax weighs a class's shortest chains by their number; as p -> 0 it is
     qecmc.min_weight_classes, the minimum-weight decoder.  params['lds_width'] (0: the default) as qecmc.class_minplus takes it.  Biased noise is
-    refused: its weights are no integer powers of one base."""
+    refused: its weights are no integer powers of one base.
+    params['site_costs'] (a table as qecmc.class_minplus_site takes it: integer [..., 4] per cell, with or without a leading n) replaces the four
+    costs of params['noise'] by a cost per (row, qubit) -- erasures, any costs that are exponents of the noise's base: the law is
+    count * base^cost under the table, base formed from p_error / alpha as above."""
     from .exact import shortest_class_law
     noise = params.get("noise", "depolarizing")
     if noise == "biased":
@@ -254,7 +257,7 @@ def _min_weight_distr(params, chains, device):
     if device != 0:
         raise ValueError("method min_weight runs on device 0: the library has no device-pointer form of it yet")
     return shortest_class_law(params["code"], chains, params["p_error"], alpha=params["alpha"] if noise == "alpha" else None, size=params["size"],
-                              lds_width=int(params.get("lds_width", 0)))
+                              lds_width=int(params.get("lds_width", 0)), site_costs=params.get("site_costs"))
 
 
 def _corrections_for(code, size, candidates, distr, device):
@@ -275,16 +278,26 @@ def _correction_route(params, method):
     return route
 
 
+def _site_costs_route(params, method):
+    """params['site_costs'] (qecmc.class_minplus_site's table) is built for method min_weight; refused by name under any other method"""
+    if params.get("site_costs") is not None and method != "min_weight":
+        raise ValueError(f"params['site_costs'] is built for method min_weight, not {method}: method exact takes params['site_weights']")
+
+
 def _shortest_corrections_for(params, chains, distr, device):
     """_corrections_for by params['correction'] = "shortest": target = argmax(distr) and, in the keys of qecmc.corrections, the traced shortest chain of
-    that class under the costs _min_weight_distr decodes with -- weight its error count, source 0, moved: target is not the start chain's class"""
-    from .exact import shortest_chains
+    that class under the costs _min_weight_distr decodes with -- params['site_costs'] where given -- weight its error count, source 0, moved: target is
+    not the start chain's class"""
+    from .exact import shortest_chains, shortest_chains_site
     noise = params.get("noise", "depolarizing")
     if device != 0:
         raise ValueError("method min_weight runs on device 0: the library has no device-pointer form of it yet")
     costs = (0, int(params["alpha"]), int(params["alpha"]), 1) if noise == "alpha" else (0, 1, 1, 1)
     target = np.argmax(distr, axis=1).astype(np.int32)
-    r = shortest_chains(params["code"], chains, costs, size=params["size"], lds_width=int(params.get("lds_width", 0)))
+    if params.get("site_costs") is not None:
+        r = shortest_chains_site(params["code"], chains, params["site_costs"], size=params["size"], lds_width=int(params.get("lds_width", 0)))
+    else:
+        r = shortest_chains(params["code"], chains, costs, size=params["size"], lds_width=int(params.get("lds_width", 0)))
     cor = r["chains"][np.arange(len(target)), target]
     return target, dict(corrections=cor, weight=(cor != 0).reshape(len(cor), -1).sum(axis=1).astype(np.int32), source=np.zeros(len(cor), np.int32),
                         moved=(target != r["cls"]).astype(np.uint8))
@@ -312,7 +325,8 @@ def decode_syndromes(params, defects, seed=0, steps=100000, conv_criteria="error
     params['method'] = "exact" decodes by coset enumeration instead (qecmc.exact_class_probabilities under the weight of params['noise'] itself;
     params['chunk_bits'] optional): distr float64[n, ncls], chains, status, weight -- no counts, no run.  params['site_weights'] is passed through:
     the exact law under a weight per (row, qubit) (_exact_distr).  params['method'] = "min_weight" returns the same keys with distr the law of the
-    shortest chains alone (_min_weight_distr).
+    shortest chains alone (_min_weight_distr); params['site_costs'] (method min_weight only, refused by name elsewhere) decodes under a cost per
+    (row, qubit), and params['correction'] = "shortest" then traces under the same table.
     corrections=True adds what a user who measured a syndrome wants (qecmc.corrections): target = argmax(distr) per row, correction -- a
     chain with the syndrome in that class --, correction_weight, correction_source and correction_moved.  The candidate is the lifted chain;
     correction_candidates="states" adds the Nc final rung states of every ladder as candidates 1 ..., where the route returns them: a fixed-length
@@ -325,6 +339,7 @@ def decode_syndromes(params, defects, seed=0, steps=100000, conv_criteria="error
     if method not in ("PTEQ", "exact", "min_weight"):
         raise ValueError("decode_syndromes decodes with PTEQ, exact or min_weight (params['method'])")
     route = _correction_route(params, method)
+    _site_costs_route(params, method)
     noise = params.get("noise", "depolarizing")
     if noise not in ("depolarizing", "biased", "alpha"):
         raise ValueError(f"noise={noise!r}")
@@ -394,18 +409,28 @@ def apply_erasures(m, erased, rng):
     return m
 
 
-def erasure_experiment(params, n, seed=0):
+def erasure_experiment(params, n, seed=0, method="exact"):
     """n shots of params['code'] at params['size'] under the noise of params (p_error, noise, eta as draw_errors takes them) AND erasures: every qubit
     erased with probability params['p_erase'], an erased qubit carrying a uniform Pauli.  Decoded from the BARE syndromes by the maximum-likelihood
     decoder that knows each shot's erased set: decode_syndromes, method exact, under qecmc.erasure_site_w4 of the noise's weights
     (params['exact_method'] and the widths as _exact_distr takes them; p_error = 0 is the pure-erasure channel, weights (1, 0, 0, 0) off the set).
+    method="min_weight" decodes the same shots -- the same draws for the same seed -- by the shortest chains instead (decode_syndromes, method
+    min_weight) under qecmc.erasure_site_costs of the noise's costs: (0, 1, 1, 1) for depolarizing noise, (0, alpha, alpha, 1) for
+    the alpha model with an integer alpha, an erased qubit free; biased noise is refused as _min_weight_distr refuses it.
     Returns dict(distr float64[n, ncls], eq_true: the class of the true error, success: argmax(distr) == eq_true, erased bool[n, ...], chains: the
     start chains the syndromes were lifted to)."""
-    from .exact import alpha_w4, biased_w4, depolarizing_w4, erasure_site_w4
+    from .exact import alpha_w4, biased_w4, depolarizing_w4, erasure_site_costs, erasure_site_w4
     code, size, p = _CODES[params["code"]], params["size"], params["p_error"]
     noise = params.get("noise", "depolarizing")
     if noise not in ("depolarizing", "biased", "alpha"):
         raise ValueError(f"noise={noise!r}")
+    if method not in ("exact", "min_weight"):
+        raise ValueError(f"method={method!r}: erasure_experiment decodes with 'exact' or 'min_weight'")
+    if method == "min_weight":
+        if noise == "biased":
+            raise ValueError("method min_weight is defined for depolarizing and alpha noise, not biased: the biased weights are no integer powers of one base")
+        if noise == "alpha" and (float(params["alpha"]) != np.floor(float(params["alpha"])) or not 0 <= float(params["alpha"]) <= 255):
+            raise ValueError(f"alpha={params['alpha']!r}: method min_weight takes integer costs, so an integer-valued alpha in 0 .. 255")
     rng = np.random.default_rng(seed)
     if noise == "alpha":
         errors = draw_errors(code, size, n, p, rng, rates=alpha_rates(p, params["alpha"]))
@@ -416,7 +441,12 @@ def erasure_experiment(params, n, seed=0):
         base = depolarizing_w4(p) if eta is None else biased_w4(p, eta)
     erased = draw_erasures(code, size, n, params["p_erase"], rng)
     errors = apply_erasures(errors, erased, rng)
-    decode = dict(params, method="exact", site_weights=erasure_site_w4(base, erased))
+    if method == "min_weight":
+        costs = (0, int(params["alpha"]), int(params["alpha"]), 1) if noise == "alpha" else (0, 1, 1, 1)
+        decode = dict(params, method="min_weight", site_costs=erasure_site_costs(costs, erased))
+        decode.pop("site_weights", None)
+    else:
+        decode = dict(params, method="exact", site_weights=erasure_site_w4(base, erased))
     out = decode_syndromes(decode, syndrome_of(code, errors))
     eq_true = np.asarray(_class_of(code, errors)).astype(np.int32)
     return dict(distr=out["distr"], eq_true=eq_true, success=np.argmax(out["distr"], axis=1) == eq_true, erased=erased, chains=out["chains"])
@@ -440,7 +470,9 @@ def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_
     on top of it; `steps` and the sampler keywords are not looked at.
     params['method'] = "min_weight" decodes by the shortest chains: distr float64[n, ncls] is the law carried by the shortest chains of every class
     alone, exact (qecmc.shortest_class_law; depolarizing noise, or alpha noise with an integer alpha; biased noise is refused), with
-    success and no counts; start="syndrome" and corrections=True work as they do for "exact".
+    success and no counts; start="syndrome" and corrections=True work as they do for "exact".  params['site_costs'] (method min_weight only, refused by
+    name under any other) decodes under a cost per (row, qubit) (qecmc.class_minplus_site), and params['correction'] = "shortest"
+    traces under the same table.
     device_generation=True draws the errors and the hiding logical operator on the GPU (`generate_syndromes`) instead of NumPy.
     start="error" (default) is the reference's recipe: the decoder starts from the error with a random logical operator on top.  start="syndrome"
     (methods PTEQ, exact and min_weight) lets nothing but syndrome(raw) reach the decoder: the start chains are qecmc.chains_from_syndromes of it and no logical
@@ -475,6 +507,7 @@ def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_
     if method == "min_weight" and noise == "biased":
         raise ValueError("method min_weight is defined for depolarizing and alpha noise, not biased: the biased weights are no integer powers of one base")
     _correction_route(params, method)
+    _site_costs_route(params, method)
     if device_generation:
         # errors, true class and the hiding logical operator drawn on the GPU (Philox keyed by the global syndrome index: the data
         # set does not depend on how it is cut into shards)
