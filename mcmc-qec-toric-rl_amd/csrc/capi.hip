@@ -640,6 +640,69 @@ int qecmc_class_sweep_info(int code, int L, int32_t *width, int32_t *ncls, int32
     return 0;
 }
 
+extern "C++" {                                                                  // (templates)
+namespace {
+// What the ten entry points of the class sweeps share: the op words and the held words of the plan and the representatives of one launch group on
+// the device, and the host loop over groups of syndromes -- no launch, and no device block, grows with the batch.
+struct SweepBatch {
+    const sweep::Plan &p;
+    const uint32_t group;
+    const size_t rep_words;                                                     // words of one syndrome's representatives
+    std::vector<uint32_t> reps;
+    DevBuf dops, dheld, dreps;
+    SweepBatch(const sweep::Plan &plan, uint32_t syndromes) : p(plan), group(syndromes), rep_words((size_t)plan.ncls * plan.W), reps((size_t)syndromes * rep_words) {}
+    // the three blocks, and the uploads that do not change from group to group; held: nullptr where the route holds nothing
+    int open(const std::vector<uint32_t> &ops, const std::vector<uint32_t> *held)
+    {
+        HIP_TRY(dops.alloc(ops.size() * sizeof(uint32_t)));
+        if (held) HIP_TRY(dheld.alloc(held->size() * sizeof(uint32_t)));
+        HIP_TRY(dreps.alloc(reps.size() * sizeof(uint32_t)));
+        HIP_TRY(hipMemcpy(dops.p, ops.data(), ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (held && !held->empty()) HIP_TRY(hipMemcpy(dheld.p, held->data(), held->size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        return 0;
+    }
+    // per group: class_representatives per syndrome, their upload, then body(first, here) -- the entry point's launches and copies back
+    template <class Body> int run(uint64_t N, const uint8_t *chains, int32_t *class_out, Body body)
+    {
+        for (uint64_t first = 0; first < N; first += group) {
+            const uint64_t here = N - first < group ? N - first : group;
+            for (uint64_t s = 0; s < here; ++s) {
+                const int cls = sweep::class_representatives(p, chains + (first + s) * (uint64_t)p.nq, reps.data() + s * rep_words);
+                if (class_out) class_out[first + s] = cls;
+            }
+            HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * rep_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+            if (int rc = body(first, here)) return rc;
+        }
+        return 0;
+    }
+    // `per` elements per (syndrome, class) of a group's results, to their place in the caller's array; out may be NULL
+    template <class T> int fetch(T *out, const DevBuf &d, uint64_t first, uint64_t here, size_t per = 1) const
+    {
+        const size_t row = (size_t)p.ncls * per;
+        if (out) HIP_TRY(hipMemcpy(out + first * row, d.p, (size_t)here * row * sizeof(T), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    uint32_t *ops() const { return dops.as<uint32_t>(); }
+    uint32_t *held() const { return dheld.as<uint32_t>(); }
+    uint32_t *rep() const { return dreps.as<uint32_t>(); }
+};
+
+SweepCutArgs cut_args(const sweep::Plan &p, int n_held)
+{
+    SweepCutArgs a = {};
+    a.ncls = p.ncls; a.W = p.W; a.width = p.width; a.n_ops = p.n_ops; a.n_held = n_held; a.scale = p.scale;
+    return a;
+}
+
+MinplusArgs minplus_args(const sweep::Plan &p, int n_held)
+{
+    MinplusArgs a = {};
+    a.ncls = p.ncls; a.W = p.W; a.width = p.width; a.n_ops = p.n_ops; a.n_held = n_held; a.shift = p.n_gen - p.rank;
+    return a;
+}
+}  // namespace
+}  // extern "C++"
+
 int qecmc_class_sweep(int code, int L, uint64_t N, const uint8_t *chains, const double *w, double *z_out, int32_t *class_out)
 {
     if (!chains || !w || !z_out) return fail(QECMC_ERR_INVALID, "qecmc_class_sweep: NULL buffer");
@@ -649,30 +712,18 @@ int qecmc_class_sweep(int code, int L, uint64_t N, const uint8_t *chains, const 
     if (int rc = report(p.refusal)) return rc;
     if (int rc = use_device(0)) return rc;
     if (N == 0) return 0;
-    const uint32_t group = sweep::launch_group(N);
-    const size_t rep_words = (size_t)p.ncls * p.W;                              // words of one syndrome's representatives
-    std::vector<uint32_t> reps((size_t)group * rep_words);
-    DevBuf dops, dreps, dz;
-    HIP_TRY(dops.alloc(p.ops.size() * sizeof(uint32_t)));
-    HIP_TRY(dreps.alloc(reps.size() * sizeof(uint32_t)));
-    HIP_TRY(dz.alloc((size_t)group * p.ncls * sizeof(double)));
-    HIP_TRY(hipMemcpy(dops.p, p.ops.data(), p.ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    SweepBatch b(p, sweep::launch_group(N));
+    DevBuf dz;
+    if (int rc = b.open(p.ops, nullptr)) return rc;
+    HIP_TRY(dz.alloc((size_t)b.group * p.ncls * sizeof(double)));
     SweepArgs a = {};
     a.ncls = p.ncls; a.W = p.W; a.width = p.width; a.n_ops = p.n_ops; a.scale = p.scale;
     sweep::weights_xz(w, a.wxz);
-    // the host loops over groups of syndromes: no launch, and no device block, grows with the batch; every z of a group is written by its workgroup
-    for (uint64_t first = 0; first < N; first += group) {
-        const uint64_t here = N - first < group ? N - first : group;
-        for (uint64_t s = 0; s < here; ++s) {
-            const int cls = sweep::class_representatives(p, chains + (first + s) * (uint64_t)p.nq, reps.data() + s * rep_words);
-            if (class_out) class_out[first + s] = cls;
-        }
-        HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * rep_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return b.run(N, chains, class_out, [&](uint64_t first, uint64_t here) {     // every z of a group is written by its workgroup
         a.S = (uint32_t)here;
-        HIP_TRY(launch_class_sweep(a, dops.as<uint32_t>(), dreps.as<uint32_t>(), dz.as<double>(), 0));
-        HIP_TRY(hipMemcpy(z_out + first * (uint64_t)p.ncls, dz.p, (size_t)here * p.ncls * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    return 0;
+        HIP_TRY(launch_class_sweep(a, b.ops(), b.rep(), dz.as<double>(), 0));
+        return b.fetch(z_out, dz, first, here);
+    });
 }
 
 // ---------------------------------------------------------------- the frontier sweep past one LDS state vector (class_sweep_cut.hpp)
@@ -702,33 +753,19 @@ int qecmc_class_sweep_cut(int code, int L, uint64_t N, const uint8_t *chains, co
     if (N == 0) return 0;
     if (class_sweep_cut_allow_lds(p.width) != hipSuccess)
         return fail(QECMC_ERR_UNSUPPORTED, "this device does not grant a workgroup the %u bytes of LDS a state vector of width %d takes", p.carve.bytes, p.width);
-    const uint32_t group = sweep::cut_launch_group(N, p.ncls, cp.n_held);
-    const size_t rep_words = (size_t)p.ncls * p.W, partials = (size_t)p.ncls << cp.n_held;   // of one syndrome
-    std::vector<uint32_t> reps((size_t)group * rep_words);
-    DevBuf dops, dheld, dreps, dpart, dz;
-    HIP_TRY(dops.alloc(p.ops.size() * sizeof(uint32_t)));
-    HIP_TRY(dheld.alloc(cp.held_words.size() * sizeof(uint32_t)));
-    HIP_TRY(dreps.alloc(reps.size() * sizeof(uint32_t)));
-    HIP_TRY(dpart.alloc((size_t)group * partials * sizeof(double)));            // kCutGridMax doubles at most; dirty: every partial is written before it is read
-    HIP_TRY(dz.alloc((size_t)group * p.ncls * sizeof(double)));
-    HIP_TRY(hipMemcpy(dops.p, p.ops.data(), p.ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (cp.n_held) HIP_TRY(hipMemcpy(dheld.p, cp.held_words.data(), cp.held_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    SweepCutArgs a = {};
-    a.ncls = p.ncls; a.W = p.W; a.width = p.width; a.n_ops = p.n_ops; a.n_held = cp.n_held; a.scale = p.scale;
+    SweepBatch b(p, sweep::cut_launch_group(N, p.ncls, cp.n_held));
+    const size_t partials = (size_t)p.ncls << cp.n_held;                        // of one syndrome
+    DevBuf dpart, dz;
+    if (int rc = b.open(p.ops, &cp.held_words)) return rc;
+    HIP_TRY(dpart.alloc((size_t)b.group * partials * sizeof(double)));          // kCutGridMax doubles at most; dirty: every partial is written before it is read
+    HIP_TRY(dz.alloc((size_t)b.group * p.ncls * sizeof(double)));
+    SweepCutArgs a = cut_args(p, cp.n_held);
     sweep::weights_xz(w, a.wxz);
-    // the host loops over groups of syndromes: no launch, and no device block, grows with the batch
-    for (uint64_t first = 0; first < N; first += group) {
-        const uint64_t here = N - first < group ? N - first : group;
-        for (uint64_t s = 0; s < here; ++s) {
-            const int cls = sweep::class_representatives(p, chains + (first + s) * (uint64_t)p.nq, reps.data() + s * rep_words);
-            if (class_out) class_out[first + s] = cls;
-        }
-        HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * rep_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return b.run(N, chains, class_out, [&](uint64_t first, uint64_t here) {
         a.S = (uint32_t)here;
-        HIP_TRY(launch_class_sweep_cut(a, dops.as<uint32_t>(), dheld.as<uint32_t>(), dreps.as<uint32_t>(), dpart.as<double>(), dz.as<double>(), 0));
-        HIP_TRY(hipMemcpy(z_out + first * (uint64_t)p.ncls, dz.p, (size_t)here * p.ncls * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    return 0;
+        HIP_TRY(launch_class_sweep_cut(a, b.ops(), b.held(), b.rep(), dpart.as<double>(), dz.as<double>(), 0));
+        return b.fetch(z_out, dz, first, here);
+    });
 }
 
 // ---------------------------------------------------------------- shortest chains per class: the sweep in (min, +, count) (class_minplus.hpp)
@@ -746,36 +783,50 @@ int qecmc_class_minplus(int code, int L, uint64_t N, const uint8_t *chains, cons
     if (class_minplus_allow_lds(p.width) != hipSuccess)
         return fail(QECMC_ERR_UNSUPPORTED, "qecmc_class_minplus: this device does not grant a workgroup the %u bytes of LDS a state vector of width %d takes", p.carve.bytes,
                     p.width);
-    const uint32_t group = sweep::cut_launch_group(N, p.ncls, cp.n_held);
-    const size_t rep_words = (size_t)p.ncls * p.W, partials = (size_t)p.ncls << cp.n_held;   // of one syndrome
-    std::vector<uint32_t> reps((size_t)group * rep_words);
-    DevBuf dops, dheld, dreps, dpart, dcost, dcount;
-    HIP_TRY(dops.alloc(p.ops.size() * sizeof(uint32_t)));
-    HIP_TRY(dheld.alloc(cp.held_words.size() * sizeof(uint32_t)));
-    HIP_TRY(dreps.alloc(reps.size() * sizeof(uint32_t)));
-    HIP_TRY(dpart.alloc((size_t)group * partials * sizeof(uint64_t)));          // kCutGridMax entries at most; dirty: every partial is written before it is read
-    HIP_TRY(dcost.alloc((size_t)group * p.ncls * sizeof(uint32_t)));
-    HIP_TRY(dcount.alloc((size_t)group * p.ncls * sizeof(uint64_t)));
-    HIP_TRY(hipMemcpy(dops.p, p.ops.data(), p.ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (cp.n_held) HIP_TRY(hipMemcpy(dheld.p, cp.held_words.data(), cp.held_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    MinplusArgs a = {};
-    a.ncls = p.ncls; a.W = p.W; a.width = p.width; a.n_ops = p.n_ops; a.n_held = cp.n_held; a.shift = p.n_gen - p.rank;
+    SweepBatch b(p, sweep::cut_launch_group(N, p.ncls, cp.n_held));
+    const size_t partials = (size_t)p.ncls << cp.n_held;                        // of one syndrome
+    DevBuf dpart, dcost, dcount;
+    if (int rc = b.open(p.ops, &cp.held_words)) return rc;
+    HIP_TRY(dpart.alloc((size_t)b.group * partials * sizeof(uint64_t)));        // kCutGridMax entries at most; dirty: every partial is written before it is read
+    HIP_TRY(dcost.alloc((size_t)b.group * p.ncls * sizeof(uint32_t)));
+    HIP_TRY(dcount.alloc((size_t)b.group * p.ncls * sizeof(uint64_t)));
+    MinplusArgs a = minplus_args(p, cp.n_held);
     minplus::costs_xz(cost, a.cxz);
-    // the host loops over groups of syndromes: no launch, and no device block, grows with the batch
-    for (uint64_t first = 0; first < N; first += group) {
-        const uint64_t here = N - first < group ? N - first : group;
-        for (uint64_t s = 0; s < here; ++s) {
-            const int cls = sweep::class_representatives(p, chains + (first + s) * (uint64_t)p.nq, reps.data() + s * rep_words);
-            if (class_out) class_out[first + s] = cls;
-        }
-        HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * rep_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return b.run(N, chains, class_out, [&](uint64_t first, uint64_t here) {
         a.S = (uint32_t)here;
-        HIP_TRY(launch_class_minplus(a, dops.as<uint32_t>(), dheld.as<uint32_t>(), dreps.as<uint32_t>(), dpart.as<uint64_t>(), dcost.as<uint32_t>(), dcount.as<uint64_t>(), 0));
-        HIP_TRY(hipMemcpy(cost_out + first * (uint64_t)p.ncls, dcost.p, (size_t)here * p.ncls * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(count_out + first * (uint64_t)p.ncls, dcount.p, (size_t)here * p.ncls * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    }
-    return 0;
+        HIP_TRY(launch_class_minplus(a, b.ops(), b.held(), b.rep(), dpart.as<uint64_t>(), dcost.as<uint32_t>(), dcount.as<uint64_t>(), 0));
+        if (int rc = b.fetch(cost_out, dcost, first, here)) return rc;
+        return b.fetch(count_out, dcount, first, here);
+    });
 }
+
+namespace {
+// the device blocks of a traceback besides the sweep's: the forget words, the picks, the decision words and the chains of one launch group
+struct TraceBlocks {
+    DevBuf dforget, dpart, dpick, ddec, dchain, dcost, dcount;
+    int open(const SweepBatch &b, const minplus::TracePlan &tp, uint64_t pair_bytes)
+    {
+        const sweep::Plan &p = b.p;
+        const size_t pairs = (size_t)b.group * p.ncls;
+        HIP_TRY(dforget.alloc(tp.forget_words.size() * sizeof(uint32_t)));
+        HIP_TRY(dpart.alloc((pairs << tp.cut.n_held) * sizeof(uint64_t)));      // dirty: every partial is written before it is read
+        HIP_TRY(dpick.alloc(pairs * sizeof(uint32_t)));
+        HIP_TRY(ddec.alloc(pairs * (size_t)pair_bytes));                        // kTraceWorkspaceBytes at most; dirty: the walk reads what the trace wrote
+        HIP_TRY(dchain.alloc(pairs * p.nq));
+        HIP_TRY(dcost.alloc(pairs * sizeof(uint32_t)));
+        HIP_TRY(dcount.alloc(pairs * sizeof(uint64_t)));
+        HIP_TRY(hipMemcpy(dforget.p, tp.forget_words.data(), tp.forget_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        return 0;
+    }
+    // the chains, and the costs and counts where the caller asked for them
+    int fetch(const SweepBatch &b, uint64_t first, uint64_t here, uint8_t *chain_out, uint32_t *cost_out, uint64_t *count_out) const
+    {
+        if (int rc = b.fetch(chain_out, dchain, first, here, (size_t)b.p.nq)) return rc;
+        if (int rc = b.fetch(cost_out, dcost, first, here)) return rc;
+        return b.fetch(count_out, dcount, first, here);
+    }
+};
+}  // namespace
 
 // ---------------------------------------------------------------- a shortest chain per class: the (min, +) sweep traced back (class_minplus_trace.hpp)
 int qecmc_class_minplus_chains(int code, int L, uint64_t N, const uint8_t *chains, const uint32_t cost[4], int lds_width, uint8_t *chain_out, uint32_t *cost_out,
@@ -794,47 +845,23 @@ int qecmc_class_minplus_chains(int code, int L, uint64_t N, const uint8_t *chain
         return fail(QECMC_ERR_UNSUPPORTED, "qecmc_class_minplus_chains: this device does not grant a workgroup the %u bytes of LDS a state vector of width %d takes",
                     p.carve.bytes, p.width);
     const uint64_t pair_bytes = minplus::trace_bytes_per_pair(tp);
-    const uint32_t group = minplus::trace_launch_group(N, p.ncls, cp.n_held, pair_bytes);
-    const size_t rep_words = (size_t)p.ncls * p.W, partials = (size_t)p.ncls << cp.n_held;   // of one syndrome
-    std::vector<uint32_t> reps((size_t)group * rep_words);
-    DevBuf dops, dheld, dreps, dforget, dpart, dpick, ddec, dchain, dcost, dcount;
-    HIP_TRY(dops.alloc(p.ops.size() * sizeof(uint32_t)));
-    HIP_TRY(dheld.alloc(cp.held_words.size() * sizeof(uint32_t)));
-    HIP_TRY(dreps.alloc(reps.size() * sizeof(uint32_t)));
-    HIP_TRY(dforget.alloc(tp.forget_words.size() * sizeof(uint32_t)));
-    HIP_TRY(dpart.alloc((size_t)group * partials * sizeof(uint64_t)));          // dirty: every partial is written before it is read
-    HIP_TRY(dpick.alloc((size_t)group * p.ncls * sizeof(uint32_t)));
-    HIP_TRY(ddec.alloc((size_t)group * p.ncls * (size_t)pair_bytes));           // kTraceWorkspaceBytes at most; dirty: the walk reads what the trace wrote
-    HIP_TRY(dchain.alloc((size_t)group * p.ncls * p.nq));
-    HIP_TRY(dcost.alloc((size_t)group * p.ncls * sizeof(uint32_t)));
-    HIP_TRY(dcount.alloc((size_t)group * p.ncls * sizeof(uint64_t)));
-    HIP_TRY(hipMemcpy(dops.p, p.ops.data(), p.ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (cp.n_held) HIP_TRY(hipMemcpy(dheld.p, cp.held_words.data(), cp.held_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dforget.p, tp.forget_words.data(), tp.forget_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    SweepBatch b(p, minplus::trace_launch_group(N, p.ncls, cp.n_held, pair_bytes));
+    TraceBlocks d;
+    if (int rc = b.open(p.ops, &cp.held_words)) return rc;
+    if (int rc = d.open(b, tp, pair_bytes)) return rc;
     MinplusTraceArgs t = {};
     MinplusArgs &a = t.m;
-    a.ncls = p.ncls; a.W = p.W; a.width = p.width; a.n_ops = p.n_ops; a.n_held = cp.n_held; a.shift = p.n_gen - p.rank;
+    a = minplus_args(p, cp.n_held);
     minplus::costs_xz(cost, a.cxz);
     t.n_forget = tp.n_forget; t.words_per_forget = tp.words_per_forget; t.nq = p.nq;
-    // the host loops over groups of syndromes: no launch, and no device block, grows with the batch
-    for (uint64_t first = 0; first < N; first += group) {
-        const uint64_t here = N - first < group ? N - first : group;
-        for (uint64_t s = 0; s < here; ++s) {
-            const int cls = sweep::class_representatives(p, chains + (first + s) * (uint64_t)p.nq, reps.data() + s * rep_words);
-            if (class_out) class_out[first + s] = cls;
-        }
-        HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * rep_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return b.run(N, chains, class_out, [&](uint64_t first, uint64_t here) {
         a.S = (uint32_t)here;
-        HIP_TRY(launch_class_minplus_sweep(a, dops.as<uint32_t>(), dheld.as<uint32_t>(), dreps.as<uint32_t>(), dpart.as<uint64_t>(), 0));
-        HIP_TRY(launch_minplus_pick(a, dpart.as<uint64_t>(), dpick.as<uint32_t>(), 0));            // (before the reduce folds the partials in place)
-        HIP_TRY(launch_class_minplus_reduce(a, dpart.as<uint64_t>(), dcost.as<uint32_t>(), dcount.as<uint64_t>(), 0));
-        HIP_TRY(launch_minplus_trace(t, dops.as<uint32_t>(), dheld.as<uint32_t>(), dreps.as<uint32_t>(), dforget.as<uint32_t>(), dpick.as<uint32_t>(), ddec.as<uint64_t>(),
-                                     dchain.as<uint8_t>(), 0));
-        HIP_TRY(hipMemcpy(chain_out + first * (uint64_t)p.ncls * (uint64_t)p.nq, dchain.p, (size_t)here * p.ncls * p.nq, hipMemcpyDeviceToHost));
-        if (cost_out) HIP_TRY(hipMemcpy(cost_out + first * (uint64_t)p.ncls, dcost.p, (size_t)here * p.ncls * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        if (count_out) HIP_TRY(hipMemcpy(count_out + first * (uint64_t)p.ncls, dcount.p, (size_t)here * p.ncls * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    }
-    return 0;
+        HIP_TRY(launch_class_minplus_sweep(a, b.ops(), b.held(), b.rep(), d.dpart.as<uint64_t>(), 0));
+        HIP_TRY(launch_minplus_pick(a, d.dpart.as<uint64_t>(), d.dpick.as<uint32_t>(), 0));          // (before the reduce folds the partials in place)
+        HIP_TRY(launch_class_minplus_reduce(a, d.dpart.as<uint64_t>(), d.dcost.as<uint32_t>(), d.dcount.as<uint64_t>(), 0));
+        HIP_TRY(launch_minplus_trace(t, b.ops(), b.held(), b.rep(), d.dforget.as<uint32_t>(), d.dpick.as<uint32_t>(), d.ddec.as<uint64_t>(), d.dchain.as<uint8_t>(), 0));
+        return d.fetch(b, first, here, chain_out, cost_out, count_out);
+    });
 }
 
 // ---------------------------------------------------------------- the frontier sweep on a state vector tiled over HBM (class_sweep_tiled.hpp)
@@ -876,6 +903,40 @@ struct TiledWorkspace {
         return hipSuccess;
     }
 };
+
+extern "C++" {                                                                  // (a template)
+// What the two tiled entry points share once the plan is accepted and the device chosen.  open_rows(group): the caller's own blocks, after the
+// sweep's; per_group(first, here): its per-group uploads; pass(unit_first, units, batch, work, partials): the launches of one pass of units.  The
+// host loops over groups of syndromes and, within a group, over passes of units: no launch, and no device block, grows with the batch.
+template <class OpenRows, class PerGroup, class Pass>
+int tiled_batch(const sweep::TiledPlan &tp, uint64_t N, const uint8_t *chains, double *z_out, int32_t *class_out, OpenRows open_rows, PerGroup per_group, Pass pass_launch)
+{
+    const sweep::Plan &p = tp.plan;
+    SweepBatch b(p, sweep::cut_launch_group(N, p.ncls, tp.n_held));
+    const uint32_t pass = sweep::tiled_pass_units(tp.state_bits);
+    const size_t partials = (size_t)p.ncls << tp.n_held;                        // of one syndrome
+    const uint64_t group_units = (uint64_t)b.group * partials;
+    DevBuf dpart, dz;
+    if (int rc = b.open(tp.dev_ops, &tp.held_words)) return rc;
+    HIP_TRY(dpart.alloc((size_t)b.group * partials * sizeof(double)));          // kCutGridMax doubles at most; dirty: every partial is written before it is read
+    HIP_TRY(dz.alloc((size_t)b.group * p.ncls * sizeof(double)));
+    if (int rc = open_rows(b.group)) return rc;
+    TiledWorkspace &ws = TiledWorkspace::get();                                 // one block, one cap of kTiledWorkspaceBytes and one lock for both entry points
+    std::lock_guard<std::mutex> hold(ws.mu);
+    double *work = nullptr;
+    HIP_TRY(ws.take((size_t)(group_units < pass ? group_units : pass) * (sizeof(double) << tp.state_bits), &work));
+    SweepCutArgs ra = cut_args(p, tp.n_held);
+    return b.run(N, chains, class_out, [&](uint64_t first, uint64_t here) {
+        const uint64_t units = here * partials;
+        if (int rc = per_group(first, here)) return rc;
+        for (uint64_t u = 0; u < units; u += pass)
+            HIP_TRY(pass_launch((uint32_t)u, (uint32_t)(units - u < pass ? units - u : pass), b, work, dpart.as<double>()));
+        ra.S = (uint32_t)here;
+        HIP_TRY(launch_class_sweep_reduce(ra, dpart.as<double>(), dz.as<double>(), 0));
+        return b.fetch(z_out, dz, first, here);
+    });
+}
+}  // extern "C++"
 }  // namespace
 
 int qecmc_class_sweep_tiled(int code, int L, uint64_t N, const uint8_t *chains, const double *w, int hbm_width, int tile_width, double *z_out, int32_t *class_out)
@@ -884,46 +945,15 @@ int qecmc_class_sweep_tiled(int code, int L, uint64_t N, const uint8_t *chains, 
     if (N > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "N=%llu syndromes exceed 32 bits", (unsigned long long)N);
     if (int rc = report(sweep::check_weights(w))) return rc;
     const sweep::TiledPlan tp = sweep::build_tiled_plan(code, L, hbm_width, tile_width);
-    const sweep::Plan &p = tp.plan;
-    if (int rc = report(p.refusal)) return rc;
+    if (int rc = report(tp.plan.refusal)) return rc;
     if (int rc = use_device(0)) return rc;
     if (N == 0) return 0;
-    const uint32_t group = sweep::cut_launch_group(N, p.ncls, tp.n_held), pass = sweep::tiled_pass_units(tp.state_bits);
-    const size_t rep_words = (size_t)p.ncls * p.W, partials = (size_t)p.ncls << tp.n_held;   // of one syndrome
-    const uint64_t group_units = (uint64_t)group * partials;
-    std::vector<uint32_t> reps((size_t)group * rep_words);
-    DevBuf dops, dheld, dreps, dpart, dz;
-    HIP_TRY(dops.alloc(tp.dev_ops.size() * sizeof(uint32_t)));
-    HIP_TRY(dheld.alloc(tp.held_words.size() * sizeof(uint32_t)));
-    HIP_TRY(dreps.alloc(reps.size() * sizeof(uint32_t)));
-    HIP_TRY(dpart.alloc((size_t)group * partials * sizeof(double)));            // kCutGridMax doubles at most; dirty: every partial is written before it is read
-    HIP_TRY(dz.alloc((size_t)group * p.ncls * sizeof(double)));
-    HIP_TRY(hipMemcpy(dops.p, tp.dev_ops.data(), tp.dev_ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (tp.n_held) HIP_TRY(hipMemcpy(dheld.p, tp.held_words.data(), tp.held_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    TiledWorkspace &ws = TiledWorkspace::get();
-    std::lock_guard<std::mutex> hold(ws.mu);
-    double *work = nullptr;
-    HIP_TRY(ws.take((size_t)(group_units < pass ? group_units : pass) * (sizeof(double) << tp.state_bits), &work));
-    SweepCutArgs ra = {};
-    ra.ncls = p.ncls; ra.W = p.W; ra.width = p.width; ra.n_ops = p.n_ops; ra.n_held = tp.n_held; ra.scale = p.scale;
     double wxz[4];
     sweep::weights_xz(w, wxz);
-    // the host loops over groups of syndromes and, within a group, over passes of units: no launch, and no device block, grows with the batch
-    for (uint64_t first = 0; first < N; first += group) {
-        const uint64_t here = N - first < group ? N - first : group, units = here * partials;
-        for (uint64_t s = 0; s < here; ++s) {
-            const int cls = sweep::class_representatives(p, chains + (first + s) * (uint64_t)p.nq, reps.data() + s * rep_words);
-            if (class_out) class_out[first + s] = cls;
-        }
-        HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * rep_words * sizeof(uint32_t), hipMemcpyHostToDevice));
-        for (uint64_t u = 0; u < units; u += pass)
-            HIP_TRY(launch_class_sweep_tiled(tp, wxz, (uint32_t)u, (uint32_t)(units - u < pass ? units - u : pass), dops.as<uint32_t>(), dheld.as<uint32_t>(),
-                                             dreps.as<uint32_t>(), work, dpart.as<double>(), 0));
-        ra.S = (uint32_t)here;
-        HIP_TRY(launch_class_sweep_reduce(ra, dpart.as<double>(), dz.as<double>(), 0));
-        HIP_TRY(hipMemcpy(z_out + first * (uint64_t)p.ncls, dz.p, (size_t)here * p.ncls * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    return 0;
+    return tiled_batch(tp, N, chains, z_out, class_out, [](uint32_t) { return 0; }, [](uint64_t, uint64_t) { return 0; },
+                       [&](uint32_t unit_first, uint32_t units, const SweepBatch &b, double *work, double *P) {
+                           return launch_class_sweep_tiled(tp, wxz, unit_first, units, b.ops(), b.held(), b.rep(), work, P, 0);
+                       });
 }
 
 // ---------------------------------------------------------------- the three sweeps under a weight per (syndrome, qubit) (class_sweep_site.hpp)
@@ -969,32 +999,20 @@ int qecmc_class_sweep_site(int code, int L, uint64_t N, const uint8_t *chains, c
     if (int rc = check_site(N, wq, wq_rows, p.nq, p.ops)) return rc;
     if (int rc = use_device(0)) return rc;
     if (N == 0) return 0;
-    const uint32_t group = sweep::launch_group(N);
-    const size_t rep_words = (size_t)p.ncls * p.W;                              // words of one syndrome's representatives
-    std::vector<uint32_t> reps((size_t)group * rep_words);
-    DevBuf dops, dreps, dz;
+    SweepBatch b(p, sweep::launch_group(N));
+    DevBuf dz;
     SiteRows rows;
-    HIP_TRY(dops.alloc(p.ops.size() * sizeof(uint32_t)));
-    HIP_TRY(dreps.alloc(reps.size() * sizeof(uint32_t)));
-    HIP_TRY(dz.alloc((size_t)group * p.ncls * sizeof(double)));
-    HIP_TRY(hipMemcpy(dops.p, p.ops.data(), p.ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (int rc = rows.open(wq, wq_rows, p.nq, group)) return rc;
+    if (int rc = b.open(p.ops, nullptr)) return rc;
+    HIP_TRY(dz.alloc((size_t)b.group * p.ncls * sizeof(double)));
+    if (int rc = rows.open(wq, wq_rows, p.nq, b.group)) return rc;
     SweepSiteArgs a = {};
     a.ncls = p.ncls; a.W = p.W; a.width = p.width; a.n_ops = p.n_ops; a.nq = p.nq; a.per_syndrome = rows.per_syndrome; a.scale = p.scale;
-    // the host loops over groups of syndromes: no launch, and no device block -- the weight rows among them -- grows with the batch
-    for (uint64_t first = 0; first < N; first += group) {
-        const uint64_t here = N - first < group ? N - first : group;
-        for (uint64_t s = 0; s < here; ++s) {
-            const int cls = sweep::class_representatives(p, chains + (first + s) * (uint64_t)p.nq, reps.data() + s * rep_words);
-            if (class_out) class_out[first + s] = cls;
-        }
-        HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * rep_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return b.run(N, chains, class_out, [&](uint64_t first, uint64_t here) {     // (the weight rows do not grow with the batch either)
         if (int rc = rows.group(first, here)) return rc;
         a.S = (uint32_t)here;
-        HIP_TRY(launch_class_sweep_site(a, dops.as<uint32_t>(), dreps.as<uint32_t>(), rows.d.as<double>(), dz.as<double>(), 0));
-        HIP_TRY(hipMemcpy(z_out + first * (uint64_t)p.ncls, dz.p, (size_t)here * p.ncls * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    return 0;
+        HIP_TRY(launch_class_sweep_site(a, b.ops(), b.rep(), rows.d.as<double>(), dz.as<double>(), 0));
+        return b.fetch(z_out, dz, first, here);
+    });
 }
 
 int qecmc_class_sweep_cut_site(int code, int L, uint64_t N, const uint8_t *chains, const double *wq, uint64_t wq_rows, int lds_width, double *z_out, int32_t *class_out)
@@ -1009,34 +1027,22 @@ int qecmc_class_sweep_cut_site(int code, int L, uint64_t N, const uint8_t *chain
     if (N == 0) return 0;
     if (class_sweep_cut_site_allow_lds(p.width) != hipSuccess)
         return fail(QECMC_ERR_UNSUPPORTED, "this device does not grant a workgroup the %u bytes of LDS a state vector of width %d takes", p.carve.bytes, p.width);
-    const uint32_t group = sweep::cut_launch_group(N, p.ncls, cp.n_held);
-    const size_t rep_words = (size_t)p.ncls * p.W, partials = (size_t)p.ncls << cp.n_held;   // of one syndrome
-    std::vector<uint32_t> reps((size_t)group * rep_words);
-    DevBuf dops, dheld, dreps, dpart, dz;
+    SweepBatch b(p, sweep::cut_launch_group(N, p.ncls, cp.n_held));
+    const size_t partials = (size_t)p.ncls << cp.n_held;                        // of one syndrome
+    DevBuf dpart, dz;
     SiteRows rows;
-    HIP_TRY(dops.alloc(p.ops.size() * sizeof(uint32_t)));
-    HIP_TRY(dheld.alloc(cp.held_words.size() * sizeof(uint32_t)));
-    HIP_TRY(dreps.alloc(reps.size() * sizeof(uint32_t)));
-    HIP_TRY(dpart.alloc((size_t)group * partials * sizeof(double)));            // kCutGridMax doubles at most; dirty: every partial is written before it is read
-    HIP_TRY(dz.alloc((size_t)group * p.ncls * sizeof(double)));
-    HIP_TRY(hipMemcpy(dops.p, p.ops.data(), p.ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (cp.n_held) HIP_TRY(hipMemcpy(dheld.p, cp.held_words.data(), cp.held_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (int rc = rows.open(wq, wq_rows, p.nq, group)) return rc;
+    if (int rc = b.open(p.ops, &cp.held_words)) return rc;
+    HIP_TRY(dpart.alloc((size_t)b.group * partials * sizeof(double)));          // kCutGridMax doubles at most; dirty: every partial is written before it is read
+    HIP_TRY(dz.alloc((size_t)b.group * p.ncls * sizeof(double)));
+    if (int rc = rows.open(wq, wq_rows, p.nq, b.group)) return rc;
     SweepSiteArgs a = {};
     a.ncls = p.ncls; a.W = p.W; a.width = p.width; a.n_ops = p.n_ops; a.n_held = cp.n_held; a.nq = p.nq; a.per_syndrome = rows.per_syndrome; a.scale = p.scale;
-    for (uint64_t first = 0; first < N; first += group) {
-        const uint64_t here = N - first < group ? N - first : group;
-        for (uint64_t s = 0; s < here; ++s) {
-            const int cls = sweep::class_representatives(p, chains + (first + s) * (uint64_t)p.nq, reps.data() + s * rep_words);
-            if (class_out) class_out[first + s] = cls;
-        }
-        HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * rep_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return b.run(N, chains, class_out, [&](uint64_t first, uint64_t here) {
         if (int rc = rows.group(first, here)) return rc;
         a.S = (uint32_t)here;
-        HIP_TRY(launch_class_sweep_cut_site(a, dops.as<uint32_t>(), dheld.as<uint32_t>(), dreps.as<uint32_t>(), rows.d.as<double>(), dpart.as<double>(), dz.as<double>(), 0));
-        HIP_TRY(hipMemcpy(z_out + first * (uint64_t)p.ncls, dz.p, (size_t)here * p.ncls * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    return 0;
+        HIP_TRY(launch_class_sweep_cut_site(a, b.ops(), b.held(), b.rep(), rows.d.as<double>(), dpart.as<double>(), dz.as<double>(), 0));
+        return b.fetch(z_out, dz, first, here);
+    });
 }
 
 int qecmc_class_sweep_tiled_site(int code, int L, uint64_t N, const uint8_t *chains, const double *wq, uint64_t wq_rows, int hbm_width, int tile_width, double *z_out,
@@ -1050,42 +1056,12 @@ int qecmc_class_sweep_tiled_site(int code, int L, uint64_t N, const uint8_t *cha
     if (int rc = check_site(N, wq, wq_rows, p.nq, tp.ops)) return rc;
     if (int rc = use_device(0)) return rc;
     if (N == 0) return 0;
-    const uint32_t group = sweep::cut_launch_group(N, p.ncls, tp.n_held), pass = sweep::tiled_pass_units(tp.state_bits);
-    const size_t rep_words = (size_t)p.ncls * p.W, partials = (size_t)p.ncls << tp.n_held;   // of one syndrome
-    const uint64_t group_units = (uint64_t)group * partials;
-    std::vector<uint32_t> reps((size_t)group * rep_words);
-    DevBuf dops, dheld, dreps, dpart, dz;
     SiteRows rows;
-    HIP_TRY(dops.alloc(tp.dev_ops.size() * sizeof(uint32_t)));
-    HIP_TRY(dheld.alloc(tp.held_words.size() * sizeof(uint32_t)));
-    HIP_TRY(dreps.alloc(reps.size() * sizeof(uint32_t)));
-    HIP_TRY(dpart.alloc((size_t)group * partials * sizeof(double)));            // kCutGridMax doubles at most; dirty: every partial is written before it is read
-    HIP_TRY(dz.alloc((size_t)group * p.ncls * sizeof(double)));
-    HIP_TRY(hipMemcpy(dops.p, tp.dev_ops.data(), tp.dev_ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (tp.n_held) HIP_TRY(hipMemcpy(dheld.p, tp.held_words.data(), tp.held_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (int rc = rows.open(wq, wq_rows, p.nq, group)) return rc;
-    TiledWorkspace &ws = TiledWorkspace::get();                                 // the uniform sweep's block, its cap of kTiledWorkspaceBytes and its lock
-    std::lock_guard<std::mutex> hold(ws.mu);
-    double *work = nullptr;
-    HIP_TRY(ws.take((size_t)(group_units < pass ? group_units : pass) * (sizeof(double) << tp.state_bits), &work));
-    SweepCutArgs ra = {};
-    ra.ncls = p.ncls; ra.W = p.W; ra.width = p.width; ra.n_ops = p.n_ops; ra.n_held = tp.n_held; ra.scale = p.scale;
-    for (uint64_t first = 0; first < N; first += group) {
-        const uint64_t here = N - first < group ? N - first : group, units = here * partials;
-        for (uint64_t s = 0; s < here; ++s) {
-            const int cls = sweep::class_representatives(p, chains + (first + s) * (uint64_t)p.nq, reps.data() + s * rep_words);
-            if (class_out) class_out[first + s] = cls;
-        }
-        HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * rep_words * sizeof(uint32_t), hipMemcpyHostToDevice));
-        if (int rc = rows.group(first, here)) return rc;
-        for (uint64_t u = 0; u < units; u += pass)
-            HIP_TRY(launch_class_sweep_tiled_site(tp, rows.per_syndrome, (uint32_t)u, (uint32_t)(units - u < pass ? units - u : pass), dops.as<uint32_t>(),
-                                                  dheld.as<uint32_t>(), dreps.as<uint32_t>(), rows.d.as<double>(), work, dpart.as<double>(), 0));
-        ra.S = (uint32_t)here;
-        HIP_TRY(launch_class_sweep_reduce(ra, dpart.as<double>(), dz.as<double>(), 0));
-        HIP_TRY(hipMemcpy(z_out + first * (uint64_t)p.ncls, dz.p, (size_t)here * p.ncls * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    return 0;
+    return tiled_batch(tp, N, chains, z_out, class_out, [&](uint32_t group) { return rows.open(wq, wq_rows, p.nq, group); },
+                       [&](uint64_t first, uint64_t here) { return rows.group(first, here); },
+                       [&](uint32_t unit_first, uint32_t units, const SweepBatch &b, double *work, double *P) {
+                           return launch_class_sweep_tiled_site(tp, rows.per_syndrome, unit_first, units, b.ops(), b.held(), b.rep(), rows.d.as<double>(), work, P, 0);
+                       });
 }
 
 // ---------------------------------------------------------------- the (min, +) sweep and its traceback under a cost per (syndrome, qubit) (class_minplus_site.hpp)
@@ -1136,40 +1112,27 @@ int qecmc_class_minplus_site(int code, int L, uint64_t N, const uint8_t *chains,
     if (class_minplus_site_allow_lds(p.width) != hipSuccess)
         return fail(QECMC_ERR_UNSUPPORTED, "qecmc_class_minplus_site: this device does not grant a workgroup the %u bytes of LDS a state vector of width %d takes",
                     p.carve.bytes, p.width);
-    const uint32_t group = sweep::cut_launch_group(N, p.ncls, cp.n_held);
-    const size_t rep_words = (size_t)p.ncls * p.W, partials = (size_t)p.ncls << cp.n_held;   // of one syndrome
-    std::vector<uint32_t> reps((size_t)group * rep_words);
-    DevBuf dops, dheld, dreps, dpart, dcost, dcount;
+    SweepBatch b(p, sweep::cut_launch_group(N, p.ncls, cp.n_held));
+    const size_t partials = (size_t)p.ncls << cp.n_held;                        // of one syndrome
+    DevBuf dpart, dcost, dcount;
     CostRows rows;
-    HIP_TRY(dops.alloc(p.ops.size() * sizeof(uint32_t)));
-    HIP_TRY(dheld.alloc(cp.held_words.size() * sizeof(uint32_t)));
-    HIP_TRY(dreps.alloc(reps.size() * sizeof(uint32_t)));
-    HIP_TRY(dpart.alloc((size_t)group * partials * sizeof(uint64_t)));          // kCutGridMax entries at most; dirty: every partial is written before it is read
-    HIP_TRY(dcost.alloc((size_t)group * p.ncls * sizeof(uint32_t)));
-    HIP_TRY(dcount.alloc((size_t)group * p.ncls * sizeof(uint64_t)));
-    HIP_TRY(hipMemcpy(dops.p, p.ops.data(), p.ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (cp.n_held) HIP_TRY(hipMemcpy(dheld.p, cp.held_words.data(), cp.held_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (int rc = rows.open(cq, cq_rows, p.nq, group)) return rc;
+    if (int rc = b.open(p.ops, &cp.held_words)) return rc;
+    HIP_TRY(dpart.alloc((size_t)b.group * partials * sizeof(uint64_t)));        // kCutGridMax entries at most; dirty: every partial is written before it is read
+    HIP_TRY(dcost.alloc((size_t)b.group * p.ncls * sizeof(uint32_t)));
+    HIP_TRY(dcount.alloc((size_t)b.group * p.ncls * sizeof(uint64_t)));
+    if (int rc = rows.open(cq, cq_rows, p.nq, b.group)) return rc;
     MinplusSiteArgs sa = {};
     MinplusArgs &a = sa.t.m;
-    a.ncls = p.ncls; a.W = p.W; a.width = p.width; a.n_ops = p.n_ops; a.n_held = cp.n_held; a.shift = p.n_gen - p.rank;
+    a = minplus_args(p, cp.n_held);
     sa.t.nq = p.nq; sa.per_syndrome = rows.per_syndrome;
-    // the host loops over groups of syndromes: no launch, and no device block -- the cost rows among them -- grows with the batch
-    for (uint64_t first = 0; first < N; first += group) {
-        const uint64_t here = N - first < group ? N - first : group;
-        for (uint64_t s = 0; s < here; ++s) {
-            const int cls = sweep::class_representatives(p, chains + (first + s) * (uint64_t)p.nq, reps.data() + s * rep_words);
-            if (class_out) class_out[first + s] = cls;
-        }
-        HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * rep_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return b.run(N, chains, class_out, [&](uint64_t first, uint64_t here) {     // (the cost rows do not grow with the batch either)
         if (int rc = rows.group(first, here)) return rc;
         a.S = (uint32_t)here;
-        HIP_TRY(launch_class_minplus_site_sweep(sa, dops.as<uint32_t>(), dheld.as<uint32_t>(), dreps.as<uint32_t>(), rows.d.as<uint32_t>(), dpart.as<uint64_t>(), 0));
+        HIP_TRY(launch_class_minplus_site_sweep(sa, b.ops(), b.held(), b.rep(), rows.d.as<uint32_t>(), dpart.as<uint64_t>(), 0));
         HIP_TRY(launch_class_minplus_reduce(a, dpart.as<uint64_t>(), dcost.as<uint32_t>(), dcount.as<uint64_t>(), 0));
-        HIP_TRY(hipMemcpy(cost_out + first * (uint64_t)p.ncls, dcost.p, (size_t)here * p.ncls * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(count_out + first * (uint64_t)p.ncls, dcount.p, (size_t)here * p.ncls * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    }
-    return 0;
+        if (int rc = b.fetch(cost_out, dcost, first, here)) return rc;
+        return b.fetch(count_out, dcount, first, here);
+    });
 }
 
 int qecmc_class_minplus_chains_site(int code, int L, uint64_t N, const uint8_t *chains, const uint8_t *cq, uint64_t cq_rows, int lds_width, uint8_t *chain_out,
@@ -1189,52 +1152,28 @@ int qecmc_class_minplus_chains_site(int code, int L, uint64_t N, const uint8_t *
         return fail(QECMC_ERR_UNSUPPORTED, "qecmc_class_minplus_chains_site: this device does not grant a workgroup the %u bytes of LDS a state vector of width %d takes",
                     p.carve.bytes, p.width);
     const uint64_t pair_bytes = minplus::trace_bytes_per_pair(tp);
-    const uint32_t group = minplus::trace_launch_group(N, p.ncls, cp.n_held, pair_bytes);
-    const size_t rep_words = (size_t)p.ncls * p.W, partials = (size_t)p.ncls << cp.n_held;   // of one syndrome
-    std::vector<uint32_t> reps((size_t)group * rep_words);
-    DevBuf dops, dheld, dreps, dforget, dpart, dpick, ddec, dchain, dcost, dcount;
+    SweepBatch b(p, minplus::trace_launch_group(N, p.ncls, cp.n_held, pair_bytes));
+    TraceBlocks d;
     CostRows rows;
-    HIP_TRY(dops.alloc(p.ops.size() * sizeof(uint32_t)));
-    HIP_TRY(dheld.alloc(cp.held_words.size() * sizeof(uint32_t)));
-    HIP_TRY(dreps.alloc(reps.size() * sizeof(uint32_t)));
-    HIP_TRY(dforget.alloc(tp.forget_words.size() * sizeof(uint32_t)));
-    HIP_TRY(dpart.alloc((size_t)group * partials * sizeof(uint64_t)));          // dirty: every partial is written before it is read
-    HIP_TRY(dpick.alloc((size_t)group * p.ncls * sizeof(uint32_t)));
-    HIP_TRY(ddec.alloc((size_t)group * p.ncls * (size_t)pair_bytes));           // kTraceWorkspaceBytes at most; dirty: the walk reads what the trace wrote
-    HIP_TRY(dchain.alloc((size_t)group * p.ncls * p.nq));
-    HIP_TRY(dcost.alloc((size_t)group * p.ncls * sizeof(uint32_t)));
-    HIP_TRY(dcount.alloc((size_t)group * p.ncls * sizeof(uint64_t)));
-    HIP_TRY(hipMemcpy(dops.p, p.ops.data(), p.ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (cp.n_held) HIP_TRY(hipMemcpy(dheld.p, cp.held_words.data(), cp.held_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dforget.p, tp.forget_words.data(), tp.forget_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (int rc = rows.open(cq, cq_rows, p.nq, group)) return rc;
+    if (int rc = b.open(p.ops, &cp.held_words)) return rc;
+    if (int rc = d.open(b, tp, pair_bytes)) return rc;
+    if (int rc = rows.open(cq, cq_rows, p.nq, b.group)) return rc;
     MinplusSiteArgs sa = {};
     MinplusTraceArgs &t = sa.t;
     MinplusArgs &a = t.m;
-    a.ncls = p.ncls; a.W = p.W; a.width = p.width; a.n_ops = p.n_ops; a.n_held = cp.n_held; a.shift = p.n_gen - p.rank;
+    a = minplus_args(p, cp.n_held);
     t.n_forget = tp.n_forget; t.words_per_forget = tp.words_per_forget; t.nq = p.nq;
     sa.per_syndrome = rows.per_syndrome;
-    // the host loops over groups of syndromes: no launch, and no device block -- the cost rows among them -- grows with the batch
-    for (uint64_t first = 0; first < N; first += group) {
-        const uint64_t here = N - first < group ? N - first : group;
-        for (uint64_t s = 0; s < here; ++s) {
-            const int cls = sweep::class_representatives(p, chains + (first + s) * (uint64_t)p.nq, reps.data() + s * rep_words);
-            if (class_out) class_out[first + s] = cls;
-        }
-        HIP_TRY(hipMemcpy(dreps.p, reps.data(), (size_t)here * rep_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return b.run(N, chains, class_out, [&](uint64_t first, uint64_t here) {     // (the cost rows do not grow with the batch either)
         if (int rc = rows.group(first, here)) return rc;
         a.S = (uint32_t)here;
-        HIP_TRY(launch_class_minplus_site_sweep(sa, dops.as<uint32_t>(), dheld.as<uint32_t>(), dreps.as<uint32_t>(), rows.d.as<uint32_t>(), dpart.as<uint64_t>(), 0));
-        HIP_TRY(launch_minplus_pick(a, dpart.as<uint64_t>(), dpick.as<uint32_t>(), 0));            // (before the reduce folds the partials in place)
-        HIP_TRY(launch_class_minplus_reduce(a, dpart.as<uint64_t>(), dcost.as<uint32_t>(), dcount.as<uint64_t>(), 0));
-        HIP_TRY(launch_minplus_trace_site(sa, dops.as<uint32_t>(), dheld.as<uint32_t>(), dreps.as<uint32_t>(), rows.d.as<uint32_t>(), dpick.as<uint32_t>(), ddec.as<uint64_t>(), 0));
-        HIP_TRY(launch_minplus_walk(t, dops.as<uint32_t>(), dheld.as<uint32_t>(), dreps.as<uint32_t>(), dforget.as<uint32_t>(), dpick.as<uint32_t>(), ddec.as<uint64_t>(),
-                                    dchain.as<uint8_t>(), 0));
-        HIP_TRY(hipMemcpy(chain_out + first * (uint64_t)p.ncls * (uint64_t)p.nq, dchain.p, (size_t)here * p.ncls * p.nq, hipMemcpyDeviceToHost));
-        if (cost_out) HIP_TRY(hipMemcpy(cost_out + first * (uint64_t)p.ncls, dcost.p, (size_t)here * p.ncls * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        if (count_out) HIP_TRY(hipMemcpy(count_out + first * (uint64_t)p.ncls, dcount.p, (size_t)here * p.ncls * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    }
-    return 0;
+        HIP_TRY(launch_class_minplus_site_sweep(sa, b.ops(), b.held(), b.rep(), rows.d.as<uint32_t>(), d.dpart.as<uint64_t>(), 0));
+        HIP_TRY(launch_minplus_pick(a, d.dpart.as<uint64_t>(), d.dpick.as<uint32_t>(), 0));          // (before the reduce folds the partials in place)
+        HIP_TRY(launch_class_minplus_reduce(a, d.dpart.as<uint64_t>(), d.dcost.as<uint32_t>(), d.dcount.as<uint64_t>(), 0));
+        HIP_TRY(launch_minplus_trace_site(sa, b.ops(), b.held(), b.rep(), rows.d.as<uint32_t>(), d.dpick.as<uint32_t>(), d.ddec.as<uint64_t>(), 0));
+        HIP_TRY(launch_minplus_walk(t, b.ops(), b.held(), b.rep(), d.dforget.as<uint32_t>(), d.dpick.as<uint32_t>(), d.ddec.as<uint64_t>(), d.dchain.as<uint8_t>(), 0));
+        return d.fetch(b, first, here, chain_out, cost_out, count_out);
+    });
 }
 
 // ---------------------------------------------------------------- chain / ladder

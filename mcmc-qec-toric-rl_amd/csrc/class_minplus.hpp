@@ -80,31 +80,9 @@ inline void costs_xz(const uint32_t *cost, uint32_t *cxz) { cxz[0] = cost[0]; cx
 // -> the packed partial
 inline uint64_t minplus_one(const sweep::Plan &p, const uint32_t *rep, const uint32_t *cxz, uint64_t *A)
 {
-    using namespace sweep;
     A[0] = 1ull;                                                                // (0, 1)
-    for (int o = 0; o < p.n_ops; ++o) {
-        const uint32_t *op = &p.ops[(size_t)o * kOpWords];
-        const uint32_t kind = op[0] & 15u, slot = (op[0] >> 4) & 15u, top = (op[0] >> 12) & 31u, mask = op[1], bit = 1u << slot;
-        if (kind == kClose) {
-            const uint32_t q = op[3], cq = pauli_to_xz((rep[q >> 4] >> ((q & 15u) * 2u)) & 3u);
-            for (uint32_t f = 0; f < (1u << top); ++f) {
-                if (f & ~mask) continue;
-                uint32_t idx = cq;
-                for (int j = 0; j < 4; ++j) {
-                    const uint32_t pr = (op[2] >> (8 * j)) & 0xFFu;
-                    idx ^= (0u - ((f >> (pr & 15u)) & 1u)) & (pr >> 4);
-                }
-                A[f] = A[f] + ((uint64_t)cxz[idx] << kCountBits);
-            }
-        } else {
-            for (uint32_t h = 0; h < (1u << (top - 1u)); ++h) {
-                const uint32_t f = insert_zero(h, slot);
-                if (f & ~mask) continue;
-                if (kind == kIntro) A[f | bit] = A[f];
-                else A[f] = mp_combine(A[f], A[f | bit]);
-            }
-        }
-    }
+    sweep::host_ops(p.ops.data(), p.n_ops, rep, A, [&](uint64_t a, uint32_t, uint32_t idx) { return a + ((uint64_t)cxz[idx] << kCountBits); }, mp_combine,
+                    sweep::NoDecisions{});
     return A[0];
 }
 
@@ -125,29 +103,16 @@ inline void minplus_cut_host(const sweep::CutPlan &cp, uint64_t N, const uint8_t
     uint32_t cxz[4];
     costs_xz(cost4, cxz);
     const uint32_t n_h = 1u << cp.n_held, n_work = (uint32_t)p.ncls * n_h;
-    if (threads == 0) threads = std::thread::hardware_concurrency();
-    if (threads > 16u) threads = 16u;
-    if (threads > n_work) threads = n_work;
-    if (threads < 1u || cp.n_held == 0) threads = 1u;
+    threads = sweep::host_threads(threads, n_work, n_work, cp.n_held == 0);
     std::vector<uint32_t> reps((size_t)p.ncls * p.W);
     std::vector<uint64_t> P((size_t)n_work);
     for (uint64_t s = 0; s < N; ++s) {
         const int a = sweep::class_representatives(p, chains + s * (uint64_t)p.nq, reps.data());
         if (cls) cls[s] = a;
-        auto work = [&](unsigned t) {
-            std::vector<uint64_t> A((size_t)1 << p.width);
-            std::vector<uint32_t> rep((size_t)p.W);
-            for (uint32_t i = t; i < n_work; i += threads) {
-                sweep::cut_representative(cp, &reps[(size_t)(i >> cp.n_held) * p.W], i & (n_h - 1u), rep.data());
-                P[i] = minplus_one(p, rep.data(), cxz, A.data());
-            }
-        };
-        if (threads == 1u) work(0);
-        else {
-            std::vector<std::thread> pool;
-            for (unsigned t = 0; t < threads; ++t) pool.emplace_back(work, t);
-            for (std::thread &t : pool) t.join();
-        }
+        sweep::host_partials(n_work, threads, p.width, p.W, P.data(), [&](uint32_t i, uint32_t *rep, uint64_t *A) {
+            sweep::cut_representative(cp, &reps[(size_t)(i >> cp.n_held) * p.W], i & (n_h - 1u), rep);
+            return minplus_one(p, rep, cxz, A);
+        });
         for (int c = 0; c < p.ncls; ++c) {
             uint64_t e = P[(size_t)c << cp.n_held];
             for (uint32_t h = 1; h < n_h; ++h) e = mp_combine(e, P[((size_t)c << cp.n_held) + h]);
@@ -155,6 +120,14 @@ inline void minplus_cut_host(const sweep::CutPlan &cp, uint64_t N, const uint8_t
         }
     }
 }
+
+#ifdef __HIPCC__
+// the device algebra (class_sweep_ops.hpp): a CLOSE adds the cost to the upper 16 bits, a FORGET is mp_combine
+struct MinPlus {
+    static __device__ __forceinline__ uint64_t close(uint64_t a, uint32_t cost) { return a + ((uint64_t)cost << kCountBits); }
+    static __device__ __forceinline__ uint64_t forget(uint64_t a, uint64_t b) { return mp_combine(a, b); }
+};
+#endif
 
 }  // namespace minplus
 

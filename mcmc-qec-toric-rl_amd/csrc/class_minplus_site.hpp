@@ -75,70 +75,19 @@ __host__ __device__ inline uint32_t site_cost(uint32_t word, uint32_t idx) { ret
 // minplus_one() with the cost word of the CLOSE's qubit: cw uint32[nq]
 inline uint64_t minplus_one_site(const sweep::Plan &p, const uint32_t *rep, const uint32_t *cw, uint64_t *A)
 {
-    using namespace sweep;
     A[0] = 1ull;                                                                // (0, 1)
-    for (int o = 0; o < p.n_ops; ++o) {
-        const uint32_t *op = &p.ops[(size_t)o * kOpWords];
-        const uint32_t kind = op[0] & 15u, slot = (op[0] >> 4) & 15u, top = (op[0] >> 12) & 31u, mask = op[1], bit = 1u << slot;
-        if (kind == kClose) {
-            const uint32_t q = op[3], cq = pauli_to_xz((rep[q >> 4] >> ((q & 15u) * 2u)) & 3u), word = cw[q];
-            for (uint32_t f = 0; f < (1u << top); ++f) {
-                if (f & ~mask) continue;
-                uint32_t idx = cq;
-                for (int j = 0; j < 4; ++j) {
-                    const uint32_t pr = (op[2] >> (8 * j)) & 0xFFu;
-                    idx ^= (0u - ((f >> (pr & 15u)) & 1u)) & (pr >> 4);
-                }
-                A[f] = A[f] + ((uint64_t)site_cost(word, idx) << kCountBits);
-            }
-        } else {
-            for (uint32_t h = 0; h < (1u << (top - 1u)); ++h) {
-                const uint32_t f = insert_zero(h, slot);
-                if (f & ~mask) continue;
-                if (kind == kIntro) A[f | bit] = A[f];
-                else A[f] = mp_combine(A[f], A[f | bit]);
-            }
-        }
-    }
+    sweep::host_ops(p.ops.data(), p.n_ops, rep, A, [&](uint64_t a, uint32_t q, uint32_t idx) { return a + ((uint64_t)site_cost(cw[q], idx) << kCountBits); }, mp_combine,
+                    sweep::NoDecisions{});
     return A[0];
 }
 
 // minplus_one_traced() with the cost word of the CLOSE's qubit
 inline uint64_t minplus_one_traced_site(const TracePlan &tp, const uint32_t *rep, const uint32_t *cw, uint64_t *A, uint64_t *D)
 {
-    using namespace sweep;
-    const Plan &p = tp.cut.plan;
-    int fi = 0;
+    const sweep::Plan &p = tp.cut.plan;
     A[0] = 1ull;
-    for (int o = 0; o < p.n_ops; ++o) {
-        const uint32_t *op = &p.ops[(size_t)o * kOpWords];
-        const uint32_t kind = op[0] & 15u, slot = (op[0] >> 4) & 15u, top = (op[0] >> 12) & 31u, mask = op[1], bit = 1u << slot;
-        if (kind == kClose) {
-            const uint32_t q = op[3], cq = pauli_to_xz((rep[q >> 4] >> ((q & 15u) * 2u)) & 3u), word = cw[q];
-            for (uint32_t f = 0; f < (1u << top); ++f) {
-                if (f & ~mask) continue;
-                uint32_t idx = cq;
-                for (int j = 0; j < 4; ++j) {
-                    const uint32_t pr = (op[2] >> (8 * j)) & 0xFFu;
-                    idx ^= (0u - ((f >> (pr & 15u)) & 1u)) & (pr >> 4);
-                }
-                A[f] = A[f] + ((uint64_t)site_cost(word, idx) << kCountBits);
-            }
-            continue;
-        }
-        const uint32_t n_h = 1u << (top - 1u);
-        uint64_t *mine = kind == kForget ? D + (size_t)fi * (size_t)tp.words_per_forget : nullptr;
-        if (mine)
-            for (uint32_t w = 0; w < (n_h + 63u) / 64u; ++w) mine[w] = 0ull;    // (a dead f leaves a 0, as the kernel's ballot does)
-        for (uint32_t h = 0; h < n_h; ++h) {
-            const uint32_t f = insert_zero(h, slot);
-            if (f & ~mask) continue;
-            if (kind == kIntro) { A[f | bit] = A[f]; continue; }
-            if ((A[f | bit] >> kCountBits) < (A[f] >> kCountBits)) mine[h >> 6] |= 1ull << (h & 63u);
-            A[f] = mp_combine(A[f], A[f | bit]);
-        }
-        if (mine) ++fi;
-    }
+    sweep::host_ops(p.ops.data(), p.n_ops, rep, A, [&](uint64_t a, uint32_t q, uint32_t idx) { return a + ((uint64_t)site_cost(cw[q], idx) << kCountBits); }, mp_combine,
+                    Decisions{D, tp.words_per_forget});
     return A[0];
 }
 
@@ -147,22 +96,10 @@ inline void site_cost_partials(const sweep::CutPlan &cp, const uint32_t *reps, c
 {
     const sweep::Plan &p = cp.plan;
     const uint32_t n_h = 1u << cp.n_held, n_work = (uint32_t)p.ncls * n_h;
-    if (threads == 0) threads = std::thread::hardware_concurrency();
-    if (threads > 16u) threads = 16u;
-    if (threads > n_work) threads = n_work;
-    if (threads < 1u || cp.n_held == 0) threads = 1u;
-    auto work = [&](unsigned t) {
-        std::vector<uint64_t> A((size_t)1 << p.width);
-        std::vector<uint32_t> rep((size_t)p.W);
-        for (uint32_t i = t; i < n_work; i += threads) {
-            sweep::cut_representative(cp, &reps[(size_t)(i >> cp.n_held) * p.W], i & (n_h - 1u), rep.data());
-            P[i] = minplus_one_site(p, rep.data(), cw, A.data());
-        }
-    };
-    if (threads == 1u) { work(0); return; }
-    std::vector<std::thread> pool;
-    for (unsigned t = 0; t < threads; ++t) pool.emplace_back(work, t);
-    for (std::thread &t : pool) t.join();
+    sweep::host_partials(n_work, sweep::host_threads(threads, n_work, n_work, cp.n_held == 0), p.width, p.W, P, [&](uint32_t i, uint32_t *rep, uint64_t *A) {
+        sweep::cut_representative(cp, &reps[(size_t)(i >> cp.n_held) * p.W], i & (n_h - 1u), rep);
+        return minplus_one_site(p, rep, cw, A);
+    });
 }
 
 // The twin of qecmc_class_minplus_site.  chains uint8[N][nq], cq uint8[cq_rows][nq][4] (I, X, Y, Z), cq_rows 1 or N -> cost_out uint32[N][ncls],

@@ -5,11 +5,10 @@
 // share of the 2^n_held partials and keeps the least cost << 12 | h (kMaxHeld = 12, a cost is below 2^16); a butterfly of shuffles leaves the least
 // of the wave in every lane: the least cost, and the lowest h that reaches it.  pick[pair] leaves through one vector store.
 //
-// k_minplus_trace: grid = pairs, block and dynamic LDS as k_class_minplus (cut_threads, lds_carve), hbits = pick[pair], the op loop k_class_minplus's
-// entry for entry.  A FORGET walks its h in whole waves -- the loop bound is wave-uniform, a lane past the bound or on a dead f stays in the wave and
-// contributes 0 -- so that __ballot(live && take) is the 64 decisions of h0 .. h0 + 63; the first lane of the wave stores it to
-// D[pair][fi][h0 >> 6] with one 64-bit vector store.  Where 2^(top - 1) < 64 the one word is word 0 of wave 0.  The LDS accesses stay behind the
-// live mask.  Dirty LDS and a dirty D are allowed: the walk reads only bits of live f, which this kernel wrote.
+// k_minplus_trace: grid = pairs, block and dynamic LDS as k_class_minplus (cut_threads, lds_carve), hbits = pick[pair]; the body is
+// minplus::trace_sweep (class_minplus_trace.hpp), which k_minplus_trace_site shares: the CLOSE and INTRO passes of class_sweep_ops.hpp and a FORGET
+// that ballots its decisions into D.  The four costs are kernel arguments.  Dirty LDS and a dirty D are allowed: the walk reads only bits of live f,
+// which this kernel wrote.
 //
 // k_minplus_walk: one wave per pair, launched after the trace kernel, so the decision words are read by a kernel that never wrote them.  The walk is
 // wave-uniform -- f, fi and the op words are the same in every lane --; lane w < W carries chain word w, and at the end the lanes unpack the words to
@@ -18,11 +17,9 @@
 // The 128 KiB state vector (width 14) needs the dynamic-LDS limit of k_minplus_trace raised: that limit is an attribute of each kernel.
 #include "class_minplus_trace.hpp"
 
-#include <mutex>
-
 namespace qecmc {
 
-constexpr int kWave = 64;
+constexpr int kWave = (int)minplus::kTraceWave;
 static_assert(sweep::kMaxHeld <= 12 && 11 * 11 * minplus::kMaxCost < (1u << 16), "cost << 12 | h fits 32 bits");
 
 __global__ __launch_bounds__(kWave) void k_minplus_pick(const MinplusArgs a, const uint64_t *__restrict__ P, uint32_t *__restrict__ pick)
@@ -45,57 +42,7 @@ __global__ __launch_bounds__(sweep::kCutThreadsMax) void k_minplus_trace(const M
                                                                    const uint32_t *__restrict__ reps, const uint32_t *__restrict__ pick, uint64_t *__restrict__ D)
 {
     extern __shared__ uint64_t trace_lds[];                   // [2^width]
-    const MinplusArgs &a = t.m;
-    const uint32_t tid = threadIdx.x, threads = blockDim.x, lane = tid & (kWave - 1u), pair = blockIdx.x, hbits = pick[pair] & ((1u << a.n_held) - 1u);
-    const uint32_t *rep = reps + (size_t)pair * (size_t)a.W;
-    uint64_t *mine = D + (size_t)pair * (size_t)t.n_forget * (size_t)t.words_per_forget;
-    int fi = 0;
-    if (tid == 0) trace_lds[0] = 1ull;                        // (0, 1)
-    __syncthreads();
-    for (int o = 0; o < a.n_ops; ++o) {
-        const uint32_t w0 = ops[4 * o], mask = ops[4 * o + 1];
-        const uint32_t kind = w0 & 15u, slot = (w0 >> 4) & 15u, top = (w0 >> 12) & 31u, bit = 1u << slot;
-        if (kind == sweep::kClose) {
-            const uint32_t pairs = ops[4 * o + 2], q = ops[4 * o + 3];
-            uint32_t word = rep[q >> 4];
-            for (uint32_t rest = hbits; rest; rest &= rest - 1u) word ^= held[(uint32_t)(__ffs(rest) - 1) * (uint32_t)a.W + (q >> 4)];
-            const uint32_t cq = sweep::pauli_to_xz((word >> ((q & 15u) * 2u)) & 3u);
-            for (uint32_t f = tid; f < (1u << top); f += threads) {
-                if (f & ~mask) continue;
-                uint32_t idx = cq;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const uint32_t pr = (pairs >> (8 * j)) & 0xFFu;
-                    idx ^= (0u - ((f >> (pr & 15u)) & 1u)) & (pr >> 4);
-                }
-                const uint32_t lo = (idx & 1u) ? a.cxz[1] : a.cxz[0], hi = (idx & 1u) ? a.cxz[3] : a.cxz[2];
-                trace_lds[f] = trace_lds[f] + ((uint64_t)((idx & 2u) ? hi : lo) << minplus::kCountBits);
-            }
-        } else if (kind == sweep::kIntro) {
-            for (uint32_t h = tid; h < (1u << (top - 1u)); h += threads) {
-                const uint32_t f = sweep::insert_zero(h, slot);
-                if (f & ~mask) continue;
-                trace_lds[f | bit] = trace_lds[f];
-            }
-        } else {
-            const uint32_t n_h = 1u << (top - 1u);
-            if (fi < t.n_forget)                              // (always: the plan counts its FORGETs; a stream that does not cannot leave its rows of D)
-                for (uint32_t h0 = tid - lane; h0 < n_h; h0 += threads) {          // whole waves: h0 is wave-uniform
-                    const uint32_t h = h0 + lane, f = sweep::insert_zero(h, slot);
-                    const bool live = h < n_h && !(f & ~mask);
-                    bool take = false;
-                    if (live) {
-                        const uint64_t off = trace_lds[f], on = trace_lds[f | bit];
-                        take = (on >> minplus::kCountBits) < (off >> minplus::kCountBits);     // strict: a tie leaves the generator off
-                        trace_lds[f] = minplus::mp_combine(off, on);
-                    }
-                    const uint64_t word = __ballot(take);
-                    if (lane == 0) mine[(size_t)fi * (size_t)t.words_per_forget + (h0 >> 6)] = word;
-                }
-            ++fi;
-        }
-        __syncthreads();
-    }
+    minplus::trace_sweep(trace_lds, t, ops, held, reps, pick, D, sweep::UniformFour<uint32_t>{t.m.cxz});
 }
 
 __global__ __launch_bounds__(kWave) void k_minplus_walk(const MinplusTraceArgs t, const uint32_t *__restrict__ ops, const uint32_t *__restrict__ held,
@@ -132,31 +79,15 @@ __global__ __launch_bounds__(kWave) void k_minplus_walk(const MinplusTraceArgs t
     }
 }
 
-// the dynamic-LDS limit of k_minplus_trace on the current device, raised once to kCutLdsBudget where a plan of this width needs more than the default
-// window; hipErrorInvalidValue where the runtime does not grant it
 hipError_t class_minplus_trace_allow_lds(int width)
 {
-    if (!sweep::cut_fits(width)) return hipErrorInvalidValue;
-    if (sweep::lds_carve(width).bytes <= sweep::kLdsBudget) return hipSuccess;
-    constexpr int kDevices = 64;
-    static std::mutex mu;
-    static signed char state[kDevices] = {};                  // 0: not asked, 1: granted, -1: refused
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev)) return e;
-    if (dev < 0 || dev >= kDevices) return hipErrorInvalidValue;
-    std::lock_guard<std::mutex> g(mu);
-    if (state[dev] == 0) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_minplus_trace), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sweep::kCutLdsBudget);
-        if (e != hipSuccess) (void)hipGetLastError();         // (the refusal is reported by value; it is not left behind as the thread's last error)
-        state[dev] = e == hipSuccess ? 1 : -1;
-    }
-    return state[dev] == 1 ? hipSuccess : hipErrorInvalidValue;
+    static LdsOptIn opt;
+    return cut_allow_lds(reinterpret_cast<const void *>(k_minplus_trace), opt, width);
 }
 
 static bool trace_args_ok(const MinplusArgs &a)
 {
-    return (a.ncls == 4 || a.ncls == 16) && sweep::cut_fits(a.width) && a.W >= 1 && a.W <= kWave && a.n_ops >= 1 && a.n_held >= 0 && a.n_held <= sweep::kMaxHeld &&
-           a.S <= sweep::cut_launch_group(a.S, a.ncls, a.n_held);
+    return sweep::cut_args_ok(a.S, a.ncls, a.width, a.W, a.n_ops, a.n_held) && a.W <= kWave;
 }
 
 hipError_t launch_minplus_pick(const MinplusArgs &a, const uint64_t *P, uint32_t *pick, hipStream_t stream)

@@ -112,42 +112,31 @@ inline uint32_t pick_assignment(const uint64_t *P, int n_held)
     return best;
 }
 
-// step 3: minplus_one with decisions.  A: 2^width entries of scratch, D: n_forget * words_per_forget words, both dirty allowed -> the packed partial
+// step 3: which branch won at every FORGET of host_ops -- the strict rule, a tie leaves the generator off; a dead f leaves a 0, as the kernel's
+// ballot does
+struct Decisions {
+    uint64_t *D;
+    int words_per_forget, fi = 0;
+    uint64_t *mine = nullptr;
+    void begin(uint32_t n_h)
+    {
+        mine = D + (size_t)fi * (size_t)words_per_forget;
+        for (uint32_t w = 0; w < (n_h + 63u) / 64u; ++w) mine[w] = 0ull;
+    }
+    void at(uint32_t h, uint64_t off, uint64_t on)
+    {
+        if ((on >> kCountBits) < (off >> kCountBits)) mine[h >> 6] |= 1ull << (h & 63u);
+    }
+    void end() { ++fi; }
+};
+
+// minplus_one with decisions.  A: 2^width entries of scratch, D: n_forget * words_per_forget words, both dirty allowed -> the packed partial
 inline uint64_t minplus_one_traced(const TracePlan &tp, const uint32_t *rep, const uint32_t *cxz, uint64_t *A, uint64_t *D)
 {
-    using namespace sweep;
-    const Plan &p = tp.cut.plan;
-    int fi = 0;
+    const sweep::Plan &p = tp.cut.plan;
     A[0] = 1ull;
-    for (int o = 0; o < p.n_ops; ++o) {
-        const uint32_t *op = &p.ops[(size_t)o * kOpWords];
-        const uint32_t kind = op[0] & 15u, slot = (op[0] >> 4) & 15u, top = (op[0] >> 12) & 31u, mask = op[1], bit = 1u << slot;
-        if (kind == kClose) {
-            const uint32_t q = op[3], cq = pauli_to_xz((rep[q >> 4] >> ((q & 15u) * 2u)) & 3u);
-            for (uint32_t f = 0; f < (1u << top); ++f) {
-                if (f & ~mask) continue;
-                uint32_t idx = cq;
-                for (int j = 0; j < 4; ++j) {
-                    const uint32_t pr = (op[2] >> (8 * j)) & 0xFFu;
-                    idx ^= (0u - ((f >> (pr & 15u)) & 1u)) & (pr >> 4);
-                }
-                A[f] = A[f] + ((uint64_t)cxz[idx] << kCountBits);
-            }
-            continue;
-        }
-        const uint32_t n_h = 1u << (top - 1u);
-        uint64_t *mine = kind == kForget ? D + (size_t)fi * (size_t)tp.words_per_forget : nullptr;
-        if (mine)
-            for (uint32_t w = 0; w < (n_h + 63u) / 64u; ++w) mine[w] = 0ull;    // (a dead f leaves a 0, as the kernel's ballot does)
-        for (uint32_t h = 0; h < n_h; ++h) {
-            const uint32_t f = insert_zero(h, slot);
-            if (f & ~mask) continue;
-            if (kind == kIntro) { A[f | bit] = A[f]; continue; }
-            if ((A[f | bit] >> kCountBits) < (A[f] >> kCountBits)) mine[h >> 6] |= 1ull << (h & 63u);
-            A[f] = mp_combine(A[f], A[f | bit]);
-        }
-        if (mine) ++fi;
-    }
+    sweep::host_ops(p.ops.data(), p.n_ops, rep, A, [&](uint64_t a, uint32_t, uint32_t idx) { return a + ((uint64_t)cxz[idx] << kCountBits); }, mp_combine,
+                    Decisions{D, tp.words_per_forget});
     return A[0];
 }
 
@@ -190,29 +179,16 @@ inline void minplus_trace_host(const TracePlan &tp, uint64_t N, const uint8_t *c
     uint32_t cxz[4];
     costs_xz(cost4, cxz);
     const uint32_t n_h = 1u << cp.n_held, n_work = (uint32_t)p.ncls * n_h;
-    if (threads == 0) threads = std::thread::hardware_concurrency();
-    if (threads > 16u) threads = 16u;
-    if (threads > n_work) threads = n_work;
-    if (threads < 1u || cp.n_held == 0) threads = 1u;
+    threads = sweep::host_threads(threads, n_work, n_work, cp.n_held == 0);
     std::vector<uint32_t> reps((size_t)p.ncls * p.W), rep((size_t)p.W);
     std::vector<uint64_t> P((size_t)n_work), A((size_t)1 << p.width), D((size_t)tp.n_forget * (size_t)tp.words_per_forget);
     for (uint64_t s = 0; s < N; ++s) {
         const int a = sweep::class_representatives(p, chains + s * (uint64_t)p.nq, reps.data());
         if (cls) cls[s] = a;
-        auto work = [&](unsigned t) {
-            std::vector<uint64_t> Amine((size_t)1 << p.width);
-            std::vector<uint32_t> mine((size_t)p.W);
-            for (uint32_t i = t; i < n_work; i += threads) {
-                sweep::cut_representative(cp, &reps[(size_t)(i >> cp.n_held) * p.W], i & (n_h - 1u), mine.data());
-                P[i] = minplus_one(p, mine.data(), cxz, Amine.data());
-            }
-        };
-        if (threads == 1u) work(0);
-        else {
-            std::vector<std::thread> pool;
-            for (unsigned t = 0; t < threads; ++t) pool.emplace_back(work, t);
-            for (std::thread &t : pool) t.join();
-        }
+        sweep::host_partials(n_work, threads, p.width, p.W, P.data(), [&](uint32_t i, uint32_t *mine, uint64_t *Amine) {
+            sweep::cut_representative(cp, &reps[(size_t)(i >> cp.n_held) * p.W], i & (n_h - 1u), mine);
+            return minplus_one(p, mine, cxz, Amine);
+        });
         for (int c = 0; c < p.ncls; ++c) {
             const uint64_t *mine = &P[(size_t)c << cp.n_held];
             const uint32_t pick = pick_assignment(mine, cp.n_held);
@@ -232,6 +208,53 @@ inline void minplus_trace_host(const TracePlan &tp, uint64_t N, const uint8_t *c
 }
 
 }  // namespace minplus
+
+#ifdef __HIPCC__
+namespace minplus {
+constexpr uint32_t kTraceWave = 64;
+
+// One workgroup of a trace kernel (k_minplus_trace, k_minplus_trace_site), pair blockIdx.x under hbits = pick[pair]: the CLOSE and INTRO passes of
+// class_sweep_ops.hpp in the algebra MinPlus, and a FORGET that walks its h in whole waves -- the loop bound is wave-uniform, a lane past the bound
+// or on a dead f stays in the wave and contributes 0 -- so that __ballot(live && take) is the 64 decisions of h0 .. h0 + 63; the first lane of the
+// wave stores it to D[pair][fi][h0 >> 6] with one 64-bit vector store.  Where 2^(top - 1) < 64 the one word is word 0 of wave 0.  The LDS accesses
+// stay behind the live mask.  src: the costs of a CLOSE.
+template <class TraceArgs, class Src>
+__device__ __forceinline__ void trace_sweep(uint64_t *A, const TraceArgs &t, const uint32_t *__restrict__ ops, const uint32_t *__restrict__ held,
+                                            const uint32_t *__restrict__ reps, const uint32_t *__restrict__ pick, uint64_t *__restrict__ D, const Src &src)
+{
+    const auto &a = t.m;
+    const uint32_t tid = threadIdx.x, threads = blockDim.x, lane = tid & (kTraceWave - 1u), pair = blockIdx.x, hbits = pick[pair] & ((1u << a.n_held) - 1u);
+    const sweep::HeldRep rep{reps + (size_t)pair * (size_t)a.W, held, hbits, (uint32_t)a.W};
+    uint64_t *mine = D + (size_t)pair * (size_t)t.n_forget * (size_t)t.words_per_forget;
+    int fi = 0;
+    if (tid == 0) A[0] = 1ull;                                // (0, 1)
+    __syncthreads();
+    for (uint32_t o = 0; o < (uint32_t)a.n_ops; ++o) {
+        const sweep::Op<sweep::NarrowOps> op(ops, o);
+        if (op.kind == sweep::kClose) sweep::close_pass<MinPlus>(A, tid, threads, op, rep, src);
+        else if (op.kind == sweep::kIntro) sweep::intro_pass<MinPlus>(A, tid, threads, op);
+        else {
+            const uint32_t n_h = 1u << (op.top - 1u), bit = 1u << op.slot;
+            if (fi < t.n_forget)                              // (always: the plan counts its FORGETs; a stream that does not cannot leave its rows of D)
+                for (uint32_t h0 = tid - lane; h0 < n_h; h0 += threads) {          // whole waves: h0 is wave-uniform
+                    const uint32_t h = h0 + lane, f = sweep::insert_zero(h, op.slot);
+                    const bool live = h < n_h && !(f & ~op.mask);
+                    bool take = false;
+                    if (live) {
+                        const uint64_t off = A[f], on = A[f | bit];
+                        take = (on >> kCountBits) < (off >> kCountBits);           // strict: a tie leaves the generator off
+                        A[f] = mp_combine(off, on);
+                    }
+                    const uint64_t word = __ballot(take);
+                    if (lane == 0) mine[(size_t)fi * (size_t)t.words_per_forget + (h0 >> 6)] = word;
+                }
+            ++fi;
+        }
+        __syncthreads();
+    }
+}
+}  // namespace minplus
+#endif
 
 // class_minplus_trace.hip: all pointers are device pointers.  ops, held, reps and P as class_minplus.hip takes them; pick uint32[S * ncls];
 // D uint64[S * ncls][n_forget][words_per_forget]: scratch, dirty allowed; forget_words uint32[n_forget][W]; chain_out uint8[S * ncls][nq]: overwritten.

@@ -30,6 +30,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "class_sweep_ops.hpp" // the op words, and the loop every twin and every kernel runs over them
 #include "corrections.hpp"     // the class function on the packed state, the logical masks and the class-move table
 #include "plan_host.hpp"       // Refusal, check_code_L
 
@@ -53,16 +54,6 @@ constexpr int max_width()
 }
 constexpr int kMaxWidth = max_width();       // 13
 static_assert(kMaxWidth == 13 && kMaxWidth <= 16, "the op words keep a slot in 4 bits and the mask in 16");
-
-// One op is four words:
-//     [0]  kind | slot << 4 | pairs << 8 | top << 12     top: the index bits the op walks -- every bit of mask, and the op's own slot, lies below it
-//     [1]  mask      the occupied slots: INTRO before it, CLOSE as they are, FORGET after it
-//     [2]  CLOSE: four bytes (slot | xz << 4), xz = x | z << 1 of the generator's Pauli at the qubit; bytes beyond `pairs` are 0 (they change nothing)
-//     [3]  CLOSE: the qubit
-constexpr uint32_t kIntro = 0, kClose = 1, kForget = 2;
-constexpr int kOpWords = 4;
-
-__host__ __device__ inline uint32_t pauli_to_xz(uint32_t p) { return (p ^ (p >> 1)) & 3u; }      // I X Y Z = 0 1 2 3 -> 0 1 3 2 (and back)
 
 struct Plan {
     int code = 0, L = 0, nq = 0, W = 0, ncls = 0, kinds = 0, n_gen = 0, rank = 0, width = 0, n_ops = 0, n_qubits = 0;
@@ -267,9 +258,6 @@ inline int class_representatives(const Plan &p, const uint8_t *chain, uint32_t *
     return a;
 }
 
-// the index with a zero inserted at bit `slot` of h
-__host__ __device__ inline uint32_t insert_zero(uint32_t h, uint32_t slot) { return ((h >> slot) << (slot + 1u)) | (h & ((1u << slot) - 1u)); }
-
 // the weight table in (x, z) order: I, X, Z, Y
 inline void weights_xz(const double *w, double *wxz) { wxz[0] = w[0]; wxz[1] = w[1]; wxz[2] = w[3]; wxz[3] = w[2]; }
 
@@ -277,29 +265,7 @@ inline void weights_xz(const double *w, double *wxz) { wxz[0] = w[0]; wxz[1] = w
 inline double sweep_one(const Plan &p, const uint32_t *rep, const double *wxz, double *A)
 {
     A[0] = 1.0;
-    for (int o = 0; o < p.n_ops; ++o) {
-        const uint32_t *op = &p.ops[(size_t)o * kOpWords];
-        const uint32_t kind = op[0] & 15u, slot = (op[0] >> 4) & 15u, top = (op[0] >> 12) & 31u, mask = op[1], bit = 1u << slot;
-        if (kind == kClose) {
-            const uint32_t q = op[3], cq = pauli_to_xz((rep[q >> 4] >> ((q & 15u) * 2u)) & 3u);
-            for (uint32_t f = 0; f < (1u << top); ++f) {
-                if (f & ~mask) continue;
-                uint32_t idx = cq;
-                for (int j = 0; j < 4; ++j) {
-                    const uint32_t pr = (op[2] >> (8 * j)) & 0xFFu;
-                    idx ^= (0u - ((f >> (pr & 15u)) & 1u)) & (pr >> 4);
-                }
-                A[f] = A[f] * wxz[idx];
-            }
-        } else {
-            for (uint32_t h = 0; h < (1u << (top - 1u)); ++h) {
-                const uint32_t f = insert_zero(h, slot);
-                if (f & ~mask) continue;
-                if (kind == kIntro) A[f | bit] = A[f];
-                else A[f] = A[f] + A[f | bit];
-            }
-        }
-    }
+    host_ops(p.ops.data(), p.n_ops, rep, A, [&](double a, uint32_t, uint32_t idx) { return a * wxz[idx]; }, [](double a, double b) { return a + b; }, NoDecisions{});
     return A[0] * p.scale;
 }
 

@@ -20,7 +20,7 @@
 #pragma once
 #include "class_sweep.hpp"
 
-#include <thread>
+#include <mutex>
 
 namespace qecmc {
 namespace sweep {
@@ -143,6 +143,12 @@ inline uint32_t cut_launch_group(uint64_t N, int ncls, int n_held)
     return N < group ? (N ? (uint32_t)N : 1u) : group;
 }
 
+// what every launch of a cut plan's sweep kernel asks of its arguments, whatever the algebra; a launch adds what is its own
+inline bool cut_args_ok(uint32_t S, int ncls, int width, int W, int n_ops, int n_held)
+{
+    return (ncls == 4 || ncls == 16) && cut_fits(width) && W >= 1 && n_ops >= 1 && n_held >= 0 && n_held <= kMaxHeld && S <= cut_launch_group(S, ncls, n_held);
+}
+
 // the representative of assignment h: rep times the held generators whose bit is set in h
 inline void cut_representative(const CutPlan &cp, const uint32_t *rep, uint32_t h, uint32_t *out)
 {
@@ -175,29 +181,16 @@ inline void sweep_cut_host(const CutPlan &cp, uint64_t N, const uint8_t *chains,
     Plan unscaled = p;
     unscaled.scale = 1.0;                                                       // (A[0] * 1.0 is A[0])
     const uint32_t n_h = 1u << cp.n_held, n_work = (uint32_t)p.ncls * n_h;
-    if (threads == 0) threads = std::thread::hardware_concurrency();
-    if (threads > 16u) threads = 16u;
-    if (threads > n_work) threads = n_work;
-    if (threads < 1u || cp.n_held == 0) threads = 1u;
+    threads = host_threads(threads, n_work, n_work, cp.n_held == 0);
     std::vector<uint32_t> reps((size_t)p.ncls * p.W);
     std::vector<double> P((size_t)n_work);
     for (uint64_t s = 0; s < N; ++s) {
         const int a = class_representatives(p, chains + s * (uint64_t)p.nq, reps.data());
         if (cls) cls[s] = a;
-        auto work = [&](unsigned t) {
-            std::vector<double> A((size_t)1 << p.width);
-            std::vector<uint32_t> rep((size_t)p.W);
-            for (uint32_t i = t; i < n_work; i += threads) {
-                cut_representative(cp, &reps[(size_t)(i >> cp.n_held) * p.W], i & (n_h - 1u), rep.data());
-                P[i] = sweep_one(unscaled, rep.data(), wxz, A.data());
-            }
-        };
-        if (threads == 1u) work(0);
-        else {
-            std::vector<std::thread> pool;
-            for (unsigned t = 0; t < threads; ++t) pool.emplace_back(work, t);
-            for (std::thread &t : pool) t.join();
-        }
+        host_partials(n_work, threads, p.width, p.W, P.data(), [&](uint32_t i, uint32_t *rep, double *A) {
+            cut_representative(cp, &reps[(size_t)(i >> cp.n_held) * p.W], i & (n_h - 1u), rep);
+            return sweep_one(unscaled, rep, wxz, A);
+        });
         for (int c = 0; c < p.ncls; ++c) Z[s * (uint64_t)p.ncls + c] = cut_reduce(&P[(size_t)c << cp.n_held], cp.n_held, p.scale);
     }
 }
@@ -211,6 +204,16 @@ struct SweepCutArgs {
     int ncls, W, width, n_ops, n_held;
     double wxz[4], scale;
 };
+// The dynamic-LDS limit of one sweep kernel of the family, raised to kCutLdsBudget where a plan of this width needs more than the default window
+// (width 14: 128 KiB, one workgroup per CU).  The limit is an attribute of each kernel, so each has a state of its own; it is asked for once per
+// device.  hipErrorInvalidValue where the runtime does not grant it -- reported by value, not left behind as the thread's last error -- which the
+// entry points report as QECMC_ERR_UNSUPPORTED.
+struct LdsOptIn {
+    static constexpr int kDevices = 64;
+    std::mutex mu;
+    signed char state[kDevices] = {};  // 0: not asked, 1: granted, -1: refused
+};
+hipError_t cut_allow_lds(const void *kernel, LdsOptIn &opt, int width);
 hipError_t class_sweep_cut_allow_lds(int width);      // hipSuccess: a state vector of this width can be launched on the current device
 hipError_t launch_class_sweep_cut(const SweepCutArgs &a, const uint32_t *ops, const uint32_t *held, const uint32_t *reps, double *P, double *z, hipStream_t stream);
 // k_class_sweep_reduce alone, on the partials of a.S syndromes (n_held, ncls and scale are read): class_sweep_tiled.hip forms its partials itself

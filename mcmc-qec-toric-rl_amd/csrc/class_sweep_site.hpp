@@ -70,30 +70,8 @@ inline void site_rows_xz(const double *wq, uint64_t rows, int nq, double *out)
 inline double sweep_one_site(const Plan &p, const uint32_t *rep, const double *wxz, double *A)
 {
     A[0] = 1.0;
-    for (int o = 0; o < p.n_ops; ++o) {
-        const uint32_t *op = &p.ops[(size_t)o * kOpWords];
-        const uint32_t kind = op[0] & 15u, slot = (op[0] >> 4) & 15u, top = (op[0] >> 12) & 31u, mask = op[1], bit = 1u << slot;
-        if (kind == kClose) {
-            const uint32_t q = op[3], cq = pauli_to_xz((rep[q >> 4] >> ((q & 15u) * 2u)) & 3u);
-            const double *w = wxz + (size_t)q * 4u;
-            for (uint32_t f = 0; f < (1u << top); ++f) {
-                if (f & ~mask) continue;
-                uint32_t idx = cq;
-                for (int j = 0; j < 4; ++j) {
-                    const uint32_t pr = (op[2] >> (8 * j)) & 0xFFu;
-                    idx ^= (0u - ((f >> (pr & 15u)) & 1u)) & (pr >> 4);
-                }
-                A[f] = A[f] * w[idx];
-            }
-        } else {
-            for (uint32_t h = 0; h < (1u << (top - 1u)); ++h) {
-                const uint32_t f = insert_zero(h, slot);
-                if (f & ~mask) continue;
-                if (kind == kIntro) A[f | bit] = A[f];
-                else A[f] = A[f] + A[f | bit];
-            }
-        }
-    }
+    host_ops(p.ops.data(), p.n_ops, rep, A, [&](double a, uint32_t q, uint32_t idx) { return a * wxz[(size_t)q * 4u + idx]; }, [](double a, double b) { return a + b; },
+             NoDecisions{});
     return A[0] * p.scale;
 }
 
@@ -101,28 +79,8 @@ inline double sweep_one_site(const Plan &p, const uint32_t *rep, const double *w
 inline double sweep_one_wide_site(const TiledPlan &tp, const uint32_t *rep, const double *wxz, double *A)
 {
     A[0] = 1.0;
-    for (int o = 0; o < tp.plan.n_ops; ++o) {
-        const uint32_t *op = &tp.ops[(size_t)o * kTiledOpWords];
-        const uint32_t kind = op[0] & 15u, bit = 1u << ((op[0] >> 4) & 31u), mask = op[1];
-        uint32_t f = 0;
-        if (kind == kClose) {
-            const uint32_t q = op[3], cq = pauli_to_xz((rep[q >> 4] >> ((q & 15u) * 2u)) & 3u);
-            const double *w = wxz + (size_t)q * 4u;
-            do {
-                uint32_t idx = cq;
-                for (int j = 0; j < 4; ++j) {
-                    const uint32_t pr = (op[2] >> (8 * j)) & 0xFFu;
-                    idx ^= (0u - ((f >> (pr & 31u)) & 1u)) & (pr >> 5);
-                }
-                A[f] = A[f] * w[idx];
-                f = (f - mask) & mask;
-            } while (f);
-        } else if (kind == kIntro) {
-            do { A[f | bit] = A[f]; f = (f - mask) & mask; } while (f);
-        } else {
-            do { A[f] = A[f] + A[f | bit]; f = (f - mask) & mask; } while (f);
-        }
-    }
+    host_ops_wide(tp.ops.data(), tp.plan.n_ops, rep, A, [&](double a, uint32_t q, uint32_t idx) { return a * wxz[(size_t)q * 4u + idx]; },
+                  [](double a, double b) { return a + b; });
     return A[0];
 }
 
@@ -141,20 +99,6 @@ inline void sweep_site_host(const Plan &p, uint64_t N, const uint8_t *chains, co
     }
 }
 
-// the (class, assignment) partials of one syndrome over host threads, each formed alone: the result does not depend on their number
-template <class One> inline void site_partials(uint32_t n_work, unsigned threads, int width, int W, double *P, One one)
-{
-    auto work = [&](unsigned t) {
-        std::vector<double> A((size_t)1 << width);
-        std::vector<uint32_t> rep((size_t)W);
-        for (uint32_t i = t; i < n_work; i += threads) P[i] = one(i, rep.data(), A.data());
-    };
-    if (threads <= 1u) { threads = 1u; work(0); return; }
-    std::vector<std::thread> pool;
-    for (unsigned t = 0; t < threads; ++t) pool.emplace_back(work, t);
-    for (std::thread &t : pool) t.join();
-}
-
 // sweep_cut_host()'s sequence: the partial of every assignment of the held generators, then cut_reduce()
 inline void sweep_cut_site_host(const CutPlan &cp, uint64_t N, const uint8_t *chains, const double *wq, uint64_t wq_rows, double *Z, int32_t *cls, unsigned threads = 0)
 {
@@ -162,10 +106,7 @@ inline void sweep_cut_site_host(const CutPlan &cp, uint64_t N, const uint8_t *ch
     Plan unscaled = p;
     unscaled.scale = 1.0;                                                       // (A[0] * 1.0 is A[0])
     const uint32_t n_h = 1u << cp.n_held, n_work = (uint32_t)p.ncls * n_h;
-    if (threads == 0) threads = std::thread::hardware_concurrency();
-    if (threads > 16u) threads = 16u;
-    if (threads > n_work) threads = n_work;
-    if (threads < 1u || cp.n_held == 0) threads = 1u;
+    threads = host_threads(threads, n_work, n_work, cp.n_held == 0);
     const size_t row = (size_t)p.nq * 4u;
     std::vector<double> wxz(row), P((size_t)n_work);
     std::vector<uint32_t> reps((size_t)p.ncls * p.W);
@@ -173,7 +114,7 @@ inline void sweep_cut_site_host(const CutPlan &cp, uint64_t N, const uint8_t *ch
         if (s == 0 || wq_rows != 1) site_rows_xz(wq + (wq_rows == 1 ? 0u : s) * row, 1, p.nq, wxz.data());
         const int a = class_representatives(p, chains + s * (uint64_t)p.nq, reps.data());
         if (cls) cls[s] = a;
-        site_partials(n_work, threads, p.width, p.W, P.data(), [&](uint32_t i, uint32_t *rep, double *A) {
+        host_partials(n_work, threads, p.width, p.W, P.data(), [&](uint32_t i, uint32_t *rep, double *A) {
             cut_representative(cp, &reps[(size_t)(i >> cp.n_held) * p.W], i & (n_h - 1u), rep);
             return sweep_one_site(unscaled, rep, wxz.data(), A);
         });
@@ -186,11 +127,7 @@ inline void sweep_tiled_site_host(const TiledPlan &tp, uint64_t N, const uint8_t
 {
     const Plan &p = tp.plan;
     const uint32_t n_h = 1u << tp.n_held, n_work = (uint32_t)p.ncls * n_h;
-    if (threads == 0) threads = std::thread::hardware_concurrency();
-    if (threads > 16u) threads = 16u;
-    if (threads > tiled_pass_units(p.width)) threads = tiled_pass_units(p.width);
-    if (threads > n_work) threads = n_work;
-    if (threads < 1u || p.width < 12) threads = 1u;
+    threads = host_threads(threads, n_work, tiled_pass_units(p.width), p.width < 12);
     const size_t row = (size_t)p.nq * 4u;
     std::vector<double> wxz(row), P((size_t)n_work);
     std::vector<uint32_t> reps((size_t)p.ncls * p.W);
@@ -198,7 +135,7 @@ inline void sweep_tiled_site_host(const TiledPlan &tp, uint64_t N, const uint8_t
         if (s == 0 || wq_rows != 1) site_rows_xz(wq + (wq_rows == 1 ? 0u : s) * row, 1, p.nq, wxz.data());
         const int a = class_representatives(p, chains + s * (uint64_t)p.nq, reps.data());
         if (cls) cls[s] = a;
-        site_partials(n_work, threads, p.width, p.W, P.data(), [&](uint32_t i, uint32_t *rep, double *A) {
+        host_partials(n_work, threads, p.width, p.W, P.data(), [&](uint32_t i, uint32_t *rep, double *A) {
             tiled_representative(tp, &reps[(size_t)(i >> tp.n_held) * p.W], i & (n_h - 1u), rep);
             return sweep_one_wide_site(tp, rep, wxz.data(), A);
         });

@@ -234,27 +234,7 @@ inline void tiled_representative(const TiledPlan &tp, const uint32_t *rep, uint3
 inline double sweep_one_wide(const TiledPlan &tp, const uint32_t *rep, const double *wxz, double *A)
 {
     A[0] = 1.0;
-    for (int o = 0; o < tp.plan.n_ops; ++o) {
-        const uint32_t *op = &tp.ops[(size_t)o * kTiledOpWords];
-        const uint32_t kind = op[0] & 15u, bit = 1u << ((op[0] >> 4) & 31u), mask = op[1];
-        uint32_t f = 0;
-        if (kind == kClose) {
-            const uint32_t q = op[3], cq = pauli_to_xz((rep[q >> 4] >> ((q & 15u) * 2u)) & 3u);
-            do {
-                uint32_t idx = cq;
-                for (int j = 0; j < 4; ++j) {
-                    const uint32_t pr = (op[2] >> (8 * j)) & 0xFFu;
-                    idx ^= (0u - ((f >> (pr & 31u)) & 1u)) & (pr >> 5);
-                }
-                A[f] = A[f] * wxz[idx];
-                f = (f - mask) & mask;
-            } while (f);
-        } else if (kind == kIntro) {
-            do { A[f | bit] = A[f]; f = (f - mask) & mask; } while (f);
-        } else {
-            do { A[f] = A[f] + A[f | bit]; f = (f - mask) & mask; } while (f);
-        }
-    }
+    host_ops_wide(tp.ops.data(), tp.plan.n_ops, rep, A, [&](double a, uint32_t, uint32_t idx) { return a * wxz[idx]; }, [](double a, double b) { return a + b; });
     return A[0];
 }
 
@@ -267,30 +247,16 @@ inline void sweep_tiled_host(const TiledPlan &tp, uint64_t N, const uint8_t *cha
     double wxz[4];
     weights_xz(w, wxz);
     const uint32_t n_h = 1u << tp.n_held, n_work = (uint32_t)p.ncls * n_h;
-    if (threads == 0) threads = std::thread::hardware_concurrency();
-    if (threads > 16u) threads = 16u;
-    if (threads > tiled_pass_units(p.width)) threads = tiled_pass_units(p.width);
-    if (threads > n_work) threads = n_work;
-    if (threads < 1u || p.width < 12) threads = 1u;
+    threads = host_threads(threads, n_work, tiled_pass_units(p.width), p.width < 12);
     std::vector<uint32_t> reps((size_t)p.ncls * p.W);
     std::vector<double> P((size_t)n_work);
     for (uint64_t s = 0; s < N; ++s) {
         const int a = class_representatives(p, chains + s * (uint64_t)p.nq, reps.data());
         if (cls) cls[s] = a;
-        auto work = [&](unsigned t) {
-            std::vector<double> A((size_t)1 << p.width);
-            std::vector<uint32_t> rep((size_t)p.W);
-            for (uint32_t i = t; i < n_work; i += threads) {
-                tiled_representative(tp, &reps[(size_t)(i >> tp.n_held) * p.W], i & (n_h - 1u), rep.data());
-                P[i] = sweep_one_wide(tp, rep.data(), wxz, A.data());
-            }
-        };
-        if (threads == 1u) work(0);
-        else {
-            std::vector<std::thread> pool;
-            for (unsigned t = 0; t < threads; ++t) pool.emplace_back(work, t);
-            for (std::thread &t : pool) t.join();
-        }
+        host_partials(n_work, threads, p.width, p.W, P.data(), [&](uint32_t i, uint32_t *rep, double *A) {
+            tiled_representative(tp, &reps[(size_t)(i >> tp.n_held) * p.W], i & (n_h - 1u), rep);
+            return sweep_one_wide(tp, rep, wxz, A);
+        });
         for (int c = 0; c < p.ncls; ++c) Z[s * (uint64_t)p.ncls + c] = cut_reduce(&P[(size_t)c << tp.n_held], tp.n_held, p.scale);
     }
 }
@@ -310,5 +276,82 @@ struct SweepTiledArgs {
 };
 hipError_t launch_class_sweep_tiled(const sweep::TiledPlan &tp, const double *wxz, uint32_t unit_first, uint32_t units, const uint32_t *dev_ops, const uint32_t *held,
                                     const uint32_t *reps, double *work, double *P, hipStream_t stream);
+
+#ifdef __HIPCC__
+namespace sweep {
+
+// HeldRep, then the CLOSE's pairs on fixed slots (word 4): the tile's own bits decide them
+struct TileRep {
+    HeldRep rep;
+    uint32_t base;
+    __device__ __forceinline__ uint32_t operator()(const uint32_t *op, uint32_t q) const
+    {
+        const uint32_t fixed = op[4];
+        uint32_t cq = rep(op, q);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t pr = (fixed >> (8 * j)) & 0xFFu;
+            cq ^= (0u - ((base >> (pr & 31u)) & 1u)) & (pr >> 5);
+        }
+        return cq;
+    }
+};
+
+// One workgroup of a tiled kernel, tile blockIdx.x of unit a.unit_first + blockIdx.y: gather the entries live at the segment's first op into lds
+// (the first segment sets A[0] = 1), run the segment's ops there, store the entries live after its last op (the last segment: P[unit]).  Args is
+// SweepTiledArgs or SweepTiledSiteArgs; src: the factors of a CLOSE.
+template <class Args, class Src>
+__device__ __forceinline__ void tile_sweep(double *lds, const Args &a, const uint32_t *__restrict__ ops, const uint32_t *__restrict__ held,
+                                           const uint32_t *__restrict__ reps, double *__restrict__ work, double *__restrict__ P, const Src &src)
+{
+    const uint32_t tid = threadIdx.x, threads = blockDim.x, unit = a.unit_first + blockIdx.y, hbits = unit & ((1u << a.n_held) - 1u);
+    const uint32_t base = bits_deposit(blockIdx.x, a.fixed_live), entries = 1u << a.tile_width;
+    double *A = work + ((size_t)blockIdx.y << a.state_bits) + base;
+    // local index l <-> offset f = l spread over T; the next one of a lane is `threads` further: an addition that carries across the bits outside T
+    const uint32_t f0 = bits_deposit(tid, a.tile), step = bits_deposit(threads, a.tile);
+    if (a.first) {
+        if (tid == 0) lds[0] = 1.0;
+    } else {
+        for (uint32_t l = tid, f = f0; l < entries; l += threads, f = ((f | ~a.tile) + step) & a.tile)
+            if (!(l & ~a.local_in)) lds[l] = A[f];
+    }
+    __syncthreads();
+    op_loop<TileOps, SumProduct>(lds, ops, a.op_first, a.op_count, tid, threads,
+                                 TileRep{HeldRep{reps + (size_t)(unit >> a.n_held) * (size_t)a.W, held, hbits, (uint32_t)a.W}, base}, src);
+    if (a.last) {
+        if (tid == 0) P[unit] = lds[0];
+    } else {
+        for (uint32_t l = tid, f = f0; l < entries; l += threads, f = ((f | ~a.tile) + step) & a.tile)
+            if (!(l & ~a.local_out)) A[f] = lds[l];
+    }
+}
+
+// The launches of one pass: one per segment of the plan, in order, on one stream.  `a` arrives with what is the caller's own; launch(a, segment)
+// starts the kernel.  hipErrorInvalidValue for a plan or a pass the kernels do not take.
+template <class Args, class Launch>
+inline hipError_t tiled_segments(const TiledPlan &tp, uint32_t unit_first, uint32_t units, Args a, Launch launch)
+{
+    const Plan &p = tp.plan;
+    if ((p.ncls != 4 && p.ncls != 16) || tp.tile_width < kTileMinWidth || tp.tile_width > kTileMaxWidth || tp.state_bits < tp.tile_width ||
+        tp.state_bits > kTiledMaxWidth || p.W < 1 || p.n_ops < 1 || tp.n_held < 0 || tp.n_held > kMaxHeld || units > tiled_pass_units(tp.state_bits) ||
+        tp.segments.empty())
+        return hipErrorInvalidValue;
+    a.unit_first = unit_first; a.units = units; a.W = p.W; a.n_held = tp.n_held; a.state_bits = tp.state_bits; a.tile_width = tp.tile_width;
+    for (size_t s = 0; s < tp.segments.size(); ++s) {
+        const Segment &sg = tp.segments[s];
+        a.op_first = sg.op_first; a.op_count = sg.op_count; a.tile = sg.tile; a.fixed_live = sg.live & ~sg.tile;
+        a.local_in = bits_extract(sg.live_in, sg.tile); a.local_out = bits_extract(sg.live_out, sg.tile);
+        a.n_tiles = sg.n_tiles; a.first = s == 0; a.last = s + 1 == tp.segments.size();
+        if ((int)popcount32(sg.tile) != tp.tile_width || (sg.tile >> tp.state_bits) != 0u || (sg.live >> tp.state_bits) != 0u ||
+            sg.n_tiles != 1u << popcount32(a.fixed_live) || sg.op_first + sg.op_count > (uint32_t)p.n_ops)
+            return hipErrorInvalidValue;
+        launch(a, sg);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    return hipSuccess;
+}
+
+}  // namespace sweep
+#endif  // __HIPCC__
 
 }  // namespace qecmc
