@@ -328,11 +328,27 @@ inline KernelKey choose_wave(const KernelShape &s)
 // SIMD moves on by one from each workgroup of a CU to the next at 8 waves as at 5 - 7, profiles/r11_wave_placement.json; the loss at 8 is unexplained.)
 // QECMC_FLAG_NO_SSW (tune & 8): the replay.
 // A statistics launch (flags = kKeyStats) always replays: its waves count the pair each of them decides.
-inline bool wave_cascade_once(const KernelShape &s)
+// (wave_cascade_once() states the rule measured on the PLAIN once form -- the waves below the top idle between the second and the third barrier -- and
+// tests/test_wave_cascade_choice.py pins it answer by answer; what a launch asks is wave_cascade_walk() below.)
+inline bool wave_cascade_eligible(const KernelShape &s)
 {
     const KernelKey k = choose_wave(s);
-    return s.scan == 3 && k.ok() && k.flags == 0 && !k.conv && !k.alpha && k.wv <= 16 && s.Nc >= 5 && s.Nc <= 7 && !(s.tune & 8) &&
+    return s.scan == 3 && k.ok() && k.flags == 0 && !k.conv && !k.alpha && k.wv <= 16 && s.Nc * 64 <= 512 && !(s.tune & 8) &&
            4 * wu_plan_lds_bytes(s.Nc, s.W, s.ncls, s.L, false, false, s.iters) <= 160 * 1024;
+}
+inline bool wave_cascade_once(const KernelShape &s) { return wave_cascade_eligible(s) && s.Nc >= 5 && s.Nc <= 7; }
+
+// What the launch puts into LadderArgs::wu_once.  With the waves below the top drawing the next step's acceptance block in the wait for the third
+// barrier (ladder_wu.hpp AHEAD: the kernels with the unrolled loop of iters = 10), the once form is a different program from the one
+// wave_cascade_once() was measured on, so the ladder lengths it serves are a rule of their own: everything wave_cascade_once() says yes to, and eight rungs
+// (config 2's ladder) where the shape is eligible in the same sense and the kernel draws ahead -- because the same-box A/B of the two forms says so
+// (kWalkAtEightRungs; DESIGN.md 4.1g, profiles/r13_wave_walk_ab.json: config 2 42.66 -> 40.20 ms walked once, 42.56 replayed; the plain once form
+// on today's kernel 41.06).  Two functions because the first is a measured record that tests pin, and this one is the choice.
+constexpr bool kWalkAtEightRungs = true;
+inline bool wave_cascade_walk(const KernelShape &s)
+{
+    if (wave_cascade_once(s)) return true;
+    return kWalkAtEightRungs && s.Nc == 8 && s.iters == 10 && wave_cascade_eligible(s);
 }
 
 // stats = 2, the shortest-chain statistics of PTEQ_alpha_with_shortest: a chooser of their own (no shape the sweeps of stats = 0 / 1 present comes here).

@@ -80,7 +80,7 @@ struct LadderArgs {
     const uint32_t *col_thr;  // [Nc][81]           scan = 2 under the biased / alpha rules: accept iff u <= col_thr[c][9 (dz + 4) + dxy + 4] (capi.hip)
     const uint32_t *wu_desc;       // scan = 3: [n_gen][16] generator descriptors (tables.hpp wave_descriptors); toric: [n_gen][8] in the wave layout (toric_wave_descriptors)
     uint32_t wu_chunk;             // scan = 3, criterion runs on a persistent grid: ladders per workgroup (a multiple of 64; 0: one ladder per lane, no queue)
-    uint32_t wu_once;              // scan = 3: the swap cascade is walked once per workgroup, by the top rung's wave (set per launch from wave_cascade_once(), kernel_choice.hpp)
+    uint32_t wu_once;              // scan = 3: the swap cascade is walked once per workgroup, by the top rung's wave (set per launch from wave_cascade_walk(), kernel_choice.hpp)
     float swap_inv_log2[kMaxNc];   // 1 / log2(p_diff[i]): first guess of the largest d with u < p_diff[i]^d (the table decides)
     int32_t swap_fast_ok;          // every swap threshold with d >= 1 fits 32 bits (false only if two rungs coincide)
     int L, Nc, W, nq, ncls;

@@ -607,6 +607,13 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
         }
     };
     refresh();
+    // The waves below the top of the lean kernels with the unrolled loop carry the step's acceptance block (one per step: iters = 10) from the tail of
+    // the step before, where it is drawn behind the second barrier: the block is addressed by (T, ladder, slot) and by nothing a step decides, and in
+    // the once-per-workgroup form of the cascade these waves have nothing else to issue there while the top rung's wave walks the pairs.  The first
+    // step's is drawn here; the last step draws one that nobody reads (a resumed run draws it again in front of its loop).
+    constexpr bool AHEAD = LEAN && !TOP && IT == 10;
+    [[maybe_unused]] u32x4 abn{0, 0, 0, 0};
+    if constexpr (AHEAD) abn = wu_philox(a.step0, kSubWuAcc, syn, slot, a.seed_lo, a.seed_hi);
 
     // (the criterion kernels book a step behind the barrier of the next one: without the queue one more, unbooked, step follows the last)
     for (uint64_t t = 0; QUEUE || t < a.nsteps + (CONV ? 1u : 0u); ++t) {
@@ -625,7 +632,8 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
         } else
         for (uint32_t c = 0; c < nch; ++c) {
             [[maybe_unused]] u32x4 ab{0, 0, 0, 0};                                 // this ladder's block of ten 12-bit acceptance uniforms
-            if (!top) ab = wu_philox(T * nch + c, kSubWuAcc, syn, slot, a.seed_lo, a.seed_hi);
+            if constexpr (AHEAD) ab = abn;                                         // (drawn in the tail of the step before)
+            else if (!top) ab = wu_philox(T * nch + c, kSubWuAcc, syn, slot, a.seed_lo, a.seed_hi);
             uint32_t left = iters - c * 10u;
             if constexpr (IT == 0) asm volatile("" : "+s"(left));                  // (a scalar bound for the guards below)
 #pragma unroll
@@ -809,6 +817,14 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
         }
         wu_ds_wait<WV>(st);                                 // (the asm stores of the exchange are not in the compiler's count)
         __syncthreads();
+        // the next step's acceptance block (AHEAD, above): one call site for both forms -- walked once, it fills the wait for the third barrier;
+        // replayed, the draw has merely moved here from the top of the step.  No barrier and no LDS access inside.
+        // (wu_philox launders the seed in front of the block and the statement behind it takes the four words: the draw stays between the two, and
+        // these between the barriers -- left alone, the compiler sinks the whole block to the loop's latch, behind the exchange)
+        if constexpr (AHEAD) {
+            abn = wu_philox(T + 1u, kSubWuAcc, syn, slot, a.seed_lo, a.seed_hi);
+            asm volatile("" : "+v"(abn.x), "+v"(abn.y), "+v"(abn.z), "+v"(abn.w));
+        }
         uint32_t mine;
         if (once) {
             // the cascade once per workgroup: the top rung's wave walks the pairs top-down and leaves in rec[i] the

@@ -111,10 +111,16 @@ void qt_choose_kernels(const KernelShape *shapes, int n, int64_t *keys)
         std::memcpy(keys + 11 * (size_t)i, v, sizeof v);
     }
 }
-// wave_cascade_once() of n shapes: 1 where the launch sets LadderArgs::wu_once
+// wave_cascade_once() of n shapes: the rule measured on the plain once-per-workgroup form of the cascade (kernel_choice.hpp)
 void qt_wave_cascade_once(const KernelShape *shapes, int n, int32_t *once)
 {
     for (int i = 0; i < n; ++i) once[i] = wave_cascade_once(shapes[i]) ? 1 : 0;
+}
+// wave_cascade_walk() of n shapes: 1 where the launch sets LadderArgs::wu_once -- the rule above, and the lengths the form serves since the waves
+// below the top draw the next step's acceptance block in its wait
+void qt_wave_cascade_walk(const KernelShape *shapes, int n, int32_t *walk)
+{
+    for (int i = 0; i < n; ++i) walk[i] = wave_cascade_walk(shapes[i]) ? 1 : 0;
 }
 int qt_kernel_shape_ints(void) { return (int)(sizeof(KernelShape) / sizeof(int)); }
 // validate_params(), then the first phase of plan_host(): the QECMC_ERR_* code and message; accepted: the shape's static fields (the others 0)
