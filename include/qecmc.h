@@ -364,6 +364,23 @@ int qecmc_class_minplus_site(int code, int L, uint64_t N, const uint8_t *chains,
 int qecmc_class_minplus_chains_site(int code, int L, uint64_t N, const uint8_t *chains, const uint8_t *cq, uint64_t cq_rows, int lds_width,
                                     uint8_t *chain_out, uint32_t *cost_out, uint64_t *count_out, int32_t *class_out);
 
+/* ---- the (min, +, count) sweep on the state vector tiled over HBM: xzzx / rotated L = 13 .. 21, planar L = 8 .. 12, toric L = 7
+ * (csrc/class_minplus_tiled.hpp) ----
+ * The arguments and results of qecmc_class_minplus and qecmc_class_minplus_site -- cost_out uint32[N][ncls], count_out uint64[N][ncls] (0 where
+ * saturated), class_out int32[N] (nullable) -- on the plans of qecmc_class_sweep_tiled: hbm_width and tile_width are that function's, and
+ * qecmc_class_sweep_tiled_info gives the plan's facts.  The result does not depend on tile_width, and where the holds are the cut plan's
+ * (hbm_width = its lds_width) it is qecmc_class_minplus's.  There is no traceback on this route.
+ * The 16 bits of an entry's cost do not cover 255 per qubit at these shapes, so the cost range is checked per call: n_qubits * max(cost) < 2^16,
+ * and for a table the sum over the plan's qubits of a row's largest cost at the qubit < 2^16 in every row (QECMC_ERR_UNSUPPORTED, the row named).
+ * Additive: QECMC_ABI_VERSION stays.  Refused before a device is looked for, the message prefixed "qecmc_class_minplus_tiled:" /
+ * "qecmc_class_minplus_tiled_site:": a NULL chains / cost / cq / cost_out / count_out, N beyond 32 bits, a cost above 255, a cq_rows that is
+ * neither 1 nor N (N > 0) with QECMC_ERR_INVALID; what qecmc_class_sweep_tiled refuses of (code, L, hbm_width, tile_width), with its codes; the
+ * cost range.  N == 0 succeeds.  Host pointers only; device 0. */
+int qecmc_class_minplus_tiled(int code, int L, uint64_t N, const uint8_t *chains, const uint32_t cost[4], int hbm_width, int tile_width,
+                              uint32_t *cost_out, uint64_t *count_out, int32_t *class_out);
+int qecmc_class_minplus_tiled_site(int code, int L, uint64_t N, const uint8_t *chains, const uint8_t *cq, uint64_t cq_rows, int hbm_width,
+                                   int tile_width, uint32_t *cost_out, uint64_t *count_out, int32_t *class_out);
+
 /* ---- chain / ladder on caller-owned state (host pointers) ----------------- */
 
 /* The supported range of a start index.  A Philox counter holds a proposal index (the swap stream: a ladder-step index) in 48 bits,

@@ -28,6 +28,7 @@
 #include "class_minplus.hpp"
 #include "class_minplus_trace.hpp"
 #include "class_minplus_site.hpp"
+#include "class_minplus_tiled.hpp"
 #include "enumerate.hpp"
 #include "syndrome_lift.hpp"
 #include "tables.hpp"
@@ -889,7 +890,7 @@ struct TiledWorkspace {
     void *p[kDevices] = {};
     size_t bytes[kDevices] = {};
     static TiledWorkspace &get() { static TiledWorkspace *w = new TiledWorkspace; return *w; }      // (never destroyed, as DevPool)
-    hipError_t take(size_t want, double **out)                                    // under mu
+    hipError_t take(size_t want, void **out)                                      // under mu
     {
         int dev = 0;
         if (hipError_t e = hipGetDevice(&dev)) return e;
@@ -899,44 +900,79 @@ struct TiledWorkspace {
             if (hipError_t e = hipMalloc(&p[dev], want)) return e;
             bytes[dev] = want;
         }
-        *out = static_cast<double *>(p[dev]);
+        *out = p[dev];
         return hipSuccess;
     }
 };
 
 extern "C++" {                                                                  // (a template)
-// What the two tiled entry points share once the plan is accepted and the device chosen.  open_rows(group): the caller's own blocks, after the
-// sweep's; per_group(first, here): its per-group uploads; pass(unit_first, units, batch, work, partials): the launches of one pass of units.  The
-// host loops over groups of syndromes and, within a group, over passes of units: no launch, and no device block, grows with the batch.
-template <class OpenRows, class PerGroup, class Pass>
-int tiled_batch(const sweep::TiledPlan &tp, uint64_t N, const uint8_t *chains, double *z_out, int32_t *class_out, OpenRows open_rows, PerGroup per_group, Pass pass_launch)
+// What the four tiled entry points share once the plan is accepted and the device chosen; T is the entry, a double or a packed (cost, count) word.
+// open_rows(group): the caller's own blocks, after the sweep's; per_group(first, here): its per-group uploads; pass(unit_first, units, batch, work,
+// partials): the launches of one pass of units; finish(batch, first, here, partials): the reduce of a group and its results' way back.  The host
+// loops over groups of syndromes and, within a group, over passes of units: no launch, and no device block, grows with the batch.
+template <class T, class OpenRows, class PerGroup, class Pass, class Finish>
+int tiled_batch(const sweep::TiledPlan &tp, uint64_t N, const uint8_t *chains, int32_t *class_out, OpenRows open_rows, PerGroup per_group, Pass pass_launch, Finish finish)
 {
+    static_assert(sizeof(T) == sizeof(double), "one workspace, one cap and one pass size for every entry");
     const sweep::Plan &p = tp.plan;
     SweepBatch b(p, sweep::cut_launch_group(N, p.ncls, tp.n_held));
     const uint32_t pass = sweep::tiled_pass_units(tp.state_bits);
     const size_t partials = (size_t)p.ncls << tp.n_held;                        // of one syndrome
     const uint64_t group_units = (uint64_t)b.group * partials;
-    DevBuf dpart, dz;
+    DevBuf dpart;
     if (int rc = b.open(tp.dev_ops, &tp.held_words)) return rc;
-    HIP_TRY(dpart.alloc((size_t)b.group * partials * sizeof(double)));          // kCutGridMax doubles at most; dirty: every partial is written before it is read
-    HIP_TRY(dz.alloc((size_t)b.group * p.ncls * sizeof(double)));
+    HIP_TRY(dpart.alloc((size_t)b.group * partials * sizeof(T)));               // kCutGridMax entries at most; dirty: every partial is written before it is read
     if (int rc = open_rows(b.group)) return rc;
-    TiledWorkspace &ws = TiledWorkspace::get();                                 // one block, one cap of kTiledWorkspaceBytes and one lock for both entry points
+    TiledWorkspace &ws = TiledWorkspace::get();                                 // one block, one cap of kTiledWorkspaceBytes and one lock for every entry point
     std::lock_guard<std::mutex> hold(ws.mu);
-    double *work = nullptr;
-    HIP_TRY(ws.take((size_t)(group_units < pass ? group_units : pass) * (sizeof(double) << tp.state_bits), &work));
-    SweepCutArgs ra = cut_args(p, tp.n_held);
+    void *work = nullptr;
+    HIP_TRY(ws.take((size_t)(group_units < pass ? group_units : pass) * (sizeof(T) << tp.state_bits), &work));
     return b.run(N, chains, class_out, [&](uint64_t first, uint64_t here) {
         const uint64_t units = here * partials;
         if (int rc = per_group(first, here)) return rc;
         for (uint64_t u = 0; u < units; u += pass)
-            HIP_TRY(pass_launch((uint32_t)u, (uint32_t)(units - u < pass ? units - u : pass), b, work, dpart.as<double>()));
-        ra.S = (uint32_t)here;
-        HIP_TRY(launch_class_sweep_reduce(ra, dpart.as<double>(), dz.as<double>(), 0));
-        return b.fetch(z_out, dz, first, here);
+            HIP_TRY(pass_launch((uint32_t)u, (uint32_t)(units - u < pass ? units - u : pass), b, static_cast<T *>(work), dpart.as<T>()));
+        return finish(b, first, here, dpart.as<T>());
     });
 }
 }  // extern "C++"
+
+// the end of a group of the two sum-product entry points: k_class_sweep_reduce, then Z to its place in the caller's array
+struct TiledSum {
+    SweepCutArgs ra;
+    double *z_out;
+    DevBuf dz;
+    TiledSum(const sweep::TiledPlan &tp, double *z) : ra(cut_args(tp.plan, tp.n_held)), z_out(z) {}
+    int open(uint32_t group) { HIP_TRY(dz.alloc((size_t)group * ra.ncls * sizeof(double))); return 0; }
+    int operator()(const SweepBatch &b, uint64_t first, uint64_t here, double *P)
+    {
+        ra.S = (uint32_t)here;
+        HIP_TRY(launch_class_sweep_reduce(ra, P, dz.as<double>(), 0));
+        return b.fetch(z_out, dz, first, here);
+    }
+};
+
+// ... and of the two (min, +) ones: k_class_minplus_reduce, then the costs and the counts
+struct TiledFold {
+    MinplusArgs ra;
+    uint32_t *cost_out;
+    uint64_t *count_out;
+    DevBuf dcost, dcount;
+    TiledFold(const sweep::TiledPlan &tp, uint32_t *cost, uint64_t *count) : ra(minplus_args(tp.plan, tp.n_held)), cost_out(cost), count_out(count) {}
+    int open(uint32_t group)
+    {
+        HIP_TRY(dcost.alloc((size_t)group * ra.ncls * sizeof(uint32_t)));
+        HIP_TRY(dcount.alloc((size_t)group * ra.ncls * sizeof(uint64_t)));
+        return 0;
+    }
+    int operator()(const SweepBatch &b, uint64_t first, uint64_t here, uint64_t *P)
+    {
+        ra.S = (uint32_t)here;
+        HIP_TRY(launch_class_minplus_reduce(ra, P, dcost.as<uint32_t>(), dcount.as<uint64_t>(), 0));
+        if (int rc = b.fetch(cost_out, dcost, first, here)) return rc;
+        return b.fetch(count_out, dcount, first, here);
+    }
+};
 }  // namespace
 
 int qecmc_class_sweep_tiled(int code, int L, uint64_t N, const uint8_t *chains, const double *w, int hbm_width, int tile_width, double *z_out, int32_t *class_out)
@@ -950,10 +986,12 @@ int qecmc_class_sweep_tiled(int code, int L, uint64_t N, const uint8_t *chains, 
     if (N == 0) return 0;
     double wxz[4];
     sweep::weights_xz(w, wxz);
-    return tiled_batch(tp, N, chains, z_out, class_out, [](uint32_t) { return 0; }, [](uint64_t, uint64_t) { return 0; },
-                       [&](uint32_t unit_first, uint32_t units, const SweepBatch &b, double *work, double *P) {
-                           return launch_class_sweep_tiled(tp, wxz, unit_first, units, b.ops(), b.held(), b.rep(), work, P, 0);
-                       });
+    TiledSum sum(tp, z_out);
+    return tiled_batch<double>(tp, N, chains, class_out, [&](uint32_t group) { return sum.open(group); }, [](uint64_t, uint64_t) { return 0; },
+                               [&](uint32_t unit_first, uint32_t units, const SweepBatch &b, double *work, double *P) {
+                                   return launch_class_sweep_tiled(tp, wxz, unit_first, units, b.ops(), b.held(), b.rep(), work, P, 0);
+                               },
+                               [&](const SweepBatch &b, uint64_t first, uint64_t here, double *P) { return sum(b, first, here, P); });
 }
 
 // ---------------------------------------------------------------- the three sweeps under a weight per (syndrome, qubit) (class_sweep_site.hpp)
@@ -1057,11 +1095,14 @@ int qecmc_class_sweep_tiled_site(int code, int L, uint64_t N, const uint8_t *cha
     if (int rc = use_device(0)) return rc;
     if (N == 0) return 0;
     SiteRows rows;
-    return tiled_batch(tp, N, chains, z_out, class_out, [&](uint32_t group) { return rows.open(wq, wq_rows, p.nq, group); },
-                       [&](uint64_t first, uint64_t here) { return rows.group(first, here); },
-                       [&](uint32_t unit_first, uint32_t units, const SweepBatch &b, double *work, double *P) {
-                           return launch_class_sweep_tiled_site(tp, rows.per_syndrome, unit_first, units, b.ops(), b.held(), b.rep(), rows.d.as<double>(), work, P, 0);
-                       });
+    TiledSum sum(tp, z_out);
+    return tiled_batch<double>(tp, N, chains, class_out, [&](uint32_t group) { const int rc = sum.open(group); return rc ? rc : rows.open(wq, wq_rows, p.nq, group); },
+                               [&](uint64_t first, uint64_t here) { return rows.group(first, here); },
+                               [&](uint32_t unit_first, uint32_t units, const SweepBatch &b, double *work, double *P) {
+                                   return launch_class_sweep_tiled_site(tp, rows.per_syndrome, unit_first, units, b.ops(), b.held(), b.rep(), rows.d.as<double>(), work, P,
+                                                                        0);
+                               },
+                               [&](const SweepBatch &b, uint64_t first, uint64_t here, double *P) { return sum(b, first, here, P); });
 }
 
 // ---------------------------------------------------------------- the (min, +) sweep and its traceback under a cost per (syndrome, qubit) (class_minplus_site.hpp)
@@ -1174,6 +1215,53 @@ int qecmc_class_minplus_chains_site(int code, int L, uint64_t N, const uint8_t *
         HIP_TRY(launch_minplus_walk(t, b.ops(), b.held(), b.rep(), d.dforget.as<uint32_t>(), d.dpick.as<uint32_t>(), d.ddec.as<uint64_t>(), d.dchain.as<uint8_t>(), 0));
         return d.fetch(b, first, here, chain_out, cost_out, count_out);
     });
+}
+
+// ---------------------------------------------------------------- the (min, +) sweep on the state vector tiled over HBM (class_minplus_tiled.hpp)
+int qecmc_class_minplus_tiled(int code, int L, uint64_t N, const uint8_t *chains, const uint32_t cost[4], int hbm_width, int tile_width, uint32_t *cost_out,
+                              uint64_t *count_out, int32_t *class_out)
+{
+    if (!chains || !cost || !cost_out || !count_out) return fail(QECMC_ERR_INVALID, "qecmc_class_minplus_tiled: NULL buffer");
+    if (N > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "qecmc_class_minplus_tiled: N=%llu syndromes exceed 32 bits", (unsigned long long)N);
+    if (int rc = report(minplus::check_tiled_costs(cost))) return rc;
+    const sweep::TiledPlan tp = minplus::build_minplus_tiled_plan(code, L, hbm_width, tile_width, "qecmc_class_minplus_tiled");
+    if (int rc = report(tp.plan.refusal)) return rc;
+    if (int rc = report(minplus::check_tiled_cost_range(tp.plan, cost))) return rc;
+    if (int rc = use_device(0)) return rc;
+    if (N == 0) return 0;
+    uint32_t cxz[4];
+    minplus::costs_xz(cost, cxz);
+    TiledFold fold(tp, cost_out, count_out);
+    return tiled_batch<uint64_t>(tp, N, chains, class_out, [&](uint32_t group) { return fold.open(group); }, [](uint64_t, uint64_t) { return 0; },
+                                 [&](uint32_t unit_first, uint32_t units, const SweepBatch &b, uint64_t *work, uint64_t *P) {
+                                     return launch_class_minplus_tiled(tp, cxz, unit_first, units, b.ops(), b.held(), b.rep(), work, P, 0);
+                                 },
+                                 [&](const SweepBatch &b, uint64_t first, uint64_t here, uint64_t *P) { return fold(b, first, here, P); });
+}
+
+int qecmc_class_minplus_tiled_site(int code, int L, uint64_t N, const uint8_t *chains, const uint8_t *cq, uint64_t cq_rows, int hbm_width, int tile_width, uint32_t *cost_out,
+                                   uint64_t *count_out, int32_t *class_out)
+{
+    if (!chains || !cq || !cost_out || !count_out) return fail(QECMC_ERR_INVALID, "qecmc_class_minplus_tiled_site: NULL buffer");
+    if (N > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "qecmc_class_minplus_tiled_site: N=%llu syndromes exceed 32 bits", (unsigned long long)N);
+    const sweep::TiledPlan tp = minplus::build_minplus_tiled_plan(code, L, hbm_width, tile_width, "qecmc_class_minplus_tiled_site");
+    const sweep::Plan &p = tp.plan;
+    if (int rc = report(p.refusal)) return rc;
+    if (int rc = report(minplus::check_cost_rows("qecmc_class_minplus_tiled_site", N, cq_rows))) return rc;
+    if (!closes_within(tp.ops, p.nq)) return fail(QECMC_ERR_UNSUPPORTED, "qecmc_class_minplus_tiled_site: internal: a CLOSE names a cell beyond the %d of the table", p.nq);
+    if (N > 0)
+        if (int rc = report(minplus::check_tiled_cost_rows_range(cq, cq_rows, p.nq, sweep::closed_qubits(tp.ops, p.nq)))) return rc;
+    if (int rc = use_device(0)) return rc;
+    if (N == 0) return 0;
+    CostRows rows;
+    TiledFold fold(tp, cost_out, count_out);
+    return tiled_batch<uint64_t>(tp, N, chains, class_out, [&](uint32_t group) { const int rc = fold.open(group); return rc ? rc : rows.open(cq, cq_rows, p.nq, group); },
+                                 [&](uint64_t first, uint64_t here) { return rows.group(first, here); },
+                                 [&](uint32_t unit_first, uint32_t units, const SweepBatch &b, uint64_t *work, uint64_t *P) {
+                                     return launch_class_minplus_tiled_site(tp, rows.per_syndrome, unit_first, units, b.ops(), b.held(), b.rep(), rows.d.as<uint32_t>(), work,
+                                                                            P, 0);
+                                 },
+                                 [&](const SweepBatch &b, uint64_t first, uint64_t here, uint64_t *P) { return fold(b, first, here, P); });
 }
 
 // ---------------------------------------------------------------- chain / ladder

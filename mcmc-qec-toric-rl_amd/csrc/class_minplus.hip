@@ -73,7 +73,10 @@ hipError_t launch_class_minplus_sweep(const MinplusArgs &a, const uint32_t *ops,
 hipError_t launch_class_minplus_reduce(const MinplusArgs &a, uint64_t *P, uint32_t *cost_out, uint64_t *count_out, hipStream_t stream)
 {
     if (a.S == 0) return hipSuccess;
-    if (!minplus_args_ok(a)) return hipErrorInvalidValue;
+    // (what the reduce reads, as launch_class_sweep_reduce asks it: the tiled route's partials come from plans wider than an LDS state vector)
+    if ((a.ncls != 4 && a.ncls != 16) || a.n_held < 0 || a.n_held > sweep::kMaxHeld || a.S > sweep::cut_launch_group(a.S, a.ncls, a.n_held) || a.shift < 0 ||
+        a.shift >= minplus::kCountBits)
+        return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_class_minplus_reduce, dim3(a.S * (uint32_t)a.ncls), dim3(sweep::kThreads), 0, stream, a, P, cost_out, count_out);
     return hipGetLastError();
 }

@@ -21,15 +21,7 @@ namespace qecmc {
 
 constexpr int kSiteWave = (int)minplus::kTraceWave;
 
-// the factor source of a CLOSE: the cost word of its qubit, one wave-uniform scalar load; the cost of idx is a shift by 8 * idx and a mask
-struct SiteCosts {
-    const uint32_t *words;
-    struct Word {
-        uint32_t word;
-        __device__ __forceinline__ uint32_t at(uint32_t idx) const { return minplus::site_cost(word, idx); }
-    };
-    __device__ __forceinline__ Word row(uint32_t q) const { return {words[q]}; }
-};
+using minplus::SiteCosts;
 
 __global__ __launch_bounds__(sweep::kCutThreadsMax) void k_class_minplus_site(const MinplusSiteArgs s, const uint32_t *__restrict__ ops, const uint32_t *__restrict__ held,
                                                                         const uint32_t *__restrict__ reps, const uint32_t *__restrict__ cw, uint64_t *__restrict__ P)

@@ -158,6 +158,18 @@ inline void minplus_trace_site_host(const TracePlan &tp, uint64_t N, const uint8
     }
 }
 
+#ifdef __HIPCC__
+// the factor source of a CLOSE: the cost word of its qubit, one wave-uniform scalar load; the cost of idx is a shift by 8 * idx and a mask
+struct SiteCosts {
+    const uint32_t *words;
+    struct Word {
+        uint32_t word;
+        __device__ __forceinline__ uint32_t at(uint32_t idx) const { return site_cost(word, idx); }
+    };
+    __device__ __forceinline__ Word row(uint32_t q) const { return {words[q]}; }
+};
+#endif
+
 }  // namespace minplus
 
 // class_minplus_site.hip: all pointers are device pointers, as the siblings take them; cw uint32[per_syndrome ? S : 1][t.nq], a word per qubit in

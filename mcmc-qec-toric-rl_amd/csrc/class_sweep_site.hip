@@ -45,7 +45,7 @@ __global__ __launch_bounds__(1024) void k_class_sweep_tiled_site(const SweepTile
     extern __shared__ double sweep_tile_site_lds[];           // [2^tile_width]
     const uint32_t unit = a.unit_first + blockIdx.y;
     const double *rows = wq + (size_t)(a.per_syndrome ? (unit >> a.n_held) / (uint32_t)a.ncls : 0u) * (size_t)a.nq * 4u;
-    sweep::tile_sweep(sweep_tile_site_lds, a, ops, held, reps, work, P, sweep::SiteFour<double>{rows});
+    sweep::tile_sweep<sweep::SumProduct>(sweep_tile_site_lds, a, ops, held, reps, work, P, sweep::SiteFour<double>{rows});
 }
 
 // what every launch asks of the table: a pointer on a 32-byte boundary, a qubit count, a flag

@@ -20,7 +20,7 @@ __global__ __launch_bounds__(1024) void k_class_sweep_tiled(const SweepTiledArgs
                                                             const uint32_t *__restrict__ reps, double *__restrict__ work, double *__restrict__ P)
 {
     extern __shared__ double sweep_tile_lds[];                // [2^tile_width]
-    sweep::tile_sweep(sweep_tile_lds, a, ops, held, reps, work, P, sweep::UniformFour<double>{a.wxz});
+    sweep::tile_sweep<sweep::SumProduct>(sweep_tile_lds, a, ops, held, reps, work, P, sweep::UniformFour<double>{a.wxz});
 }
 
 hipError_t launch_class_sweep_tiled(const sweep::TiledPlan &tp, const double *wxz, uint32_t unit_first, uint32_t units, const uint32_t *dev_ops, const uint32_t *held,

@@ -299,25 +299,27 @@ struct TileRep {
 
 // One workgroup of a tiled kernel, tile blockIdx.x of unit a.unit_first + blockIdx.y: gather the entries live at the segment's first op into lds
 // (the first segment sets A[0] = 1), run the segment's ops there, store the entries live after its last op (the last segment: P[unit]).  Args is
-// SweepTiledArgs or SweepTiledSiteArgs; src: the factors of a CLOSE.
-template <class Args, class Src>
-__device__ __forceinline__ void tile_sweep(double *lds, const Args &a, const uint32_t *__restrict__ ops, const uint32_t *__restrict__ held,
-                                           const uint32_t *__restrict__ reps, double *__restrict__ work, double *__restrict__ P, const Src &src)
+// SweepTiledArgs or SweepTiledSiteArgs (or the (min, +) pair of class_minplus_tiled.hpp); src: the factors of a CLOSE.  Alg is the entry algebra and T
+// its entry -- SumProduct over double, minplus::MinPlus over uint64_t --, T(1) the entry of the empty frontier: 1.0, or (cost 0, count 1).
+template <class Alg, class T, class Args, class Src>
+__device__ __forceinline__ void tile_sweep(T *lds, const Args &a, const uint32_t *__restrict__ ops, const uint32_t *__restrict__ held,
+                                           const uint32_t *__restrict__ reps, T *__restrict__ work, T *__restrict__ P, const Src &src)
 {
+    static_assert(sizeof(T) == sizeof(double), "an entry is one 64-bit word: the workspace, tiled_pass_units and lds_carve are shared");
     const uint32_t tid = threadIdx.x, threads = blockDim.x, unit = a.unit_first + blockIdx.y, hbits = unit & ((1u << a.n_held) - 1u);
     const uint32_t base = bits_deposit(blockIdx.x, a.fixed_live), entries = 1u << a.tile_width;
-    double *A = work + ((size_t)blockIdx.y << a.state_bits) + base;
+    T *A = work + ((size_t)blockIdx.y << a.state_bits) + base;
     // local index l <-> offset f = l spread over T; the next one of a lane is `threads` further: an addition that carries across the bits outside T
     const uint32_t f0 = bits_deposit(tid, a.tile), step = bits_deposit(threads, a.tile);
     if (a.first) {
-        if (tid == 0) lds[0] = 1.0;
+        if (tid == 0) lds[0] = T(1);
     } else {
         for (uint32_t l = tid, f = f0; l < entries; l += threads, f = ((f | ~a.tile) + step) & a.tile)
             if (!(l & ~a.local_in)) lds[l] = A[f];
     }
     __syncthreads();
-    op_loop<TileOps, SumProduct>(lds, ops, a.op_first, a.op_count, tid, threads,
-                                 TileRep{HeldRep{reps + (size_t)(unit >> a.n_held) * (size_t)a.W, held, hbits, (uint32_t)a.W}, base}, src);
+    op_loop<TileOps, Alg>(lds, ops, a.op_first, a.op_count, tid, threads,
+                          TileRep{HeldRep{reps + (size_t)(unit >> a.n_held) * (size_t)a.W, held, hbits, (uint32_t)a.W}, base}, src);
     if (a.last) {
         if (tid == 0) P[unit] = lds[0];
     } else {

@@ -10,6 +10,7 @@
 #include "class_minplus.hpp"
 #include "class_minplus_trace.hpp"
 #include "class_minplus_site.hpp"
+#include "class_minplus_tiled.hpp"
 #include "corrections.hpp"
 #include "enumerate.hpp"
 #include "kernel_choice.hpp"
@@ -511,6 +512,34 @@ int qt_class_minplus_chains_site(int code, int L, uint64_t N, const uint8_t *cha
     return site_answer({}, msg, msg_cap);
 }
 void qt_site_cost_words(const uint8_t *cq, uint64_t rows, int nq, uint32_t *out) { minplus::site_cost_words(cq, rows, nq, out); }
+// the (min, +) sweep on the tiled plans (class_minplus_tiled.hpp): the host twins of qecmc_class_minplus_tiled and qecmc_class_minplus_tiled_site behind
+// the same host checks, in the same order -- the QECMC_ERR_* code of the refusal, its message in msg (nullable)
+int qt_class_minplus_tiled(int code, int L, uint64_t N, const uint8_t *chains, const uint32_t *cost, int hbm_width, int tile_width, uint32_t *cost_out, uint64_t *count_out,
+                           int32_t *cls, char *msg, int msg_cap)
+{
+    if (!chains || !cost || !cost_out || !count_out) return site_answer(refuse_params(QECMC_ERR_INVALID, "qecmc_class_minplus_tiled: NULL buffer"), msg, msg_cap);
+    if (N > 0xFFFFFFFFull) return site_answer(refuse_params(QECMC_ERR_INVALID, "qecmc_class_minplus_tiled: N=%llu syndromes exceed 32 bits", (unsigned long long)N), msg, msg_cap);
+    if (const Refusal r = minplus::check_tiled_costs(cost); r.code) return site_answer(r, msg, msg_cap);
+    const sweep::TiledPlan tp = minplus::build_minplus_tiled_plan(code, L, hbm_width, tile_width, "qecmc_class_minplus_tiled");
+    if (tp.plan.refusal.code) return site_answer(tp.plan.refusal, msg, msg_cap);
+    if (const Refusal r = minplus::check_tiled_cost_range(tp.plan, cost); r.code) return site_answer(r, msg, msg_cap);
+    minplus::minplus_tiled_host(tp, N, chains, cost, cost_out, count_out, cls);
+    return site_answer({}, msg, msg_cap);
+}
+int qt_class_minplus_tiled_site(int code, int L, uint64_t N, const uint8_t *chains, const uint8_t *cq, uint64_t cq_rows, int hbm_width, int tile_width, uint32_t *cost_out,
+                                uint64_t *count_out, int32_t *cls, char *msg, int msg_cap)
+{
+    if (!chains || !cq || !cost_out || !count_out) return site_answer(refuse_params(QECMC_ERR_INVALID, "qecmc_class_minplus_tiled_site: NULL buffer"), msg, msg_cap);
+    if (N > 0xFFFFFFFFull)
+        return site_answer(refuse_params(QECMC_ERR_INVALID, "qecmc_class_minplus_tiled_site: N=%llu syndromes exceed 32 bits", (unsigned long long)N), msg, msg_cap);
+    const sweep::TiledPlan tp = minplus::build_minplus_tiled_plan(code, L, hbm_width, tile_width, "qecmc_class_minplus_tiled_site");
+    if (tp.plan.refusal.code) return site_answer(tp.plan.refusal, msg, msg_cap);
+    if (const Refusal r = minplus::check_cost_rows("qecmc_class_minplus_tiled_site", N, cq_rows); r.code) return site_answer(r, msg, msg_cap);
+    if (N > 0)
+        if (const Refusal r = minplus::check_tiled_cost_rows_range(cq, cq_rows, tp.plan.nq, sweep::closed_qubits(tp.ops, tp.plan.nq)); r.code) return site_answer(r, msg, msg_cap);
+    minplus::minplus_tiled_site_host(tp, N, chains, cq, cq_rows, cost_out, count_out, cls);
+    return site_answer({}, msg, msg_cap);
+}
 // the top rung's frames of a pick window (wu_frames.hpp) for an accepted scan = wave block, from the window's 64 pick blocks picks[64][4]: the plan's
 // descriptors and logical masks (rows padded to the kernel's WV words, as the kernel stages them), thr16 from the plan's thr_logical as wu_run forms it.
 // Writes frames[128 / iters][WV + 1] and returns WV; -1: refused, an unsupported width, or too small a buffer

@@ -17,7 +17,8 @@ from .exact import (coset_enumerator, class_weights, depolarizing_weight, biased
                     exact_rung_observables, class_sweep, class_sweep_cut, sweep_cut_info, class_sweep_tiled, sweep_tiled_info, depolarizing_w4, biased_w4, alpha_w4,
                     class_sweep_site, resolve_site_method, exact_site_probabilities, depolarizing_site_w4, biased_site_w4, erasure_site_w4,
                     class_minplus, min_weight_classes, shortest_class_law, shortest_chains, min_weight_corrections,
-                    class_minplus_site, shortest_chains_site, min_weight_classes_site, min_weight_corrections_site, erasure_site_costs, llr_site_costs)
+                    class_minplus_site, shortest_chains_site, min_weight_classes_site, min_weight_corrections_site, erasure_site_costs, llr_site_costs,
+                    class_minplus_tiled, class_minplus_tiled_site)
 
 __all__ = ["QecmcError", "device_count", "lib", "TORIC", "XZZX", "ROTATED", "PLANAR", "Toric_code", "xzzx_code", "RotSurCode", "Planar_code",
            "Chain", "Ladder", "Chain_xyz", "Chain_biased", "Ladder_biased", "Chain_alpha", "Ladder_alpha", "PTEQ", "PTDC", "STDC", "STRC", "PTRC", "STDC_general_noise", "STDC_general_noise_shortest", "STDC_Nall_n_alpha", "single_temp", "PTEQ_biased", "PTEQ_alpha", "PTEQ_alpha_with_shortest", "pteq_shortest_batch", "shortest_distribution", "ptdc_batch", "ptdc_distribution", "pteq_batch", "percent_from_counts", "chains_from_syndromes", "corrections",
@@ -25,4 +26,5 @@ __all__ = ["QecmcError", "device_count", "lib", "TORIC", "XZZX", "ROTATED", "PLA
            "class_sweep", "class_sweep_cut", "sweep_cut_info", "class_sweep_tiled", "sweep_tiled_info", "depolarizing_w4", "biased_w4", "alpha_w4",
            "class_sweep_site", "resolve_site_method", "exact_site_probabilities", "depolarizing_site_w4", "biased_site_w4", "erasure_site_w4",
            "class_minplus", "min_weight_classes", "shortest_class_law", "shortest_chains", "min_weight_corrections",
-           "class_minplus_site", "shortest_chains_site", "min_weight_classes_site", "min_weight_corrections_site", "erasure_site_costs", "llr_site_costs"]
+           "class_minplus_site", "shortest_chains_site", "min_weight_classes_site", "min_weight_corrections_site", "erasure_site_costs", "llr_site_costs",
+           "class_minplus_tiled", "class_minplus_tiled_site"]

@@ -169,10 +169,30 @@ def _rank_classes(cost, count):
     return order[:, 0].astype(np.int32)
 
 
-def min_weight_classes(code, chains, costs=(0, 1, 1, 1), size=None, lds_width=0):
+_MINPLUS_METHODS = ("cut", "tiled")
+
+
+def _minplus_by_method(code, chains, costs, site_costs, method, size=None, lds_width=0, hbm_width=0, tile_width=0):
+    """class_minplus / class_minplus_site (method "cut", the default everywhere: lds_width) or class_minplus_tiled / class_minplus_tiled_site (method
+    "tiled", only where it is named: hbm_width, tile_width); a width of the other route is refused by name"""
+    if method not in _MINPLUS_METHODS:
+        raise ValueError(f"method={method!r}: the (min, +) sweep runs on the cut plans ('cut') or tiled over HBM ('tiled')")
+    if method == "cut":
+        if hbm_width or tile_width:
+            raise ValueError("hbm_width and tile_width belong to method='tiled'; method='cut' takes lds_width")
+        return class_minplus(code, chains, costs, size=size, lds_width=lds_width) if site_costs is None else \
+            class_minplus_site(code, chains, site_costs, size=size, lds_width=lds_width)
+    if lds_width:
+        raise ValueError("lds_width belongs to method='cut'; method='tiled' takes hbm_width and tile_width")
+    return class_minplus_tiled(code, chains, costs, size=size, hbm_width=hbm_width, tile_width=tile_width) if site_costs is None else \
+        class_minplus_tiled_site(code, chains, site_costs, size=size, hbm_width=hbm_width, tile_width=tile_width)
+
+
+def min_weight_classes(code, chains, costs=(0, 1, 1, 1), size=None, lds_width=0, method="cut", hbm_width=0, tile_width=0):
     """int32[N]: the class class_minplus gives the least cost -- ties broken by the larger count, then by the lower class index.  At the default costs
-    this is the minimum-weight decoder of depolarizing noise over Pauli chains: a Y costs 1, which matching on separate X and Z graphs cannot say."""
-    r = class_minplus(code, chains, costs, size=size, lds_width=lds_width)
+    this is the minimum-weight decoder of depolarizing noise over Pauli chains: a Y costs 1, which matching on separate X and Z graphs cannot say.
+    method="tiled" ranks class_minplus_tiled's result instead (hbm_width, tile_width as it takes them): the shapes past the cut plans."""
+    r = _minplus_by_method(code, chains, costs, None, method, size=size, lds_width=lds_width, hbm_width=hbm_width, tile_width=tile_width)
     return _rank_classes(r["cost"], r["count"])
 
 
@@ -225,7 +245,8 @@ def _law_from_minplus(cost, count, saturated, base):
 
 def shortest_class_law(code, chains, p, alpha=None, site_costs=None, **kw):
     """float64[N, ncls]: the class law carried by the shortest chains alone, count_c * base^cost_c normalised per row (class_minplus, which takes the
-    keywords size and lds_width) -- computed relative to the row's least cost, so nothing underflows.  Depolarizing noise p: unit costs,
+    keywords size and lds_width; method="tiled": class_minplus_tiled, which takes size, hbm_width and tile_width) -- computed relative to the row's
+    least cost, so nothing underflows.  Depolarizing noise p: unit costs,
     base = (p / 3) / (1 - p).  The alpha model (p is pz_tilde) with an integer-valued alpha: costs (0, alpha, alpha, 1), base = pz_tilde; a
     non-integer alpha raises ValueError.  A row with a saturated count raises OverflowError naming it.
     site_costs (a table as class_minplus_site takes it): count_c * base^cost_c under those costs instead, base formed from p / alpha as above -- the
@@ -238,7 +259,7 @@ def shortest_class_law(code, chains, p, alpha=None, site_costs=None, **kw):
         if float(alpha) != np.floor(float(alpha)) or not 0 <= float(alpha) <= 255:
             raise ValueError(f"alpha={alpha!r}: shortest_class_law takes integer costs, so an integer-valued alpha in 0 .. 255 (non-integer costs are out of scope)")
         costs, base = (0, int(alpha), int(alpha), 1), float(p)
-    r = class_minplus(code, chains, costs, **kw) if site_costs is None else class_minplus_site(code, chains, site_costs, **kw)
+    r = _minplus_by_method(code, chains, costs, site_costs, kw.pop("method", "cut"), **kw)
     return _law_from_minplus(r["cost"], r["count"], r["saturated"], base)
 
 
@@ -298,10 +319,10 @@ def shortest_chains_site(code, chains, site_costs, size=None, lds_width=0):
                 held=info["held"])
 
 
-def min_weight_classes_site(code, chains, site_costs, size=None, lds_width=0):
-    """int32[N]: min_weight_classes under site costs -- the class class_minplus_site gives the least cost, ties broken by the larger count, then by the
-    lower class index"""
-    r = class_minplus_site(code, chains, site_costs, size=size, lds_width=lds_width)
+def min_weight_classes_site(code, chains, site_costs, size=None, lds_width=0, method="cut", hbm_width=0, tile_width=0):
+    """int32[N]: min_weight_classes under site costs -- the class class_minplus_site (method="tiled": class_minplus_tiled_site) gives the least cost,
+    ties broken by the larger count, then by the lower class index"""
+    r = _minplus_by_method(code, chains, None, site_costs, method, size=size, lds_width=lds_width, hbm_width=hbm_width, tile_width=tile_width)
     return _rank_classes(r["cost"], r["count"])
 
 
@@ -377,6 +398,47 @@ def class_sweep_tiled(code, chains, weights, size=None, hbm_width=0, tile_width=
     L_.check(L_.lib().qecmc_class_sweep_tiled(code, L, n, L_.u8(flat), w.ctypes.data_as(f64p), int(hbm_width), int(tile_width), z.ctypes.data_as(f64p),
                                               L_.i32(cls)))
     return dict(Z=z, cls=cls, width=info["width"], held=info["held"], segments=info["segments"])
+
+
+def class_minplus_tiled(code, chains, costs=(0, 1, 1, 1), size=None, hbm_width=0, tile_width=0):
+    """class_minplus on the state vector tiled over HBM (qecmc_class_minplus_tiled): the least cost of every class and the number of
+    chains that reach it at xzzx / rotated L = 13 .. 21, planar L = 8 .. 12 and the toric code at L = 7 -- class_sweep_tiled's plans in the semiring of
+    (cost, count) pairs.  code, chains and costs as class_minplus takes them, hbm_width and tile_width as class_sweep_tiled's; the result does not depend
+    on tile_width.  The costs must keep a chain's cost below 2^16: n_qubits * max(costs) < 65536, refused by name otherwise.  There is no traceback on
+    this route.
+    Returns class_minplus's dict, key for key -- cost uint32[N, ncls], count uint64[N, ncls], saturated bool[N, ncls], cls int32[N], width, held: the
+    tiled plan's -- plus segments: the launches one pass of state vectors takes."""
+    code = _CODES.get(code, code)
+    flat, L = _as_chains(code, chains, size)
+    c = np.asarray(costs, dtype=np.float64)
+    if c.shape != (4,) or not np.all((c >= 0) & (c <= 0xFFFFFFFF) & (c == np.floor(c))):
+        raise ValueError(f"costs={costs!r}: the four integer costs of I, X, Y and Z, each >= 0")
+    c = c.astype(np.uint32)
+    n, ncls = flat.shape[0], 16 if code == L_.TORIC else 4
+    cost = np.zeros((n, ncls), dtype=np.uint32)
+    count = np.zeros((n, ncls), dtype=np.uint64)
+    cls = np.zeros(n, dtype=np.int32)
+    L_.check(L_.lib().qecmc_class_minplus_tiled(code, L, n, L_.u8(flat), c.ctypes.data_as(L_._u32p), int(hbm_width), int(tile_width), cost.ctypes.data_as(L_._u32p),
+                                                count.ctypes.data_as(L_._u64p), L_.i32(cls)))
+    info = sweep_tiled_info(code, L, hbm_width, tile_width)
+    return dict(cost=cost, count=count, saturated=count == 0, cls=cls, width=info["width"], held=info["held"], segments=info["segments"])
+
+
+def class_minplus_tiled_site(code, chains, site_costs, size=None, hbm_width=0, tile_width=0):
+    """class_minplus_tiled under a cost per qubit, or per (syndrome, qubit) (qecmc_class_minplus_tiled_site): site_costs as
+    class_minplus_site takes them, the widths as class_minplus_tiled's.  Every row must keep a chain's cost below 2^16: the sum over the qubits of the
+    row's largest cost at the qubit < 65536, refused otherwise with the row named.  Returns class_minplus_tiled's dict, key for key."""
+    code = _CODES.get(code, code)
+    flat, L = _as_chains(code, chains, size)
+    n, ncls = flat.shape[0], 16 if code == L_.TORIC else 4
+    cq, rows = _as_site_costs(code, site_costs, L, n)
+    cost = np.zeros((n, ncls), dtype=np.uint32)
+    count = np.zeros((n, ncls), dtype=np.uint64)
+    cls = np.zeros(n, dtype=np.int32)
+    L_.check(L_.lib().qecmc_class_minplus_tiled_site(code, L, n, L_.u8(flat), L_.u8(cq), rows, int(hbm_width), int(tile_width), cost.ctypes.data_as(L_._u32p),
+                                                     count.ctypes.data_as(L_._u64p), L_.i32(cls)))
+    info = sweep_tiled_info(code, L, hbm_width, tile_width)
+    return dict(cost=cost, count=count, saturated=count == 0, cls=cls, width=info["width"], held=info["held"], segments=info["segments"])
 
 
 def class_weights(hist, weight):

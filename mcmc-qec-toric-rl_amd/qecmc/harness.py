@@ -244,7 +244,9 @@ def _min_weight_distr(params, chains, device):
     (min, +, count) sweep: under depolarizing noise count * ((p / 3) / (1 - p))^(errors of the shortest chain), under the alpha model (an
     integer-valued params['alpha']) count * pz_tilde^(n_z + alpha n_xy).  Its argmax weighs a class's shortest chains by their number; as p -> 0 it is
     qecmc.min_weight_classes, the minimum-weight decoder.  params['lds_width'] (0: the default) as qecmc.class_minplus takes it.  Biased noise is
-    refused: its weights are no integer powers of one base.
+    refused: its weights are no integer powers of one base.  params['exact_method'] = "tiled" runs the sweep tiled over HBM instead
+    (qecmc.class_minplus_tiled, DESIGN.md 4.1r: rotated L = 13 .. 21, planar L = 8 .. 12, toric L = 7) with params['hbm_width'] and
+    params['tile_width'] (0: the defaults), as _exact_distr takes them; it runs only where it is named.
     params['site_costs'] (a table as qecmc.class_minplus_site takes it: integer [..., 4] per cell, with or without a leading n) replaces the four
     costs of params['noise'] by a cost per (row, qubit) -- erasures, any costs that are exponents of the noise's base: the law is
     count * base^cost under the table, base formed from p_error / alpha as above."""
@@ -256,8 +258,11 @@ def _min_weight_distr(params, chains, device):
         raise ValueError(f"method min_weight on the toric code is defined for depolarizing noise, not {noise} (its errors are drawn without a bias)")
     if device != 0:
         raise ValueError("method min_weight runs on device 0: the library has no device-pointer form of it yet")
+    kw = dict(lds_width=int(params.get("lds_width", 0)))
+    if params.get("exact_method") == "tiled":                                   # (only where it is named: every other value leaves the cut plans, as before)
+        kw = dict(method="tiled", hbm_width=int(params.get("hbm_width", 0)), tile_width=int(params.get("tile_width", 0)))
     return shortest_class_law(params["code"], chains, params["p_error"], alpha=params["alpha"] if noise == "alpha" else None, size=params["size"],
-                              lds_width=int(params.get("lds_width", 0)), site_costs=params.get("site_costs"))
+                              site_costs=params.get("site_costs"), **kw)
 
 
 def _corrections_for(code, size, candidates, distr, device):
@@ -275,6 +280,9 @@ def _correction_route(params, method):
         raise ValueError(f"params['correction']={route!r}: 'shortest', or absent for qecmc.corrections")
     if route == "shortest" and method != "min_weight":
         raise ValueError(f"params['correction']='shortest' is built for method min_weight, not {method}: only the (min, +) sweep traces a shortest chain")
+    if route == "shortest" and params.get("exact_method") == "tiled":
+        raise ValueError("params['correction']='shortest' is not built for params['exact_method']='tiled': the tiled (min, +) sweep has no traceback; "
+                         "leave 'correction' out for qecmc.corrections")
     return route
 
 
