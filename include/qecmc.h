@@ -253,7 +253,11 @@ int qecmc_coset_enumerate(int code, int L, uint64_t N, const uint8_t *chains, in
  * Additive: QECMC_ABI_VERSION stays.  Refused before a device is looked for: a NULL chains / w / z_out, a weight that is not finite and
  * > 0 or a (code, L) the library does not know with QECMC_ERR_INVALID; a (code, L) without a class move (the toric code at even L) or a
  * plan wider than 13 with QECMC_ERR_UNSUPPORTED -- which leaves toric L = 3, planar L = 3 .. 6 and xzzx / rotated L = 3, 5, 7, 9.
- * N == 0 succeeds.  Host pointers only.  (qecmc_class_sweep_cut below takes the next shapes.) */
+ * N == 0 succeeds.  Host pointers only.  (qecmc_class_sweep_cut below takes the next shapes.)
+ * Range: z_out is raw -- what IEEE double arithmetic gives, with no rescaling: about count * f^cost in ratio form, so it may be subnormal
+ * (kept, not flushed: the device gives the host twin's bits there too) or 0 at low error rates and large L, and inf under weights above 1.
+ * That holds for qecmc_class_sweep_cut, _tiled and the three _site forms below as well.  Whether a row still carries a law is judged where
+ * it is normalised (qecmc.exact.law_from_class_weights: refused by name below a row total of 2^-960 and where a weight is not finite). */
 int qecmc_class_sweep_info(int code, int L, int32_t *width, int32_t *ncls, int32_t *nq, int32_t *n_ops);
 int qecmc_class_sweep(int code, int L, uint64_t N, const uint8_t *chains, const double *w, double *z_out, int32_t *class_out);
 
@@ -305,7 +309,7 @@ int qecmc_class_sweep_tiled(int code, int L, uint64_t N, const uint8_t *chains, 
  * Plans, widths, holds, segments and launch groups are the sibling's -- its _info call reports them, and what it accepts and refuses is what
  * the site entry point accepts and refuses, with the same code and message.  The device holds the weight rows of one launch group at a time.
  * Weights are finite and >= 0: zero is allowed (off an erased set the pure-erasure limit is (1, 0, 0, 0)), the arithmetic stays copies,
- * multiplies and adds of finite non-negative numbers.  Only the rows of qubits the plan closes are read: a cell that holds no qubit (the planar
+ * multiplies and adds of finite non-negative numbers -- which stay finite for weights <= 1; weights above 1 can take z_out to inf.  Only the rows of qubits the plan closes are read: a cell that holds no qubit (the planar
  * code's unused cells) is neither read nor validated.  With constant rows the result is the uniform sibling's, bit for bit.
  * Additive: QECMC_ABI_VERSION stays.  Refused before a device is looked for, with QECMC_ERR_INVALID: everything the sibling refuses so, a
  * NULL wq, a wq_rows that is neither 1 nor N (N > 0), a weight that is negative, NaN or infinite -- by row, qubit and Pauli --, a qubit whose

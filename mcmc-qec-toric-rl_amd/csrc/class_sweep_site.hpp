@@ -9,8 +9,9 @@
 //     ((per_syndrome ? s : 0) * nq + q) * 4.
 // The device holds the rows of one launch group at a time (s counts within the group), or the one table once: nothing grows with N.
 //
-// WEIGHTS are finite and >= 0.  Zero is allowed -- off an erased set the pure-erasure limit is (1, 0, 0, 0) -- and the arithmetic stays finite:
-// copies, multiplies and adds of finite non-negative numbers.  A qubit whose four weights are all zero makes every class weight zero and is refused
+// WEIGHTS are finite and >= 0.  Zero is allowed -- off an erased set the pure-erasure limit is (1, 0, 0, 0) -- and for weights <= 1 the arithmetic stays finite:
+// copies, multiplies and adds of finite non-negative numbers.  Weights above 1 are accepted and can take a class weight to inf; small ones take it
+// into the subnormals or to 0.  Z is returned as IEEE gives it, and qecmc.exact.law_from_class_weights judges it where it is normalised.  A qubit whose four weights are all zero makes every class weight zero and is refused
 // by name.  Only the rows of qubits some CLOSE names are read or validated: a cell that holds no qubit (the planar code's unused cells) may hold
 // anything.
 //

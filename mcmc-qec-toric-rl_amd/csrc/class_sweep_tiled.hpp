@@ -26,7 +26,9 @@
 // HBM and LDS is a copy.  The twin (sweep_tiled_host) is a plain loop over the wide stream, then cut_reduce(); the kernels (class_sweep_tiled.hip)
 // agree with it bit for bit for every tile_width.  With nothing held and width <= 13 the result is qecmc_class_sweep's bit for bit, and where the holds
 // are qecmc_class_sweep_cut's (hbm_width = its lds_width) it is that one's.  Both sides are built with -ffp-contract=off, without fast-math and without
-// flush-to-zero: at L = 21 single entries reach the denormals, and host and device both keep them.
+// flush-to-zero: at L = 21 single entries reach the denormals, and host and device both keep them (tests/test_gpu_class_law_range.py feeds every
+// sum-product kernel class weights below 2^-1022, down to 0: device and twin agree bit for bit there, class_sweep.hip and class_sweep_cut.hip,
+// which are built without the two flags, included).
 //
 // DIRTY MEMORY.  Neither the workspace in HBM nor LDS is cleared.  The invariant: a live entry is always written by the INTRO that made it live
 // before anything reads it.  A gather reads exactly the entries live at the segment's first op, and each of those was live at the end of the segment

@@ -90,7 +90,8 @@ def class_sweep(code, chains, weights, size=None, device=0):
     """The class weights of every syndrome, on the GPU.  code and chains as coset_enumerator takes them; weights: the four weights of I, X, Y and Z
     at one qubit, finite and > 0 (depolarizing_w4 / biased_w4 / alpha_w4, or any other).
     Returns dict(Z float64[N, ncls]: Z[s, c] = the sum over the chains of class c with the syndrome of chain s of the product of the weights of their
-    Paulis, cls int32[N]: the class of each input chain, width: the widest frontier of the plan)."""
+    Paulis, cls int32[N]: the class of each input chain, width: the widest frontier of the plan).  Z is raw: what IEEE double arithmetic gives with no
+    rescaling, so it may be subnormal, 0 or inf; law_from_class_weights (exact_class_probabilities) is where that is judged."""
     code = _CODES.get(code, code)
     if int(device) != 0:
         raise ValueError("class_sweep runs on device 0: the library has no device-pointer form of it yet")
@@ -119,7 +120,8 @@ def class_sweep_cut(code, chains, weights, size=None, lds_width=0):
     """class_sweep past one LDS state vector (qecmc_class_sweep_cut): `held` generators are held out of the elimination and summed over
     by 2^held workgroups per (class, syndrome) -- the toric code at L = 5, and with nothing held xzzx / rotated L = 11 and planar L = 7 at width 14.
     lds_width: the widest state vector a workgroup may hold, 2 .. 14, 0: the default.
-    Returns dict(Z float64[N, ncls], cls int32[N], width: the widest frontier of the cut plan, held: the number of held generators)."""
+    Returns dict(Z float64[N, ncls], cls int32[N], width: the widest frontier of the cut plan, held: the number of held generators).  Z is raw, as
+    class_sweep's: it may be subnormal, 0 or inf, and law_from_class_weights is where that is judged."""
     code = _CODES.get(code, code)
     flat, L = _as_chains(code, chains, size)
     w = np.ascontiguousarray(weights, dtype=np.float64)
@@ -384,7 +386,7 @@ def class_sweep_tiled(code, chains, weights, size=None, hbm_width=0, tile_width=
     (2^24 doubles are 128 MiB per class and assignment), 0: the default; tile_width: the index bits of a tile in LDS, 4 .. 13, 0: the default.  The
     result does not depend on tile_width, bit for bit.
     Returns dict(Z float64[N, ncls], cls int32[N], width: the widest frontier of the plan, held: the number of held generators, segments: the launches
-    one pass of state vectors takes)."""
+    one pass of state vectors takes).  Z is raw, as class_sweep's: it may be subnormal, 0 or inf, and law_from_class_weights is where that is judged."""
     code = _CODES.get(code, code)
     flat, L = _as_chains(code, chains, size)
     w = np.ascontiguousarray(weights, dtype=np.float64)
@@ -527,7 +529,8 @@ def class_sweep_site(code, chains, site_weights, size=None, method="auto", lds_w
     (resolve_site_method).  This "auto" does reach the tiled sweep -- unlike exact_class_probabilities, whose routing is kept as it was: there is no
     earlier answer to preserve here.
     Returns dict(Z float64[N, ncls]: Z[s, c] = the sum over the chains of class c with the syndrome of chain s of the product over the qubits of the
-    weight of their Pauli there, cls int32[N], method: the one that ran, width, held)."""
+    weight of their Pauli there, cls int32[N], method: the one that ran, width, held).  Z is raw: with weights above 1 it may reach inf, with small
+    ones the subnormals or 0; law_from_class_weights (exact_site_probabilities) is where that is judged."""
     code = _CODES.get(code, code)
     if method not in _SITE_METHODS:
         raise ValueError(f"method={method!r}: class_sweep_site runs {_SITE_METHODS[1:]} or 'auto'")
@@ -549,14 +552,44 @@ def class_sweep_site(code, chains, site_weights, size=None, method="auto", lds_w
     return dict(Z=z, cls=cls, method=ran, width=info["width"], held=info["held"])
 
 
+# The least row total law_from_class_weights normalises.  The sweeps and the enumerator's sum work in ratio form with no rescaling, so a class weight
+# is about count * f^cost and leaves the normal range of float64 at low p and large L.  Below 2^-1022 every product and sum rounds to a multiple of
+# 2^-1074, an absolute error of at most 2^-1075 each.  The largest accepted plan performs fewer than 2^46 additions per output (2^24 entries of the
+# tiled state vector x about 10^3 ops x 2^12 held assignments), so a class weight is off by less than 2^46 * 2^-1075 = 2^-1029 absolute whatever the
+# route, and a law to 1e-12 (about 2^-40) needs a total above 2^-989.  2^-960 leaves a factor 2^29 over that crude bound.  The comparison is made at
+# half of it, so that a row whose exact total is 2^-960 or more is never refused on account of the sweep's own relative error.
+LAW_FLOOR = 2.0 ** -961
+_ALL_ZERO = "every class weight of a syndrome underflows to 0 in float64: the law of that row is not representable"
+
+
+def law_from_class_weights(z):
+    """float64[..., ncls]: class weights Z normalised per row -- the one place where the range of a sweep's raw Z is judged.  Raises
+    FloatingPointError naming the first offending row and the end of float64's range it met: a class weight (or the row's total) that is not finite
+    -- overflow, weights above 1 --, or a row total below 2^-960 (LAW_FLOOR, compared at half of it) -- underflow: its class weights were rounded in the subnormal range, or
+    to 0, and their ratios are no longer the law.  A class that underflows to 0 beside a total >= LAW_FLOOR stays: its probability is below 2^-60."""
+    z = np.asarray(z, dtype=np.float64)
+    rows = z.reshape(-1, z.shape[-1])
+    with np.errstate(over="ignore", invalid="ignore"):
+        tot = rows.sum(axis=1)
+    high = ~(np.isfinite(rows).all(axis=1) & np.isfinite(tot))
+    low = ~high & ~(tot >= LAW_FLOOR)
+    if (high | low).any():
+        r = int(np.flatnonzero(high | low)[0])
+        if high[r]:
+            raise FloatingPointError(f"row {r}: a class weight of the syndrome overflows float64 (class weights {rows[r].tolist()}): weights above 1 took "
+                                     "the sweep past the top of the range, and the law of that row is not representable")
+        if tot[r] == 0.0:
+            raise FloatingPointError(f"{_ALL_ZERO} (row {r}: underflow)")
+        raise FloatingPointError(f"row {r}: the class weights of the syndrome total {tot[r]:.3g}, below 2^-960 = {2.0 * LAW_FLOOR:.3g}: they underflow into "
+                                 "the subnormal range of float64, where their ratios are rounded away, and the law of that row is not representable")
+    return z / tot.reshape(z.shape[:-1] + (1,))
+
+
 def exact_site_probabilities(code, chains, site_weights, **kw):
     """float64[N, ncls]: the exact class law of every syndrome under site weights -- class_sweep_site's Z, which takes the keywords, normalised per
-    row.  Raises FloatingPointError where every class weight of a row is 0, as exact_class_probabilities does."""
-    z = class_sweep_site(code, chains, site_weights, **kw)["Z"]
-    tot = z.sum(axis=-1, keepdims=True)
-    if not np.all(tot > 0.0):
-        raise FloatingPointError("every class weight of a syndrome underflows to 0 in float64: the law of that row is not representable")
-    return z / tot
+    row by law_from_class_weights.  Raises FloatingPointError naming the first row whose class weights overflow, or total less than 2^-960 (all 0
+    among them), as exact_class_probabilities does."""
+    return law_from_class_weights(class_sweep_site(code, chains, site_weights, **kw)["Z"])
 
 
 def depolarizing_site_w4(p_map):
@@ -614,7 +647,9 @@ def exact_class_probabilities(code, chains, p, eta=None, alpha=None, hist=None, 
     means nothing to it); "cut": by class_sweep_cut (size, and lds_width); "auto" (default): the enumerator wherever it accepts the (code, size), the
     sweep where it does not, the cut-set sweep where neither does; "tiled": by class_sweep_tiled (size, hbm_width and tile_width), which "auto"
     never picks.
-    hist: a histogram already enumerated (coset_enumerator(...)['hist']) -- chains is then not looked at, and the method is the enumerator's."""
+    hist: a histogram already enumerated (coset_enumerator(...)['hist']) -- chains is then not looked at, and the method is the enumerator's.
+    Range: the class weights are formed in ratio form (1, f, f, f) with no rescaling, about count * f^cost; law_from_class_weights normalises them and
+    raises FloatingPointError naming the first row whose weights overflow or total less than 2^-960 (about 1e-289) -- right, or refused by name."""
     if eta is not None and alpha is not None:
         raise ValueError("eta and alpha name two noise models")
     if method not in _METHODS:
@@ -639,10 +674,7 @@ def exact_class_probabilities(code, chains, p, eta=None, alpha=None, hist=None, 
             hist = coset_enumerator(code, chains, **enumerator_kw)["hist"]
         weight = alpha_weight(p, alpha) if alpha is not None else biased_weight(p, eta) if eta is not None else depolarizing_weight(p)
         z = class_weights(hist, weight)
-    tot = z.sum(axis=-1, keepdims=True)
-    if not np.all(tot > 0.0):
-        raise FloatingPointError("every class weight of a syndrome underflows to 0 in float64: the law of that row is not representable")
-    return z / tot
+    return law_from_class_weights(z)
 
 
 def exact_rung_observables(hist, p_ladder):
