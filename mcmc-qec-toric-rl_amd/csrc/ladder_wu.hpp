@@ -36,6 +36,7 @@
 #pragma once
 #include "ladder_kernel.hpp"
 #include "shortest_book.hpp"
+#include "wu_bounds.hpp"
 #include "wu_frames.hpp"
 
 namespace qecmc {
@@ -501,25 +502,45 @@ __device__ __forceinline__ void wu_stage_lds(const LadderArgs &a, uint64_t lad, 
     if (CODE == kCodeXzzx) cls = cls == 0 ? 0u : cls == 1 ? 1u : cls == 2 ? 3u : 2u;   // the internal value v with class = v ^ (v >> 1)
 }
 
-// One rung pair of the swap sweep (mcmc.py:97-99, _r_flip :146-149) under the depolarizing rule: do slots i and i + 1 trade states?  car / lo: the
-// records slots i + 1 / i hold, x: the pair's uniform, trow: LDS byte address of the pair's row of swapT.  x < ceil(p_diff[i]^d 2^32) from the row for
-// d < kSwapFast -- its entry 0 never passes, and d <= 0 flips anyway --: the one read that depends on the records.  If some pair of the wave is
-// kSwapFast or more apart (rare once a ladder has settled; the first steps of a run have them), every lane looks its d up in the plan's table in global
-// memory -- whose entries fit 32 bits: swap_fast_ok, wu_supported() -- and the lanes that far apart take that value: one test the wave shares, no
-// exec-mask region, the global address formed behind the test (the laundered i keeps it from being stepped along the cascade).
-__device__ __forceinline__ bool wu_pair_flips(const LadderArgs &a, uint32_t car, uint32_t lo, uint32_t x, uint32_t trow, int i)
+// The swap sweep (mcmc.py:97-99, _r_flip :146-149) under the depolarizing rule, lean tail: slots i and i + 1 trade states iff ne_hi - ne_lo <= D_i(x)
+// (wu_bounds.hpp), and whoever draws a block of swap uniforms leaves the bounds in their place, in front of the step's first barrier.  v: the block's four
+// words, of pairs i0 .. i0 + 3 (`left` of them exist); trow: LDS byte address of pair i0's row of swapT.  Every word's guess is checked on two adjacent
+// entries of its row -- one read, no branch, the four independent of each other --, and one test the wave shares sends the lanes whose check failed
+// somewhere (a quotient within rounding of an integer, x = 0, 1, 2, ladders kSwapFast apart: about one step in a hundred) through the table walk, which
+// leaves the row for the plan's table in global memory -- whose entries fit 32 bits: swap_fast_ok, wu_supported().  The cascade then reads no
+// table and has no far path: a subtraction and a compare per pair.
+__device__ __forceinline__ void wu_bound_block(const LadderArgs &a, u32x4 &v, uint32_t trow, int i0, int left)
 {
-    const int d = (int)(car & 0xFFFFu) - (int)(lo & 0xFFFFu);                        // ne_hi - ne_lo
-    const int dt = d < 0 ? 0 : d > kSwapFast - 1 ? kSwapFast - 1 : d;
-    uint32_t thr = *(wu_lds_ptr)(uintptr_t)(trow + 4u * (uint32_t)dt);
-    if (__builtin_amdgcn_sicmp(d, kSwapFast - 1, 38) != 0) {                         // (ICMP_SGT, over the wave)
-        int il = i, nql = a.nq;
-        asm volatile("" : "+s"(il), "+s"(nql));
-        const int dg = d < 0 ? 0 : d > nql ? nql : d;
-        const uint32_t far = (uint32_t)a.swap_thr[(size_t)il * (size_t)(nql + 1) + (size_t)dg];
-        thr = d >= kSwapFast ? far : thr;
+    int nql = a.nq;
+    asm volatile("" : "+s"(nql));
+    constexpr uint32_t RB = (uint32_t)(kSwapFast * 4);
+    auto near = [&](uint32_t row) { return [row](int d) { return *(wu_lds_ptr)(uintptr_t)(row + 4u * (uint32_t)d); }; };
+    uint32_t g0 = 0, g1 = 0, g2 = 0, g3 = 0;
+    bool ok = true, ok1 = true, ok2 = true, ok3 = true;
+    if (left > 2) {
+        // (three or four pairs: all four words in one stretch, their reads in flight together -- the fourth, if its pair does not exist, on the idle last
+        // row of swapT, its answer dropped)
+        g0 = wu_swap_first(v.x, a.swap_inv_log2[i0], nql); g1 = wu_swap_first(v.y, a.swap_inv_log2[i0 + 1], nql);
+        g2 = wu_swap_first(v.z, a.swap_inv_log2[i0 + 2], nql); g3 = wu_swap_first(v.w, a.swap_inv_log2[i0 + 3], nql);
+        uint32_t a0 = near(trow)((int)g0), b0 = near(trow)((int)g0 + 1), a1 = near(trow + RB)((int)g1), b1 = near(trow + RB)((int)g1 + 1);
+        uint32_t a2 = near(trow + 2u * RB)((int)g2), b2 = near(trow + 2u * RB)((int)g2 + 1), a3 = near(trow + 3u * RB)((int)g3), b3 = near(trow + 3u * RB)((int)g3 + 1);
+        asm volatile("" : "+v"(a0), "+v"(b0), "+v"(a1), "+v"(b1), "+v"(a2), "+v"(b2), "+v"(a3), "+v"(b3));      // (all eight here: one wait)
+        ok = wu_swap_holds(v.x, a0, b0); ok1 = wu_swap_holds(v.y, a1, b1); ok2 = wu_swap_holds(v.z, a2, b2);
+        ok3 = left == 3 || wu_swap_holds(v.w, a3, b3);
+    } else {
+        ok = wu_swap_guess(v.x, a.swap_inv_log2[i0], nql, near(trow), g0);
+        if (left > 1) ok1 = wu_swap_guess(v.y, a.swap_inv_log2[i0 + 1], nql, near(trow + RB), g1);
     }
-    return d <= 0 || x < thr;
+    if (__builtin_amdgcn_ballot_w64(!(ok && ok1 && ok2 && ok3)) != 0) {
+        int il = i0;
+        asm volatile("" : "+s"(il));
+        auto far = [&](int k) { return [&a, il, nql, k](int d) { return (uint32_t)a.swap_thr[(size_t)(il + k) * (size_t)(nql + 1) + (size_t)d]; }; };
+        if (!ok) g0 = wu_swap_walk(v.x, g0, nql, near(trow), far(0));
+        if (!ok1) g1 = wu_swap_walk(v.y, g1, nql, near(trow + RB), far(1));
+        if (!ok2) g2 = wu_swap_walk(v.z, g2, nql, near(trow + 2u * RB), far(2));
+        if (!ok3) g3 = wu_swap_walk(v.w, g3, nql, near(trow + 3u * RB), far(3));
+    }
+    v.x = g0; v.y = g1; v.z = g2; v.w = g3;
 }
 
 // the step loop of one wave: TOP = the rung that accepts every move (its stabilizers unseen, its logical operators through a frame);
@@ -774,7 +795,7 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
         int NCl = a.Nc, ncl = a.ncls;
         uint32_t slotl = ev.slot, lds0l = ev.lds0, once = a.wu_once;
         asm volatile("" : "+s"(NCl), "+s"(ncl), "+s"(slotl), "+s"(lds0l), "+s"(once));
-        if constexpr (STATS) once = 0;                     // (the replay: every wave decides the pair below its own slot)
+        if constexpr (STATS || LONG) once = 0;             // (the replay: every wave decides the pair below its own slot; more than 8 rungs: never walked once)
         const int NC = NCl;
         const uint32_t slot = slotl;
         const WuLds ol = wu_lds(NC, WV, ncl, 0, false, false);                       // (the offsets up to swapT: functions of Nc, WV and ncls alone)
@@ -788,15 +809,23 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
         // test nor the call: -1.7 % at 8 rungs, -2.8 % at 6.  LONG, the 1 024-thread kernels, keep a block per wave: +1.5 % at 12 rungs with the top
         // wave drawing two)
         constexpr bool TOPDRAWS = !LONG && wu_frame_steps(WV, CONV, ALPHA, IT) != 0;
+        // Behind the draw, still in front of the first barrier, the drawer turns every word into its pair's bound (wu_bound_block): the rows of swd hold
+        // bounds, and the cascade below compares.
         u32x4 sb{0, 0, 0, 0};
         [[maybe_unused]] u32x4 sb1{0, 0, 0, 0};
         [[maybe_unused]] bool duty = false;
+        auto bound_block = [&](int blk, u32x4 &v) { wu_bound_block(a, v, tb0 + (uint32_t)(blk * 4) * (uint32_t)(kSwapFast * 4), blk * 4, NC - 1 - blk * 4); };
         if constexpr (TOPDRAWS && TOP) {
             sb = wu_philox(T, 0u, syn, kSwapStream, a.seed_lo, a.seed_hi);
             if (NC > 5) sb1 = wu_philox(T, 1u, syn, kSwapStream, a.seed_lo, a.seed_hi);
+            bound_block(0, sb);
+            if (NC > 5) bound_block(1, sb1);
         } else if constexpr (!TOPDRAWS) {
             duty = swb >= 0 && swb < 4 && swb * 4 < NC - 1;
-            if (duty) sb = wu_philox(T, (uint32_t)swb, syn, kSwapStream, a.seed_lo, a.seed_hi);
+            if (duty) {
+                sb = wu_philox(T, (uint32_t)swb, syn, kSwapStream, a.seed_lo, a.seed_hi);
+                bound_block(swb, sb);
+            }
         }
         auto put_block = [&](int blk, const u32x4 &v) {
             wu_lds_rw p = swdl + (uint32_t)(blk * 4) * 64u;
@@ -829,36 +858,50 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
         if (once) {
             // the cascade once per workgroup: the top rung's wave walks the pairs top-down and leaves in rec[i] the
             // record slot i now holds (rec[i + 1] is dead once pair i is decided: `car` has it); behind a third barrier a wave reads its slot's
-            if constexpr (TOP) {
-                wu_lds_rw pr = recl + (NC - 2) * 64, px = swdl + (NC - 2) * 64;
-                uint32_t trow = tb0 + (uint32_t)(NC - 2) * (uint32_t)(kSwapFast * 4);
-                uint32_t car = pr[64], lo = pr[0], x = px[0];
-                for (int i = NC - 2; i >= 0; --i) {                                  // mcmc.py:96
-                    // (the next pair's record and uniform travel while this one is decided; behind pair 0: a row of the region in front, dropped)
-                    const uint32_t lo_n = pr[-64], x_n = px[-64];
-                    const bool flip = wu_pair_flips(a, car, lo, x, trow, i);
-                    pr[64] = flip ? lo : car;                                        // what slot i + 1 now holds (:98-99)
-                    car = flip ? car : lo;
-                    lo = lo_n; x = x_n; pr -= 64; px -= 64; trow -= (uint32_t)(kSwapFast * 4);
+            // Every read the walk needs is issued in front of its first decision -- the records, and beside each the bound of the pair below it, counted
+            // from the top: constant offsets from one base, at most 8 rungs here (!LONG), the rows below rung 0's are rows of the exchange buffer, read and
+            // dropped -- and waited for once; the chain itself runs in registers, a compare and two selects per pair on ne(lo) + D, which is formed off
+            // the chain.  The stores of rec[i + 1] go out as the chain advances and are waited for in front of the barrier alone.
+            if constexpr (TOP && !LONG) {
+                wu_lds_rw const pr = recl + (NC - 8) * 64;
+                wu_lds_ptr const px = swdl + (NC - 8) * 64;
+                uint32_t r[8], s[7];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) r[j] = pr[64 * (7 - j)];                  // slot NC - 1 - j's record
+#pragma unroll
+                for (int j = 0; j < 7; ++j) s[j] = px[64 * (6 - j)];                  // pair NC - 2 - j's bound
+                asm volatile("" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7]),
+                                  "+v"(s[0]), "+v"(s[1]), "+v"(s[2]), "+v"(s[3]), "+v"(s[4]), "+v"(s[5]), "+v"(s[6]));   // (all of them here: one wait)
+#pragma unroll
+                for (int j = 0; j < 7; ++j) s[j] += r[j + 1] & 0xFFFFu;
+                uint32_t car = r[0], nc = car & 0xFFFFu;
+#pragma unroll
+                for (int j = 0; j < 7; ++j) {                                        // pair i = NC - 2 - j, mcmc.py:96
+                    if (j < NC - 1) {
+                        const uint32_t lo = r[j + 1];
+                        const bool flip = nc <= s[j];                                // ne_hi - ne_lo <= D
+                        pr[64 * (7 - j)] = flip ? lo : car;                             // what slot i + 1 now holds (:98-99)
+                        car = flip ? car : lo;
+                        nc = flip ? nc : lo & 0xFFFFu;
+                    }
                 }
-                pr[64] = car;
+                recl[0] = car;
             }
             __syncthreads();
             mine = recl[slot * 64u];
         } else {
             // every wave replays the top-down cascade on the published records: the pairs above its slot move `car` alone, the pair below it decides
             wu_lds_ptr pr = recl + (NC - 2) * 64, px = swdl + (NC - 2) * 64;
-            uint32_t trow = tb0 + (uint32_t)(NC - 2) * (uint32_t)(kSwapFast * 4);
             uint32_t car = pr[64];
             for (int i = NC - 2; i >= (int)slot; --i) {                              // mcmc.py:96
                 const uint32_t lo = pr[0];
-                car = wu_pair_flips(a, car, lo, px[0], trow, i) ? car : lo;
-                pr -= 64; px -= 64; trow -= (uint32_t)(kSwapFast * 4);
+                car = wu_bound_flips(car, lo, px[0]) ? car : lo;
+                pr -= 64; px -= 64;
             }
             mine = car;
             if (slot != 0) {
                 const uint32_t lo = pr[0];
-                if (wu_pair_flips(a, car, lo, px[0], trow, (int)slot - 1)) {
+                if (wu_bound_flips(car, lo, px[0])) {
                     mine = lo;                                                          // what slot i + 1 now holds (:98-99)
                     if constexpr (STATS) swapc += 1u;
                 }

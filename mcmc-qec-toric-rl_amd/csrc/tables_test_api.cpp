@@ -17,6 +17,7 @@
 #include "plan_host.hpp"
 #include "syndrome_lift.hpp"
 #include "tables.hpp"
+#include "wu_bounds.hpp"
 #include "wu_frames.hpp"
 
 #include <cstdio>
@@ -560,5 +561,31 @@ int qt_wave_frames(const qecmc_params *p, const uint32_t *picks, uint32_t *frame
 #undef QT_FRAMES_W
 #undef QT_FRAMES
     return WV;
+}
+// the swap sweep's bound of rung pair `pair` (wu_bounds.hpp) for an accepted scan = wave block under the depolarizing rule, on n words xs: the pair's row of
+// swapT as the kernels stage it (ladder_wu_body.inc), the plan's swap_thr behind it, the plan's swap_inv_log2.  Returns nq; -1: refused or no such pair
+int qt_wave_swap_bound(const qecmc_params *p, int pair, const uint32_t *xs, uint64_t n, uint32_t *out)
+{
+    HostPlan hp;
+    if (validate_params(p).code || plan_host(*p, hp).code || p->scan != QECMC_SCAN_WAVE || p->noise != QECMC_NOISE_DEPOLARIZING) return -1;
+    const LadderArgs &a = hp.args;
+    if (pair < 0 || pair + 1 >= a.Nc || !a.swap_fast_ok) return -1;
+    const int nq = a.nq;
+    const uint64_t *thr = hp.swap_thr.data() + (size_t)pair * (nq + 1);
+    uint32_t row[kSwapFast];
+    for (int d = 0; d < kSwapFast; ++d) row[d] = (d >= 1 && d <= nq) ? (uint32_t)thr[d] : 0u;
+    for (uint64_t k = 0; k < n; ++k)
+        out[k] = wu_swap_bound(xs[k], a.swap_inv_log2[pair], nq, [&](int d) { return row[d]; }, [&](int d) { return (uint32_t)thr[d]; });
+    return nq;
+}
+// ... and the pair's row of the plan's thresholds, swap_thr[pair][0 .. nq]: returns nq + 1; -1: refused, no such pair, or too small a buffer
+int qt_wave_swap_row(const qecmc_params *p, int pair, uint64_t *out, int cap)
+{
+    HostPlan hp;
+    if (validate_params(p).code || plan_host(*p, hp).code || p->scan != QECMC_SCAN_WAVE) return -1;
+    const LadderArgs &a = hp.args;
+    if (pair < 0 || pair + 1 >= a.Nc || cap < a.nq + 1) return -1;
+    for (int d = 0; d <= a.nq; ++d) out[d] = hp.swap_thr[(size_t)pair * (a.nq + 1) + d];
+    return a.nq + 1;
 }
 }
