@@ -110,8 +110,9 @@ typedef struct qecmc_params {
 enum qecmc_flag {
     QECMC_FLAG_NO_PRE   = 2,   /* no instantiations that draw the top chain's Philox blocks ahead */
     QECMC_FLAG_NO_DELUT = 4,   /* no dE look-up table (popcount form) */
-    QECMC_FLAG_NO_SSW   = 8    /* no swap sweep run once per workgroup (every wave replays the cascade): ladder_kernel's variant run by wave 0, and
-                                  the scan = wave kernels' cascade walked by the top rung's wave (5 - 7 rungs, fixed length, up to 16 words) */
+    QECMC_FLAG_NO_SSW   = 8,   /* no swap sweep run once per workgroup (every wave replays the cascade): ladder_kernel's variant run by wave 0, and
+                                  the scan = wave kernels' cascade walked by the top rung's wave (5 - 8 rungs, fixed length, up to 16 words) */
+    QECMC_FLAG_NO_SPREAD = 16  /* the scan = wave kernels' walked cascade with every swap bound found by the top rung's wave, not a pair per wave below it */
 };
 #define QECMC_FLAGS_QUEUE_GRID(n) ((uint32_t)(n) << 16)
 

@@ -323,13 +323,13 @@ inline KernelKey choose_wave(const KernelShape &s)
 // kernel key: both forms live in the one kernel behind a wave-uniform test of LadderArgs::wu_once, which the launch sets from here.  Where ladder_kernel's
 // SSW variant would be eligible (choose_ladder_toric: fixed length, depolarizing rule, at most 16 words, workgroups of up to 512 threads of which four fit
 // a CU -- the serial section is covered by the CU's other workgroups) the measurement decides, and it turns on the ladder's length alone, whatever the code
-// and the state width: once per workgroup gains 2.6 - 5.2 % at 5, 6 and 7 rungs and loses 0.5 - 3.8 % at 2, 3, 4 -- too few replays to pay
-// for the barrier -- and at 8.  (Not because a workgroup's waves fall on the same SIMDs in every workgroup of a CU, as this comment once guessed: the starting
-// SIMD moves on by one from each workgroup of a CU to the next at 8 waves as at 5 - 7, profiles/r11_wave_placement.json; the loss at 8 is unexplained.)
+// and the state width.  wave_cascade_once() is the record of the PLAIN once form -- the waves below the top idle between the second and the
+// third barrier --: it gained 2.6 - 5.2 % at 5, 6 and 7 rungs and lost 0.5 - 3.8 % at 2, 3, 4 (too few replays to pay for the barrier) and, on the kernel of
+// that day, at 8.  tests/test_wave_cascade_choice.py pins it answer by answer.  What a launch asks is wave_cascade_walk() below, which adds eight rungs for
+// the kernels that draw ahead in the wait: re-measured on today's kernel the once form gains there too (42.66 -> 41.06 ms plain, 40.20 with
+// the draw), so nothing about eight rungs is left unexplained or lost.
 // QECMC_FLAG_NO_SSW (tune & 8): the replay.
 // A statistics launch (flags = kKeyStats) always replays: its waves count the pair each of them decides.
-// (wave_cascade_once() states the rule measured on the PLAIN once form -- the waves below the top idle between the second and the third barrier -- and
-// tests/test_wave_cascade_choice.py pins it answer by answer; what a launch asks is wave_cascade_walk() below.)
 inline bool wave_cascade_eligible(const KernelShape &s)
 {
     const KernelKey k = choose_wave(s);
@@ -349,6 +349,21 @@ inline bool wave_cascade_walk(const KernelShape &s)
 {
     if (wave_cascade_once(s)) return true;
     return kWalkAtEightRungs && s.Nc == 8 && s.iters == 10 && wave_cascade_eligible(s);
+}
+
+// The form of the walk (LadderArgs::wu_once: 0 the replay, 1, 2).  In the kernels whose top rung's wave draws both blocks of swap uniforms (ladder_wu.hpp
+// TOPDRAWS: the frame kernels -- fixed length, depolarizing rule, at most 16 words, iters = 10 -- of up to 8 rungs) that wave was the last of its workgroup at
+// the step's first barrier by the bounds it found behind the draw.  Form 2 spreads them: the top wave draws the NEXT step's words and hands them over raw
+// behind its walk, and each wave below the top turns the word of the pair above its own slot into the bound.  Form 1 is the walk as it was.  The ladder
+// lengths of form 2 are the ones at which the same-box A/B of the two forms had it ahead by the project's bar (kSpreadRungs, bit Nc;
+// profiles/r15_wave_spread_ab.json): eight rungs -- config 2 39.85 -> 38.97 ms, 9.5 times the larger spread -- and no other: at 5, 6 and 7
+// rungs form 2 lost 2.1, 1.0 and 1.2 % (the top wave is not the late one there).  QECMC_FLAG_NO_SPREAD (tune & 16): form 1 wherever form 2 would run.
+constexpr uint32_t kSpreadRungs = 1u << 8;
+inline int wave_cascade_mode(const KernelShape &s)
+{
+    if (!wave_cascade_walk(s)) return 0;
+    const bool topdraws = s.Nc <= 8 && wu_frame_steps(wu_words(s.W), s.conv != 0, s.noise == 2, s.iters == 10 ? 10 : 0) != 0;
+    return topdraws && ((kSpreadRungs >> s.Nc) & 1u) && !(s.tune & 16) ? 2 : 1;
 }
 
 // stats = 2, the shortest-chain statistics of PTEQ_alpha_with_shortest: a chooser of their own (no shape the sweeps of stats = 0 / 1 present comes here).

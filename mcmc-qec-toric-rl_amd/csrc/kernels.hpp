@@ -80,7 +80,7 @@ struct LadderArgs {
     const uint32_t *col_thr;  // [Nc][81]           scan = 2 under the biased / alpha rules: accept iff u <= col_thr[c][9 (dz + 4) + dxy + 4] (capi.hip)
     const uint32_t *wu_desc;       // scan = 3: [n_gen][16] generator descriptors (tables.hpp wave_descriptors); toric: [n_gen][8] in the wave layout (toric_wave_descriptors)
     uint32_t wu_chunk;             // scan = 3, criterion runs on a persistent grid: ladders per workgroup (a multiple of 64; 0: one ladder per lane, no queue)
-    uint32_t wu_once;              // scan = 3: the swap cascade is walked once per workgroup, by the top rung's wave (set per launch from wave_cascade_walk(), kernel_choice.hpp)
+    uint32_t wu_once;              // scan = 3: 0 every wave replays the swap cascade; 1, 2 the top rung's wave walks it once per workgroup -- 2: on bounds the waves below the top found, a pair each (set per launch from wave_cascade_mode(), kernel_choice.hpp)
     float swap_inv_log2[kMaxNc];   // 1 / log2(p_diff[i]): first guess of the largest d with u < p_diff[i]^d (the table decides)
     int32_t swap_fast_ok;          // every swap threshold with d >= 1 fits 32 bits (false only if two rungs coincide)
     int L, Nc, W, nq, ncls;
@@ -93,7 +93,7 @@ struct LadderArgs {
     // and tops0 to the outputs of syndrome l / R (atomics; the caller zeroes them) -- decoders.py:215-225 "droplets"
     uint32_t *queue;          // QUEUE kernels: the batch's counter of ladders handed out after launch (zeroed by the caller)
     uint32_t grid_cap;        // ... the persistent grid: at most this many workgroups (0: one per 64 ladders)
-    uint32_t tune;            // development knobs (qecmc_params.flags bits 0-15, include/qecmc.h qecmc_flag; 0 in production): bit 1 = no PRE instantiations, bit 2 = no dE table, bit 3 = no SSW instantiations
+    uint32_t tune;            // development knobs (qecmc_params.flags bits 0-15, include/qecmc.h qecmc_flag; 0 in production): bit 1 = no PRE instantiations, bit 2 = no dE table, bit 3 = no SSW instantiations, bit 4 = no bounds spread over the lower waves
     uint32_t replicas;
     int accumulate;           // counts / samples are added to (qecmc_pteq_resume_dev)
     // equilibrium observables (qecmc_plan_set_stats; nullable): accepted swaps per rung pair, sum of error counts per rung

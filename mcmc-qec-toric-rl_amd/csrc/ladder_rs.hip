@@ -77,7 +77,7 @@ hipError_t launch_ladder(const LadderArgs &a, hipStream_t stream)
         if (k.conv && (a.nlog == nullptr || a.resume || a.write_states || a.wu_chunk < 64u || (a.wu_chunk & 63u))) return hipErrorInvalidValue;
         const uint64_t per = k.conv ? a.wu_chunk : 64u;
         LadderArgs b = a;
-        b.wu_once = wave_cascade_walk(kernel_shape(a)) ? 1u : 0u;
+        b.wu_once = (uint32_t)wave_cascade_mode(kernel_shape(a));
         note_kernel(k);
         return launch_fn(fn, b, stream, (unsigned)((a.N + per - 1) / per), wu_lds_bytes(a.Nc, a.W, a.ncls, a.L, k.conv, k.alpha, false, wu_frame_steps(k.wv, k.conv, k.alpha, k.it)));
     }

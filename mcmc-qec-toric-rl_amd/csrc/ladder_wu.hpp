@@ -542,6 +542,37 @@ __device__ __forceinline__ void wu_bound_block(const LadderArgs &a, u32x4 &v, ui
     }
     v.x = g0; v.y = g1; v.z = g2; v.w = g3;
 }
+// ... and of ONE word, for the form of the walk in which every wave below the top finds the bound of one pair (LadderArgs::wu_once == 2, below): x the raw
+// swap word of pair i, trow the LDS byte address of that pair's row of swapT.  The same functions on the same inputs as a word of wu_bound_block.
+__device__ __forceinline__ uint32_t wu_bound_word(const LadderArgs &a, uint32_t x, uint32_t trow, int i)
+{
+    int nql = a.nq;
+    asm volatile("" : "+s"(nql));
+    auto near = [trow](int d) { return *(wu_lds_ptr)(uintptr_t)(trow + 4u * (uint32_t)d); };
+    uint32_t g;
+    const bool ok = wu_swap_guess(x, a.swap_inv_log2[i], nql, near, g);
+    if (__builtin_amdgcn_ballot_w64(!ok) != 0) {
+        int il = i;
+        asm volatile("" : "+s"(il));
+        if (!ok) g = wu_swap_walk(x, g, nql, near, [&a, il, nql](int d) { return (uint32_t)a.swap_thr[(size_t)il * (size_t)(nql + 1) + (size_t)d]; });
+    }
+    return g;
+}
+// the words of a block of swap uniforms (or their bounds) into the rows of swd: p = row of the block's first pair, lane's column; `left` pairs exist from there
+__device__ __forceinline__ void wu_put_block(wu_lds_rw p, const u32x4 &v, int left)
+{
+    p[0] = v.x;
+    if (left > 1) p[64] = v.y;
+    if (left > 2) p[128] = v.z;
+    if (left > 3) p[192] = v.w;
+}
+// Where a wave below the top turns its pair's word into the bound under wu_once == 2: 0 right behind the exchange's read (the top of its stretch between the
+// third barrier and the next step's first), 1 behind the proposals (the end of that stretch).  The results are the same; -DQECMC_WU_SPREAD_AT=n builds the
+// other one for an A/B (bench.py --library; DESIGN.md 4.1g has the measurement that chose the default; the other build was timed, the tests run the default).
+#ifndef QECMC_WU_SPREAD_AT
+#define QECMC_WU_SPREAD_AT 0
+#endif
+constexpr int kWuSpreadAt = QECMC_WU_SPREAD_AT;
 
 // the step loop of one wave: TOP = the rung that accepts every move (its stabilizers unseen, its logical operators through a frame);
 // IT = 10: `iters` known at compile time (decoders.py:25 iters=10), the proposal loop unrolled without guards; IT = 0: any 1 <= iters <= 128.
@@ -635,6 +666,28 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
     constexpr bool AHEAD = LEAN && !TOP && IT == 10;
     [[maybe_unused]] u32x4 abn{0, 0, 0, 0};
     if constexpr (AHEAD) abn = wu_philox(a.step0, kSubWuAcc, syn, slot, a.seed_lo, a.seed_hi);
+    // The walk on bounds the waves below the top found (wu_once == 2; the lean tail below has the schedule): in step T the top rung's wave draws the swap
+    // words of step T + 1 and stores them raw behind its walk, and the wave of slot s turns row s of swd -- pair s -- into the bound somewhere between that
+    // step's third barrier and the next step's first.  The first step of a launch (of every resumed chunk) has no step before it: its words are drawn and
+    // stored here, in front of ONE barrier outside the step loop, which every wave of the workgroup meets (wu_once is uniform over the launch).
+    constexpr bool SPREAD = LEAN && !STATS && !LONG && wu_frame_steps(WV, CONV, ALPHA, IT) != 0;
+    if constexpr (SPREAD) {
+        if (a.wu_once == 2u) {
+            const int NC = a.Nc;
+            const WuLds ol = wu_lds(NC, WV, a.ncls, 0, false, false);
+            const uint32_t col = lds0 + (uint32_t)lane * 4u;
+            if constexpr (TOP) {
+                wu_lds_rw const swd0 = (wu_lds_rw)(uintptr_t)(col + (uint32_t)ol.swd * 4u);
+                wu_put_block(swd0, wu_philox(a.step0, 0u, syn, kSwapStream, a.seed_lo, a.seed_hi), NC - 1);
+                if (NC > 5) wu_put_block(swd0 + 256, wu_philox(a.step0, 1u, syn, kSwapStream, a.seed_lo, a.seed_hi), NC - 5);
+            }
+            __syncthreads();
+            if constexpr (!TOP && kWuSpreadAt == 0) {
+                wu_lds_rw const row = (wu_lds_rw)(uintptr_t)(col + (uint32_t)(ol.swd + (int)slot * 64) * 4u);
+                row[0] = wu_bound_word(a, row[0], lds0 + (uint32_t)(ol.swapT + (int)slot * kSwapFast) * 4u, (int)slot);
+            }
+        }
+    }
 
     // (the criterion kernels book a step behind the barrier of the next one: without the queue one more, unbooked, step follows the last)
     for (uint64_t t = 0; QUEUE || t < a.nsteps + (CONV ? 1u : 0u); ++t) {
@@ -811,15 +864,28 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
         constexpr bool TOPDRAWS = !LONG && wu_frame_steps(WV, CONV, ALPHA, IT) != 0;
         // Behind the draw, still in front of the first barrier, the drawer turns every word into its pair's bound (wu_bound_block): the rows of swd hold
         // bounds, and the cascade below compares.
+        // once == 2 (a TOPDRAWS kernel's walk; STATS and LONG have folded it to 0): the bounds are spread over the waves below the top.  The top wave draws
+        // the words of step T + 1 here, keeps them raw in registers over both barriers and stores them behind its walk's reads, into the rows it has just
+        // read: behind the second barrier nobody but the walker reads swd.  The wave of slot s converts row s in place (own_bound) between the third
+        // barrier and the next step's first, and nobody else touches row s from the third barrier to the walker's read behind the next step's second
+        // one: the step gets no barrier for it.  The addressing of the words is unchanged -- only who turns a word into a bound, and when.
+        const bool spread = once == 2u;
         u32x4 sb{0, 0, 0, 0};
         [[maybe_unused]] u32x4 sb1{0, 0, 0, 0};
         [[maybe_unused]] bool duty = false;
         auto bound_block = [&](int blk, u32x4 &v) { wu_bound_block(a, v, tb0 + (uint32_t)(blk * 4) * (uint32_t)(kSwapFast * 4), blk * 4, NC - 1 - blk * 4); };
         if constexpr (TOPDRAWS && TOP) {
-            sb = wu_philox(T, 0u, syn, kSwapStream, a.seed_lo, a.seed_hi);
-            if (NC > 5) sb1 = wu_philox(T, 1u, syn, kSwapStream, a.seed_lo, a.seed_hi);
-            bound_block(0, sb);
-            if (NC > 5) bound_block(1, sb1);
+            // (two stretches of straight-line code: the walk on the top wave's own bounds keeps the parent's order of draw and bounds.  One draw site with a
+            // selected step number measured the same in both forms, profiles/r15_wave_spread_ab.json)
+            if (spread) {
+                sb = wu_philox(T + 1u, 0u, syn, kSwapStream, a.seed_lo, a.seed_hi);
+                if (NC > 5) sb1 = wu_philox(T + 1u, 1u, syn, kSwapStream, a.seed_lo, a.seed_hi);
+            } else {
+                sb = wu_philox(T, 0u, syn, kSwapStream, a.seed_lo, a.seed_hi);
+                if (NC > 5) sb1 = wu_philox(T, 1u, syn, kSwapStream, a.seed_lo, a.seed_hi);
+                bound_block(0, sb);
+                if (NC > 5) bound_block(1, sb1);
+            }
         } else if constexpr (!TOPDRAWS) {
             duty = swb >= 0 && swb < 4 && swb * 4 < NC - 1;
             if (duty) {
@@ -827,20 +893,22 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
                 bound_block(swb, sb);
             }
         }
-        auto put_block = [&](int blk, const u32x4 &v) {
-            wu_lds_rw p = swdl + (uint32_t)(blk * 4) * 64u;
-            const int left = NC - 1 - blk * 4;
-            p[0] = v.x;
-            if (left > 1) p[64] = v.y;
-            if (left > 2) p[128] = v.z;
-            if (left > 3) p[192] = v.w;
+        auto put_block = [&](int blk, const u32x4 &v) { wu_put_block(swdl + (uint32_t)(blk * 4) * 64u, v, NC - 1 - blk * 4); };
+        // (a wave below the top, once == 2: the word of the pair above its slot, read, turned into the bound and stored in one place -- the role has no
+        // register to carry it across the proposal loop)
+        [[maybe_unused]] auto own_bound = [&]() {
+            wu_lds_rw const row = swdl + slot * 64u;
+            row[0] = wu_bound_word(a, row[0], tb0 + slot * (uint32_t)(kSwapFast * 4), (int)slot);
         };
+        if constexpr (TOPDRAWS && !TOP && kWuSpreadAt == 1) { if (spread) own_bound(); }
         __syncthreads();                                   // (everybody has read the exchange buffer, the records and the swap uniforms of the step before)
         wu_put_all<WV>(st, xaddr + slot * xstride);
         recl[slot * 64u] = pack_info(n4 >> 2, slot, cls, flag);
         if constexpr (TOPDRAWS && TOP) {
-            put_block(0, sb);
-            if (NC > 5) put_block(1, sb1);
+            if (!spread) {
+                put_block(0, sb);
+                if (NC > 5) put_block(1, sb1);
+            }
         } else if constexpr (!TOPDRAWS) {
             if (duty) put_block(swb, sb);
         }
@@ -872,6 +940,13 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
                 for (int j = 0; j < 7; ++j) s[j] = px[64 * (6 - j)];                  // pair NC - 2 - j's bound
                 asm volatile("" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7]),
                                   "+v"(s[0]), "+v"(s[1]), "+v"(s[2]), "+v"(s[3]), "+v"(s[4]), "+v"(s[5]), "+v"(s[6]));   // (all of them here: one wait)
+                if constexpr (TOPDRAWS) {
+                    // (the next step's raw words, into the rows just read: the stores go out beside the chain and are waited for in front of the barrier)
+                    if (spread) {
+                        put_block(0, sb);
+                        if (NC > 5) put_block(1, sb1);
+                    }
+                }
 #pragma unroll
                 for (int j = 0; j < 7; ++j) s[j] += r[j + 1] & 0xFFFFu;
                 uint32_t car = r[0], nc = car & 0xFFFFu;
@@ -908,6 +983,7 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
             }
         }
         wu_take_all<WV>(st, xaddr + ((mine >> 16) & 0xFFu) * xstride);               // this rung's new state: the words of the rung it comes from
+        if constexpr (TOPDRAWS && !TOP && kWuSpreadAt == 0) { if (spread) own_bound(); }   // (the next step's bound of this wave's pair: the first step's, in front of the loop)
         n4 = (mine & 0xFFFFu) << 2; cls = (mine >> 24) & 0x3Fu; flag = mine >> 31;
         if constexpr (STATS) nsum += mine & 0xFFFFu;
         if (top) flag = 1;                                                           // chains[-1].flag = 1, mcmc.py:100

@@ -124,6 +124,12 @@ void qt_wave_cascade_walk(const KernelShape *shapes, int n, int32_t *walk)
 {
     for (int i = 0; i < n; ++i) walk[i] = wave_cascade_walk(shapes[i]) ? 1 : 0;
 }
+// wave_cascade_mode() of n shapes: what the launch puts into LadderArgs::wu_once -- 0 the replay, 1 the walk on bounds the top rung's wave found, 2 the walk
+// on bounds the waves below the top found, a pair each
+void qt_wave_cascade_mode(const KernelShape *shapes, int n, int32_t *mode)
+{
+    for (int i = 0; i < n; ++i) mode[i] = wave_cascade_mode(shapes[i]);
+}
 int qt_kernel_shape_ints(void) { return (int)(sizeof(KernelShape) / sizeof(int)); }
 // validate_params(), then the first phase of plan_host(): the QECMC_ERR_* code and message; accepted: the shape's static fields (the others 0)
 int qt_plan_dims(const qecmc_params *p, int32_t *shape_ints, char *msg, int msg_cap)

@@ -11,7 +11,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libqecmc.so")
-FLAG_NO_PRE, FLAG_NO_DELUT, FLAG_NO_SSW = 2, 4, 8          # qecmc_flag (include/qecmc.h): developer switches between equivalent kernel variants
+FLAG_NO_PRE, FLAG_NO_DELUT, FLAG_NO_SSW, FLAG_NO_SPREAD = 2, 4, 8, 16          # qecmc_flag (include/qecmc.h): developer switches between equivalent kernel variants
 
 
 def dev_flags(switches=0, queue_grid=0):
