@@ -11,8 +11,6 @@ Everything but the low-p limit is integer and compared exactly.  The low-p bound
 differ from the nearest integer pair by 2.0e-7 at most over these inputs, the next-order term being A(d + 1) / A(d) * f with f = 3.3e-10; the bound
 carries a x50 margin over that."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -20,10 +18,11 @@ import pytest
 import test_class_sweep_cpu as S
 import test_class_sweep_cut_cpu as SC
 import test_enumerate_cpu as E
+from hostlib import run_selftest
 from qecmc import _lib as L_
 from qecmc import exact as ex
 from test_corrections_cpu import classes, generators
-from test_syndrome_lift_cpu import CSRC, PLANAR, ROTATED, TORIC, XZZX, random_errors, state_shape
+from test_syndrome_lift_cpu import PLANAR, ROTATED, TORIC, XZZX, random_errors, state_shape
 from util_minplus import brute_force_minplus, eliminate_minplus
 
 NAME = S.NAME
@@ -399,7 +398,4 @@ def test_harness_refusals():
 def test_minplus_under_sanitizers():
     """a stand-alone program (its own main) built from class_minplus.hpp with -fsanitize=address,undefined: every plan, accepted or refused, against the
     cut plan; the twin over poisoned scratch, threaded and not, held and not, against a brute force; saturation; run as a child process"""
-    subprocess.check_call(["make", "-C", CSRC, "-s", "minplus_asan"])
-    run = subprocess.run([os.path.join(CSRC, "build", "class_minplus_selftest_asan")], capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "selftest OK" in run.stdout
+    run_selftest("minplus_asan", "class_minplus_selftest_asan")

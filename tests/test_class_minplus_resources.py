@@ -2,23 +2,15 @@
 sweep kernel's LDS is the dynamic window sweep::lds_carve() promises the launch, one uint64_t where the sibling keeps a double, up to 128 KiB at
 width 14; the reduce kernel has none -- and their names outside the sealed registry of ladder / wave / colour kernels.  Read the way
 tests/test_class_sweep_cut_resources.py reads its siblings.  The VGPR counts are recorded in DESIGN.md 4.1o, not bounded here."""
-import importlib.util
-import os
-import re
-
 import kernel_cases
 import test_class_sweep_cut_cpu as SC
-import test_class_sweep_resources as R
+from hostlib import SEALED_HEADS, resource_rows, static_lds
 
 KERNELS = ["k_class_minplus", "k_class_minplus_reduce"]
 
 
 def _rows():
-    R._rows()                                                          # make: a no-op when the library is built
-    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(R.ROOT, "tools", "kernel_resources.py"))
-    kr = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kr)
-    return kr.all_rows(["class_minplus"])
+    return resource_rows(["class_minplus"])
 
 
 def test_two_kernels_without_scratch():
@@ -30,9 +22,7 @@ def test_two_kernels_without_scratch():
 
 
 def test_no_static_lds_and_the_dynamic_window_the_host_function_sizes():
-    _rows()
-    text = open(os.path.join(R.CSRC, "build", "class_minplus.res"), errors="replace").read()
-    static = [int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", text)]
+    static = static_lds("class_minplus")
     assert static == [0, 0], static
     T = SC.load_twin()
     for code, L, w in SC.ACCEPTED:                                     # the plans are the cut sweep's: a uint64_t entry is as wide as its double
@@ -42,5 +32,5 @@ def test_no_static_lds_and_the_dynamic_window_the_host_function_sizes():
 
 def test_the_minplus_kernels_stay_out_of_the_sealed_registry():
     for r in _rows():
-        assert not r["label"].startswith(R.SEALED_HEADS)
+        assert not r["label"].startswith(SEALED_HEADS)
         assert r["label"] not in kernel_cases.built_labels()

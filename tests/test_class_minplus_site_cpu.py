@@ -8,8 +8,6 @@ its argmin where unique; constant rows are the uniform twins, chains included; o
 planar code's unused cells are not read; pure erasure ties the twin to the site sweep's twin exactly; llr_site_costs, and the brute-force max-product
 chain; refusals by code and prefix; the Python layer; the harness; the sanitizers.  Every comparison is integer or bytes and exact."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -20,11 +18,12 @@ import test_class_sweep_cpu as S
 import test_class_sweep_cut_cpu as SC
 import test_class_sweep_site_cpu as SS
 import test_enumerate_cpu as E
+from hostlib import run_selftest
 from qecmc import _lib as L_
 from qecmc import exact as ex
 from qecmc import harness
 from test_corrections_cpu import classes, generators, syndromes
-from test_syndrome_lift_cpu import CSRC, PLANAR, ROTATED, TORIC, XZZX, random_errors, state_shape
+from test_syndrome_lift_cpu import PLANAR, ROTATED, TORIC, XZZX, random_errors, state_shape
 from util_minplus_site import brute_force_max_product, brute_force_minplus, eliminate_minplus, site_cost
 from util_minplus_trace import coset
 
@@ -489,7 +488,4 @@ def test_harness_refuses_site_costs_under_another_method_and_biased_erasures():
 def test_minplus_site_under_sanitizers():
     """a stand-alone program (its own main) built from class_minplus_site.hpp with -fsanitize=address,undefined: the site plans against the uniform
     plans, the twins over cost tables, scratch, decision words and outputs allocated at their exact size; run as a child process"""
-    subprocess.check_call(["make", "-C", CSRC, "-s", "minplus_site_asan"])
-    run = subprocess.run([os.path.join(CSRC, "build", "class_minplus_site_selftest_asan")], capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "selftest OK" in run.stdout
+    run_selftest("minplus_site_asan", "class_minplus_site_selftest_asan")

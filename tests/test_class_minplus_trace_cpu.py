@@ -8,8 +8,6 @@ On rows with count == 1 the chain is the argmin of a brute force over the group 
 The tie rule: all-zero costs return the class representative itself.  Held generators change costs and classes of no chain.  Refusals by name; the
 Python layer; the sanitizers.  Every comparison is integer and exact."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,10 +15,11 @@ import pytest
 import test_class_minplus_cpu as M
 import test_class_sweep_cut_cpu as SC
 import test_enumerate_cpu as E
+from hostlib import run_selftest
 from qecmc import _lib as L_
 from qecmc import exact as ex
 from test_corrections_cpu import classes, generators, syndromes
-from test_syndrome_lift_cpu import CSRC, PLANAR, ROTATED, TORIC, XZZX, random_errors, state_shape
+from test_syndrome_lift_cpu import PLANAR, ROTATED, TORIC, XZZX, random_errors, state_shape
 from util_minplus_trace import brute_force_argmin, chain_cost, coset, qubit_cells
 
 NAME = M.NAME
@@ -359,7 +358,4 @@ def test_python_layer_shapes_unique_and_min_weight_corrections(T, monkeypatch):
 def test_minplus_trace_under_sanitizers():
     """a stand-alone program (its own main) built from class_minplus_trace.hpp with -fsanitize=address,undefined: the trace plans against the cut plans,
     the twin over poisoned scratch, decision words and outputs allocated at their exact size; run as a child process"""
-    subprocess.check_call(["make", "-C", CSRC, "-s", "minplus_trace_asan"])
-    run = subprocess.run([os.path.join(CSRC, "build", "class_minplus_trace_selftest_asan")], capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "selftest OK" in run.stdout
+    run_selftest("minplus_trace_asan", "class_minplus_trace_selftest_asan")

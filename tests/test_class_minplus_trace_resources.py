@@ -2,27 +2,15 @@
 static LDS (the trace kernel's LDS is the dynamic window sweep::lds_carve() promises the launch, as k_class_minplus's; pick and walk reduce and
 unpack through shuffles and have none), their names outside the sealed registry of ladder / wave / colour kernels; and class_minplus.res still holds
 its two kernels: the split of launch_class_minplus added host functions only.  Read the way tests/test_class_minplus_resources.py reads its unit."""
-import importlib.util
-import os
-import re
-
 import kernel_cases
-import test_class_minplus_resources as MR
-import test_class_sweep_resources as R
+from hostlib import SEALED_HEADS, resource_rows, static_lds
+from test_class_minplus_resources import KERNELS as MINPLUS_KERNELS
 
 KERNELS = ["k_minplus_pick", "k_minplus_trace", "k_minplus_walk"]
 
 
-def _rows(unit):
-    R._rows()                                                          # make: a no-op when the library is built
-    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(R.ROOT, "tools", "kernel_resources.py"))
-    kr = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kr)
-    return kr.all_rows([unit])
-
-
 def test_three_kernels_without_scratch():
-    rows = _rows("class_minplus_trace")
+    rows = resource_rows(["class_minplus_trace"])
     assert sorted(r["label"] for r in rows) == KERNELS, rows
     for r in rows:
         print(r["label"], "VGPRs", r["VGPRs"], "occupancy", r["Occupancy"])
@@ -30,19 +18,17 @@ def test_three_kernels_without_scratch():
 
 
 def test_no_static_lds():
-    _rows("class_minplus_trace")
-    text = open(os.path.join(R.CSRC, "build", "class_minplus_trace.res"), errors="replace").read()
-    static = [int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", text)]
+    static = static_lds("class_minplus_trace")
     assert static == [0, 0, 0], static
 
 
 def test_the_trace_kernels_stay_out_of_the_sealed_registry():
-    for r in _rows("class_minplus_trace"):
-        assert not r["label"].startswith(R.SEALED_HEADS)
+    for r in resource_rows(["class_minplus_trace"]):
+        assert not r["label"].startswith(SEALED_HEADS)
         assert r["label"] not in kernel_cases.built_labels()
 
 
 def test_class_minplus_keeps_its_two_kernels():
-    rows = _rows("class_minplus")
-    assert sorted(r["label"] for r in rows) == MR.KERNELS == ["k_class_minplus", "k_class_minplus_reduce"], rows
+    rows = resource_rows(["class_minplus"])
+    assert sorted(r["label"] for r in rows) == MINPLUS_KERNELS == ["k_class_minplus", "k_class_minplus_reduce"], rows
     assert all(r["ScratchSize"] == 0 for r in rows)

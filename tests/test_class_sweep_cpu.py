@@ -10,20 +10,19 @@ qubit order, at xzzx L = 7, rotated L = 9 and planar L = 5; Z as a function of t
 Tolerance 1e-12 relative per class weight: all terms are positive, either side errs by about (nq + G) 2^-53 < 2e-14 at L = 9, and 1e-12 is what the
 enumerator's tests use."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import test_enumerate_cpu as E
+from hostlib import run_selftest
 from oracle import oracle as orc
 from qecmc import _lib as L_
 from qecmc import exact as ex
 from test_corrections_cpu import class_moves, classes, generators
 from test_corrections_cpu import load_twin as load_corrections_twin
 from test_exact_cpu import ORC_API, _rand_surf
-from test_syndrome_lift_cpu import CSRC, ORC_CODE, PLANAR, ROTATED, TORIC, XZZX, random_errors, state_shape
+from test_syndrome_lift_cpu import ORC_CODE, PLANAR, ROTATED, TORIC, XZZX, random_errors, state_shape
 from util_exact import SurfEnumeration
 
 REQUIRED = [(XZZX, 3), (XZZX, 5), (XZZX, 7), (XZZX, 9), (ROTATED, 3), (ROTATED, 5), (ROTATED, 7), (ROTATED, 9), (PLANAR, 3), (PLANAR, 4), (PLANAR, 5),
@@ -363,7 +362,4 @@ def test_a_row_whose_weights_all_underflow_raises():
 def test_sweep_under_sanitizers():
     """a stand-alone program (its own main) built from class_sweep.hpp with -fsanitize=address,undefined: the plan of every (code, L), accepted or
     refused, and the twin on random chains of every plan up to width 10; run as a child process"""
-    subprocess.check_call(["make", "-C", CSRC, "-s", "sweep_asan"])
-    run = subprocess.run([os.path.join(CSRC, "build", "class_sweep_selftest_asan")], capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "selftest OK" in run.stdout
+    run_selftest("sweep_asan", "class_sweep_selftest_asan")

@@ -11,18 +11,17 @@ Tolerance against the uncut twin 1e-12 relative per class weight: all terms are 
 1e-12 is what the uncut sweep's tests use.  Against the sector product 1e-10 relative: the sector sums are sums of 2^24 positive terms in NumPy's
 pairwise order (error below 24 * 2^-53 relative each), far inside."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import test_class_sweep_cpu as S
+from hostlib import run_selftest
 from qecmc import _lib as L_
 from qecmc import exact as ex
 from test_corrections_cpu import classes, generators
 from test_enumerate_cpu import class_chains
-from test_syndrome_lift_cpu import CSRC, PLANAR, ROTATED, TORIC, XZZX, random_errors, state_shape
+from test_syndrome_lift_cpu import PLANAR, ROTATED, TORIC, XZZX, random_errors, state_shape
 
 NAME = S.NAME
 INTRO, CLOSE, FORGET = 0, 1, 2
@@ -368,7 +367,4 @@ def test_auto_is_the_cut_sweep_where_enumerator_and_sweep_both_refuse(T):
 def test_cut_sweep_under_sanitizers():
     """a stand-alone program (its own main) built from class_sweep_cut.hpp with -fsanitize=address,undefined: cut plans of every (code, L) up to 13,
     accepted or refused, under several widths, and the twin -- threaded and not -- against the uncut twin; run as a child process"""
-    subprocess.check_call(["make", "-C", CSRC, "-s", "sweep_cut_asan"])
-    run = subprocess.run([os.path.join(CSRC, "build", "class_sweep_cut_selftest_asan")], capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "selftest OK" in run.stdout
+    run_selftest("sweep_cut_asan", "class_sweep_cut_selftest_asan")

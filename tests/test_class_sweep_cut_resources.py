@@ -4,23 +4,15 @@ outside the sealed registry of ladder / wave / colour kernels.
 
 VGPR budget: the build gives 11 (sweep) and 12 (reduce); the plan, the representative, the held words and the weights are scalar, a lane holds an
 index and an entry.  32 keeps the full 8 waves per SIMD with room to spare and still catches a lane that starts to carry the plan."""
-import re
-
 import kernel_cases
 import test_class_sweep_cut_cpu as SC
-import test_class_sweep_resources as R
+from hostlib import SEALED_HEADS, resource_rows, static_lds
 
 KERNELS = ["k_class_sweep_cut", "k_class_sweep_reduce"]
 
 
 def _rows():
-    R._rows()                                                          # make: a no-op when the library is built
-    import importlib.util
-    import os
-    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(R.ROOT, "tools", "kernel_resources.py"))
-    kr = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kr)
-    return kr.all_rows(["class_sweep_cut"])
+    return resource_rows(["class_sweep_cut"])
 
 
 def test_two_kernels_without_scratch():
@@ -31,10 +23,7 @@ def test_two_kernels_without_scratch():
 
 
 def test_no_static_lds_and_the_dynamic_window_the_host_function_sizes():
-    _rows()
-    import os
-    text = open(os.path.join(R.CSRC, "build", "class_sweep_cut.res"), errors="replace").read()
-    static = [int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", text)]
+    static = static_lds("class_sweep_cut")
     assert static == [0, 0], static
     T = SC.load_twin()
     for code, L, w in SC.ACCEPTED:
@@ -45,5 +34,5 @@ def test_no_static_lds_and_the_dynamic_window_the_host_function_sizes():
 
 def test_the_cut_kernels_stay_out_of_the_sealed_registry():
     for r in _rows():
-        assert not r["label"].startswith(R.SEALED_HEADS)
+        assert not r["label"].startswith(SEALED_HEADS)
         assert r["label"] not in kernel_cases.built_labels()

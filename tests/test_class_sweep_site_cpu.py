@@ -9,8 +9,6 @@ that hold no qubit; every refusal by name; the shapes and the routing of the Pyt
 Tolerances: 1e-13 relative for the elimination against the brute force and 1e-12 relative per class weight for a twin against the elimination, as
 tests/test_class_sweep_cpu.py -- all terms are non-negative and either side errs by about (nq + G) 2^-53."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -20,11 +18,12 @@ import test_class_sweep_cut_cpu as SC
 import test_class_sweep_tiled_cpu as ST
 import test_enumerate_cpu as E
 import test_syndrome_lift_cpu as lift_cpu
+from hostlib import run_selftest
 from qecmc import _lib as L_
 from qecmc import exact as ex
 from qecmc import harness
 from test_corrections_cpu import classes, generators
-from test_syndrome_lift_cpu import CSRC, PLANAR, ROTATED, TORIC, XZZX, random_errors, state_shape
+from test_syndrome_lift_cpu import PLANAR, ROTATED, TORIC, XZZX, random_errors, state_shape
 from util_sectors import order_for
 from util_site import eliminate_site, random_site_weights
 
@@ -404,7 +403,4 @@ def test_constant_rows_give_the_law_of_the_uniform_entry_points():
 def test_site_sweeps_under_sanitizers():
     """a stand-alone program (its own main) built from class_sweep_site.hpp with -fsanitize=address,undefined: the three twins on weight tables
     allocated at exactly rows * nq * 4 doubles, wq_rows 1 and N, zero weights and the refusals; run as a child process"""
-    subprocess.check_call(["make", "-C", CSRC, "-s", "sweep_site_asan"])
-    run = subprocess.run([os.path.join(CSRC, "build", "class_sweep_site_selftest_asan")], capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "selftest OK" in run.stdout
+    run_selftest("sweep_site_asan", "class_sweep_site_selftest_asan")

@@ -5,22 +5,14 @@ reduce kernel the cut and the tiled route share is class_sweep_cut's (tests/test
 VGPR budget: the build gives 11 or 12; the plan, the representative, the held words AND the four weights of a CLOSE are scalar -- the table's row is
 wave-uniform --, a lane holds an index and an entry.  32 keeps the full 8 waves per SIMD under 1 024 threads and catches a lane that starts to carry
 the table."""
-import importlib.util
-import os
-import re
-
 import kernel_cases
-import test_class_sweep_resources as R
+from hostlib import SEALED_HEADS, resource_rows, static_lds
 
 KERNELS = ["k_class_sweep_cut_site", "k_class_sweep_site", "k_class_sweep_tiled_site"]
 
 
 def _rows():
-    R._rows()                                                          # make: a no-op when the library is built
-    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(R.ROOT, "tools", "kernel_resources.py"))
-    kr = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kr)
-    return kr.all_rows(["class_sweep_site"])
+    return resource_rows(["class_sweep_site"])
 
 
 def test_three_kernels_without_scratch_at_full_occupancy():
@@ -31,13 +23,11 @@ def test_three_kernels_without_scratch_at_full_occupancy():
 
 
 def test_no_static_lds():
-    _rows()
-    text = open(os.path.join(R.CSRC, "build", "class_sweep_site.res"), errors="replace").read()
-    static = [int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", text)]
+    static = static_lds("class_sweep_site")
     assert static == [0, 0, 0], static                                 # all of it is asked for at the launch, as the siblings ask
 
 
 def test_the_site_kernels_stay_out_of_the_sealed_registry():
     for r in _rows():
-        assert not r["label"].startswith(R.SEALED_HEADS)
+        assert not r["label"].startswith(SEALED_HEADS)
         assert r["label"] not in kernel_cases.built_labels()

@@ -12,19 +12,18 @@ entry points' among them; resolve_method as it was.
 Tolerance 1e-12 relative per class weight, as tests/test_class_sweep_cut_cpu.py: all terms are positive and either side errs by about
 (nq + G) 2^-53 -- 7e-14 at rotated L = 13."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import test_class_sweep_cpu as S
 import test_class_sweep_cut_cpu as SC
+from hostlib import run_selftest
 from qecmc import _lib as L_
 from qecmc import exact as ex
 from test_corrections_cpu import classes, generators
 from test_enumerate_cpu import class_chains
-from test_syndrome_lift_cpu import CSRC, PLANAR, ROTATED, TORIC, XZZX, random_errors, state_shape
+from test_syndrome_lift_cpu import PLANAR, ROTATED, TORIC, XZZX, random_errors, state_shape
 
 NAME = S.NAME
 INTRO, CLOSE, FORGET = 0, 1, 2
@@ -396,7 +395,4 @@ def test_tiled_sweep_under_sanitizers():
     """a stand-alone program (its own main) built from class_sweep_tiled.hpp with -fsanitize=address,undefined: tiled plans of every (code, L) up to 13
     and a few beyond, accepted or refused, under several widths; the twin against the cut twin; and the segment table walked tile by tile, as the
     kernel walks it, over NaN-filled memory against the twin bit for bit; run as a child process"""
-    subprocess.check_call(["make", "-C", CSRC, "-s", "sweep_tiled_asan"])
-    run = subprocess.run([os.path.join(CSRC, "build", "class_sweep_tiled_selftest_asan")], capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "selftest OK" in run.stdout
+    run_selftest("sweep_tiled_asan", "class_sweep_tiled_selftest_asan")

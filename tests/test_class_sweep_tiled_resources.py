@@ -5,23 +5,15 @@ kernels.  The reduce kernel it shares is class_sweep_cut's (tests/test_class_swe
 VGPR budget: the build gives 12; the segment, the ops, the representative, the held words and the weights are scalar, a lane holds a local index,
 its offset in the state vector and an entry.  32 keeps the full 8 waves per SIMD -- 1 024 threads need no more than 64 -- and still catches a lane
 that starts to carry the plan."""
-import re
-
 import kernel_cases
-import test_class_sweep_resources as R
 import test_class_sweep_tiled_cpu as ST
+from hostlib import SEALED_HEADS, resource_rows, static_lds
 
 KERNELS = ["k_class_sweep_tiled"]
 
 
 def _rows():
-    R._rows()                                                          # make: a no-op when the library is built
-    import importlib.util
-    import os
-    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(R.ROOT, "tools", "kernel_resources.py"))
-    kr = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kr)
-    return kr.all_rows(["class_sweep_tiled"])
+    return resource_rows(["class_sweep_tiled"])
 
 
 def test_one_kernel_without_scratch_that_allows_1024_threads():
@@ -32,10 +24,7 @@ def test_one_kernel_without_scratch_that_allows_1024_threads():
 
 
 def test_no_static_lds_and_the_dynamic_window_of_one_tile():
-    _rows()
-    import os
-    text = open(os.path.join(R.CSRC, "build", "class_sweep_tiled.res"), errors="replace").read()
-    static = [int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", text)]
+    static = static_lds("class_sweep_tiled")
     assert static == [0], static
     T = ST.load_twin()
     for code, L, hw, tw in ST.ACCEPTED:
@@ -46,5 +35,5 @@ def test_no_static_lds_and_the_dynamic_window_of_one_tile():
 
 def test_the_tiled_kernel_stays_out_of_the_sealed_registry():
     for r in _rows():
-        assert not r["label"].startswith(R.SEALED_HEADS)
+        assert not r["label"].startswith(SEALED_HEADS)
         assert r["label"] not in kernel_cases.built_labels()

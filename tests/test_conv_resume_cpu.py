@@ -4,16 +4,13 @@ kernel choice of a continued launch, and harness.LadderRun's log-growth arithmet
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mcmc-qec-toric-rl_amd", "csrc")
-
-from qecmc import _lib as L_                      # noqa: E402
-from qecmc import harness                         # noqa: E402
+from hostlib import ROOT, tables_lib
+from qecmc import _lib as L_
+from qecmc import harness
 
 INVALID, NO_DEVICE, UNSUPPORTED = -1, -2, -4
 NEW = ("qecmc_pteq_resume_conv_dev", "qecmc_plan_resume_conv_bytes")
@@ -21,16 +18,10 @@ NEW = ("qecmc_pteq_resume_conv_dev", "qecmc_plan_resume_conv_bytes")
 
 @pytest.fixture(scope="module")
 def T():
-    path = os.environ.get("QECMC_TABLES_LIB")
-    if not path:
-        subprocess.check_call(["make", "-C", CSRC, "-s", "tables"])
-        path = os.path.join(CSRC, "build", "libqecmc_tables.so")
-    lib = C.CDLL(path)
+    lib = tables_lib()
     lib.qt_resume_conv_bytes.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.qt_resume_conv_bytes.restype = None
     lib.qt_resume_conv_check.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
-    lib.qt_choose_kernels.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    lib.qt_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
     return lib
 
 

@@ -6,16 +6,15 @@ What is pinned: need[a][b] takes any chain of class a to class b; a correction h
 says, and -- after the descent -- is a local minimum of the weight; source and moved follow the pick rule; placing a logical operator never costs
 more than position 0; and the identity the harness flag success_correction rests on: error ^ correction is a stabilizer iff target == class(error)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import test_syndrome_lift_cpu as lift_cpu
+from hostlib import run_selftest
 from oracle import oracle as orc
 from qecmc import _lib as L_
-from test_syndrome_lift_cpu import CSRC, ORC_CODE, PLANAR, ROTATED, TORIC, XZZX, oracle_syndrome, state_shape
+from test_syndrome_lift_cpu import ORC_CODE, PLANAR, ROTATED, TORIC, XZZX, oracle_syndrome, state_shape
 
 SHAPES = [(c, L) for c in (TORIC, XZZX, ROTATED, PLANAR) for L in (3, 5, 7)]
 SETTINGS = [(0, 0), (0, 1), (1, 0), (1, 1)]                              # (place, descend)
@@ -298,7 +297,4 @@ def test_host_checks_need_no_device():
 def test_corrections_under_sanitizers():
     """a stand-alone program (its own main) built from corrections.hpp with -fsanitize=address,undefined: builds the tables of the four codes, checks
     which (code, L) have no class move, runs the body on random candidates and on out-of-range targets; run as a child process"""
-    subprocess.check_call(["make", "-C", CSRC, "-s", "corrections_asan"])
-    run = subprocess.run([os.path.join(CSRC, "build", "corrections_selftest_asan")], capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "selftest OK" in run.stdout
+    run_selftest("corrections_asan", "corrections_selftest_asan")

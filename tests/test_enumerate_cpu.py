@@ -12,19 +12,18 @@ L x L plaquette code are no shapes of this library: they are refused (QECMC_ERR_
 (rank 16), planar L = 3 (rank 12) and xzzx / rotated L = 5 (rank 24).  No accepted (code, L) has more than 32 qubits and a rank within 36, so there
 is no 64-bit instantiation to test."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import test_syndrome_lift_cpu as lift_cpu
+from hostlib import run_selftest
 from oracle import oracle as orc
 from qecmc import _lib as L_
 from qecmc import exact as ex
 from test_corrections_cpu import classes, generators, oracle_class
 from test_exact_cpu import ORC_API, _enum, _rand_surf
-from test_syndrome_lift_cpu import CSRC, ORC_CODE, PLANAR, ROTATED, TORIC, XZZX, random_errors, state_shape
+from test_syndrome_lift_cpu import ORC_CODE, PLANAR, ROTATED, TORIC, XZZX, random_errors, state_shape
 from util_exact import (SurfEnumeration, alpha_counts_weight, biased_counts_weight, depolarizing_counts_weight, toric_class_probabilities)
 
 SUPPORTED = [(TORIC, 3), (PLANAR, 3), (PLANAR, 4), (XZZX, 3), (XZZX, 5), (ROTATED, 3), (ROTATED, 5)]
@@ -376,7 +375,4 @@ def test_the_planar_pin_syndrome_separates_its_two_largest_classes(T):
 def test_enumeration_under_sanitizers():
     """a stand-alone program (its own main) built from enumerate.hpp with -fsanitize=address,undefined: builds the table of every (code, L), accepted or
     refused, and runs the twin on random chains of every supported shape up to rank 16: class totals, partial sums, refusals; run as a child process"""
-    subprocess.check_call(["make", "-C", CSRC, "-s", "enumerate_asan"])
-    run = subprocess.run([os.path.join(CSRC, "build", "enumerate_selftest_asan")], capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "selftest OK" in run.stdout
+    run_selftest("enumerate_asan", "enumerate_selftest_asan")

@@ -1,25 +1,15 @@
 """The coset-enumeration kernels in the build's resource tables (csrc/build/enumerate.res): both instantiations are built (4 and 16 classes), neither
 uses scratch, their LDS is the dynamic window alone -- no static LDS on top of what enumr::lds_carve() promises the launch, which stays within
 64 KiB for every supported shape -- and their name stays outside the sealed registry of ladder / wave / colour kernels."""
-import importlib.util
-import os
 import re
-import subprocess
 
 import kernel_cases
 import test_enumerate_cpu as E
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mcmc-qec-toric-rl_amd", "csrc")
-SEALED_HEADS = ("ladder<", "wave<", "colour<", "wave-stats<", "colour-stats<", "wave-shortest<", "colour-shortest<")
+from hostlib import SEALED_HEADS, resource_rows, static_lds
 
 
 def _rows():
-    subprocess.check_call(["make", "-C", CSRC, "-s", "-j8"])          # a no-op when the library is built (build() ran)
-    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))
-    kr = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kr)
-    return kr.all_rows(["enumerate"])
+    return resource_rows(["enumerate"])
 
 
 def test_both_instantiations_are_built_without_scratch():
@@ -32,9 +22,7 @@ def test_both_instantiations_are_built_without_scratch():
 
 
 def test_lds_is_the_dynamic_window_the_host_function_sizes():
-    _rows()
-    text = open(os.path.join(CSRC, "build", "enumerate.res"), errors="replace").read()
-    static = [int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", text)]
+    static = static_lds("enumerate")
     assert static == [0, 0], static                                    # all of it is asked for at the launch: enumr::lds_carve()
     T = E.load_twin()
     for code, L in E.SUPPORTED:

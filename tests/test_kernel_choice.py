@@ -9,24 +9,17 @@ and one beyond what scan = wave is built for, and all 8 combinations of the deve
   (c) the kernels of BASELINE configurations 2-5 at the shapes `bench.py --config N` resolves to by default;
   (d) what plan_host() itself says of the sweep: which of its blocks get no plan and why, the ladders its plans present, the persistent grid."""
 import ctypes as C
-import importlib.util
 import itertools
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from hostlib import KERNEL_SHAPE_FIELDS as FIELDS
+from hostlib import ROTATED, TORIC, XZZX, resource_rows, tables_lib
 from qecmc import _lib as L_
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mcmc-qec-toric-rl_amd", "csrc")
-TORIC, XZZX, ROTATED, PLANAR = 0, 1, 2, 3
 CODES = ["toric", "xzzx", "rotated", "planar"]
-# KernelShape (kernel_choice.hpp), field by field
-FIELDS = ["code", "noise", "scan", "L", "Nc", "W", "nq", "ncls", "n_gen", "n_types", "gen_type", "top_acc", "lower_acc", "logical", "conv", "queue",
-          "uset", "xyz", "stats", "resume", "neff", "f32ok", "swap_fast_ok", "iters", "tune"]
 FLAGS = ["conv", "gsplit", "biased", "scan", "gentop", "uset", "alpha", "pre", "delut", "queue", "ssw"]   # LadderFlag bit order
 
 # the kernels of BASELINE configurations 2-5 (bench.py CONFIGS, --scan auto, iters 10, p_logical 0.5, fixed length), and -- bench.py --full
@@ -53,16 +46,7 @@ REFUSALS = {
 
 @pytest.fixture(scope="module")
 def T():
-    path = os.environ.get("QECMC_TABLES_LIB")
-    if not path:
-        subprocess.check_call(["make", "-C", CSRC, "-s", "tables"])
-        path = os.path.join(CSRC, "build", "libqecmc_tables.so")
-    lib = C.CDLL(path)
-    assert lib.qt_kernel_shape_ints() == len(FIELDS)
-    lib.qt_choose_kernels.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    lib.qt_plan_dims.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
-    lib.qt_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
-    return lib
+    return tables_lib()          # (qt_choose_kernels, qt_plan_dims and qt_plan get their signatures there)
 
 
 def label(key):
@@ -160,12 +144,8 @@ def all_shapes(T):
 
 def built_kernels():
     """label -> row of every ladder / wave / colour kernel in csrc/build/*.res"""
-    subprocess.check_call(["make", "-C", CSRC, "-s", "-j8"])          # a no-op when the library is built (build() ran)
-    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))
-    kr = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kr)
     out = {}
-    for r in kr.all_rows():
+    for r in resource_rows():
         m = re.search(r"ladder_colour_kernelILi(\d+)ELb([01])ELi(\d+)ELi(\d+)ELi(\d+)E", r["kernel"])
         if m:   # ladder_colour_kernel<CODE, CONV, RULE, MAXT, MINW>
             code, conv, rule, maxt, minw = (int(x) for x in m.groups())

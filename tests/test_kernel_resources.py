@@ -4,10 +4,8 @@ held BASELINE config 4 at 0.39 of its roofline in round 2 -- unless it is on the
 grow.  The list is a ratchet: the kernels the BASELINE configurations launch are not on it."""
 import importlib.util
 import os
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mcmc-qec-toric-rl_amd", "csrc")
+from hostlib import ROOT, resource_rows
 
 # bytes of scratch per lane allowed today.  What is left: the 64-VGPR instantiations that carry the convergence criterion's
 # window sums (conv), the general top-chain path (gentop on the toric code), the unique-chain estimators' set insertion (uset), the
@@ -126,11 +124,7 @@ BASELINE_KERNELS = sorted({label for _, label in _choice.BASELINE.values()})
 
 
 def _rows():
-    subprocess.check_call(["make", "-C", CSRC, "-s", "-j8"])          # a no-op when the library is built (build() ran)
-    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))
-    kr = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kr)
-    return kr.all_rows()
+    return resource_rows()
 
 
 def test_no_kernel_spills_outside_the_allow_list():

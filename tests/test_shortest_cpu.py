@@ -6,15 +6,13 @@ import ctypes as C
 import importlib.util
 import inspect
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import util_shortest_batch as U
+from hostlib import ROOT, resource_rows, tables_lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mcmc-qec-toric-rl_amd", "csrc")
 ERR_INVALID, ERR_UNSUPPORTED = -1, -4
 
 
@@ -27,16 +25,10 @@ def _load(name, path):
 
 @pytest.fixture(scope="module")
 def T():
-    path = os.environ.get("QECMC_TABLES_LIB")
-    if not path:
-        subprocess.check_call(["make", "-C", CSRC, "-s", "tables"])
-        path = os.path.join(CSRC, "build", "libqecmc_tables.so")
-    lib = C.CDLL(path)
+    lib = tables_lib()
     lib.qt_shortest_check.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     lib.qt_shortest_set_need.argtypes = [C.c_uint64, C.c_uint64]
     lib.qt_shortest_set_need.restype = C.c_uint64
-    lib.qt_choose_kernels.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    lib.qt_plan_dims.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
     return lib
 
 
@@ -183,9 +175,7 @@ def test_a_ladder_that_never_left_burn_in_divides_by_zero_like_the_reference():
 
 @pytest.fixture(scope="module")
 def built():
-    subprocess.check_call(["make", "-C", CSRC, "-s", "-j8"])          # a no-op when the library is built (build() ran)
-    kr = _load("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))
-    return {r["label"]: r for r in kr.all_rows() if r["label"].startswith(("wave-shortest<", "colour-shortest<"))}
+    return {r["label"]: r for r in resource_rows() if r["label"].startswith(("wave-shortest<", "colour-shortest<"))}
 
 
 WANT = {"wave-shortest<1024,4,%s: %d words%s>" % (c, w, it) for c in ("xzzx", "rotated") for w in (4, 8) for it in ("", ", iters 10")} | \

@@ -7,13 +7,11 @@ import ctypes as C
 import importlib.util
 import itertools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mcmc-qec-toric-rl_amd", "csrc")
+from hostlib import ROOT, resource_rows, tables_lib
 
 
 def _load(name, path):
@@ -36,14 +34,7 @@ ONE_RUNG = "swap statistics need Nc >= 2"
 
 @pytest.fixture(scope="module")
 def T():
-    path = os.environ.get("QECMC_TABLES_LIB")
-    if not path:
-        subprocess.check_call(["make", "-C", CSRC, "-s", "tables"])
-        path = os.path.join(CSRC, "build", "libqecmc_tables.so")
-    lib = C.CDLL(path)
-    assert lib.qt_kernel_shape_ints() == len(FIELDS)
-    lib.qt_choose_kernels.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    lib.qt_plan_dims.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
+    lib = tables_lib()
     lib.qt_wave_cascade_once.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     return lib
 
@@ -130,9 +121,7 @@ def test_stats_shapes_get_a_statistics_key_or_a_named_refusal(sweep):
 @pytest.fixture(scope="module")
 def built():
     """label -> row of every statistics kernel in csrc/build/*.res"""
-    subprocess.check_call(["make", "-C", CSRC, "-s", "-j8"])          # a no-op when the library is built (build() ran)
-    kr = _load("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))
-    rows = kr.all_rows()
+    rows = resource_rows()
     assert len(rows) > 100
     return {r["label"]: r for r in rows if r["label"].startswith(("wave-stats<", "colour-stats<"))}, rows
 

@@ -6,19 +6,15 @@ defects it came from, with and without the greedy descent; the descent ends in a
 because the lifted chain has the error's syndrome -- the exact class law computed from it is the law computed from the error itself.  No
 class-law test of a finite run from a lifted start: the lift lands in an arbitrary class and only the burn-in depends on it."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from hostlib import PLANAR, ROTATED, TORIC, XZZX, run_selftest, tables_lib
 from oracle import oracle as orc
 from qecmc import _lib as L_
 from util_exact import toric_class_probabilities
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mcmc-qec-toric-rl_amd", "csrc")
-TORIC, XZZX, ROTATED, PLANAR = 0, 1, 2, 3
 ORC_CODE = {TORIC: orc.TORIC, XZZX: orc.XZZX, ROTATED: orc.ROTATED, PLANAR: orc.PLANAR}
 SHAPES = [(c, L) for c in (TORIC, XZZX, ROTATED, PLANAR) for L in (3, 5, 7)] + [(TORIC, 4), (TORIC, 15), (ROTATED, 21)]
 _u8p, _u32p, _i32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
@@ -26,11 +22,7 @@ _u8p, _u32p, _i32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_
 
 def load_twin():
     """the host-table test library with the lift's two entry points (tests/test_gpu_syndrome_lift.py compares the GPU with it)"""
-    path = os.environ.get("QECMC_TABLES_LIB")
-    if not path:
-        subprocess.check_call(["make", "-C", CSRC, "-s", "tables"])
-        path = os.path.join(CSRC, "build", "libqecmc_tables.so")
-    lib = C.CDLL(path)
+    lib = tables_lib()
     lib.qt_lift_table.restype = C.c_int
     lib.qt_lift_table.argtypes = [C.c_int, C.c_int, _u32p, C.c_int]
     lib.qt_chains_from_syndromes.restype = C.c_int
@@ -208,7 +200,4 @@ def test_host_checks_need_no_device():
 def test_lift_under_sanitizers():
     """a stand-alone program (its own main) built from syndrome_lift.hpp with -fsanitize=address,undefined: builds the tables, lifts random
     syndromes and refusals with and without the descent, checks every chain; run as a child process"""
-    subprocess.check_call(["make", "-C", CSRC, "-s", "lift_asan"])
-    run = subprocess.run([os.path.join(CSRC, "build", "syndrome_lift_selftest_asan")], capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "selftest OK" in run.stdout
+    run_selftest("lift_asan", "syndrome_lift_selftest_asan")

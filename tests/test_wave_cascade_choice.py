@@ -5,55 +5,25 @@ decides (once per workgroup is 2.6 - 5.2 % faster at 5, 6 and 7 
 and 8 rungs -- config 2's ladder, 57.2 against 56.6 ms --, so config 2 keeps the replay).  QECMC_FLAG_NO_SSW (flags bit 8) asks for the replay everywhere.
 Host code only: asked through the g++-built test API (csrc/tables_test_api.cpp), no GPU."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from qecmc import _lib as L_
+from hostlib import PLANAR, ROTATED, TORIC, XZZX, ask, tables_lib
+from hostlib import launch_shape as shape
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mcmc-qec-toric-rl_amd", "csrc")
-TORIC, XZZX, ROTATED, PLANAR = 0, 1, 2, 3
-# KernelShape (kernel_choice.hpp), field by field
-FIELDS = ["code", "noise", "scan", "L", "Nc", "W", "nq", "ncls", "n_gen", "n_types", "gen_type", "top_acc", "lower_acc", "logical", "conv", "queue",
-          "uset", "xyz", "stats", "resume", "neff", "f32ok", "swap_fast_ok", "iters", "tune"]
 NO_SSW = 8
 
 
 @pytest.fixture(scope="module")
 def T():
-    path = os.environ.get("QECMC_TABLES_LIB")
-    if not path:
-        subprocess.check_call(["make", "-C", CSRC, "-s", "tables"])
-        path = os.path.join(CSRC, "build", "libqecmc_tables.so")
-    lib = C.CDLL(path)
-    assert lib.qt_kernel_shape_ints() == len(FIELDS)
-    lib.qt_plan_dims.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
+    lib = tables_lib()
     lib.qt_wave_cascade_once.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    lib.qt_choose_kernels.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     return lib
 
 
-def shape(T, code, L, Nc, noise=0, scan=3, **kw):
-    """the shape of a fixed-length launch of the plan of (code, L, rule, scan) with Nc rungs: the static fields from plan_dims(), the ladder's as
-    tests/test_kernel_choice.py bench_shape() sets them (depolarizing rule: a top rung at p = 0.75 over distinct temperatures)"""
-    dims, msg = np.zeros(len(FIELDS), dtype=np.int32), C.create_string_buffer(600)
-    pr = L_.make_params(p=0.1, eta=3.0, alpha=1.5, iters=10, steps=10, code=code, L=L, Nc=2, noise=noise, scan=scan)
-    assert T.qt_plan_dims(C.byref(pr), dims.ctypes.data, msg, len(msg)) == 0, msg.value
-    s = dict(zip(FIELDS, (int(x) for x in dims)))
-    s.update(Nc=Nc, top_acc=int(noise == 0), lower_acc=0, logical=1, conv=0, queue=0, uset=0, xyz=0, stats=0, resume=0, neff=0, f32ok=int(noise == 2),
-             swap_fast_ok=1, iters=10, tune=0)
-    s.update(kw)
-    return [s[f] for f in FIELDS]
-
-
 def once(T, shapes):
-    shapes = np.ascontiguousarray(shapes, dtype=np.int32)
-    out = np.zeros(len(shapes), dtype=np.int32)
-    T.qt_wave_cascade_once(shapes.ctypes.data, len(shapes), out.ctypes.data)
-    return [int(x) for x in out]
+    return ask(T.qt_wave_cascade_once, shapes)
 
 
 def family(T, s):

@@ -7,20 +7,14 @@ most 8 rungs) at the ladder lengths where the same-box A/B had the spread form a
 (csrc/tables_test_api.cpp), no GPU."""
 import ctypes as C
 import itertools
-import os
-import subprocess
 
-import numpy as np
 import pytest
 
-from qecmc import _lib as L_
+from hostlib import KERNEL_SHAPE_FIELDS as FIELDS
+from hostlib import PLANAR, ROTATED, TORIC, XZZX, tables_lib
+from hostlib import ask as _ask
+from hostlib import launch_shape as shape
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mcmc-qec-toric-rl_amd", "csrc")
-TORIC, XZZX, ROTATED, PLANAR = 0, 1, 2, 3
-# KernelShape (kernel_choice.hpp), field by field
-FIELDS = ["code", "noise", "scan", "L", "Nc", "W", "nq", "ncls", "n_gen", "n_types", "gen_type", "top_acc", "lower_acc", "logical", "conv", "queue",
-          "uset", "xyz", "stats", "resume", "neff", "f32ok", "swap_fast_ok", "iters", "tune"]
 NO_SSW, NO_SPREAD = 8, 16
 SPREAD_RUNGS = (8,)      # the A/B's answer: the ladder lengths at which the spread form cleared the bar (profiles/r15_wave_spread_ab.json)
 # a lattice size per state width (4, 8, 12, 16 words per rung) of every code
@@ -29,40 +23,10 @@ WIDTHS = {TORIC: (3, 7, 9, 11), XZZX: (5, 9, 13, 15), ROTATED: (5, 9, 13, 15), P
 
 @pytest.fixture(scope="module")
 def T():
-    path = os.environ.get("QECMC_TABLES_LIB")
-    if not path:
-        subprocess.check_call(["make", "-C", CSRC, "-s", "tables"])
-        path = os.path.join(CSRC, "build", "libqecmc_tables.so")
-    lib = C.CDLL(path)
-    assert lib.qt_kernel_shape_ints() == len(FIELDS)
-    lib.qt_plan_dims.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
+    lib = tables_lib()
     lib.qt_wave_cascade_walk.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.qt_wave_cascade_mode.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     return lib
-
-
-_DIMS = {}
-
-
-def shape(T, code, L, Nc, noise=0, scan=3, **kw):
-    """the shape of a fixed-length launch of the plan of (code, L, rule, scan) with Nc rungs, as tests/test_wave_walk_choice.py builds it"""
-    if (code, L, noise, scan) not in _DIMS:
-        dims, msg = np.zeros(len(FIELDS), dtype=np.int32), C.create_string_buffer(600)
-        pr = L_.make_params(p=0.1, eta=3.0, alpha=1.5, iters=10, steps=10, code=code, L=L, Nc=2, noise=noise, scan=scan)
-        assert T.qt_plan_dims(C.byref(pr), dims.ctypes.data, msg, len(msg)) == 0, msg.value
-        _DIMS[(code, L, noise, scan)] = dict(zip(FIELDS, (int(x) for x in dims)))
-    s = dict(_DIMS[(code, L, noise, scan)])
-    s.update(Nc=Nc, top_acc=int(noise == 0), lower_acc=0, logical=1, conv=0, queue=0, uset=0, xyz=0, stats=0, resume=0, neff=0, f32ok=int(noise == 2),
-             swap_fast_ok=1, iters=10, tune=0)
-    s.update(kw)
-    return [s[f] for f in FIELDS]
-
-
-def _ask(fn, shapes):
-    shapes = np.ascontiguousarray(shapes, dtype=np.int32)
-    out = np.zeros(len(shapes), dtype=np.int32)
-    fn(shapes.ctypes.data, len(shapes), out.ctypes.data)
-    return [int(x) for x in out]
 
 
 def walk(T, shapes):

@@ -3,29 +3,21 @@ moves of a ladder step are one XOR mask of the state's words plus a class change
 function; here it runs through the plain tables library (g++ alone, no HIP, no GPU) on given pick words, and a window's rows must equal applying the same
 operators one after another to a byte state with the oracle's stabilizer and logical routines -- the configuration and the equivalence class."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from hostlib import PLANAR, ROTATED, TORIC, XZZX, tables_lib
 from oracle import oracle as orc
 from qecmc import _lib as L_
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mcmc-qec-toric-rl_amd", "csrc")
-TORIC, XZZX, ROTATED, PLANAR = 0, 1, 2, 3
 P_LOGICAL = [0.0, 0.25, 0.5, 1.0]
 CASES = [(TORIC, 3), (TORIC, 4), (TORIC, 9), (TORIC, 11), (XZZX, 9), (XZZX, 5), (ROTATED, 7), (PLANAR, 5)]
 
 
 @pytest.fixture(scope="module")
 def T():
-    path = os.environ.get("QECMC_TABLES_LIB")
-    if not path:
-        subprocess.check_call(["make", "-C", CSRC, "-s", "tables"])
-        path = os.path.join(CSRC, "build", "libqecmc_tables.so")
-    lib = C.CDLL(path)
+    lib = tables_lib()
     lib.qt_wave_position.restype = C.c_uint32; lib.qt_wave_position.argtypes = [C.c_int, C.c_int, C.c_uint32]
     lib.qt_wave_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     return lib

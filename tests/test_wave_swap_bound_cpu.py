@@ -5,16 +5,13 @@ tables library (g++ alone, no HIP, no GPU) on the plans' own tables, for every p
 at every threshold and its two neighbours, at 0, 1, 2 (where the thresholds have saturated at 1 and the answer is nq: the table walk) and 2^32 - 1, and
 on seeded words -- and d <= bound must be the old rule for every d in [-nq, nq]."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from hostlib import tables_lib
 from qecmc import _lib as L_
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "mcmc-qec-toric-rl_amd", "csrc")
 PLANS = [  # L, p, Nc (toric)
     pytest.param(9, 0.15, 8, id="config2"),
     pytest.param(5, 0.10, 5, id="L5-Nc5"),
@@ -26,11 +23,7 @@ PLANS = [  # L, p, Nc (toric)
 
 @pytest.fixture(scope="module")
 def T():
-    path = os.environ.get("QECMC_TABLES_LIB")
-    if not path:
-        subprocess.check_call(["make", "-C", CSRC, "-s", "tables"])
-        path = os.path.join(CSRC, "build", "libqecmc_tables.so")
-    lib = C.CDLL(path)
+    lib = tables_lib()
     lib.qt_wave_swap_bound.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
     lib.qt_wave_swap_row.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     return lib
