@@ -65,7 +65,10 @@ typedef enum qecmc_code { QECMC_TORIC = 0, QECMC_XZZX = 1, QECMC_ROTATED = 2, QE
  * first_syndrome a multiple of 64, 1 <= iters <= 128.  With conv_mode error_based the launch runs on a persistent grid
  * whose workgroups own contiguous shares of the batch and reuse the lane of a stopped ladder for the next one of their share: the
  * generator picks then belong to the lane's position in the grid, so results are reproducible for a given (batch size, grid,
- * first_syndrome) and equal to the one-ladder-per-lane layout whenever the batch fits the grid; no final states in that mode. */
+ * first_syndrome) and equal to the one-ladder-per-lane layout whenever the batch fits the grid; no final states in that mode.
+ * Range of p (depolarizing rule): RANDOM and WAVE serve (0, 0.75] -- WAVE below the p at which a swap threshold leaves 32 bits (rungs that
+ * coincide at p = 0.75 or nearly, p_diff > 1 - 2^-32) --; SWEEP and COLOUR are refused (QECMC_ERR_UNSUPPORTED) where ((p / 3) / (1 - p))^4
+ * underflows to 0 in double precision, below p = 3.76e-81: every p >= 1e-80 is served ("Range"). */
 typedef enum qecmc_scan { QECMC_SCAN_RANDOM = 0, QECMC_SCAN_SWEEP = 1, QECMC_SCAN_COLOUR = 2, QECMC_SCAN_WAVE = 3 } qecmc_scan;
 typedef enum qecmc_noise { QECMC_NOISE_DEPOLARIZING = 0, QECMC_NOISE_BIASED = 1, QECMC_NOISE_ALPHA = 2 } qecmc_noise;
 typedef enum qecmc_conv { QECMC_CONV_NONE = 0, QECMC_CONV_ERROR_BASED = 1 } qecmc_conv;

@@ -185,6 +185,14 @@ inline Refusal plan_host(const qecmc_params &p, HostPlan &hp)
             }
         }
         for (int d = 1; d <= nq; ++d) hp.acc_top[d] = thr32(std::pow(chain_factor(pladder[Nc - 1]), (double)d));
+        // scan = sweep and scan = colour test x <= ceil(f^dE 2^32) - 1 (ladder_kernel.hpp thrT, ladder_colour_body.inc thr1 .. thr4), which has no
+        // word for "never": a threshold of 0 -- f^dE underflows to 0 in double precision, f^4 first, at p below about 3.7e-81 -- would wrap to
+        // "always".  (scan = random and scan = wave test x < threshold and serve every p.)
+        if (p.scan == QECMC_SCAN_SWEEP || p.scan == QECMC_SCAN_COLOUR)
+            for (int c = 0; c < Nc; ++c)
+                if (!((a.acc_all_mask >> c) & 1u) && a.acc_thr[c][3] == 0)
+                    return refuse_params(QECMC_ERR_UNSUPPORTED, "scan = %s: the acceptance ratio f^4 of rung %d underflows to 0 at p=%g (f = (p / 3) / (1 - p); every p >= 1e-80 "
+                                         "is served, and scan = random / scan = wave serve every p)", p.scan == QECMC_SCAN_SWEEP ? "sweep" : "colour", c, pladder[c]);
     }
     hp.swap_thr = swap_thresholds(pdiff, nq);                                // mcmc.py:149
     a.swap_fast_ok = 1;

@@ -153,6 +153,25 @@ int qt_plan(const qecmc_params *p, int cu_count, int32_t *shape_ints, uint64_t *
     if (!r.code) { *lds_bytes = hp.lds_bytes; *grid = queue_grid(hp, cu_count, p->flags); }
     return answer(r, hp.shape, shape_ints, msg, msg_cap);
 }
+// validate_params(), then plan_host(): the temperature ladder of an accepted block, as the kernels read it.  head[4] = acc_all_mask, swap_fast_ok,
+// bias_f32ok, nq; inv_log2[kMaxNc] = swap_inv_log2; acc_thr[kMaxNc][4], acc_thr44[kMaxNc][4]; acc_top[nq + 1]; swap_thr[(Nc - 1)(nq + 1)] (either
+// buffer may be null).  Returns the QECMC_ERR_* code with its message; QECMC_ERR_INVALID for too small a buffer
+int qt_plan_ladder(const qecmc_params *p, uint32_t *head, float *inv_log2, uint32_t *acc_thr, uint64_t *acc_thr44, uint32_t *acc_top, int acc_top_cap,
+                   uint64_t *swap_thr, int swap_thr_cap, char *msg, int msg_cap)
+{
+    HostPlan hp;
+    Refusal r = validate_params(p);
+    if (!r.code) r = plan_host(*p, hp);
+    if (msg && msg_cap > 0) std::snprintf(msg, (size_t)msg_cap, "%s", r.msg.c_str());
+    if (r.code) return r.code;
+    const LadderArgs &a = hp.args;
+    head[0] = a.acc_all_mask; head[1] = (uint32_t)a.swap_fast_ok; head[2] = a.bias_f32ok; head[3] = (uint32_t)a.nq;
+    std::memcpy(inv_log2, a.swap_inv_log2, sizeof a.swap_inv_log2);
+    std::memcpy(acc_thr, a.acc_thr, sizeof a.acc_thr);
+    std::memcpy(acc_thr44, a.acc_thr44, sizeof a.acc_thr44);
+    if ((acc_top && put(hp.acc_top, acc_top, acc_top_cap) < 0) || (swap_thr && put(hp.swap_thr, swap_thr, swap_thr_cap) < 0)) return QECMC_ERR_INVALID;
+    return 0;
+}
 int qt_plan_key_equal(const qecmc_params *a, const qecmc_params *b)
 {
     const qecmc_params ka = plan_key(*a), kb = plan_key(*b);
