@@ -372,6 +372,25 @@ int qecmc_class_minplus_site(int code, int L, uint64_t N, const uint8_t *chains,
 int qecmc_class_minplus_chains_site(int code, int L, uint64_t N, const uint8_t *chains, const uint8_t *cq, uint64_t cq_rows, int lds_width,
                                     uint8_t *chain_out, uint32_t *cost_out, uint64_t *count_out, int32_t *class_out);
 
+/* ---- exact chains of every class: the traced sum-product sweep, forward filtering and backward sampling (csrc/class_sample.hpp) --------
+ * chains, N, lds_width and the plans are qecmc_class_sweep_cut's; w[4] / wq, wq_rows are that function's and qecmc_class_sweep_cut_site's, except
+ * that the four weights may hold zeros (finite and >= 0, not all zero).  K: samples per syndrome (mode 1) or per (syndrome, class) (mode 0),
+ * 1 .. 2^32 - 1.  mode 0, every class: chain_out uint8[N][ncls][K][nq], chain_out[s][c][k] a chain with the syndrome of chain s, in class
+ * c, drawn with probability w(chain) / Z_c; class_out is not looked at.  mode 1, posterior: the class is drawn first with probability
+ * Z_c / Z -- class_out int32[N][K] -- and chain_out uint8[N][K][nq] is sample (s, class_out[s][k], k) of mode 0.  z_out double[N][ncls] in
+ * both modes: qecmc_class_sweep_cut's bits.  Bytes 0 .. 3 are I, X, Y, Z; a cell no generator touches keeps the byte of the class
+ * representative.  A sample is a function of (seed, first_syndrome + s, c, k, the plan, chain s, the weights) alone -- not of N, K or the
+ * batch around it -- drawn from Philox sub-stream 0x53 (DESIGN.md "RNG addressing"); each branch is taken with its probability up to 2^-53.
+ * Additive: QECMC_ABI_VERSION stays.  Refused before a device is looked for, the message prefixed "qecmc_class_sample:" /
+ * "qecmc_class_sample_site:": a NULL chains / w / wq / chain_out / z_out (class_out in mode 1), K = 0 or K >= 2^32, first_syndrome + N past
+ * 2^32, a mode other than 0 and 1, a weight that is negative or not finite, and whatever qecmc_class_sweep_cut / _cut_site refuses, with its
+ * code.  Refused once z is known, with QECMC_ERR_INVALID: in mode 0 a class whose weight is 0 or not finite, by row and class; in mode 1 a
+ * row whose total is.  N == 0 succeeds.  Host pointers only; device 0. */
+int qecmc_class_sample(int code, int L, uint64_t N, const uint8_t *chains, const double w[4], int lds_width, uint64_t K, uint64_t seed,
+                       uint32_t first_syndrome, int mode, uint8_t *chain_out, int32_t *class_out, double *z_out);
+int qecmc_class_sample_site(int code, int L, uint64_t N, const uint8_t *chains, const double *wq, uint64_t wq_rows, int lds_width, uint64_t K,
+                            uint64_t seed, uint32_t first_syndrome, int mode, uint8_t *chain_out, int32_t *class_out, double *z_out);
+
 /* ---- the (min, +, count) sweep on the state vector tiled over HBM: xzzx / rotated L = 13 .. 21, planar L = 8 .. 12, toric L = 7
  * (csrc/class_minplus_tiled.hpp) ----
  * The arguments and results of qecmc_class_minplus and qecmc_class_minplus_site -- cost_out uint32[N][ncls], count_out uint64[N][ncls] (0 where

@@ -29,6 +29,7 @@
 #include "class_minplus_trace.hpp"
 #include "class_minplus_site.hpp"
 #include "class_minplus_tiled.hpp"
+#include "class_sample.hpp"
 #include "enumerate.hpp"
 #include "syndrome_lift.hpp"
 #include "tables.hpp"
@@ -1105,6 +1106,124 @@ int qecmc_class_sweep_tiled_site(int code, int L, uint64_t N, const uint8_t *cha
                                [&](const SweepBatch &b, uint64_t first, uint64_t here, double *P) { return sum(b, first, here, P); });
 }
 
+// ---------------------------------------------------------------- exact chains of every class: the traced sum-product sweep (class_sample.hpp)
+namespace {
+int class_sample_impl(const char *name, int code, int L, uint64_t N, const uint8_t *chains, const double *w, const double *wq, uint64_t wq_rows, int lds_width, uint64_t K,
+                      uint64_t seed, uint32_t first_syndrome, int mode, uint8_t *chain_out, int32_t *class_out, double *z_out)
+{
+    const bool site = w == nullptr;
+    if (!chains || (site && !wq) || !chain_out || !z_out || (mode == 1 && !class_out)) return fail(QECMC_ERR_INVALID, "%s: NULL buffer", name);
+    if (int rc = report(sample::check_sample_args(name, N, K, first_syndrome, mode))) return rc;
+    if (!site)
+        if (int rc = report(sample::check_sample_weights(name, w))) return rc;
+    const sample::SamplePlan sp = sample::build_sample_plan(code, L, lds_width, name);
+    const sweep::CutPlan &cp = sp.cut;
+    const sweep::Plan &p = cp.plan;
+    if (int rc = report(p.refusal)) return rc;
+    if (site)
+        if (int rc = report(sample::check_sample_site(name, N, wq, wq_rows, p))) return rc;
+    if (int rc = use_device(0)) return rc;
+    if (N == 0) return 0;
+    if ((site ? class_sweep_cut_site_allow_lds(p.width) : class_sweep_cut_allow_lds(p.width)) != hipSuccess || class_sample_allow_lds(p.width, site) != hipSuccess)
+        return fail(QECMC_ERR_UNSUPPORTED, "%s: this device does not grant a workgroup the %u bytes of LDS a state vector of width %d takes", name, p.carve.bytes, p.width);
+    const uint64_t job_bytes = sample::sample_bytes_per_job(sp);
+    const sample::LaunchGroup g = sample::sample_launch_group(N, p.ncls, cp.n_held, K, job_bytes);
+    SweepBatch b(p, g.syndromes);
+    const size_t pairs = (size_t)g.syndromes * p.ncls, per_syndrome = mode ? 1u : (size_t)p.ncls, max_samples = (size_t)g.syndromes * per_syndrome * g.k_chunk;
+    DevBuf dforget, dpart, dfold, dz, dcls, dspair, dsh, djob, drec, drecord, dchain;
+    SiteRows rows;
+    if (int rc = b.open(p.ops, &cp.held_words)) return rc;
+    HIP_TRY(dforget.alloc(sp.forget_words.size() * sizeof(uint32_t)));
+    HIP_TRY(dpart.alloc((pairs << cp.n_held) * sizeof(double)));                // dirty: every partial is written before it is read
+    HIP_TRY(dfold.alloc((pairs << cp.n_held) * sizeof(double)));                // the copy the reduce folds: the pick reads the partials as they were
+    HIP_TRY(dz.alloc(pairs * sizeof(double)));
+    HIP_TRY(dcls.alloc(max_samples * sizeof(int32_t)));
+    HIP_TRY(dspair.alloc(max_samples * sizeof(uint32_t)));
+    HIP_TRY(dsh.alloc(max_samples * sizeof(uint32_t)));
+    HIP_TRY(djob.alloc(pairs * sizeof(uint32_t)));
+    HIP_TRY(drec.alloc(pairs * sizeof(uint32_t)));
+    HIP_TRY(drecord.alloc((size_t)g.jobs * (size_t)job_bytes));                 // kSampleWorkspaceBytes at most; dirty: the walk reads what the record kernel wrote
+    HIP_TRY(dchain.alloc(max_samples * (size_t)p.nq));
+    HIP_TRY(hipMemcpy(dforget.p, sp.forget_words.data(), sp.forget_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (site)
+        if (int rc = rows.open(wq, wq_rows, p.nq, b.group)) return rc;
+    SweepCutArgs ca = cut_args(p, cp.n_held);
+    SweepSiteArgs sa = {};
+    sa.ncls = p.ncls; sa.W = p.W; sa.width = p.width; sa.n_ops = p.n_ops; sa.n_held = cp.n_held; sa.nq = p.nq; sa.per_syndrome = site ? rows.per_syndrome : 0; sa.scale = p.scale;
+    SampleArgs a = {};
+    a.ncls = p.ncls; a.W = p.W; a.width = p.width; a.n_ops = p.n_ops; a.n_held = cp.n_held; a.n_forget = sp.n_forget; a.nq = p.nq; a.per_syndrome = sa.per_syndrome; a.mode = mode;
+    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
+    if (!site) { sweep::weights_xz(w, ca.wxz); sweep::weights_xz(w, a.wxz); }
+    const double *dwq = site ? rows.d.as<double>() : nullptr;
+    std::vector<int32_t> cls_h(max_samples);
+    std::vector<uint32_t> job_h(pairs), rec_h(pairs);
+    std::vector<uint8_t> chain_h(max_samples * (size_t)p.nq);
+    return b.run(N, chains, nullptr, [&](uint64_t first, uint64_t here) {
+        if (site)
+            if (int rc = rows.group(first, here)) return rc;
+        ca.S = sa.S = (uint32_t)here;
+        const size_t part_bytes = ((size_t)here * p.ncls << cp.n_held) * sizeof(double);
+        if (site) HIP_TRY(launch_class_sweep_cut_site_partials(sa, b.ops(), b.held(), b.rep(), dwq, dpart.as<double>(), 0));
+        else HIP_TRY(launch_class_sweep_cut_partials(ca, b.ops(), b.held(), b.rep(), dpart.as<double>(), 0));
+        HIP_TRY(hipMemcpyAsync(dfold.p, dpart.p, part_bytes, hipMemcpyDeviceToDevice, 0));
+        HIP_TRY(launch_class_sweep_reduce(ca, dfold.as<double>(), dz.as<double>(), 0));
+        if (int rc = b.fetch(z_out, dz, first, here)) return rc;
+        for (uint64_t s = 0; s < here; ++s)
+            if (int rc = report(sample::check_sample_z(name, first + s, z_out + (first + s) * (uint64_t)p.ncls, p.ncls, mode))) return rc;
+        a.syndrome0 = first_syndrome + (uint32_t)first;
+        for (uint64_t k0 = 0; k0 < K; k0 += g.k_chunk) {
+            const uint32_t kc = (uint32_t)(K - k0 < g.k_chunk ? K - k0 : g.k_chunk);
+            a.k0 = (uint32_t)k0; a.k_chunk = kc; a.n_samples = (uint32_t)(here * per_syndrome * kc);
+            HIP_TRY(launch_sample_pick(a, dpart.as<double>(), dz.as<double>(), dcls.as<int32_t>(), dspair.as<uint32_t>(), dsh.as<uint32_t>(), 0));
+            if (mode) {
+                HIP_TRY(hipMemcpy(cls_h.data(), dcls.p, (size_t)a.n_samples * sizeof(int32_t), hipMemcpyDeviceToHost));
+                for (uint64_t s = 0; s < here; ++s) std::memcpy(class_out + (first + s) * K + k0, cls_h.data() + s * kc, (size_t)kc * sizeof(int32_t));
+            }
+            if (cp.n_held == 0) {                                               // a job per pair: every pair in mode 0, the drawn pairs in mode 1
+                uint32_t jobs = 0;
+                std::fill(rec_h.begin(), rec_h.end(), 0xFFFFFFFFu);
+                if (mode) {
+                    for (uint32_t i = 0; i < a.n_samples; ++i) {
+                        const uint32_t pair = (i / kc) * (uint32_t)p.ncls + (uint32_t)cls_h[i];
+                        if (pair >= pairs) return fail(QECMC_ERR_HIP, "%s: internal: sample %u drew a class outside the %d of the code", name, i, p.ncls);
+                        if (rec_h[pair] == 0xFFFFFFFFu) { rec_h[pair] = jobs; job_h[jobs++] = pair; }
+                    }
+                } else
+                    for (; jobs < (uint32_t)(here * p.ncls); ++jobs) rec_h[jobs] = job_h[jobs] = jobs;
+                HIP_TRY(hipMemcpy(djob.p, job_h.data(), (size_t)jobs * sizeof(uint32_t), hipMemcpyHostToDevice));
+                HIP_TRY(hipMemcpy(drec.p, rec_h.data(), (size_t)here * p.ncls * sizeof(uint32_t), hipMemcpyHostToDevice));
+                HIP_TRY(launch_sample_record(a, jobs, b.ops(), b.held(), b.rep(), dwq, djob.as<uint32_t>(), nullptr, drecord.as<sample::PairRecord>(), 0));
+                HIP_TRY(launch_sample_walk(a, 0, a.n_samples, b.ops(), b.held(), b.rep(), dforget.as<uint32_t>(), dspair.as<uint32_t>(), dsh.as<uint32_t>(), drec.as<uint32_t>(),
+                                           drecord.as<sample::PairRecord>(), jobs, dchain.as<uint8_t>(), 0));
+            } else                                                              // a job per sample, as many at a time as the workspace holds records
+                for (uint32_t j0 = 0; j0 < a.n_samples; j0 += g.jobs) {
+                    const uint32_t jobs = a.n_samples - j0 < g.jobs ? a.n_samples - j0 : g.jobs;
+                    HIP_TRY(launch_sample_record(a, jobs, b.ops(), b.held(), b.rep(), dwq, dspair.as<uint32_t>() + j0, dsh.as<uint32_t>() + j0, drecord.as<sample::PairRecord>(), 0));
+                    HIP_TRY(launch_sample_walk(a, j0, jobs, b.ops(), b.held(), b.rep(), dforget.as<uint32_t>(), dspair.as<uint32_t>(), dsh.as<uint32_t>(), nullptr,
+                                               drecord.as<sample::PairRecord>(), jobs, dchain.as<uint8_t>(), 0));
+                }
+            HIP_TRY(hipMemcpy(chain_h.data(), dchain.p, (size_t)a.n_samples * p.nq, hipMemcpyDeviceToHost));
+            const size_t run = (size_t)kc * p.nq;                               // the kc chains of one (syndrome[, class]) are contiguous on both sides
+            for (uint64_t r = 0; r < here * per_syndrome; ++r) std::memcpy(chain_out + ((first * per_syndrome + r) * K + k0) * (uint64_t)p.nq, chain_h.data() + r * run, run);
+        }
+        return 0;
+    });
+}
+}  // namespace
+
+int qecmc_class_sample(int code, int L, uint64_t N, const uint8_t *chains, const double w[4], int lds_width, uint64_t K, uint64_t seed, uint32_t first_syndrome, int mode,
+                       uint8_t *chain_out, int32_t *class_out, double *z_out)
+{
+    if (!w) return fail(QECMC_ERR_INVALID, "qecmc_class_sample: NULL buffer");
+    return class_sample_impl("qecmc_class_sample", code, L, N, chains, w, nullptr, 0, lds_width, K, seed, first_syndrome, mode, chain_out, class_out, z_out);
+}
+
+int qecmc_class_sample_site(int code, int L, uint64_t N, const uint8_t *chains, const double *wq, uint64_t wq_rows, int lds_width, uint64_t K, uint64_t seed,
+                            uint32_t first_syndrome, int mode, uint8_t *chain_out, int32_t *class_out, double *z_out)
+{
+    return class_sample_impl("qecmc_class_sample_site", code, L, N, chains, nullptr, wq, wq_rows, lds_width, K, seed, first_syndrome, mode, chain_out, class_out, z_out);
+}
+
 // ---------------------------------------------------------------- the (min, +) sweep and its traceback under a cost per (syndrome, qubit) (class_minplus_site.hpp)
 namespace {
 // The cost words on the device: the one table once, or the rows of a launch group at a time -- `group` rows at most, whatever N.
@@ -1974,3 +2093,6 @@ int qecmc_ptdc_batch_xyz(const qecmc_params *params, const uint8_t *init, uint64
 }
 
 }  // extern "C"
+
+// the kernels of qecmc_class_sample / _site and their launch functions: this unit's only device code (class_sample.inc says why it is here)
+#include "class_sample.inc"

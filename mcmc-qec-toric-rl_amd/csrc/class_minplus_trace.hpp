@@ -50,15 +50,14 @@ constexpr int trace_words_per_forget(int width) { return width - 1 > 6 ? 1 << (w
 // the index f without its bit `slot`: the inverse of insert_zero on the f whose bit is clear
 __host__ __device__ inline uint32_t remove_bit(uint32_t f, uint32_t slot) { return ((f >> (slot + 1u)) << slot) | (f & ((1u << slot) - 1u)); }
 
-// build_minplus_plan, its refusals renamed, and the generator every FORGET retires: Trace::forget_at of the final stream, in stream order
-inline TracePlan build_trace_plan(int code, int L, int lds_width)
+// the generator every FORGET of a cut plan's stream retires: Trace::forget_at of the final stream, in stream order -> forget_gen [n_forget] and
+// forget_words [n_forget][W]; false where the stream does not retire every generator that is not held exactly once.  The (min, +) traceback and the
+// exact sampler (class_sample.hpp) both walk their sweep back through these.
+inline bool forget_generators(const sweep::CutPlan &cut, int code, int L, std::vector<int> &forget_gen, std::vector<uint32_t> &forget_words)
 {
-    TracePlan tp;
-    tp.cut = build_minplus_plan(code, L, lds_width);
-    sweep::Plan &p = tp.cut.plan;
-    if (p.refusal.code) { p.refusal = chains_prefix(p.refusal); return tp; }
+    const sweep::Plan &p = cut.plan;
     std::vector<char> held((size_t)p.n_gen, 0);
-    for (const int g : tp.cut.held) held[(size_t)g] = 1;
+    for (const int g : cut.held) held[(size_t)g] = 1;
     sweep::Trace tr;
     const sweep::Stream st = sweep::build_stream(code, L, held, &tr);
     const correct::Table &ct = st.table;
@@ -74,17 +73,28 @@ inline TracePlan build_trace_plan(int code, int L, int lds_width)
         if ((p.ops[(size_t)o * sweep::kOpWords] & 15u) != sweep::kForget) continue;
         const int g = at_op[(size_t)o];
         if (g < 0) { ok = false; break; }
-        tp.forget_gen.push_back(g);
+        forget_gen.push_back(g);
         std::vector<uint32_t> words((size_t)ct.W, 0u);
         for (int i = 0; i < 4; ++i) {
             const uint32_t e = (ct.gen[(size_t)(2 * g + (i >> 1))] >> ((i & 1) * 16)) & 0xFFFFu, pauli = e & 3u, site = e >> 2;
             words[site >> 4] ^= pauli << ((site & 15u) * 2u);                   // (Pauli values XOR as the Pauli product)
         }
-        tp.forget_words.insert(tp.forget_words.end(), words.begin(), words.end());
+        forget_words.insert(forget_words.end(), words.begin(), words.end());
     }
+    return ok && (int)forget_gen.size() == p.n_gen - cut.n_held;
+}
+
+// build_minplus_plan, its refusals renamed, and the generator every FORGET retires
+inline TracePlan build_trace_plan(int code, int L, int lds_width)
+{
+    TracePlan tp;
+    tp.cut = build_minplus_plan(code, L, lds_width);
+    sweep::Plan &p = tp.cut.plan;
+    if (p.refusal.code) { p.refusal = chains_prefix(p.refusal); return tp; }
+    const bool ok = forget_generators(tp.cut, code, L, tp.forget_gen, tp.forget_words);
     tp.n_forget = (int)tp.forget_gen.size();
     tp.words_per_forget = trace_words_per_forget(p.width);
-    if (!ok || tp.n_forget != p.n_gen - tp.cut.n_held)
+    if (!ok)
         p.refusal = refuse_params(QECMC_ERR_UNSUPPORTED, "qecmc_class_minplus_chains: internal: the stream of code %d at L=%d does not retire every generator once", code, L);
     return tp;
 }

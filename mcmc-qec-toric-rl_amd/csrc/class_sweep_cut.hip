@@ -60,7 +60,7 @@ hipError_t class_sweep_cut_allow_lds(int width)
     return cut_allow_lds(reinterpret_cast<const void *>(k_class_sweep_cut), opt, width);
 }
 
-hipError_t launch_class_sweep_cut(const SweepCutArgs &a, const uint32_t *ops, const uint32_t *held, const uint32_t *reps, double *P, double *z, hipStream_t stream)
+hipError_t launch_class_sweep_cut_partials(const SweepCutArgs &a, const uint32_t *ops, const uint32_t *held, const uint32_t *reps, double *P, hipStream_t stream)
 {
     if (a.S == 0) return hipSuccess;
     if (!sweep::cut_args_ok(a.S, a.ncls, a.width, a.W, a.n_ops, a.n_held)) return hipErrorInvalidValue;
@@ -68,7 +68,12 @@ hipError_t launch_class_sweep_cut(const SweepCutArgs &a, const uint32_t *ops, co
     if (hipError_t e = class_sweep_cut_allow_lds(a.width)) return e;
     const uint32_t pairs = a.S * (uint32_t)a.ncls;
     hipLaunchKernelGGL(k_class_sweep_cut, dim3(pairs << a.n_held), dim3(sweep::cut_threads(a.width)), carve.bytes, stream, a, ops, held, reps, P);
-    if (hipError_t e = hipGetLastError()) return e;
+    return hipGetLastError();
+}
+
+hipError_t launch_class_sweep_cut(const SweepCutArgs &a, const uint32_t *ops, const uint32_t *held, const uint32_t *reps, double *P, double *z, hipStream_t stream)
+{
+    if (hipError_t e = launch_class_sweep_cut_partials(a, ops, held, reps, P, stream)) return e;
     return launch_class_sweep_reduce(a, P, z, stream);
 }
 

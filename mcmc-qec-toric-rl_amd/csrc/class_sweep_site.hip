@@ -72,8 +72,8 @@ hipError_t class_sweep_cut_site_allow_lds(int width)
     return cut_allow_lds(reinterpret_cast<const void *>(k_class_sweep_cut_site), opt, width);
 }
 
-hipError_t launch_class_sweep_cut_site(const SweepSiteArgs &a, const uint32_t *ops, const uint32_t *held, const uint32_t *reps, const double *wq, double *P, double *z,
-                                       hipStream_t stream)
+hipError_t launch_class_sweep_cut_site_partials(const SweepSiteArgs &a, const uint32_t *ops, const uint32_t *held, const uint32_t *reps, const double *wq, double *P,
+                                                hipStream_t stream)
 {
     if (a.S == 0) return hipSuccess;
     if (!sweep::cut_args_ok(a.S, a.ncls, a.width, a.W, a.n_ops, a.n_held) || !site_table_ok(wq, a.nq, a.per_syndrome)) return hipErrorInvalidValue;
@@ -81,7 +81,14 @@ hipError_t launch_class_sweep_cut_site(const SweepSiteArgs &a, const uint32_t *o
     if (hipError_t e = class_sweep_cut_site_allow_lds(a.width)) return e;
     const uint32_t pairs = a.S * (uint32_t)a.ncls;
     hipLaunchKernelGGL(k_class_sweep_cut_site, dim3(pairs << a.n_held), dim3(sweep::cut_threads(a.width)), carve.bytes, stream, a, ops, held, reps, wq, P);
-    if (hipError_t e = hipGetLastError()) return e;
+    return hipGetLastError();
+}
+
+hipError_t launch_class_sweep_cut_site(const SweepSiteArgs &a, const uint32_t *ops, const uint32_t *held, const uint32_t *reps, const double *wq, double *P, double *z,
+                                       hipStream_t stream)
+{
+    if (a.S == 0) return hipSuccess;
+    if (hipError_t e = launch_class_sweep_cut_site_partials(a, ops, held, reps, wq, P, stream)) return e;
     SweepCutArgs ra = {};
     ra.S = a.S; ra.ncls = a.ncls; ra.W = a.W; ra.width = a.width; ra.n_ops = a.n_ops; ra.n_held = a.n_held; ra.scale = a.scale;
     return launch_class_sweep_reduce(ra, P, z, stream);

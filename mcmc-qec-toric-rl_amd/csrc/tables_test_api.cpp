@@ -11,6 +11,7 @@
 #include "class_minplus_trace.hpp"
 #include "class_minplus_site.hpp"
 #include "class_minplus_tiled.hpp"
+#include "class_sample.hpp"
 #include "corrections.hpp"
 #include "enumerate.hpp"
 #include "kernel_choice.hpp"
@@ -538,6 +539,44 @@ int qt_class_minplus_chains_site(int code, int L, uint64_t N, const uint8_t *cha
     return site_answer({}, msg, msg_cap);
 }
 void qt_site_cost_words(const uint8_t *cq, uint64_t rows, int nq, uint32_t *out) { minplus::site_cost_words(cq, rows, nq, out); }
+// the exact chain sampler (class_sample.hpp).  qt_class_sample: the host twin of qecmc_class_sample (w given) and qecmc_class_sample_site (w NULL) behind
+// the same host checks, in the same order -- the QECMC_ERR_* code of the refusal, its message in msg (nullable); qt_class_sample_plan: forget_gen
+// int32[n_forget] and forget_words uint32[n_forget][W] (both nullable) -> n_forget, -1 where refused or too small a buffer, and through out6 (nullable)
+// n_forget, W, width, n_held, the workspace bound and the bytes of one job's record; qt_class_sample_group: syndromes, k_chunk and jobs of one launch;
+// qt_class_sample_u53: the uniform of one Philox address
+int qt_class_sample(int code, int L, uint64_t N, const uint8_t *chains, const double *w, const double *wq, uint64_t wq_rows, int lds_width, uint64_t K, uint64_t seed,
+                    uint32_t first_syndrome, int mode, uint8_t *chain_out, int32_t *class_out, double *z_out, char *msg, int msg_cap)
+{
+    const char *name = w ? "qecmc_class_sample" : "qecmc_class_sample_site";
+    if (!chains || (!w && !wq) || !chain_out || !z_out || (mode == 1 && !class_out)) return site_answer(refuse_params(QECMC_ERR_INVALID, "%s: NULL buffer", name), msg, msg_cap);
+    if (const Refusal r = sample::check_sample_args(name, N, K, first_syndrome, mode); r.code) return site_answer(r, msg, msg_cap);
+    if (w)
+        if (const Refusal r = sample::check_sample_weights(name, w); r.code) return site_answer(r, msg, msg_cap);
+    const sample::SamplePlan sp = sample::build_sample_plan(code, L, lds_width, name);
+    if (sp.cut.plan.refusal.code) return site_answer(sp.cut.plan.refusal, msg, msg_cap);
+    if (!w)
+        if (const Refusal r = sample::check_sample_site(name, N, wq, wq_rows, sp.cut.plan); r.code) return site_answer(r, msg, msg_cap);
+    return site_answer(sample::sample_host(sp, name, N, chains, w, wq, wq_rows, K, seed, first_syndrome, mode, chain_out, class_out, z_out), msg, msg_cap);
+}
+int qt_class_sample_plan(int code, int L, int lds_width, int32_t *forget_gen, uint32_t *forget_words, int cap_words, uint64_t *out6)
+{
+    const sample::SamplePlan sp = sample::build_sample_plan(code, L, lds_width);
+    if (sp.cut.plan.refusal.code || (forget_words && (int)sp.forget_words.size() > cap_words)) return -1;
+    if (forget_gen)
+        for (int i = 0; i < sp.n_forget; ++i) forget_gen[i] = sp.forget_gen[(size_t)i];
+    if (forget_words && !sp.forget_words.empty()) std::memcpy(forget_words, sp.forget_words.data(), sp.forget_words.size() * sizeof(uint32_t));
+    if (out6) {
+        out6[0] = (uint64_t)sp.n_forget; out6[1] = (uint64_t)sp.cut.plan.W; out6[2] = (uint64_t)sp.cut.plan.width; out6[3] = (uint64_t)sp.cut.n_held;
+        out6[4] = sample::kSampleWorkspaceBytes; out6[5] = sample::sample_bytes_per_job(sp);
+    }
+    return sp.n_forget;
+}
+void qt_class_sample_group(uint64_t N, int ncls, int n_held, uint64_t K, uint64_t bytes_per_job, uint32_t *out3)
+{
+    const sample::LaunchGroup g = sample::sample_launch_group(N, ncls, n_held, K, bytes_per_job);
+    out3[0] = g.syndromes; out3[1] = g.k_chunk; out3[2] = g.jobs;
+}
+double qt_class_sample_u53(uint64_t k, uint32_t block, uint32_t j, uint32_t syndrome, uint32_t stream, uint64_t seed) { return sample::draw_u53(k, block, j, syndrome, stream, seed); }
 // the (min, +) sweep on the tiled plans (class_minplus_tiled.hpp): the host twins of qecmc_class_minplus_tiled and qecmc_class_minplus_tiled_site behind
 // the same host checks, in the same order -- the QECMC_ERR_* code of the refusal, its message in msg (nullable)
 int qt_class_minplus_tiled(int code, int L, uint64_t N, const uint8_t *chains, const uint32_t *cost, int hbm_width, int tile_width, uint32_t *cost_out, uint64_t *count_out,

@@ -26,7 +26,11 @@ cost and count, min_weight_corrections the minimum-weight decoder's correction.
 
 Both under a cost per (syndrome, qubit) (qecmc_class_minplus_site, qecmc_class_minplus_chains_site): class_minplus_site,
 shortest_chains_site, min_weight_classes_site and min_weight_corrections_site take a table of integer costs in place of the four numbers --
-erasures (erasure_site_costs), integer log-likelihoods of any site weights (llr_site_costs): the most likely chain of a class, exactly."""
+erasures (erasure_site_costs), integer log-likelihoods of any site weights (llr_site_costs): the most likely chain of a class, exactly.
+
+Exact draws (qecmc_class_sample, qecmc_class_sample_site): the cut-set sweep run forward with a record of every FORGET and walked back
+with one uniform per generator -- sample_chains and sample_chains_site draw independent chains of every class with probability w(chain) / Z_c,
+sample_posterior draws the class first, posterior_error_counts is the exact yardstick of a sampler's mean error count."""
 import ctypes as C
 
 import numpy as np
@@ -617,6 +621,82 @@ def erasure_site_w4(base_w4, erased):
     out = np.array(np.broadcast_to(np.asarray(base_w4, dtype=np.float64), erased.shape + (4,)))
     out[erased] = 1.0
     return out
+
+
+def _sample_w4(p, w4, eta, alpha):
+    """the four weights of a sampler call: w4 itself, or the noise model of (p, eta, alpha) as exact_class_probabilities names it"""
+    if (w4 is None) == (p is None):
+        raise ValueError("give either p (with eta or alpha for the biased / alpha models) or the four weights w4")
+    if eta is not None and alpha is not None:
+        raise ValueError("eta and alpha name two noise models")
+    if w4 is None:
+        w4 = alpha_w4(p, alpha) if alpha is not None else biased_w4(p, eta) if eta is not None else depolarizing_w4(p)
+    w = np.ascontiguousarray(w4, dtype=np.float64)
+    if w.shape != (4,):
+        raise ValueError(f"weights of shape {w.shape}: the four weights of I, X, Y and Z")
+    return w
+
+
+def _sample(code, chains, w, site_weights, n_samples, seed, first_syndrome, size, lds_width, mode):
+    code = _CODES.get(code, code)
+    flat, L = _as_chains(code, chains, size)
+    n, nq, ncls, K = flat.shape[0], flat.shape[1], 16 if code == L_.TORIC else 4, int(n_samples)
+    if not 1 <= K < 2 ** 32:
+        raise ValueError(f"n_samples={n_samples!r}: 1 .. 2^32 - 1 samples")
+    out = np.zeros((n, K, nq) if mode else (n, ncls, K, nq), dtype=np.uint8)
+    cls = np.zeros((n, K), dtype=np.int32)
+    z = np.zeros((n, ncls), dtype=np.float64)
+    f64p = C.POINTER(C.c_double)
+    tail = (int(lds_width), K, int(seed), int(first_syndrome), mode, L_.u8(out), L_.i32(cls), z.ctypes.data_as(f64p))
+    if site_weights is None:
+        L_.check(L_.lib().qecmc_class_sample(code, L, n, L_.u8(flat), w.ctypes.data_as(f64p), *tail))
+    else:
+        wq, rows = _as_site_weights(code, site_weights, L, n)
+        L_.check(L_.lib().qecmc_class_sample_site(code, L, n, L_.u8(flat), wq.ctypes.data_as(f64p), rows, *tail))
+    info = sweep_cut_info(code, L, lds_width)
+    state = (2, L, L) if code in (L_.TORIC, L_.PLANAR) else (L, L)
+    res = dict(chains=out.reshape(out.shape[:-1] + state), z=z, width=info["width"], held=info["held"])
+    if mode:
+        res["cls"] = cls
+    return res
+
+
+def sample_chains(code, chains, p=None, w4=None, eta=None, alpha=None, n_samples=1, seed=0, first_syndrome=0, size=None, lds_width=0):
+    """Exact, independent chains of every class of every syndrome, on the GPU (qecmc_class_sample): the cut-set sweep run forward
+    with a record and walked back with draws.  code and chains as class_sweep_cut takes them; the weights are w4 -- finite and >= 0, zeros allowed --
+    or the noise model of p / (p, eta) / (p as pz_tilde, alpha).  n_samples chains per (syndrome, class).
+    Returns dict(chains uint8[N, ncls, n_samples, ...]: chains[s, c, k] has the syndrome of chain s, lies in class c and was drawn with probability
+    w(chain) / Z[s, c]; z float64[N, ncls]: class_sweep_cut's Z, bit for bit; width, held).  Sample (s, c, k) is a function of (seed,
+    first_syndrome + s, c, k, chain s, the weights) alone: a batch cut into pieces, with first_syndrome moved along, draws the same chains.  A class
+    whose Z is 0 or not finite is refused by row and class."""
+    return _sample(code, chains, _sample_w4(p, w4, eta, alpha), None, n_samples, seed, first_syndrome, size, lds_width, 0)
+
+
+def sample_chains_site(code, chains, site_weights, n_samples=1, seed=0, first_syndrome=0, size=None, lds_width=0):
+    """sample_chains under a weight per qubit, or per (syndrome, qubit) (qecmc_class_sample_site): site_weights as class_sweep_site takes them --
+    erasure_site_w4, depolarizing_site_w4, any per-shot prior.  A weight of 0 is never drawn: under erasure_site_w4 with base (1, 0, 0, 0) no sample
+    carries an error off the erased set."""
+    return _sample(code, chains, None, site_weights, n_samples, seed, first_syndrome, size, lds_width, 0)
+
+
+def sample_posterior(code, chains, p=None, w4=None, eta=None, alpha=None, site_weights=None, n_samples=1, seed=0, first_syndrome=0, size=None, lds_width=0):
+    """Exact, independent draws from P(chain | syndrome): the class first, with probability Z_c / Z, then a chain of it.  The weights are sample_chains',
+    or site_weights as sample_chains_site takes them.
+    Returns dict(chains uint8[N, n_samples, ...], cls int32[N, n_samples], z float64[N, ncls], width, held); chains[s, k] is sample_chains' chains[s,
+    cls[s, k], k] under the same seed.  A row whose class weights total 0, or are not finite, is refused by name."""
+    if site_weights is not None:
+        if p is not None or w4 is not None:
+            raise ValueError("site_weights replace p and w4")
+        return _sample(code, chains, None, site_weights, n_samples, seed, first_syndrome, size, lds_width, 1)
+    return _sample(code, chains, _sample_w4(p, w4, eta, alpha), None, n_samples, seed, first_syndrome, size, lds_width, 1)
+
+
+def posterior_error_counts(code, chains, p, n_samples, seed=0, eta=None, alpha=None, first_syndrome=0, size=None, lds_width=0):
+    """float64[N]: the mean number of errors (cells that hold X, Y or Z) of n_samples exact draws from P(chain | syndrome) at error rate p -- what a
+    sampler's rung at p converges to, with an error bar that shrinks as 1 / sqrt(n_samples)"""
+    r = sample_posterior(code, chains, p=p, eta=eta, alpha=alpha, n_samples=n_samples, seed=seed, first_syndrome=first_syndrome, size=size, lds_width=lds_width)
+    c = r["chains"]
+    return (c.reshape(c.shape[0], c.shape[1], -1) != 0).sum(axis=2).mean(axis=1)
 
 
 _METHODS = ("auto", "enumerate", "sweep", "cut", "tiled")
