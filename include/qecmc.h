@@ -391,6 +391,22 @@ int qecmc_class_sample(int code, int L, uint64_t N, const uint8_t *chains, const
 int qecmc_class_sample_site(int code, int L, uint64_t N, const uint8_t *chains, const double *wq, uint64_t wq_rows, int lds_width, uint64_t K,
                             uint64_t seed, uint32_t first_syndrome, int mode, uint8_t *chain_out, int32_t *class_out, double *z_out);
 
+/* ---- exact per-qubit marginals of every class: forward filtering and a backward sum on the cut-set sweep (csrc/class_marginal.hpp) --------
+ * chains, N, lds_width and the plans are qecmc_class_sweep_cut's; w[4] / wq, wq_rows are qecmc_class_sample's / _sample_site's: finite and >= 0,
+ * zeros allowed, not all zero.  weights_out double[N][ncls][nq][4]: weights_out[s][c][q][P] is the sum of w(chain) over the chains of class c
+ * with the syndrome of chain s that carry Pauli P (I, X, Y, Z) at cell q, so weights_out / z_out is P(q carries P | syndrome, class) and the
+ * four sum to z_out[s][c] up to rounding.  A cell no generator touches gets z_out[s][c] at the byte of the class representative and 0
+ * elsewhere.  z_out double[N][ncls]: qecmc_class_sweep_cut's bits.  class_out int32[N] (nullable): the class of every input chain.  Every
+ * number is a sum of products of non-negative doubles in an order that is a function of the plan alone (THE RULE of class_marginal.hpp): no
+ * subtraction, no division; a weight of 0 gives exact zeros.  The device holds the forward records of 512 MiB of jobs at a time, whatever N.
+ * Additive: QECMC_ABI_VERSION stays.  Refused before a device is looked for, the message prefixed "qecmc_class_marginals:" /
+ * "qecmc_class_marginals_site:": a NULL chains / w / wq / weights_out / z_out, N past 32 bits, a weight that is negative or not finite, four
+ * zero weights, and whatever qecmc_class_sweep_cut / _cut_site refuses, with its code.  N == 0 succeeds.  Host pointers only; device 0. */
+int qecmc_class_marginals(int code, int L, uint64_t N, const uint8_t *chains, const double w[4], int lds_width, double *weights_out,
+                          double *z_out, int32_t *class_out);
+int qecmc_class_marginals_site(int code, int L, uint64_t N, const uint8_t *chains, const double *wq, uint64_t wq_rows, int lds_width,
+                               double *weights_out, double *z_out, int32_t *class_out);
+
 /* ---- the (min, +, count) sweep on the state vector tiled over HBM: xzzx / rotated L = 13 .. 21, planar L = 8 .. 12, toric L = 7
  * (csrc/class_minplus_tiled.hpp) ----
  * The arguments and results of qecmc_class_minplus and qecmc_class_minplus_site -- cost_out uint32[N][ncls], count_out uint64[N][ncls] (0 where

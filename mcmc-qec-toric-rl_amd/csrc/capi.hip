@@ -30,6 +30,7 @@
 #include "class_minplus_site.hpp"
 #include "class_minplus_tiled.hpp"
 #include "class_sample.hpp"
+#include "class_marginal.hpp"
 #include "enumerate.hpp"
 #include "syndrome_lift.hpp"
 #include "tables.hpp"
@@ -1222,6 +1223,81 @@ int qecmc_class_sample_site(int code, int L, uint64_t N, const uint8_t *chains, 
                             uint32_t first_syndrome, int mode, uint8_t *chain_out, int32_t *class_out, double *z_out)
 {
     return class_sample_impl("qecmc_class_sample_site", code, L, N, chains, nullptr, wq, wq_rows, lds_width, K, seed, first_syndrome, mode, chain_out, class_out, z_out);
+}
+
+// ---------------------------------------------------------------- exact per-qubit marginals of every class: the backward sweep (class_marginal.hpp)
+namespace {
+int class_marginals_impl(const char *name, int code, int L, uint64_t N, const uint8_t *chains, const double *w, const double *wq, uint64_t wq_rows, int lds_width,
+                         double *weights_out, double *z_out, int32_t *class_out)
+{
+    const bool site = w == nullptr;
+    if (!chains || (site && !wq) || !weights_out || !z_out) return fail(QECMC_ERR_INVALID, "%s: NULL buffer", name);
+    if (int rc = report(marginal::check_marginal_args(name, N))) return rc;
+    if (!site)
+        if (int rc = report(marginal::check_marginal_weights(name, w))) return rc;
+    const marginal::MarginalPlan mp = marginal::build_marginal_plan(code, L, lds_width, name);
+    const sweep::CutPlan &cp = mp.cut;
+    const sweep::Plan &p = cp.plan;
+    if (int rc = report(p.refusal)) return rc;
+    if (site)
+        if (int rc = report(marginal::check_marginal_site(name, N, wq, wq_rows, p))) return rc;
+    if (int rc = use_device(0)) return rc;
+    if (N == 0) return 0;
+    if (class_marginal_allow_lds(p.width, site) != hipSuccess)
+        return fail(QECMC_ERR_UNSUPPORTED, "%s: this device does not grant a workgroup the %u bytes of LDS a state vector of width %d takes", name, p.carve.bytes, p.width);
+    const uint64_t job_bytes = marginal::marginal_bytes_per_job(mp);
+    const marginal::LaunchGroup g = marginal::marginal_launch_group(N, p.ncls, cp.n_held, mp.n_close, job_bytes);
+    SweepBatch b(p, g.syndromes);
+    const size_t pairs = (size_t)g.syndromes * p.ncls, all_jobs = pairs << cp.n_held, row = (size_t)p.nq * 4u;
+    DevBuf dclose, dcloseof, dpart, dz, dfwd, dmh, dout;
+    SiteRows rows;
+    if (int rc = b.open(p.ops, &cp.held_words)) return rc;
+    HIP_TRY(dclose.alloc(mp.close_op.size() * sizeof(uint32_t)));
+    HIP_TRY(dcloseof.alloc(mp.close_of.size() * sizeof(int32_t)));
+    HIP_TRY(dpart.alloc(all_jobs * sizeof(double)));                            // kCutGridMax doubles at most; dirty: every partial is written before it is read
+    HIP_TRY(dz.alloc(pairs * sizeof(double)));
+    HIP_TRY(dfwd.alloc((size_t)g.jobs * (size_t)job_bytes));                    // kMarginalWorkspaceBytes at most; dirty: only live entries are written and read
+    HIP_TRY(dmh.alloc(all_jobs * (size_t)marginal::marginal_fold_per_job(mp.n_close) * sizeof(double)));      // every row is written by the fold before the combine reads it
+    HIP_TRY(dout.alloc(pairs * row * sizeof(double)));
+    HIP_TRY(hipMemcpy(dclose.p, mp.close_op.data(), mp.close_op.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dcloseof.p, mp.close_of.data(), mp.close_of.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (site)
+        if (int rc = rows.open(wq, wq_rows, p.nq, b.group)) return rc;
+    SweepCutArgs ca = cut_args(p, cp.n_held);
+    MarginalArgs a = {};
+    a.ncls = p.ncls; a.W = p.W; a.width = p.width; a.n_ops = p.n_ops; a.n_held = cp.n_held; a.n_close = mp.n_close; a.nq = p.nq; a.per_syndrome = site ? rows.per_syndrome : 0;
+    a.scale = p.scale;
+    if (!site) sweep::weights_xz(w, a.wxz);
+    const double *dwq = site ? rows.d.as<double>() : nullptr;
+    return b.run(N, chains, class_out, [&](uint64_t first, uint64_t here) {
+        if (site)
+            if (int rc = rows.group(first, here)) return rc;
+        ca.S = a.S = (uint32_t)here;
+        const uint32_t jobs_here = (uint32_t)(((size_t)here * p.ncls) << cp.n_held);
+        for (uint32_t j0 = 0; j0 < jobs_here; j0 += g.jobs) {                   // as many jobs at a time as the workspace holds records
+            a.job0 = j0; a.jobs = jobs_here - j0 < g.jobs ? jobs_here - j0 : g.jobs;
+            HIP_TRY(launch_marginal_forward(a, b.ops(), b.held(), b.rep(), dwq, dfwd.as<double>(), dpart.as<double>(), 0));
+            HIP_TRY(launch_marginal_backward(a, b.ops(), b.held(), b.rep(), dwq, dfwd.as<double>(), 0));
+            HIP_TRY(launch_marginal_fold(a, b.ops(), b.held(), b.rep(), dclose.as<uint32_t>(), dfwd.as<double>(), dmh.as<double>(), 0));
+        }
+        HIP_TRY(launch_class_sweep_reduce(ca, dpart.as<double>(), dz.as<double>(), 0));
+        HIP_TRY(launch_marginal_combine(a, b.rep(), dcloseof.as<int32_t>(), dmh.as<double>(), dz.as<double>(), dout.as<double>(), 0));
+        if (int rc = b.fetch(z_out, dz, first, here)) return rc;
+        return b.fetch(weights_out, dout, first, here, row);
+    });
+}
+}  // namespace
+
+int qecmc_class_marginals(int code, int L, uint64_t N, const uint8_t *chains, const double w[4], int lds_width, double *weights_out, double *z_out, int32_t *class_out)
+{
+    if (!w) return fail(QECMC_ERR_INVALID, "qecmc_class_marginals: NULL buffer");
+    return class_marginals_impl("qecmc_class_marginals", code, L, N, chains, w, nullptr, 0, lds_width, weights_out, z_out, class_out);
+}
+
+int qecmc_class_marginals_site(int code, int L, uint64_t N, const uint8_t *chains, const double *wq, uint64_t wq_rows, int lds_width, double *weights_out, double *z_out,
+                               int32_t *class_out)
+{
+    return class_marginals_impl("qecmc_class_marginals_site", code, L, N, chains, nullptr, wq, wq_rows, lds_width, weights_out, z_out, class_out);
 }
 
 // ---------------------------------------------------------------- the (min, +) sweep and its traceback under a cost per (syndrome, qubit) (class_minplus_site.hpp)

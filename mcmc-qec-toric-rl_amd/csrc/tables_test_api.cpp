@@ -12,6 +12,7 @@
 #include "class_minplus_site.hpp"
 #include "class_minplus_tiled.hpp"
 #include "class_sample.hpp"
+#include "class_marginal.hpp"
 #include "corrections.hpp"
 #include "enumerate.hpp"
 #include "kernel_choice.hpp"
@@ -577,6 +578,42 @@ void qt_class_sample_group(uint64_t N, int ncls, int n_held, uint64_t K, uint64_
     out3[0] = g.syndromes; out3[1] = g.k_chunk; out3[2] = g.jobs;
 }
 double qt_class_sample_u53(uint64_t k, uint32_t block, uint32_t j, uint32_t syndrome, uint32_t stream, uint64_t seed) { return sample::draw_u53(k, block, j, syndrome, stream, seed); }
+// the exact marginals (class_marginal.hpp).  qt_class_marginals: the host twin of qecmc_class_marginals (w given) and qecmc_class_marginals_site (w NULL)
+// behind the same host checks, in the same order -- the QECMC_ERR_* code of the refusal, its message in msg (nullable); qt_class_marginals_plan: through
+// out8 width, n_held, n_close, the bytes of one job's forward record, the workspace bound, the bound on a group's M_h, n_ops and nq, and through close_qubit
+// (nullable, cap entries) the qubit of every CLOSE -> n_close, -1 where refused or too small a buffer; qt_class_marginals_group: syndromes and jobs of one launch
+int qt_class_marginals(int code, int L, uint64_t N, const uint8_t *chains, const double *w, const double *wq, uint64_t wq_rows, int lds_width, double *weights_out,
+                       double *z_out, int32_t *class_out, char *msg, int msg_cap)
+{
+    const char *name = w ? "qecmc_class_marginals" : "qecmc_class_marginals_site";
+    if (!chains || (!w && !wq) || !weights_out || !z_out) return site_answer(refuse_params(QECMC_ERR_INVALID, "%s: NULL buffer", name), msg, msg_cap);
+    if (const Refusal r = marginal::check_marginal_args(name, N); r.code) return site_answer(r, msg, msg_cap);
+    if (w)
+        if (const Refusal r = marginal::check_marginal_weights(name, w); r.code) return site_answer(r, msg, msg_cap);
+    const marginal::MarginalPlan mp = marginal::build_marginal_plan(code, L, lds_width, name);
+    if (mp.cut.plan.refusal.code) return site_answer(mp.cut.plan.refusal, msg, msg_cap);
+    if (!w)
+        if (const Refusal r = marginal::check_marginal_site(name, N, wq, wq_rows, mp.cut.plan); r.code) return site_answer(r, msg, msg_cap);
+    marginal::marginal_host(mp, N, chains, w, wq, wq_rows, weights_out, z_out, class_out);
+    return site_answer({}, msg, msg_cap);
+}
+int qt_class_marginals_plan(int code, int L, int lds_width, uint32_t *close_qubit, int cap, uint64_t *out8)
+{
+    const marginal::MarginalPlan mp = marginal::build_marginal_plan(code, L, lds_width);
+    if (mp.cut.plan.refusal.code || (close_qubit && mp.n_close > cap)) return -1;
+    if (close_qubit)
+        for (int i = 0; i < mp.n_close; ++i) close_qubit[i] = mp.close_qubit[(size_t)i];
+    if (out8) {
+        out8[0] = (uint64_t)mp.cut.plan.width; out8[1] = (uint64_t)mp.cut.n_held; out8[2] = (uint64_t)mp.n_close; out8[3] = marginal::marginal_bytes_per_job(mp);
+        out8[4] = marginal::kMarginalWorkspaceBytes; out8[5] = marginal::kMarginalFoldBytes; out8[6] = (uint64_t)mp.cut.plan.n_ops; out8[7] = (uint64_t)mp.cut.plan.nq;
+    }
+    return mp.n_close;
+}
+void qt_class_marginals_group(uint64_t N, int ncls, int n_held, int n_close, uint64_t bytes_per_job, uint32_t *out2)
+{
+    const marginal::LaunchGroup g = marginal::marginal_launch_group(N, ncls, n_held, n_close, bytes_per_job);
+    out2[0] = g.syndromes; out2[1] = g.jobs;
+}
 // the (min, +) sweep on the tiled plans (class_minplus_tiled.hpp): the host twins of qecmc_class_minplus_tiled and qecmc_class_minplus_tiled_site behind
 // the same host checks, in the same order -- the QECMC_ERR_* code of the refusal, its message in msg (nullable)
 int qt_class_minplus_tiled(int code, int L, uint64_t N, const uint8_t *chains, const uint32_t *cost, int hbm_width, int tile_width, uint32_t *cost_out, uint64_t *count_out,

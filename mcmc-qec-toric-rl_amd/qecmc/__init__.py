@@ -19,6 +19,7 @@ from .exact import (coset_enumerator, class_weights, depolarizing_weight, biased
                     class_minplus, min_weight_classes, shortest_class_law, shortest_chains, min_weight_corrections,
                     class_minplus_site, shortest_chains_site, min_weight_classes_site, min_weight_corrections_site, erasure_site_costs, llr_site_costs,
                     sample_chains, sample_chains_site, sample_posterior, posterior_error_counts,
+                    class_marginals, class_marginals_site, posterior_marginals, exact_error_counts,
                     class_minplus_tiled, class_minplus_tiled_site)
 
 __all__ = ["QecmcError", "device_count", "lib", "TORIC", "XZZX", "ROTATED", "PLANAR", "Toric_code", "xzzx_code", "RotSurCode", "Planar_code",
@@ -29,4 +30,5 @@ __all__ = ["QecmcError", "device_count", "lib", "TORIC", "XZZX", "ROTATED", "PLA
            "class_minplus", "min_weight_classes", "shortest_class_law", "shortest_chains", "min_weight_corrections",
            "class_minplus_site", "shortest_chains_site", "min_weight_classes_site", "min_weight_corrections_site", "erasure_site_costs", "llr_site_costs",
            "sample_chains", "sample_chains_site", "sample_posterior", "posterior_error_counts",
+           "class_marginals", "class_marginals_site", "posterior_marginals", "exact_error_counts",
            "class_minplus_tiled", "class_minplus_tiled_site"]

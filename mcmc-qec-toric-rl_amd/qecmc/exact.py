@@ -30,7 +30,11 @@ erasures (erasure_site_costs), integer log-likelihoods of any site weights (llr_
 
 Exact draws (qecmc_class_sample, qecmc_class_sample_site): the cut-set sweep run forward with a record of every FORGET and walked back
 with one uniform per generator -- sample_chains and sample_chains_site draw independent chains of every class with probability w(chain) / Z_c,
-sample_posterior draws the class first, posterior_error_counts is the exact yardstick of a sampler's mean error count."""
+sample_posterior draws the class first, posterior_error_counts is the exact yardstick of a sampler's mean error count.
+
+Exact marginals (qecmc_class_marginals, qecmc_class_marginals_site): the same forward sweep with a record of every CLOSE and a
+backward sweep over the same stream -- class_marginals and class_marginals_site give, per class, the weight with which every qubit carries I, X, Y
+or Z; posterior_marginals mixes the classes with Z_c / Z; exact_error_counts is the exact value of what posterior_error_counts estimates."""
 import ctypes as C
 
 import numpy as np
@@ -693,10 +697,100 @@ def sample_posterior(code, chains, p=None, w4=None, eta=None, alpha=None, site_w
 
 def posterior_error_counts(code, chains, p, n_samples, seed=0, eta=None, alpha=None, first_syndrome=0, size=None, lds_width=0):
     """float64[N]: the mean number of errors (cells that hold X, Y or Z) of n_samples exact draws from P(chain | syndrome) at error rate p -- what a
-    sampler's rung at p converges to, with an error bar that shrinks as 1 / sqrt(n_samples)"""
+    sampler's rung at p converges to, with an error bar that shrinks as 1 / sqrt(n_samples).  exact_error_counts(...)["posterior"] is the exact value
+    this estimates, without draws"""
     r = sample_posterior(code, chains, p=p, eta=eta, alpha=alpha, n_samples=n_samples, seed=seed, first_syndrome=first_syndrome, size=size, lds_width=lds_width)
     c = r["chains"]
     return (c.reshape(c.shape[0], c.shape[1], -1) != 0).sum(axis=2).mean(axis=1)
+
+
+def _marginals(code, chains, w, site_weights, size, lds_width):
+    code = _CODES.get(code, code)
+    flat, L = _as_chains(code, chains, size)
+    n, nq, ncls = flat.shape[0], flat.shape[1], 16 if code == L_.TORIC else 4
+    weights = np.zeros((n, ncls, nq, 4), dtype=np.float64)
+    z = np.zeros((n, ncls), dtype=np.float64)
+    cls = np.zeros(n, dtype=np.int32)
+    f64p = C.POINTER(C.c_double)
+    tail = (int(lds_width), weights.ctypes.data_as(f64p), z.ctypes.data_as(f64p), L_.i32(cls))
+    if site_weights is None:
+        L_.check(L_.lib().qecmc_class_marginals(code, L, n, L_.u8(flat), w.ctypes.data_as(f64p), *tail))
+    else:
+        wq, rows = _as_site_weights(code, site_weights, L, n)
+        L_.check(L_.lib().qecmc_class_marginals_site(code, L, n, L_.u8(flat), wq.ctypes.data_as(f64p), rows, *tail))
+    info = sweep_cut_info(code, L, lds_width)
+    state = (2, L, L) if code in (L_.TORIC, L_.PLANAR) else (L, L)
+    return dict(weights=weights.reshape((n, ncls) + state + (4,)), z=z, cls=cls, width=info["width"], held=info["held"])
+
+
+def _normalized(res, normalize):
+    """res with marginals = weights / their sum over the last axis; a (row, class) whose four weights total 0 or are not finite is refused by name"""
+    w = res["weights"]
+    if not normalize:
+        return res
+    n, ncls = w.shape[:2]
+    with np.errstate(over="ignore", invalid="ignore"):
+        tot = w.sum(axis=-1)
+    bad = ~(np.isfinite(tot) & (tot > 0.0)).reshape(n, ncls, -1).all(axis=2)
+    if bad.any():
+        r, c = (int(x) for x in np.argwhere(bad)[0])
+        raise FloatingPointError(f"row {r}, class {c}: the four weights of a qubit total {float(np.nanmin(tot[r, c])):.3g} at the least (class weight "
+                                 f"{float(res['z'][r, c]):.3g}) -- a class whose weight is 0 or not finite has no marginals")
+    res["marginals"] = w / tot[..., None]
+    return res
+
+
+def class_marginals(code, chains, p=None, w4=None, eta=None, alpha=None, size=None, lds_width=0, normalize=True):
+    """The exact marginals of every qubit in every class, on the GPU (qecmc_class_marginals): the cut-set sweep run forward with a
+    record of every CLOSE, and a backward sweep over the same stream.  code and chains as class_sweep_cut takes them; the weights are w4 -- finite and
+    >= 0, zeros allowed -- or the noise model of p / (p, eta) / (p as pz_tilde, alpha).
+    Returns dict(weights float64[N, ncls, ..., 4]: weights[s, c, q, P] = the sum of w(chain) over the chains of class c with the syndrome of chain s
+    that carry Pauli P (I, X, Y, Z) at q; marginals = weights / their sum over the last axis (normalize=True): P(q carries P | syndrome, class);
+    z float64[N, ncls]: class_sweep_cut's Z, bit for bit; cls int32[N]; width, held).  With normalize=True a (row, class) whose four weights total 0
+    or are not finite raises FloatingPointError naming row and class."""
+    return _normalized(_marginals(code, chains, _sample_w4(p, w4, eta, alpha), None, size, lds_width), normalize)
+
+
+def class_marginals_site(code, chains, site_weights, size=None, lds_width=0, normalize=True):
+    """class_marginals under a weight per qubit, or per (syndrome, qubit) (qecmc_class_marginals_site): site_weights as class_sweep_site takes them --
+    erasure_site_w4, depolarizing_site_w4, any per-shot prior.  A weight of 0 gives exact zeros: under erasure_site_w4 with base (1, 0, 0, 0) a
+    qubit off the erased set carries I with weight z, exactly."""
+    return _normalized(_marginals(code, chains, None, site_weights, size, lds_width), normalize)
+
+
+def posterior_marginals(code, chains, p=None, w4=None, eta=None, alpha=None, site_weights=None, size=None, lds_width=0):
+    """float64[N, ..., 4]: P(q carries P | syndrome), the classes mixed with Z_c / Z: sum_c weights_c / sum_c z_c.  The weights are class_marginals',
+    or site_weights as class_marginals_site takes them.  A row whose class weights total 0, or are not finite, is refused by name."""
+    if site_weights is not None:
+        if p is not None or w4 is not None:
+            raise ValueError("site_weights replace p and w4")
+        r = _marginals(code, chains, None, site_weights, size, lds_width)
+    else:
+        r = _marginals(code, chains, _sample_w4(p, w4, eta, alpha), None, size, lds_width)
+    with np.errstate(over="ignore", invalid="ignore"):
+        tot = r["z"].sum(axis=1)
+        num = r["weights"].sum(axis=1)
+    bad = ~(np.isfinite(tot) & (tot > 0.0) & np.isfinite(num.reshape(len(tot), -1)).all(axis=1))
+    if bad.any():
+        row = int(np.flatnonzero(bad)[0])
+        raise FloatingPointError(f"row {row}: the class weights total {float(tot[row]):.3g} -- a row whose total is 0 or not finite has no posterior marginals")
+    return num / tot.reshape((-1,) + (1,) * (num.ndim - 1))
+
+
+def exact_error_counts(code, chains, p, eta=None, alpha=None, size=None, lds_width=0):
+    """dict(per_class float64[N, ncls], posterior float64[N]): the exact mean number of errors (cells that hold X, Y or Z) of a chain of class c, and of
+    a chain drawn from P(chain | syndrome), at error rate p: sum_q (1 - marginal[q][I]) over the cells that hold a qubit.  posterior is the exact
+    value of what posterior_error_counts estimates with n_samples draws.  A class, or a row, of weight 0 is refused by name."""
+    r = class_marginals(code, chains, p=p, eta=eta, alpha=alpha, size=size, lds_width=lds_width, normalize=True)
+    n, ncls = r["z"].shape
+    m = r["marginals"].reshape(n, ncls, -1, 4)
+    per_class = (1.0 - m[..., 0]).sum(axis=2)                                   # (a cell that holds no qubit carries the representative's I: 1 - 1)
+    ztot = r["z"].sum(axis=1)
+    if not (np.isfinite(ztot) & (ztot > 0.0)).all():
+        row = int(np.flatnonzero(~(np.isfinite(ztot) & (ztot > 0.0)))[0])
+        raise FloatingPointError(f"row {row}: the class weights total {float(ztot[row]):.3g} -- a row whose total is 0 or not finite has no posterior")
+    post = r["weights"].reshape(n, ncls, -1, 4).sum(axis=1) / ztot[:, None, None]
+    return dict(per_class=per_class, posterior=(1.0 - post[..., 0]).sum(axis=1))
 
 
 _METHODS = ("auto", "enumerate", "sweep", "cut", "tiled")
