@@ -170,6 +170,8 @@ template <int WV, int w, int row = w> __device__ __forceinline__ void wu_ds_read
     WU_BY_WV(M)
 #undef M
 }
+// (behind stores alone: nothing the tuple receives is waited for, so the statement does not name it and may stand inside a branch -- see the lean tail)
+__device__ __forceinline__ void wu_ds_drain() { asm volatile("s_waitcnt lgkmcnt(0)" : : : "memory"); }
 template <int WV> __device__ __forceinline__ void wu_ds_wait(typename WuVec<WV>::type &st)
 {
 #define M(PIN) asm volatile("s_waitcnt lgkmcnt(0)" : "+" PIN(st) : : "memory");
@@ -573,6 +575,30 @@ __device__ __forceinline__ void wu_put_block(wu_lds_rw p, const u32x4 &v, int le
 #define QECMC_WU_SPREAD_AT 0
 #endif
 constexpr int kWuSpreadAt = QECMC_WU_SPREAD_AT;
+// The barriers of a step of the walked forms (wu_once 1, 2; the lean tail has the schedule and the access argument): 2 -- every wave publishes its record
+// in FRONT of the step's first barrier, the top rung's wave walks right behind it and the state stores of every wave go into the walk's shadow --, 3 -- the
+// parent's step: first barrier, stores and record, second barrier, walk, third barrier.  The replay (wu_once 0) has its two barriers in either build.
+// -DQECMC_WU_STEP_BARRIERS=3 builds the other form for an A/B (bench.py --library; DESIGN.md 4.1g has the measurement; the tests run the default).
+#ifndef QECMC_WU_STEP_BARRIERS
+#define QECMC_WU_STEP_BARRIERS 2
+#endif
+constexpr int kWuStepBarriers = QECMC_WU_STEP_BARRIERS;
+// (the walker's own state stores of the two-barrier step: 0 behind the walk's loads, in whose wait they are issued; 1 in front of them)
+#ifndef QECMC_WU_WALK_PUTS_FIRST
+#define QECMC_WU_WALK_PUTS_FIRST 0
+#endif
+constexpr bool kWuWalkPutsFirst = QECMC_WU_WALK_PUTS_FIRST != 0;
+static_assert(kWuStepBarriers == 2 || kWuStepBarriers == 3, "a step of the walked forms: two or three barriers");
+// Who books rung 0's new record (tops0, the class histogram, samples) in the walked forms: 0 -- the wave of slot 0, as in the replay --, 1 -- the top
+// rung's wave, which ends its walk holding exactly that record.  By the static counts the walker has the workgroup's shortest stretch to the next step's
+// first barrier and wave 0 the longest; measured, the walker's booking LOST 0.8 - 1.4 % at 5 .. 8 rungs, with either number of barriers (DESIGN.md 4.1g,
+// profiles/r16_wave_two_barriers_ab.json), so 0 is the default and -DQECMC_WU_TOP_BOOKS=1 builds the other one (timed; the tests run the default).
+#ifndef QECMC_WU_TOP_BOOKS
+#define QECMC_WU_TOP_BOOKS 0
+#endif
+constexpr bool kWuTopBooks = QECMC_WU_TOP_BOOKS != 0;
+// (the kernels whose lean tail can walk at all: what folds LadderArgs::wu_once to 0 in wu_run, for ladder_wu_body.inc's hand-over of the booked values)
+constexpr bool wu_top_books_family(int WV, bool CONV, bool ALPHA, bool STATS, bool LONG) { return kWuTopBooks && !CONV && !ALPHA && WV <= 16 && !STATS && !LONG; }
 
 // the step loop of one wave: TOP = the rung that accepts every move (its stabilizers unseen, its logical operators through a frame);
 // IT = 10: `iters` known at compile time (decoders.py:25 iters=10), the proposal loop unrolled without guards; IT = 0: any 1 <= iters <= 128.
@@ -865,10 +891,10 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
         // Behind the draw, still in front of the first barrier, the drawer turns every word into its pair's bound (wu_bound_block): the rows of swd hold
         // bounds, and the cascade below compares.
         // once == 2 (a TOPDRAWS kernel's walk; STATS and LONG have folded it to 0): the bounds are spread over the waves below the top.  The top wave draws
-        // the words of step T + 1 here, keeps them raw in registers over both barriers and stores them behind its walk's reads, into the rows it has just
-        // read: behind the second barrier nobody but the walker reads swd.  The wave of slot s converts row s in place (own_bound) between the third
-        // barrier and the next step's first, and nobody else touches row s from the third barrier to the walker's read behind the next step's second
-        // one: the step gets no barrier for it.  The addressing of the words is unchanged -- only who turns a word into a bound, and when.
+        // the words of step T + 1 here, keeps them raw in registers up to its walk and stores them behind the walk's reads, into the rows it has just
+        // read: in a walked step nobody but the walker reads swd.  The wave of slot s converts row s in place (own_bound) between the step's last
+        // barrier and the next step's first, and nobody else touches row s from that last barrier to the walker's read in the next step (behind its first
+        // barrier; in a build of three barriers behind its second): the step gets no barrier for it.  The addressing of the words is unchanged -- only who turns a word into a bound, and when.
         const bool spread = once == 2u;
         u32x4 sb{0, 0, 0, 0};
         [[maybe_unused]] u32x4 sb1{0, 0, 0, 0};
@@ -901,69 +927,131 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
             row[0] = wu_bound_word(a, row[0], tb0 + slot * (uint32_t)(kSwapFast * 4), (int)slot);
         };
         if constexpr (TOPDRAWS && !TOP && kWuSpreadAt == 1) { if (spread) own_bound(); }
-        __syncthreads();                                   // (everybody has read the exchange buffer, the records and the swap uniforms of the step before)
-        wu_put_all<WV>(st, xaddr + slot * xstride);
-        recl[slot * 64u] = pack_info(n4 >> 2, slot, cls, flag);
-        if constexpr (TOPDRAWS && TOP) {
-            if (!spread) {
-                put_block(0, sb);
-                if (NC > 5) put_block(1, sb1);
+        // this wave's record, and the bounds of the pairs whose words it drew (once == 2: the top wave's words stay raw in registers, above)
+        auto publish = [&]() {
+            recl[slot * 64u] = pack_info(n4 >> 2, slot, cls, flag);
+            if constexpr (TOPDRAWS && TOP) {
+                if (!spread) {
+                    put_block(0, sb);
+                    if (NC > 5) put_block(1, sb1);
+                }
+            } else if constexpr (!TOPDRAWS) {
+                if (duty) put_block(swb, sb);
             }
-        } else if constexpr (!TOPDRAWS) {
-            if (duty) put_block(swb, sb);
-        }
-        wu_ds_wait<WV>(st);                                 // (the asm stores of the exchange are not in the compiler's count)
-        __syncthreads();
-        // the next step's acceptance block (AHEAD, above): one call site for both forms -- walked once, it fills the wait for the third barrier;
-        // replayed, the draw has merely moved here from the top of the step.  No barrier and no LDS access inside.
+        };
+        // the next step's acceptance block (AHEAD, above): walked once, it fills the wait for the step's last barrier; replayed, the draw has merely moved
+        // behind the second barrier from the top of the step.  No barrier and no LDS access inside.
         // (wu_philox launders the seed in front of the block and the statement behind it takes the four words: the draw stays between the two, and
         // these between the barriers -- left alone, the compiler sinks the whole block to the loop's latch, behind the exchange)
-        if constexpr (AHEAD) {
-            abn = wu_philox(T + 1u, kSubWuAcc, syn, slot, a.seed_lo, a.seed_hi);
-            asm volatile("" : "+v"(abn.x), "+v"(abn.y), "+v"(abn.z), "+v"(abn.w));
-        }
-        uint32_t mine;
-        if (once) {
-            // the cascade once per workgroup: the top rung's wave walks the pairs top-down and leaves in rec[i] the
-            // record slot i now holds (rec[i + 1] is dead once pair i is decided: `car` has it); behind a third barrier a wave reads its slot's
-            // Every read the walk needs is issued in front of its first decision -- the records, and beside each the bound of the pair below it, counted
-            // from the top: constant offsets from one base, at most 8 rungs here (!LONG), the rows below rung 0's are rows of the exchange buffer, read and
-            // dropped -- and waited for once; the chain itself runs in registers, a compare and two selects per pair on ne(lo) + D, which is formed off
-            // the chain.  The stores of rec[i + 1] go out as the chain advances and are waited for in front of the barrier alone.
-            if constexpr (TOP && !LONG) {
-                wu_lds_rw const pr = recl + (NC - 8) * 64;
-                wu_lds_ptr const px = swdl + (NC - 8) * 64;
-                uint32_t r[8], s[7];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) r[j] = pr[64 * (7 - j)];                  // slot NC - 1 - j's record
-#pragma unroll
-                for (int j = 0; j < 7; ++j) s[j] = px[64 * (6 - j)];                  // pair NC - 2 - j's bound
-                asm volatile("" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7]),
-                                  "+v"(s[0]), "+v"(s[1]), "+v"(s[2]), "+v"(s[3]), "+v"(s[4]), "+v"(s[5]), "+v"(s[6]));   // (all of them here: one wait)
-                if constexpr (TOPDRAWS) {
-                    // (the next step's raw words, into the rows just read: the stores go out beside the chain and are waited for in front of the barrier)
-                    if (spread) {
-                        put_block(0, sb);
-                        if (NC > 5) put_block(1, sb1);
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < 7; ++j) s[j] += r[j + 1] & 0xFFFFu;
-                uint32_t car = r[0], nc = car & 0xFFFFu;
-#pragma unroll
-                for (int j = 0; j < 7; ++j) {                                        // pair i = NC - 2 - j, mcmc.py:96
-                    if (j < NC - 1) {
-                        const uint32_t lo = r[j + 1];
-                        const bool flip = nc <= s[j];                                // ne_hi - ne_lo <= D
-                        pr[64 * (7 - j)] = flip ? lo : car;                             // what slot i + 1 now holds (:98-99)
-                        car = flip ? car : lo;
-                        nc = flip ? nc : lo & 0xFFFFu;
-                    }
-                }
-                recl[0] = car;
+        auto draw_ahead = [&]() {
+            if constexpr (AHEAD) {
+                abn = wu_philox(T + 1u, kSubWuAcc, syn, slot, a.seed_lo, a.seed_hi);
+                asm volatile("" : "+v"(abn.x), "+v"(abn.y), "+v"(abn.z), "+v"(abn.w));
             }
+        };
+        // The cascade once per workgroup: the top rung's wave walks the pairs top-down and leaves in rec[i] the record slot i now holds (rec[i + 1] is dead
+        // once pair i is decided: `car` has it); behind the step's last barrier a wave reads its slot's.  Every read the walk needs is issued in front of its
+        // first decision -- the records, and beside each the bound of the pair below it, counted from the top: constant offsets from one base, at most 8 rungs
+        // here (!LONG) -- and waited for once; the chain itself runs in registers, a compare and two selects per pair on ne(lo) + D, which is formed off the
+        // chain.  The stores of rec[i + 1] go out as the chain advances and are waited for in front of the barrier alone.  Returns rung 0's new record.
+        // At fewer than 8 rungs (the walk serves 5 .. 8) the record loads of "slots below 0" (r[NC] .. r[7]) fall into the last 8 - NC rows of the exchange
+        // buffer, which lies in front of rec -- rows of the top rung's own region, which in the two-barrier step the walker itself stores into behind these
+        // loads, while the other waves store into theirs -- and the bound loads of "pairs below 0" (s[NC - 1] .. s[6]) into rows 2 NC - 8 .. NC - 1 of rec.
+        // No such value reaches a use: the chain reads r[0], r[j + 1] and s[j] for j < NC - 1 alone, and the sums s[j] += r[j + 1] of j >= NC - 1 end in
+        // registers nobody reads.
+        // Two halves -- the loads, then the wait and the chain --, because the two-barrier step issues the walker's own state stores between them, in the
+        // wait for the loads, and those stand on the path every form shares: a state store (an asm statement that names the pinned tuple) inside a branch
+        // makes the compiler merge two copies of the tuple where the paths meet, a round trip of the state through scratch per step.
+        [[maybe_unused]] uint32_t r[8] = {0, 0, 0, 0, 0, 0, 0, 0}, s[7] = {0, 0, 0, 0, 0, 0, 0};
+        [[maybe_unused]] auto walk_loads = [&]() __attribute__((always_inline)) {
+            wu_lds_ptr const pr = recl + (NC - 8) * 64, px = swdl + (NC - 8) * 64;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) r[j] = pr[64 * (7 - j)];                  // slot NC - 1 - j's record
+#pragma unroll
+            for (int j = 0; j < 7; ++j) s[j] = px[64 * (6 - j)];                  // pair NC - 2 - j's bound
+        };
+        [[maybe_unused]] auto walk_chain = [&]() __attribute__((always_inline)) {
+            wu_lds_rw const pr = recl + (NC - 8) * 64;
+            asm volatile("" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7]),
+                              "+v"(s[0]), "+v"(s[1]), "+v"(s[2]), "+v"(s[3]), "+v"(s[4]), "+v"(s[5]), "+v"(s[6]));   // (all of them here: one wait)
+            if constexpr (TOPDRAWS) {
+                // (the next step's raw words, into the rows just read: the stores go out beside the chain and are waited for in front of the barrier)
+                if (spread) {
+                    put_block(0, sb);
+                    if (NC > 5) put_block(1, sb1);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 7; ++j) s[j] += r[j + 1] & 0xFFFFu;
+            uint32_t car = r[0], nc = car & 0xFFFFu;
+#pragma unroll
+            for (int j = 0; j < 7; ++j) {                                        // pair i = NC - 2 - j, mcmc.py:96
+                if (j < NC - 1) {
+                    const uint32_t lo = r[j + 1];
+                    const bool flip = nc <= s[j];                                // ne_hi - ne_lo <= D
+                    pr[64 * (7 - j)] = flip ? lo : car;                             // what slot i + 1 now holds (:98-99)
+                    car = flip ? car : lo;
+                    nc = flip ? nc : lo & 0xFFFFu;
+                }
+            }
+            recl[0] = car;
+            return car;
+        };
+        // ladder + PTEQ bookkeeping on rung 0's new record: by the wave of slot 0, or -- a build with kWuTopBooks, walked -- by the walker, which ends its
+        // chain holding that record (`car`, what it stored to rec[0]).  Whoever books carries tops0 and samples, and is the only wave that touches hist
+        // (ladder_wu_body.inc loads a resumed run's tops0 into that wave and hands both values to wave 0's write-out behind the loop).
+        auto book = [&](uint32_t fl, uint32_t c0) {                                  // r0's flag and class
+            tops0 += (NC == 1) | fl;                                                 // :101-102
+            if (a.counts != nullptr && tops0 >= a.tops_burn) {                       // decoders.py:60-67
+                wu_lds_rw const hist = (wu_lds_rw)(uintptr_t)(xaddr + (uint32_t)ol.hist * 4u);
+                hist[(CODE == kCodeXzzx ? (c0 ^ (c0 >> 1)) : c0) * 64] += 1;
+                samples++;
+            }
+        };
+        constexpr bool TBOOKS = wu_top_books_family(WV, CONV, ALPHA, STATS, LONG);
+        constexpr bool WALKS = !STATS && !LONG;            // (the kernels in which `once` can be non-zero)
+        // The walked forms' step of TWO barriers (kWuStepBarriers == 2), B1 and B3 -- the replay below keeps B1, B2.  Who touches what, per lane column:
+        //   exchange buffer, region of rung s: wave s stores it between B1 and B3 (wu_put_all; the walker behind its loads); any wave may take it, between B3
+        //             and the next step's B1 (wu_take_all waits for its data).  B1: every take of step T - 1 is done before a row is overwritten; B3: every
+        //             store is complete -- each wave waits for its own (wu_ds_drain) in front of it -- before a row is taken.
+        //   rec[s]:   wave s publishes it in FRONT of B1 -- behind its own read of the row, `mine`, in program order --; the walker reads it and rewrites it in
+        //             place between B1 and B3; wave s reads it behind B3.  Every cross-wave access is the walker's and lies between the two barriers; no third
+        //             wave ever addresses row s (a wave's only rec address is its slot's row).
+        //   swd[i]:   once == 1, and the kernels whose lower waves draw (no TOPDRAWS): whoever drew the block stores the bounds in front of B1, the walker
+        //             reads them between B1 and B3, its reads of step T - 1 lie in front of that step's B3.  once == 2: the walker stores the raw word of step
+        //             T + 1 behind its reads, in front of B3; wave i turns it into the bound in place between B3 and the next step's B1 (own_bound); the
+        //             walker reads behind that B1 -- the hand-over of the three-barrier step with B1 in B2's place.  Nobody but the walker and wave i
+        //             addresses row i.  "The conversion's store is complete at B1": the barrier's own wait covers it, as it covers the record's.
+        // So B1 now means "everybody has taken, every record is published, every bound is stored", and the walker starts right behind it.
+        const bool two = WALKS && kWuStepBarriers == 2 && once != 0;
+        if (two) publish();
+        __syncthreads();                                   // B1 (everybody has read the exchange buffer, the records and the swap uniforms of the step before)
+        uint32_t mine;
+        [[maybe_unused]] uint32_t car0 = 0;                 // the walker: rung 0's new record
+        if constexpr (TOP && WALKS && !kWuWalkPutsFirst) { if (two) walk_loads(); }
+        wu_put_all<WV>(st, xaddr + slot * xstride);        // (every form, on the one path: the walker's go out in the wait for its loads)
+        if (two) {
+            if constexpr (TOP && WALKS) {
+                if constexpr (kWuWalkPutsFirst) walk_loads();
+                car0 = walk_chain();
+            }
+            draw_ahead();                                  // (the waves below the top: in the walk's shadow, behind their stores)
+            wu_ds_drain();                                 // (the asm stores of the exchange are not in the compiler's count)
+            __syncthreads();                               // B3
+            mine = recl[slot * 64u];
+            if constexpr (TBOOKS && TOP) book(car0 >> 31, (car0 >> 24) & 0x3Fu);     // (here, under the form's own test: no test of its own)
+        } else {
+        publish();
+        // (the asm stores of the exchange are not in the compiler's count; the kernels without the fork above keep the statement that names the tuple)
+        if constexpr (WALKS && kWuStepBarriers == 2) wu_ds_drain(); else wu_ds_wait<WV>(st);
+        __syncthreads();                                   // B2
+        draw_ahead();                                      // (one call site for the replay and the three-barrier walk)
+        if (kWuStepBarriers != 2 && once) {
+            // the three-barrier walk: stores and records behind B1, B2, the walk, B3
+            if constexpr (TOP && WALKS) { walk_loads(); car0 = walk_chain(); }
             __syncthreads();
             mine = recl[slot * 64u];
+            if constexpr (TBOOKS && TOP) book(car0 >> 31, (car0 >> 24) & 0x3Fu);
         } else {
             // every wave replays the top-down cascade on the published records: the pairs above its slot move `car` alone, the pair below it decides
             wu_lds_ptr pr = recl + (NC - 2) * 64, px = swdl + (NC - 2) * 64;
@@ -982,18 +1070,14 @@ __device__ __forceinline__ void wu_run(const LadderArgs &a, typename WuVec<WV>::
                 }
             }
         }
+        }
         wu_take_all<WV>(st, xaddr + ((mine >> 16) & 0xFFu) * xstride);               // this rung's new state: the words of the rung it comes from
         if constexpr (TOPDRAWS && !TOP && kWuSpreadAt == 0) { if (spread) own_bound(); }   // (the next step's bound of this wave's pair: the first step's, in front of the loop)
         n4 = (mine & 0xFFFFu) << 2; cls = (mine >> 24) & 0x3Fu; flag = mine >> 31;
         if constexpr (STATS) nsum += mine & 0xFFFFu;
         if (top) flag = 1;                                                           // chains[-1].flag = 1, mcmc.py:100
-        if (slot == 0) {                                                             // ladder + PTEQ bookkeeping on rung 0's new state
-            tops0 += (NC == 1) | flag;                                               // :101-102
-            if (a.counts != nullptr && tops0 >= a.tops_burn) {                       // decoders.py:60-67
-                wu_lds_rw const hist = (wu_lds_rw)(uintptr_t)(xaddr + (uint32_t)ol.hist * 4u);
-                hist[(CODE == kCodeXzzx ? (cls ^ (cls >> 1)) : cls) * 64] += 1;
-                samples++;
-            }
+        if (slot == 0) {
+            if (!(TBOOKS && once)) book(flag, cls);
             flag = 0;                                                                // :103
         }
         } else {

@@ -85,8 +85,11 @@
         }
         if (a.resume) flag = a.flags[ladder * NC + slot];
     }
-    uint32_t tops0 = 0;                                               // wave 0's per-ladder bookkeeping (the criterion kernels: in LDS)
-    if (slot == 0 && a.resume && live) tops0 = a.tops0[s0 + lane];
+    // the booking wave's per-ladder bookkeeping (the criterion kernels: in LDS): wave 0's, or -- the walked forms of the lean tail, ladder_wu.hpp
+    // kWuTopBooks -- the top rung's, which hands tops0 and samples to wave 0's write-out below
+    const bool tbooks = wu_top_books_family(WV, CONV, ALPHA, STATS, LONG) && a.wu_once != 0;
+    uint32_t tops0 = 0;
+    if ((tbooks ? top : slot == 0) && a.resume && live) tops0 = a.tops0[s0 + lane];
     __syncthreads();
 
     uint32_t nef0 = 0;
@@ -126,8 +129,12 @@
         WU_EACH(QECMC_WU_PUT)
         wu_ds_wait<WV>(st);
         rec[slot * 64u + (uint32_t)lane] = pack_info(n4 >> 2, slot, cls, flag);
+        // (rows 0 and 1 of swd -- a walked ladder has five rungs or more -- are dead behind the barrier above: the last conversion of a swap word in place,
+        // by a wave that had left the step loop, lies in front of it)
+        if (tbooks && top) { lds[o.swd + lane] = tops0; lds[o.swd + 64 + lane] = samples; }
     }
     __syncthreads();
+    if (tbooks && slot == 0) { tops0 = lds[o.swd + lane]; samples = lds[o.swd + 64 + lane]; }
     if (a.counts != nullptr)
 #pragma unroll 1
         for (int i = tid; i < cnt * ncls; i += nthreads) {

@@ -5,7 +5,10 @@ usage: hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only -o wu.s 
        tools/wave_step_segments.py wu.s [mangled-name fragment of the kernel] [--rare N] [--verbose] [--keep i,j]
 
 For every outermost loop of the kernel that holds an s_barrier (the two roles: the top rung's wave, a wave below it) the script follows ONE path from the
-loop's header round to its back edge and prints the instructions between consecutive barriers.  The path is the common one by a simple rule: a forward
+loop's header round to its back edge and prints the instructions between consecutive barriers: header -> B1 -> B3 on the walked path of a step (two
+barriers since the records are published in front of the first), header -> B1 -> B2 on the replay's; which of the two the common-path rule follows is the
+compiler's layout -- --verbose lists the blocks it skipped and --keep follows the other (what stands between the barriers tells them apart: the walked
+path's stretch holds the next step's acceptance draw, the replay's the stores and the record alone).  The path is the common one by a simple rule: a forward
 conditional branch is taken when it skips --rare instructions or more, up to 400 (default 40: the refinement draw of a tie, the walk of a swap bound into the table,
 the refresh of a pick window) and falls through otherwise (an
 accepted move's update, a width test); unconditional branches are followed; inner loops are passed once.  Approximate by construction: CPU only, no GPU."""
@@ -45,8 +48,10 @@ def parse(body):
     return ins, labels, headers, member
 
 
-def walk(ins, labels, member, head, rare, fall=(), verbose=False):
+def walk(ins, labels, member, head, rare, fall=(), verbose=False, ops=None):
+    """the instruction counts of the stretches of one path round the loop of `head`, cut at its barriers; ops (a list): receives the stretches' opcodes"""
     at, n, segs, seen, steps = labels[head], 0, [], set(), 0
+    cur = []
     # the loop's extent: the blocks the compiler's comments assign to it (a forward branch beyond it leaves the loop and is not followed)
     blocks = [labels[l] for l, h in member.items() if h == head]
     if not blocks:
@@ -63,8 +68,12 @@ def walk(ins, labels, member, head, rare, fall=(), verbose=False):
             return None
         op = ins[at].split()
         n += 1
+        cur.append(op[0])
         if op[0] == "s_barrier":
             segs.append(n); n = 0
+            if ops is not None:
+                ops.append(cur)
+            cur = []
         elif op[0] == "s_branch" and op[1] in labels:
             if labels[op[1]] > at or labels[op[1]] == labels[head] or (at, 0) not in seen:      # (an inner loop: round once, then on)
                 seen.add((at, 0)); at = labels[op[1]]; continue
@@ -82,6 +91,8 @@ def walk(ins, labels, member, head, rare, fall=(), verbose=False):
             return None
         at += 1
     segs.append(n)
+    if ops is not None:
+        ops.append(cur)
     return segs
 
 
@@ -100,7 +111,7 @@ def main():
         segs = walk(ins, labels, member, h, rare, fall, "--verbose" in sys.argv)
         if not segs or len(segs) < 3:
             continue
-        # a step: header -> B1 -> B2 -> (B3) -> back edge; the stretch behind the last barrier and the one in front of the first are one segment
+        # a step: header -> B1 -> B3 (walked) or B1 -> B2 (replay) -> back edge; the stretch behind the last barrier and the one in front of the first are one segment
         print("%s  barriers %d  last barrier -> first: %d  then: %s  step total %d" % (h, len(segs) - 1, segs[-1] + segs[0], segs[1:-1], sum(segs)))
 
 
