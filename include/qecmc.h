@@ -412,7 +412,7 @@ int qecmc_class_marginals_site(int code, int L, uint64_t N, const uint8_t *chain
  * The arguments and results of qecmc_class_minplus and qecmc_class_minplus_site -- cost_out uint32[N][ncls], count_out uint64[N][ncls] (0 where
  * saturated), class_out int32[N] (nullable) -- on the plans of qecmc_class_sweep_tiled: hbm_width and tile_width are that function's, and
  * qecmc_class_sweep_tiled_info gives the plan's facts.  The result does not depend on tile_width, and where the holds are the cut plan's
- * (hbm_width = its lds_width) it is qecmc_class_minplus's.  There is no traceback on this route.
+ * (hbm_width = its lds_width) it is qecmc_class_minplus's.  qecmc_class_minplus_tiled_chains (below) traces a chain back.
  * The 16 bits of an entry's cost do not cover 255 per qubit at these shapes, so the cost range is checked per call: n_qubits * max(cost) < 2^16,
  * and for a table the sum over the plan's qubits of a row's largest cost at the qubit < 2^16 in every row (QECMC_ERR_UNSUPPORTED, the row named).
  * Additive: QECMC_ABI_VERSION stays.  Refused before a device is looked for, the message prefixed "qecmc_class_minplus_tiled:" /
@@ -423,6 +423,21 @@ int qecmc_class_minplus_tiled(int code, int L, uint64_t N, const uint8_t *chains
                               uint32_t *cost_out, uint64_t *count_out, int32_t *class_out);
 int qecmc_class_minplus_tiled_site(int code, int L, uint64_t N, const uint8_t *chains, const uint8_t *cq, uint64_t cq_rows, int hbm_width,
                                    int tile_width, uint32_t *cost_out, uint64_t *count_out, int32_t *class_out);
+
+/* ---- a shortest chain of every class on the tiled route: the tiled (min, +) sweep traced back (csrc/class_minplus_tiled_trace.hpp) ----
+ * qecmc_class_minplus_chains and qecmc_class_minplus_chains_site on the plans of qecmc_class_minplus_tiled: chain_out uint8[N][ncls][nq] --
+ * chain_out[s][c] has the syndrome of chain s, lies in class c and costs cost_out[s][c] --; cost_out, count_out and class_out are nullable and exactly
+ * those of qecmc_class_minplus_tiled / _site.  The chain is a pure function of (plan's stream and holds, representative, costs) under the tie rule
+ * of qecmc_class_minplus_chains: it does not depend on tile_width, and where the tiled plan's stream and holds are the cut plan's it is that
+ * function's chain byte for byte.  One more tiled pass per (syndrome, class) pair records one decision bit per FORGET and live state in a device
+ * block of its own, 2 GiB at most, kept per device; a plan whose single pair takes more is refused by name with its bytes.
+ * Additive: QECMC_ABI_VERSION stays.  Refused before a device is looked for, the message prefixed "qecmc_class_minplus_tiled_chains:" /
+ * "qecmc_class_minplus_tiled_chains_site:": a NULL chains / cost / cq / chain_out, N beyond 32 bits, and whatever qecmc_class_minplus_tiled / _site
+ * refuses, with its code -- the cost range included.  N == 0 succeeds.  Host pointers only; device 0. */
+int qecmc_class_minplus_tiled_chains(int code, int L, uint64_t N, const uint8_t *chains, const uint32_t cost[4], int hbm_width, int tile_width,
+                                     uint8_t *chain_out, uint32_t *cost_out, uint64_t *count_out, int32_t *class_out);
+int qecmc_class_minplus_tiled_chains_site(int code, int L, uint64_t N, const uint8_t *chains, const uint8_t *cq, uint64_t cq_rows, int hbm_width,
+                                          int tile_width, uint8_t *chain_out, uint32_t *cost_out, uint64_t *count_out, int32_t *class_out);
 
 /* ---- chain / ladder on caller-owned state (host pointers) ----------------- */
 

@@ -29,6 +29,7 @@
 #include "class_minplus_trace.hpp"
 #include "class_minplus_site.hpp"
 #include "class_minplus_tiled.hpp"
+#include "class_minplus_tiled_trace.hpp"
 #include "class_sample.hpp"
 #include "class_marginal.hpp"
 #include "enumerate.hpp"
@@ -1457,6 +1458,118 @@ int qecmc_class_minplus_tiled_site(int code, int L, uint64_t N, const uint8_t *c
                                                                             P, 0);
                                  },
                                  [&](const SweepBatch &b, uint64_t first, uint64_t here, uint64_t *P) { return fold(b, first, here, P); });
+}
+
+// ---------------------------------------------------------------- a shortest chain per class on the tiled route (class_minplus_tiled_trace.hpp)
+namespace {
+// The decision words of one trace pass: one block per device, taken when a traced call first needs more than is there and kept --
+// kTiledTraceWorkspaceBytes at most, never cleared.  Only the traced entry points touch it, and only while they hold the tiled workspace's lock.
+struct TiledTraceBlock {
+    void *p[TiledWorkspace::kDevices] = {};
+    size_t bytes[TiledWorkspace::kDevices] = {};
+    static TiledTraceBlock &get() { static TiledTraceBlock *b = new TiledTraceBlock; return *b; }   // (never destroyed, as DevPool)
+    hipError_t take(size_t want, void **out)                                      // under TiledWorkspace::mu
+    {
+        int dev = 0;
+        if (hipError_t e = hipGetDevice(&dev)) return e;
+        if (dev < 0 || dev >= TiledWorkspace::kDevices || want > minplus::kTiledTraceWorkspaceBytes) return hipErrorInvalidValue;
+        if (bytes[dev] < want) {
+            if (p[dev]) { (void)hipFree(p[dev]); p[dev] = nullptr; bytes[dev] = 0; }
+            if (hipError_t e = hipMalloc(&p[dev], want)) return e;
+            bytes[dev] = want;
+        }
+        *out = p[dev];
+        return hipSuccess;
+    }
+};
+
+// both traced entry points: cost (the four costs) or cq (a site table).  Per group of syndromes: the sweep passes of qecmc_class_minplus_tiled(_site),
+// the pick, the reduce, then trace passes of pairs -- as many as the state workspace and the decision block take -- each ending with its walk.
+int tiled_chains_impl(const char *name, int code, int L, uint64_t N, const uint8_t *chains, const uint32_t *cost, const uint8_t *cq, uint64_t cq_rows, int hbm_width,
+                      int tile_width, uint8_t *chain_out, uint32_t *cost_out, uint64_t *count_out, int32_t *class_out)
+{
+    if (!chains || (!cost && !cq) || !chain_out) return fail(QECMC_ERR_INVALID, "%s: NULL buffer", name);
+    if (N > 0xFFFFFFFFull) return fail(QECMC_ERR_INVALID, "%s: N=%llu syndromes exceed 32 bits", name, (unsigned long long)N);
+    if (cost)
+        if (int rc = report(minplus::check_tiled_chain_costs(nullptr, cost))) return rc;
+    const minplus::TiledTracePlan ttp = minplus::build_tiled_trace_plan(code, L, hbm_width, tile_width, name);
+    const sweep::TiledPlan &tp = ttp.tiled;
+    const sweep::Plan &p = tp.plan;
+    if (int rc = report(p.refusal)) return rc;
+    if (cost) {
+        if (int rc = report(minplus::check_tiled_chain_costs(&p, cost))) return rc;
+    } else {
+        if (int rc = report(minplus::check_cost_rows(name, N, cq_rows))) return rc;
+        if (!closes_within(tp.ops, p.nq)) return fail(QECMC_ERR_UNSUPPORTED, "%s: internal: a CLOSE names a cell beyond the %d of the table", name, p.nq);
+        if (N > 0)
+            if (int rc = report(minplus::check_tiled_chain_cost_rows_range(cq, cq_rows, p.nq, sweep::closed_qubits(tp.ops, p.nq)))) return rc;
+    }
+    if (p.W > 64) return fail(QECMC_ERR_UNSUPPORTED, "%s: internal: a chain of %d state words does not fit the lanes of the walk", name, p.W);
+    if (int rc = use_device(0)) return rc;
+    if (N == 0) return 0;
+    uint32_t cxz[4] = {0, 0, 0, 0};
+    if (cost) minplus::costs_xz(cost, cxz);
+    CostRows rows;
+    TiledFold fold(tp, cost_out, count_out);
+    DevBuf dwide, dftile, dfwords, dpick, dchain;
+    MinplusArgs pa = minplus_args(p, tp.n_held);
+    pa.width = tp.tile_width;                                                   // (k_minplus_pick reads n_held alone; its launch asks for a width an LDS vector has)
+    const uint64_t pair_bytes = minplus::tiled_trace_bytes_per_pair(ttp);
+    uint64_t *work = nullptr;                                                   // the state workspace, as the sweep passes of the call were handed it
+    return tiled_batch<uint64_t>(
+        tp, N, chains, class_out,
+        [&](uint32_t group) {
+            const size_t pairs = (size_t)group * p.ncls;
+            if (int rc = fold.open(group)) return rc;
+            if (cq)
+                if (int rc = rows.open(cq, cq_rows, p.nq, group)) return rc;
+            HIP_TRY(dwide.alloc(tp.ops.size() * sizeof(uint32_t)));
+            HIP_TRY(dftile.alloc(ttp.forget_tile.size() * sizeof(uint32_t)));
+            HIP_TRY(dfwords.alloc(ttp.forget_words.size() * sizeof(uint32_t)));
+            HIP_TRY(dpick.alloc(pairs * sizeof(uint32_t)));
+            HIP_TRY(dchain.alloc(pairs * (size_t)p.nq));
+            HIP_TRY(hipMemcpy(dwide.p, tp.ops.data(), tp.ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(dftile.p, ttp.forget_tile.data(), ttp.forget_tile.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(dfwords.p, ttp.forget_words.data(), ttp.forget_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            return 0;
+        },
+        [&](uint64_t first, uint64_t here) { return cq ? rows.group(first, here) : 0; },
+        [&](uint32_t unit_first, uint32_t units, const SweepBatch &b, uint64_t *w, uint64_t *P) {
+            work = w;
+            return cq ? launch_class_minplus_tiled_site(tp, rows.per_syndrome, unit_first, units, b.ops(), b.held(), b.rep(), rows.d.as<uint32_t>(), w, P, 0)
+                      : launch_class_minplus_tiled(tp, cxz, unit_first, units, b.ops(), b.held(), b.rep(), w, P, 0);
+        },
+        [&](const SweepBatch &b, uint64_t first, uint64_t here, uint64_t *P) {
+            pa.S = (uint32_t)here;
+            HIP_TRY(launch_minplus_pick(pa, P, dpick.as<uint32_t>(), 0));         // (before the reduce folds the partials in place)
+            if (int rc = fold(b, first, here, P)) return rc;
+            const uint64_t pairs = here * (uint64_t)p.ncls;
+            void *dec = nullptr;
+            HIP_TRY(TiledTraceBlock::get().take((size_t)(minplus::tiled_trace_pass_pairs(tp.state_bits, pair_bytes, pairs) * pair_bytes), &dec));
+            for (uint64_t first_pair = 0; first_pair < pairs;) {
+                const uint32_t n = minplus::tiled_trace_pass_pairs(tp.state_bits, pair_bytes, pairs - first_pair);
+                HIP_TRY(launch_minplus_tiled_trace(ttp, cq ? nullptr : cxz, cq ? rows.per_syndrome : 0, (uint32_t)first_pair, n, b.ops(), dwide.as<uint32_t>(), b.held(), b.rep(),
+                                                   cq ? rows.d.as<uint32_t>() : nullptr, dpick.as<uint32_t>(), dftile.as<uint32_t>(), dfwords.as<uint32_t>(), work,
+                                                   static_cast<uint64_t *>(dec), dchain.as<uint8_t>(), 0));
+                first_pair += n;
+            }
+            return b.fetch(chain_out, dchain, first, here, (size_t)p.nq);
+        });
+}
+}  // namespace
+
+int qecmc_class_minplus_tiled_chains(int code, int L, uint64_t N, const uint8_t *chains, const uint32_t cost[4], int hbm_width, int tile_width, uint8_t *chain_out,
+                                     uint32_t *cost_out, uint64_t *count_out, int32_t *class_out)
+{
+    if (!cost) return fail(QECMC_ERR_INVALID, "qecmc_class_minplus_tiled_chains: NULL buffer");
+    return tiled_chains_impl("qecmc_class_minplus_tiled_chains", code, L, N, chains, cost, nullptr, 0, hbm_width, tile_width, chain_out, cost_out, count_out, class_out);
+}
+
+int qecmc_class_minplus_tiled_chains_site(int code, int L, uint64_t N, const uint8_t *chains, const uint8_t *cq, uint64_t cq_rows, int hbm_width, int tile_width,
+                                          uint8_t *chain_out, uint32_t *cost_out, uint64_t *count_out, int32_t *class_out)
+{
+    if (!cq) return fail(QECMC_ERR_INVALID, "qecmc_class_minplus_tiled_chains_site: NULL buffer");
+    return tiled_chains_impl("qecmc_class_minplus_tiled_chains_site", code, L, N, chains, nullptr, cq, cq_rows, hbm_width, tile_width, chain_out, cost_out, count_out, class_out);
 }
 
 // ---------------------------------------------------------------- chain / ladder

@@ -11,6 +11,7 @@
 #include "class_minplus_trace.hpp"
 #include "class_minplus_site.hpp"
 #include "class_minplus_tiled.hpp"
+#include "class_minplus_tiled_trace.hpp"
 #include "class_sample.hpp"
 #include "class_marginal.hpp"
 #include "corrections.hpp"
@@ -641,6 +642,71 @@ int qt_class_minplus_tiled_site(int code, int L, uint64_t N, const uint8_t *chai
         if (const Refusal r = minplus::check_tiled_cost_rows_range(cq, cq_rows, tp.plan.nq, sweep::closed_qubits(tp.ops, tp.plan.nq)); r.code) return site_answer(r, msg, msg_cap);
     minplus::minplus_tiled_site_host(tp, N, chains, cq, cq_rows, cost_out, count_out, cls);
     return site_answer({}, msg, msg_cap);
+}
+// the traceback on the tiled plans (class_minplus_tiled_trace.hpp).  qt_class_minplus_tiled_chains (cost given) / ..._site (cq given): the host twins of
+// qecmc_class_minplus_tiled_chains and ..._chains_site behind the same host checks, in the same order -- the QECMC_ERR_* code of the refusal, its message
+// in msg (nullable); qt_class_minplus_tiled_trace_plan: forget_gen int32[n_forget], forget_words uint32[n_forget][W], forget_tile uint32[n_forget][4] and
+// seg_forget uint32[n_segments] (all nullable) under a decision block of `cap` bytes (0: the library's) -> n_forget, -1 where refused (the message in msg)
+// or too small a buffer (cap_forget rows), and through out8 (nullable) n_forget, words_per_tile, W, bytes_per_pair, the library's cap, state_bits,
+// n_segments and n_held; qt_class_minplus_tiled_trace_pass: the pairs of one trace pass
+static int tiled_chains_answer(const char *name, int code, int L, uint64_t N, const uint8_t *chains, const uint32_t *cost, const uint8_t *cq, uint64_t cq_rows, int hbm_width,
+                               int tile_width, uint8_t *chain_out, uint32_t *cost_out, uint64_t *count_out, int32_t *cls, char *msg, int msg_cap)
+{
+    if (!chains || (!cost && !cq) || !chain_out) return site_answer(refuse_params(QECMC_ERR_INVALID, "%s: NULL buffer", name), msg, msg_cap);
+    if (N > 0xFFFFFFFFull) return site_answer(refuse_params(QECMC_ERR_INVALID, "%s: N=%llu syndromes exceed 32 bits", name, (unsigned long long)N), msg, msg_cap);
+    if (cost)
+        if (const Refusal r = minplus::check_tiled_chain_costs(nullptr, cost); r.code) return site_answer(r, msg, msg_cap);
+    const minplus::TiledTracePlan ttp = minplus::build_tiled_trace_plan(code, L, hbm_width, tile_width, name);
+    const sweep::TiledPlan &tp = ttp.tiled;
+    if (tp.plan.refusal.code) return site_answer(tp.plan.refusal, msg, msg_cap);
+    if (cost) {
+        if (const Refusal r = minplus::check_tiled_chain_costs(&tp.plan, cost); r.code) return site_answer(r, msg, msg_cap);
+        minplus::minplus_tiled_trace_host(ttp, N, chains, cost, chain_out, cost_out, count_out, cls);
+    } else {
+        if (const Refusal r = minplus::check_cost_rows(name, N, cq_rows); r.code) return site_answer(r, msg, msg_cap);
+        if (N > 0)
+            if (const Refusal r = minplus::check_tiled_chain_cost_rows_range(cq, cq_rows, tp.plan.nq, sweep::closed_qubits(tp.ops, tp.plan.nq)); r.code)
+                return site_answer(r, msg, msg_cap);
+        minplus::minplus_tiled_trace_site_host(ttp, N, chains, cq, cq_rows, chain_out, cost_out, count_out, cls);
+    }
+    return site_answer({}, msg, msg_cap);
+}
+int qt_class_minplus_tiled_chains(int code, int L, uint64_t N, const uint8_t *chains, const uint32_t *cost, int hbm_width, int tile_width, uint8_t *chain_out,
+                                  uint32_t *cost_out, uint64_t *count_out, int32_t *cls, char *msg, int msg_cap)
+{
+    if (!cost) return site_answer(refuse_params(QECMC_ERR_INVALID, "qecmc_class_minplus_tiled_chains: NULL buffer"), msg, msg_cap);
+    return tiled_chains_answer("qecmc_class_minplus_tiled_chains", code, L, N, chains, cost, nullptr, 0, hbm_width, tile_width, chain_out, cost_out, count_out, cls, msg, msg_cap);
+}
+int qt_class_minplus_tiled_chains_site(int code, int L, uint64_t N, const uint8_t *chains, const uint8_t *cq, uint64_t cq_rows, int hbm_width, int tile_width,
+                                       uint8_t *chain_out, uint32_t *cost_out, uint64_t *count_out, int32_t *cls, char *msg, int msg_cap)
+{
+    if (!cq) return site_answer(refuse_params(QECMC_ERR_INVALID, "qecmc_class_minplus_tiled_chains_site: NULL buffer"), msg, msg_cap);
+    return tiled_chains_answer("qecmc_class_minplus_tiled_chains_site", code, L, N, chains, nullptr, cq, cq_rows, hbm_width, tile_width, chain_out, cost_out, count_out, cls,
+                               msg, msg_cap);
+}
+int qt_class_minplus_tiled_trace_plan(int code, int L, int hbm_width, int tile_width, uint64_t cap, int32_t *forget_gen, uint32_t *forget_words, uint32_t *forget_tile,
+                                      uint32_t *seg_forget, int cap_forget, uint64_t *out8, char *msg, int msg_cap)
+{
+    const minplus::TiledTracePlan ttp =
+        minplus::build_tiled_trace_plan(code, L, hbm_width, tile_width, "qecmc_class_minplus_tiled_chains", cap ? cap : minplus::kTiledTraceWorkspaceBytes);
+    const sweep::TiledPlan &tp = ttp.tiled;
+    if (tp.plan.refusal.code) { site_answer(tp.plan.refusal, msg, msg_cap); return -1; }
+    if ((forget_gen || forget_words || forget_tile) && ttp.n_forget > cap_forget) return -1;
+    if (seg_forget && (int)tp.segments.size() > cap_forget) return -1;
+    if (forget_gen)
+        for (int i = 0; i < ttp.n_forget; ++i) forget_gen[i] = ttp.forget_gen[(size_t)i];
+    if (forget_words) std::memcpy(forget_words, ttp.forget_words.data(), ttp.forget_words.size() * sizeof(uint32_t));
+    if (forget_tile) std::memcpy(forget_tile, ttp.forget_tile.data(), ttp.forget_tile.size() * sizeof(uint32_t));
+    if (seg_forget) std::memcpy(seg_forget, ttp.seg_forget.data(), ttp.seg_forget.size() * sizeof(uint32_t));
+    if (out8) {
+        out8[0] = (uint64_t)ttp.n_forget; out8[1] = (uint64_t)ttp.words_per_tile; out8[2] = (uint64_t)tp.plan.W; out8[3] = minplus::tiled_trace_bytes_per_pair(ttp);
+        out8[4] = minplus::kTiledTraceWorkspaceBytes; out8[5] = (uint64_t)tp.state_bits; out8[6] = (uint64_t)tp.segments.size(); out8[7] = (uint64_t)tp.n_held;
+    }
+    return ttp.n_forget;
+}
+uint32_t qt_class_minplus_tiled_trace_pass(int state_bits, uint64_t bytes_per_pair, uint64_t pairs_left, uint64_t cap)
+{
+    return minplus::tiled_trace_pass_pairs(state_bits, bytes_per_pair, pairs_left, cap ? cap : minplus::kTiledTraceWorkspaceBytes);
 }
 // the top rung's frames of a pick window (wu_frames.hpp) for an accepted scan = wave block, from the window's 64 pick blocks picks[64][4]: the plan's
 // descriptors and logical masks (rows padded to the kernel's WV words, as the kernel stages them), thr16 from the plan's thr_logical as wu_run forms it.

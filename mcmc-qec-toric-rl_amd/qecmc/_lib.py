@@ -104,6 +104,8 @@ SIGNATURES = {
     "qecmc_class_minplus_chains_site": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, _u8p, C.c_uint64, C.c_int, _u8p, _u32p, _u64p, _i32p]),
     "qecmc_class_minplus_tiled": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, _u32p, C.c_int, C.c_int, _u32p, _u64p, _i32p]),
     "qecmc_class_minplus_tiled_site": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, _u8p, C.c_uint64, C.c_int, C.c_int, _u32p, _u64p, _i32p]),
+    "qecmc_class_minplus_tiled_chains": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, _u32p, C.c_int, C.c_int, _u8p, _u32p, _u64p, _i32p]),
+    "qecmc_class_minplus_tiled_chains_site": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, _u8p, C.c_uint64, C.c_int, C.c_int, _u8p, _u32p, _u64p, _i32p]),
     "qecmc_class_marginals": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32p]),
     "qecmc_class_marginals_site": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, C.POINTER(C.c_double), C.c_uint64, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                              _i32p]),

@@ -34,7 +34,11 @@ sample_posterior draws the class first, posterior_error_counts is the exact yard
 
 Exact marginals (qecmc_class_marginals, qecmc_class_marginals_site): the same forward sweep with a record of every CLOSE and a
 backward sweep over the same stream -- class_marginals and class_marginals_site give, per class, the weight with which every qubit carries I, X, Y
-or Z; posterior_marginals mixes the classes with Z_c / Z; exact_error_counts is the exact value of what posterior_error_counts estimates."""
+or Z; posterior_marginals mixes the classes with Z_c / Z; exact_error_counts is the exact value of what posterior_error_counts estimates.
+
+The traceback on the tiled route (qecmc_class_minplus_tiled_chains, _chains_site): shortest_chains_tiled and
+shortest_chains_tiled_site return a shortest chain of every class at the shapes only the tiled sweep takes; min_weight_corrections and
+min_weight_corrections_site reach them with method="tiled"."""
 import ctypes as C
 
 import numpy as np
@@ -233,11 +237,28 @@ def shortest_chains(code, chains, costs=(0, 1, 1, 1), size=None, lds_width=0):
                 held=info["held"])
 
 
-def min_weight_corrections(code, chains, costs=(0, 1, 1, 1), size=None, lds_width=0):
+def _chains_by_method(code, chains, costs, site_costs, method, size=None, lds_width=0, hbm_width=0, tile_width=0):
+    """shortest_chains / shortest_chains_site (method "cut", the default: lds_width) or shortest_chains_tiled / shortest_chains_tiled_site (method
+    "tiled", only where it is named: hbm_width, tile_width); a width of the other route is refused by name, as _minplus_by_method refuses it"""
+    if method not in _MINPLUS_METHODS:
+        raise ValueError(f"method={method!r}: the (min, +) sweep runs on the cut plans ('cut') or tiled over HBM ('tiled')")
+    if method == "cut":
+        if hbm_width or tile_width:
+            raise ValueError("hbm_width and tile_width belong to method='tiled'; method='cut' takes lds_width")
+        return shortest_chains(code, chains, costs, size=size, lds_width=lds_width) if site_costs is None else \
+            shortest_chains_site(code, chains, site_costs, size=size, lds_width=lds_width)
+    if lds_width:
+        raise ValueError("lds_width belongs to method='cut'; method='tiled' takes hbm_width and tile_width")
+    return shortest_chains_tiled(code, chains, costs, size=size, hbm_width=hbm_width, tile_width=tile_width) if site_costs is None else \
+        shortest_chains_tiled_site(code, chains, site_costs, size=size, hbm_width=hbm_width, tile_width=tile_width)
+
+
+def min_weight_corrections(code, chains, costs=(0, 1, 1, 1), size=None, lds_width=0, method="cut", hbm_width=0, tile_width=0):
     """The minimum-weight decoder's correction: dict(correction uint8[N, ...]: the traced shortest chain (shortest_chains) of target, target int32[N]:
     the class min_weight_classes picks -- the least cost, ties by the larger count, then by the lower class index --, weight uint32[N]: the
-    correction's cost, the least of its row).  Nothing with the syndrome of the input is cheaper than the correction."""
-    r = shortest_chains(code, chains, costs, size=size, lds_width=lds_width)
+    correction's cost, the least of its row).  Nothing with the syndrome of the input is cheaper than the correction.
+    method="tiled" traces shortest_chains_tiled's sweep instead (hbm_width, tile_width as it takes them): the shapes past the cut plans."""
+    r = _chains_by_method(code, chains, costs, None, method, size=size, lds_width=lds_width, hbm_width=hbm_width, tile_width=tile_width)
     target = _rank_classes(r["cost"], r["count"])
     rows = np.arange(len(target))
     return dict(correction=r["chains"][rows, target], target=target, weight=r["cost"][rows, target])
@@ -336,10 +357,11 @@ def min_weight_classes_site(code, chains, site_costs, size=None, lds_width=0, me
     return _rank_classes(r["cost"], r["count"])
 
 
-def min_weight_corrections_site(code, chains, site_costs, size=None, lds_width=0):
-    """min_weight_corrections under site costs: dict(correction: the traced shortest chain (shortest_chains_site) of target, target: the class
-    min_weight_classes_site picks, weight uint32[N]: the correction's cost under the table, the least of its row)"""
-    r = shortest_chains_site(code, chains, site_costs, size=size, lds_width=lds_width)
+def min_weight_corrections_site(code, chains, site_costs, size=None, lds_width=0, method="cut", hbm_width=0, tile_width=0):
+    """min_weight_corrections under site costs: dict(correction: the traced shortest chain (shortest_chains_site; method="tiled":
+    shortest_chains_tiled_site) of target, target: the class min_weight_classes_site picks, weight uint32[N]: the correction's cost under the table,
+    the least of its row)"""
+    r = _chains_by_method(code, chains, None, site_costs, method, size=size, lds_width=lds_width, hbm_width=hbm_width, tile_width=tile_width)
     target = _rank_classes(r["cost"], r["count"])
     rows = np.arange(len(target))
     return dict(correction=r["chains"][rows, target], target=target, weight=r["cost"][rows, target])
@@ -414,8 +436,8 @@ def class_minplus_tiled(code, chains, costs=(0, 1, 1, 1), size=None, hbm_width=0
     """class_minplus on the state vector tiled over HBM (qecmc_class_minplus_tiled): the least cost of every class and the number of
     chains that reach it at xzzx / rotated L = 13 .. 21, planar L = 8 .. 12 and the toric code at L = 7 -- class_sweep_tiled's plans in the semiring of
     (cost, count) pairs.  code, chains and costs as class_minplus takes them, hbm_width and tile_width as class_sweep_tiled's; the result does not depend
-    on tile_width.  The costs must keep a chain's cost below 2^16: n_qubits * max(costs) < 65536, refused by name otherwise.  There is no traceback on
-    this route.
+    on tile_width.  The costs must keep a chain's cost below 2^16: n_qubits * max(costs) < 65536, refused by name otherwise.  shortest_chains_tiled
+    traces a chain back.
     Returns class_minplus's dict, key for key -- cost uint32[N, ncls], count uint64[N, ncls], saturated bool[N, ncls], cls int32[N], width, held: the
     tiled plan's -- plus segments: the launches one pass of state vectors takes."""
     code = _CODES.get(code, code)
@@ -449,6 +471,50 @@ def class_minplus_tiled_site(code, chains, site_costs, size=None, hbm_width=0, t
                                                      count.ctypes.data_as(L_._u64p), L_.i32(cls)))
     info = sweep_tiled_info(code, L, hbm_width, tile_width)
     return dict(cost=cost, count=count, saturated=count == 0, cls=cls, width=info["width"], held=info["held"], segments=info["segments"])
+
+
+def shortest_chains_tiled(code, chains, costs=(0, 1, 1, 1), size=None, hbm_width=0, tile_width=0):
+    """shortest_chains on the state vector tiled over HBM (qecmc_class_minplus_tiled_chains): a shortest chain of every class at xzzx /
+    rotated L = 13 .. 21, planar L = 8 .. 12 and the toric code at L = 7 -- class_minplus_tiled's sweep traced back.  The arguments are
+    class_minplus_tiled's.  Returns shortest_chains' dict -- chains uint8[N, ncls, ...], cost, count, saturated, unique, cls, width, held: the tiled
+    plan's -- plus segments.  The chain obeys shortest_chains' tie rule in the plan's own stream: it does not depend on tile_width, and where the
+    tiled plan's stream and holds are the cut plan's it is shortest_chains' chain byte for byte."""
+    code = _CODES.get(code, code)
+    flat, L = _as_chains(code, chains, size)
+    c = np.asarray(costs, dtype=np.float64)
+    if c.shape != (4,) or not np.all((c >= 0) & (c <= 0xFFFFFFFF) & (c == np.floor(c))):
+        raise ValueError(f"costs={costs!r}: the four integer costs of I, X, Y and Z, each >= 0")
+    c = c.astype(np.uint32)
+    n, ncls = flat.shape[0], 16 if code == L_.TORIC else 4
+    out = np.zeros((n, ncls, flat.shape[1]), dtype=np.uint8)
+    cost = np.zeros((n, ncls), dtype=np.uint32)
+    count = np.zeros((n, ncls), dtype=np.uint64)
+    cls = np.zeros(n, dtype=np.int32)
+    L_.check(L_.lib().qecmc_class_minplus_tiled_chains(code, L, n, L_.u8(flat), c.ctypes.data_as(L_._u32p), int(hbm_width), int(tile_width), L_.u8(out),
+                                                       cost.ctypes.data_as(L_._u32p), count.ctypes.data_as(L_._u64p), L_.i32(cls)))
+    info = sweep_tiled_info(code, L, hbm_width, tile_width)
+    state = (2, L, L) if code in (L_.TORIC, L_.PLANAR) else (L, L)
+    return dict(chains=out.reshape((n, ncls) + state), cost=cost, count=count, saturated=count == 0, unique=count == 1, cls=cls, width=info["width"],
+                held=info["held"], segments=info["segments"])
+
+
+def shortest_chains_tiled_site(code, chains, site_costs, size=None, hbm_width=0, tile_width=0):
+    """shortest_chains_tiled under a cost per qubit, or per (syndrome, qubit) (qecmc_class_minplus_tiled_chains_site): site_costs as
+    class_minplus_site takes them, the widths and the cost range as class_minplus_tiled_site's.  Returns shortest_chains_tiled's dict, key for key."""
+    code = _CODES.get(code, code)
+    flat, L = _as_chains(code, chains, size)
+    n, ncls = flat.shape[0], 16 if code == L_.TORIC else 4
+    cq, rows = _as_site_costs(code, site_costs, L, n)
+    out = np.zeros((n, ncls, flat.shape[1]), dtype=np.uint8)
+    cost = np.zeros((n, ncls), dtype=np.uint32)
+    count = np.zeros((n, ncls), dtype=np.uint64)
+    cls = np.zeros(n, dtype=np.int32)
+    L_.check(L_.lib().qecmc_class_minplus_tiled_chains_site(code, L, n, L_.u8(flat), L_.u8(cq), rows, int(hbm_width), int(tile_width), L_.u8(out),
+                                                            cost.ctypes.data_as(L_._u32p), count.ctypes.data_as(L_._u64p), L_.i32(cls)))
+    info = sweep_tiled_info(code, L, hbm_width, tile_width)
+    state = (2, L, L) if code in (L_.TORIC, L_.PLANAR) else (L, L)
+    return dict(chains=out.reshape((n, ncls) + state), cost=cost, count=count, saturated=count == 0, unique=count == 1, cls=cls, width=info["width"],
+                held=info["held"], segments=info["segments"])
 
 
 def class_weights(hist, weight):

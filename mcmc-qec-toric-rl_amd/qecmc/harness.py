@@ -273,16 +273,20 @@ def _corrections_for(code, size, candidates, distr, device):
 
 
 def _correction_route(params, method):
-    """params['correction']: None (default: qecmc.corrections -- class move and greedy descent) or "shortest" (method min_weight only: the traced
-    shortest chain of the target class, qecmc.shortest_chains); refused by name under any other method"""
+    """params['correction']: None (default: qecmc.corrections -- class move and greedy descent), "shortest" (method min_weight on the cut plans: the
+    traced shortest chain of the target class, qecmc.shortest_chains) or "shortest_tiled" (method min_weight with
+    params['exact_method'] = "tiled": qecmc.shortest_chains_tiled); refused by name under any other method or route"""
     route = params.get("correction")
-    if route not in (None, "shortest"):
-        raise ValueError(f"params['correction']={route!r}: 'shortest', or absent for qecmc.corrections")
-    if route == "shortest" and method != "min_weight":
-        raise ValueError(f"params['correction']='shortest' is built for method min_weight, not {method}: only the (min, +) sweep traces a shortest chain")
+    if route not in (None, "shortest", "shortest_tiled"):
+        raise ValueError(f"params['correction']={route!r}: 'shortest', 'shortest_tiled', or absent for qecmc.corrections")
+    if route is not None and method != "min_weight":
+        raise ValueError(f"params['correction']={route!r} is built for method min_weight, not {method}: only the (min, +) sweep traces a shortest chain")
     if route == "shortest" and params.get("exact_method") == "tiled":
         raise ValueError("params['correction']='shortest' is not built for params['exact_method']='tiled': the tiled (min, +) sweep has no traceback; "
-                         "leave 'correction' out for qecmc.corrections")
+                         "leave 'correction' out for qecmc.corrections (its own traceback goes by params['correction']='shortest_tiled')")
+    if route == "shortest_tiled" and params.get("exact_method") != "tiled":
+        raise ValueError(f"params['correction']='shortest_tiled' is built for params['exact_method']='tiled', not {params.get('exact_method')!r}: "
+                         "the cut plans trace by params['correction']='shortest'")
     return route
 
 
@@ -293,19 +297,25 @@ def _site_costs_route(params, method):
 
 
 def _shortest_corrections_for(params, chains, distr, device):
-    """_corrections_for by params['correction'] = "shortest": target = argmax(distr) and, in the keys of qecmc.corrections, the traced shortest chain of
+    """_corrections_for by params['correction'] = "shortest" / "shortest_tiled": target = argmax(distr) and, in the keys of qecmc.corrections, the traced shortest chain of
     that class under the costs _min_weight_distr decodes with -- params['site_costs'] where given -- weight its error count, source 0, moved: target is
     not the start chain's class"""
-    from .exact import shortest_chains, shortest_chains_site
+    from .exact import shortest_chains, shortest_chains_site, shortest_chains_tiled, shortest_chains_tiled_site
     noise = params.get("noise", "depolarizing")
     if device != 0:
         raise ValueError("method min_weight runs on device 0: the library has no device-pointer form of it yet")
     costs = (0, int(params["alpha"]), int(params["alpha"]), 1) if noise == "alpha" else (0, 1, 1, 1)
     target = np.argmax(distr, axis=1).astype(np.int32)
-    if params.get("site_costs") is not None:
-        r = shortest_chains_site(params["code"], chains, params["site_costs"], size=params["size"], lds_width=int(params.get("lds_width", 0)))
+    if params.get("correction") == "shortest_tiled":                            # (the widths _min_weight_distr swept with)
+        kw = dict(size=params["size"], hbm_width=int(params.get("hbm_width", 0)), tile_width=int(params.get("tile_width", 0)))
+        one, site = shortest_chains_tiled, shortest_chains_tiled_site
     else:
-        r = shortest_chains(params["code"], chains, costs, size=params["size"], lds_width=int(params.get("lds_width", 0)))
+        kw = dict(size=params["size"], lds_width=int(params.get("lds_width", 0)))
+        one, site = shortest_chains, shortest_chains_site
+    if params.get("site_costs") is not None:
+        r = site(params["code"], chains, params["site_costs"], **kw)
+    else:
+        r = one(params["code"], chains, costs, **kw)
     cor = r["chains"][np.arange(len(target)), target]
     return target, dict(corrections=cor, weight=(cor != 0).reshape(len(cor), -1).sum(axis=1).astype(np.int32), source=np.zeros(len(cor), np.int32),
                         moved=(target != r["cls"]).astype(np.uint8))
@@ -313,7 +323,7 @@ def _shortest_corrections_for(params, chains, distr, device):
 
 def _correction_outputs(code, size, raw, init, distr, device, params=None):
     """generate's corrections=True: the correction of every start chain towards argmax(distr), its weight, and whether raw ^ correction is a stabilizer"""
-    if params is not None and params.get("correction") == "shortest":
+    if params is not None and params.get("correction") in ("shortest", "shortest_tiled"):
         _, cor = _shortest_corrections_for(params, init, distr, device)
     else:
         _, cor = _corrections_for(code, size, init, distr, device)
@@ -341,7 +351,8 @@ def decode_syndromes(params, defects, seed=0, steps=100000, conv_criteria="error
     run (conv_criteria=None).  A run the convergence criterion stops may go to the work-queue kernels, which write no final states: ValueError.
     params['correction'] = "shortest" (method min_weight only, refused by name elsewhere): correction is the traced shortest chain of the target class
     (qecmc.shortest_chains) instead of qecmc.corrections' class move and descent; correction_source is 0 and correction_moved says whether the target
-    is another class than the lifted chain's."""
+    is another class than the lifted chain's.  params['correction'] = "shortest_tiled" is the same on the tiled route (params['exact_method'] = "tiled",
+    qecmc.shortest_chains_tiled), refused by name elsewhere."""
     from .syndrome_lift import chains_from_syndromes
     method = params.get("method", "PTEQ")
     if method not in ("PTEQ", "exact", "min_weight"):
@@ -366,7 +377,7 @@ def decode_syndromes(params, defects, seed=0, steps=100000, conv_criteria="error
         distr_of = _exact_distr if method == "exact" else _min_weight_distr
         out = dict(distr=distr_of(params, chains, int(pteq_kw.get("device", 0))), chains=chains, status=status, weight=weight)
         if corrections:
-            if route == "shortest":
+            if route in ("shortest", "shortest_tiled"):
                 target, cor = _shortest_corrections_for(params, chains, out["distr"], int(pteq_kw.get("device", 0)))
             else:
                 target, cor = _corrections_for(_CODES[params["code"]], params["size"], chains, out["distr"], int(pteq_kw.get("device", 0)))
@@ -426,7 +437,9 @@ def erasure_experiment(params, n, seed=0, method="exact"):
     min_weight) under qecmc.erasure_site_costs of the noise's costs: (0, 1, 1, 1) for depolarizing noise, (0, alpha, alpha, 1) for
     the alpha model with an integer alpha, an erased qubit free; biased noise is refused as _min_weight_distr refuses it.
     Returns dict(distr float64[n, ncls], eq_true: the class of the true error, success: argmax(distr) == eq_true, erased bool[n, ...], chains: the
-    start chains the syndromes were lifted to)."""
+    start chains the syndromes were lifted to).  params['correction'] ("shortest", or "shortest_tiled" with params['exact_method'] = "tiled"; method
+    min_weight) adds target, correction -- the shortest chain of the target class under the shot's erasure costs -- and correction_weight, its error
+    count (erased cells included)."""
     from .exact import alpha_w4, biased_w4, depolarizing_w4, erasure_site_costs, erasure_site_w4
     code, size, p = _CODES[params["code"]], params["size"], params["p_error"]
     noise = params.get("noise", "depolarizing")
@@ -455,9 +468,13 @@ def erasure_experiment(params, n, seed=0, method="exact"):
         decode.pop("site_weights", None)
     else:
         decode = dict(params, method="exact", site_weights=erasure_site_w4(base, erased))
-    out = decode_syndromes(decode, syndrome_of(code, errors))
+    traced = decode.get("correction") is not None                               # (method min_weight only: _correction_route refuses it elsewhere)
+    out = decode_syndromes(decode, syndrome_of(code, errors), corrections=traced)
     eq_true = np.asarray(_class_of(code, errors)).astype(np.int32)
-    return dict(distr=out["distr"], eq_true=eq_true, success=np.argmax(out["distr"], axis=1) == eq_true, erased=erased, chains=out["chains"])
+    res = dict(distr=out["distr"], eq_true=eq_true, success=np.argmax(out["distr"], axis=1) == eq_true, erased=erased, chains=out["chains"])
+    if traced:
+        res.update(target=out["target"], correction=out["correction"], correction_weight=out["correction_weight"])
+    return res
 
 
 def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_criteria="error_based", biased_decoder="alpha",
@@ -493,7 +510,9 @@ def generate(params, nbr_datapoints, seed=0, file_path=None, steps=100000, conv_
     raw[s] ^ correction[s] (byte values XOR as the Pauli product) is a stabilizer: an all-zero syndrome and the class of the zero chain.
     params['correction'] = "shortest" (method min_weight with corrections=True; refused by name under any other method) makes correction the traced
     shortest chain of argmax(distr) instead (qecmc.shortest_chains): no chain of that class is lighter; correction_weight and
-    success_correction keep their meaning.  The default stays the qecmc.corrections route.
+    success_correction keep their meaning.  The default stays the qecmc.corrections route.  params['correction'] = "shortest_tiled" is the same with
+    params['exact_method'] = "tiled" (qecmc.shortest_chains_tiled, DESIGN.md 4.1u: rotated L = 13 .. 21, planar L = 8 .. 12, toric L = 7), refused by name elsewhere;
+    "shortest" stays refused there.
     Returns (and optionally saves as npz) qubit_matrix uint8[n,...] (the raw errors, generate_data.py:120),
     eq_true int32[n], counts uint32[n,ncls], distr uint8[n,ncls] (what PTEQ returns), success bool[n]
     (argmax(distr) == eq_true, generate_data.py:139), steps_done, converged."""
