@@ -384,8 +384,9 @@ int qecmc_class_minplus_chains_site(int code, int L, uint64_t N, const uint8_t *
  * Additive: QECMC_ABI_VERSION stays.  Refused before a device is looked for, the message prefixed "qecmc_class_sample:" /
  * "qecmc_class_sample_site:": a NULL chains / w / wq / chain_out / z_out (class_out in mode 1), K = 0 or K >= 2^32, first_syndrome + N past
  * 2^32, a mode other than 0 and 1, a weight that is negative or not finite, and whatever qecmc_class_sweep_cut / _cut_site refuses, with its
- * code.  Refused once z is known, with QECMC_ERR_INVALID: in mode 0 a class whose weight is 0 or not finite, by row and class; in mode 1 a
- * row whose total is.  N == 0 succeeds.  Host pointers only; device 0. */
+ * code.  Refused once z is known, with QECMC_ERR_INVALID: in mode 0 a class whose weight is 0, not finite or below 2^-960 (the sweep is not
+ * rescaled: below that the record is rounded in the subnormal range and the draws would not follow the law), by row and class; in mode 1 a
+ * row whose total is.  A drawn chain has weight > 0 at every range.  N == 0 succeeds.  Host pointers only; device 0. */
 int qecmc_class_sample(int code, int L, uint64_t N, const uint8_t *chains, const double w[4], int lds_width, uint64_t K, uint64_t seed,
                        uint32_t first_syndrome, int mode, uint8_t *chain_out, int32_t *class_out, double *z_out);
 int qecmc_class_sample_site(int code, int L, uint64_t N, const uint8_t *chains, const double *wq, uint64_t wq_rows, int lds_width, uint64_t K,

@@ -8,21 +8,28 @@
 // of philox_block(k << 16 | block, kSubSample, first_syndrome + s, stream, seed).
 //     1. PARTIALS   P[h] for every assignment h of the held generators, as sweep_cut_host forms them; Z_c = cut_reduce of them: qecmc_class_sweep_cut's bits.
 //     2. PICK       (n_held > 0 only; else h* = 0 and no draw is spent)  C_0 = P[0], C_h = C_(h-1) + P[h], sequential adds in ascending h;
-//                   u = u53(0, 0) on stream c; h* = the lowest h with u * C_last < C_h.  One multiply, one compare, no division anywhere.
+//                   u = u53(0, 0) on stream c; h* = the lowest h with u * C_last < C_h || C_h == C_last.  One multiply, two compares, no division anywhere.
 //     3. RECORD     the op loop under h*; at FORGET number fi (its ordinal in the stream), for every live f with the slot bit clear the pair
 //                       (on, s) = (A[f | bit], A[f] + A[f | bit])        -- s is the very double the FORGET leaves in A[f] --
 //                   is kept at (fi, h), h = remove_bit(f, slot): 16 bytes, record[fi * 2^(width - 1) + h].  Dead f keep nothing and are never read.
 //     4. WALK       f = 0, chain = cut_representative(cp, rep_c, h*); through the ops in reverse: FORGET: (on, s) at (fi, remove_bit(f, slot)),
-//                   u = u53(1 + (fi >> 1), fi & 1) on stream c, the generator is taken iff u * s < on: f |= bit, chain ^= forget_words[fi];
+//                   u = u53(1 + (fi >> 1), fi & 1) on stream c, the generator is taken iff u * s < on || on == s: f |= bit, chain ^= forget_words[fi];
 //                   INTRO: f &= ~bit; CLOSE: nothing.  The walk ends at f == 0.
 //     5. RESULT     the chain as bytes uint8[nq]; a cell no generator touches keeps the representative's byte.
 // POSTERIOR MODE draws the class first: running sums of Z_c in ascending c, u = u53(0, 0) on stream ncls -- which no class owns --, the class is
-// the lowest c with u * Z_total < (running sum); sample (s, k) of the posterior is then sample (s, cls[s, k], k) of the every-class mode.
+// the lowest c with u * Z_total < (running sum) || (running sum) == Z_total; sample (s, k) of the posterior is then sample (s, cls[s, k], k) of the
+// every-class mode.
 //
 // A sample depends on (seed, first_syndrome + s, c, k, plan, representative, weights) alone: not on N, K, the launch grouping or the other samples.
-// Every taken branch has probability on / s up to the 2^-53 grain of u and one rounding; a branch of weight 0 is never taken (u * s < 0 is false),
-// so pure erasure is exact.  The kernels (class_sample.inc) and the twin below run the same single multiplies, adds and compares -- both built
-// without floating-point contraction -- and agree byte for byte.
+// Every taken branch has probability on / s up to the 2^-53 grain of u and one rounding.  SUPPORT holds at every range by construction, not by a
+// floor: the walk starts at a partial > 0 (a pick never lands on an entry of 0: its running sum is its predecessor's, which would have been picked) and
+// s > 0 at every FORGET on its path, so on == 0 is never taken (u * s < 0 is false, and on == s would make s 0), and a branch is declined only where
+// on != s, that is off != 0.  Every state the walk visits therefore has A > 0, every CLOSE factor on its path is positive, and the drawn chain has
+// weight > 0 -- pure erasure is exact, and so is a subnormal s, where u * s rounds back up to s and the first compare alone would decline a forced
+// branch.  In the normal range the second compare of either rule is implied by the first (u <= 1 - 2^-53): no draw there depends on it.  THE LAW is a
+// question of range: below kSampleFloor the pairs are rounded subnormals and their ratios are no longer the law, so check_sample_z refuses by name.
+// The kernels (class_sample.inc) and the twin below run the same single multiplies, adds and compares -- both built without floating-point
+// contraction -- and agree byte for byte.
 //
 // THE JOB is what one record serves.  With nothing held it is the (syndrome, class) pair: all K samples of the pair walk one record.  With held
 // generators it is the (syndrome, class, sample) triple: every sample picks its own h* and gets its own forward sweep under it -- 2^-n_held of a
@@ -31,7 +38,7 @@
 //
 // Refused, before a device is looked for, under the entry point's name: what build_cut_plan refuses, with its code; a weight that is negative or
 // not finite, four zero weights; K = 0 or K >= 2^32; syndrome indices past 32 bits; a mode other than 0 and 1.  Refused by name once Z is known: in
-// every-class mode a class whose Z_c is 0 or not finite (row and class), in posterior mode a row whose total is.
+// every-class mode a class whose Z_c is 0, not finite or below 2^-960 (row and class), in posterior mode a row whose total is.
 #pragma once
 #include "class_minplus_trace.hpp"   // forget_generators, remove_bit, unpack_chain
 #include "class_sweep_site.hpp"
@@ -45,6 +52,10 @@ constexpr uint32_t kSubSample = 0x53u;                       // the sub-stream o
 constexpr uint64_t kSampleWorkspaceBytes = 512ull << 20;     // the records of one launch
 constexpr uint32_t kLaunchSamples = 1u << 18;                // the samples of one pick / walk launch: their chains are 64 MiB on the device at most
 constexpr int kMaxWords = 8;                                 // packed words of a chain a walk lane keeps in registers: rotated L = 11 has 8
+// The least class weight (every-class mode) or row total (posterior mode) a draw is made from: qecmc.exact.LAW_FLOOR, 2^-960 compared at half of it so
+// that an exact 2^-960 is never refused on account of the sweep's own relative error.  Below it the record's pairs are multiples of 2^-1074 rounded by
+// up to 2^-1075 each, and on / s is no longer the branch's probability to 1e-12 (DESIGN.md 4.1s "Range")
+constexpr double kSampleFloor = 0x1p-961;
 
 struct PairRecord { double on, s; };
 static_assert(sizeof(PairRecord) == 16, "one 16-byte store per lane");
@@ -135,12 +146,20 @@ inline Refusal check_sample_z(const char *name, uint64_t row, const double *Z, i
             if (!(Z[c] > 0.0) || !std::isfinite(Z[c]))
                 return named(name, refuse_params(QECMC_ERR_INVALID, "row %llu, class %d: the class weight is %g -- a class whose weight is 0 or not finite has no chain to draw",
                                                  (unsigned long long)row, c, Z[c]));
+            else if (Z[c] < kSampleFloor)
+                return named(name, refuse_params(QECMC_ERR_INVALID, "row %llu, class %d: the class weight is %g, below 2^-960 = %g: it underflows into the subnormal range of "
+                                                 "float64, where the ratios of the record are rounded away, and the chains of that class cannot be drawn by their law",
+                                                 (unsigned long long)row, c, Z[c], 2.0 * kSampleFloor));
         return {};
     }
     double total = Z[0];
     for (int c = 1; c < ncls; ++c) total = total + Z[c];
     if (!(total > 0.0) || !std::isfinite(total))
         return named(name, refuse_params(QECMC_ERR_INVALID, "row %llu: the class weights total %g -- a row whose total is 0 or not finite has no class to draw", (unsigned long long)row, total));
+    if (total < kSampleFloor)
+        return named(name, refuse_params(QECMC_ERR_INVALID, "row %llu: the class weights total %g, below 2^-960 = %g: they underflow into the subnormal range of float64, where "
+                                         "their ratios are rounded away, and the posterior of that row cannot be drawn by its law", (unsigned long long)row, total,
+                                         2.0 * kSampleFloor));
     return {};
 }
 
@@ -163,7 +182,8 @@ inline double draw_u53(uint64_t k, uint32_t block, uint32_t j, uint32_t syndrome
     return u53_of(c[2u * j], c[2u * j + 1u]);
 }
 
-// step 2, and the class of posterior mode: the lowest index whose running sum passes u * (the last running sum)
+// step 2, and the class of posterior mode: the lowest index whose running sum passes u * (the last running sum), or has reached it -- where the product
+// rounds up to the last sum (a subnormal one) no sum passes it, and the first to reach the last is an entry > 0, which the last index need not be
 inline uint32_t pick_running(const double *v, uint32_t n, double u)
 {
     double last = v[0];
@@ -171,7 +191,7 @@ inline uint32_t pick_running(const double *v, uint32_t n, double u)
     const double t = u * last;
     double run = v[0];
     uint32_t i = 0;
-    while (!(t < run) && i + 1u < n) { ++i; run = run + v[i]; }
+    while (!(t < run || run == last) && i + 1u < n) { ++i; run = run + v[i]; }
     return i;
 }
 
@@ -213,7 +233,7 @@ inline uint32_t sample_walk(const SamplePlan &sp, const PairRecord *R, uint64_t 
             --fi;
             const PairRecord r = R[(size_t)fi * half + minplus::remove_bit(f, slot)];
             const double u = draw_u53(k, 1u + ((uint32_t)fi >> 1), (uint32_t)fi & 1u, syndrome, stream, seed);
-            if (u * r.s < r.on) {
+            if (u * r.s < r.on || r.on == r.s) {
                 f |= bit;
                 for (int w = 0; w < p.W; ++w) chain[w] ^= sp.forget_words[(size_t)fi * p.W + w];
             }

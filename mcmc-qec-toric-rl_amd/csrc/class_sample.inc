@@ -4,7 +4,7 @@
 //
 // k_class_sample_pick: one lane per sample of the launch.  In posterior mode the lane first draws its class from the running sums of z; then, where
 // generators are held, it forms the running sums of its pair's partials by sequential adds in ascending h -- the twin's order: every lane is the
-// "one lane" of its own sample -- and keeps the lowest h with u * C_last < C_h.  pair, h* and class leave through vector stores.
+// "one lane" of its own sample -- and keeps the lowest h with u * C_last < C_h || C_h == C_last.  pair, h* and class leave through vector stores.
 //
 // k_class_sample_record, k_class_sample_record_site: the grid is the jobs; block size and dynamic LDS are k_class_sweep_cut's (cut_threads,
 // lds_carve).  Job blockIdx.x sweeps pair job_pair[job] under hbits = job_h[job] with the CLOSE and INTRO passes of class_sweep_ops.hpp and a FORGET
@@ -35,7 +35,7 @@ __device__ __forceinline__ double sample_u53(uint64_t k, uint32_t block, uint32_
     return sample::u53_of(b.x, b.y);
 }
 
-// the lowest index whose running sum passes u * (the last running sum): sequential adds in ascending order
+// the lowest index whose running sum passes u * (the last running sum), or has reached it: sequential adds in ascending order
 __device__ __forceinline__ uint32_t lowest_running(const double *__restrict__ v, uint32_t n, double u)
 {
     double last = v[0];
@@ -43,7 +43,7 @@ __device__ __forceinline__ uint32_t lowest_running(const double *__restrict__ v,
     const double t = u * last;
     double run = v[0];
     uint32_t i = 0;
-    while (!(t < run) && i + 1u < n) { ++i; run = run + v[i]; }
+    while (!(t < run || run == last) && i + 1u < n) { ++i; run = run + v[i]; }
     return i;
 }
 
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(kSampleWave) void k_class_sample_walk(const SampleA
             }
             const double u = (fi & 1) ? sample::u53_of(blk.z, blk.w) : sample::u53_of(blk.x, blk.y);
             const double2 r = mine[((size_t)fi << half_bits) + minplus::remove_bit(f, slot)];      // (on, s); f has bits below width only
-            const bool take = u * r.y < r.x;
+            const bool take = u * r.y < r.x || r.x == r.y;
             if (take) f |= bit;
             const uint32_t *g = forget_words + (size_t)fi * W;
 #pragma unroll

@@ -188,6 +188,12 @@ int main()
           sample::check_sample_z("n", 3, z_none, 4, 1).code != QECMC_ERR_INVALID;
     const double one[3] = {0.0, 2.0, 0.0};
     rc |= sample::pick_running(one, 3, 0.0) != 1u || sample::pick_running(one, 3, 0.999) != 1u;     // a weight of 0 is never picked
+    const double tiny[3] = {0.0, 0x1p-1074, 0.0}, u_top = 1.0 - 0x1p-53;                            // ... nor at the last positive double, where u * last rounds up to last
+    rc |= sample::pick_running(tiny, 3, 0.0) != 1u || sample::pick_running(tiny, 3, 0.75) != 1u || sample::pick_running(tiny, 3, u_top) != 1u;
+    const double z_low[4] = {1.0, 0x1p-962, 2.0, 3.0}, z_floor[4] = {0x1p-961, 0x1p-961, 0x1p-961, 0x1p-961}, z_under[4] = {0x1p-964, 0x1p-964, 0x1p-964, 0x1p-964};
+    rc |= sample::check_sample_z("n", 3, z_low, 4, 0).code != QECMC_ERR_INVALID || sample::check_sample_z("n", 3, z_low, 4, 1).code != 0 ||
+          sample::check_sample_z("n", 3, z_floor, 4, 0).code != 0 || sample::check_sample_z("n", 3, z_under, 4, 1).code != QECMC_ERR_INVALID;
+    rc |= sample::check_sample_z("n", 3, z_low, 4, 0).msg.find("row 3, class 1") == std::string::npos || sample::check_sample_z("n", 3, z_low, 4, 0).msg.find("below 2^-960") == std::string::npos;
     rc |= twins < 12 || held < 2;
     std::printf(rc ? "class sample selftest FAILED\n" : "class sample selftest OK\n");
     return rc;

@@ -579,6 +579,48 @@ void qt_class_sample_group(uint64_t N, int ncls, int n_held, uint64_t K, uint64_
     out3[0] = g.syndromes; out3[1] = g.k_chunk; out3[2] = g.jobs;
 }
 double qt_class_sample_u53(uint64_t k, uint32_t block, uint32_t j, uint32_t syndrome, uint32_t stream, uint64_t seed) { return sample::draw_u53(k, block, j, syndrome, stream, seed); }
+double qt_class_sample_floor() { return sample::kSampleFloor; }
+// qt_class_sample_record: what one job of the twin walks, for the tests that compute the law THE RULE assigns without draws.  One syndrome (chain
+// uint8[nq]; w[4], or one table row wq double[nq][4] where w is NULL), class cls, held assignment h -> pairs double[n_forget][2^(width - 1)][2] as (on, s)
+// -- record_one's, zeros at dead f --, the unfolded partials of the class double[2^n_held] and z double[ncls] as sample_host forms them, the start
+// chain cut_representative(rep_cls, h) as uint32[W], and word 0 of every op uint32[n_ops].  No check of z: the caller judges.  -> n_ops, -1 where a
+// buffer is NULL or too small, the class or h out of range, or the plan or the weights refused
+int qt_class_sample_record(int code, int L, const uint8_t *chain, const double *w, const double *wq, int lds_width, int cls, uint32_t h, double *pairs_out, uint64_t pairs_cap,
+                           double *partials_out, double *z_out, uint32_t *rep_out, uint32_t *ops_out, int ops_cap)
+{
+    const char *name = w ? "qecmc_class_sample" : "qecmc_class_sample_site";
+    if (!chain || (!w && !wq) || !pairs_out || !partials_out || !z_out || !rep_out || !ops_out) return -1;
+    if (w && sample::check_sample_weights(name, w).code) return -1;
+    const sample::SamplePlan sp = sample::build_sample_plan(code, L, lds_width, name);
+    const sweep::CutPlan &cp = sp.cut;
+    const sweep::Plan &p = cp.plan;
+    if (p.refusal.code || (!w && sample::check_sample_site(name, 1, wq, 1, p).code)) return -1;
+    const uint32_t n_h = 1u << cp.n_held;
+    const uint64_t pairs = sample::sample_pairs_per_job(sp.n_forget, p.width);
+    if (cls < 0 || cls >= p.ncls || h >= n_h || pairs > pairs_cap || p.n_ops > ops_cap) return -1;
+    sweep::Plan unscaled = p;
+    unscaled.scale = 1.0;
+    std::vector<double> wxz(w ? 4u : (size_t)p.nq * 4u), A((size_t)1 << p.width), fold((size_t)n_h);
+    std::vector<uint32_t> reps((size_t)p.ncls * p.W), rep((size_t)p.W);
+    if (w) sweep::weights_xz(w, wxz.data());
+    else sweep::site_rows_xz(wq, 1, p.nq, wxz.data());
+    sweep::class_representatives(p, chain, reps.data());
+    for (int c = 0; c < p.ncls; ++c) {
+        for (uint32_t i = 0; i < n_h; ++i) {
+            sweep::cut_representative(cp, &reps[(size_t)c * p.W], i, rep.data());
+            fold[i] = w ? sweep::sweep_one(unscaled, rep.data(), wxz.data(), A.data()) : sweep::sweep_one_site(unscaled, rep.data(), wxz.data(), A.data());
+        }
+        if (c == cls) std::memcpy(partials_out, fold.data(), (size_t)n_h * sizeof(double));
+        z_out[c] = sweep::cut_reduce(fold.data(), cp.n_held, p.scale);
+    }
+    sweep::cut_representative(cp, &reps[(size_t)cls * p.W], h, rep.data());
+    std::vector<sample::PairRecord> R((size_t)pairs, sample::PairRecord{0.0, 0.0});
+    sample::record_one(sp, rep.data(), sample::Factors{wxz.data(), w ? 0u : 4u}, A.data(), R.data());
+    std::memcpy(pairs_out, R.data(), (size_t)pairs * sizeof(sample::PairRecord));
+    std::memcpy(rep_out, rep.data(), (size_t)p.W * sizeof(uint32_t));
+    for (int o = 0; o < p.n_ops; ++o) ops_out[o] = p.ops[(size_t)o * sweep::kOpWords];
+    return p.n_ops;
+}
 // the exact marginals (class_marginal.hpp).  qt_class_marginals: the host twin of qecmc_class_marginals (w given) and qecmc_class_marginals_site (w NULL)
 // behind the same host checks, in the same order -- the QECMC_ERR_* code of the refusal, its message in msg (nullable); qt_class_marginals_plan: through
 // out8 width, n_held, n_close, the bytes of one job's forward record, the workspace bound, the bound on a group's M_h, n_ops and nq, and through close_qubit

@@ -737,15 +737,16 @@ def sample_chains(code, chains, p=None, w4=None, eta=None, alpha=None, n_samples
     or the noise model of p / (p, eta) / (p as pz_tilde, alpha).  n_samples chains per (syndrome, class).
     Returns dict(chains uint8[N, ncls, n_samples, ...]: chains[s, c, k] has the syndrome of chain s, lies in class c and was drawn with probability
     w(chain) / Z[s, c]; z float64[N, ncls]: class_sweep_cut's Z, bit for bit; width, held).  Sample (s, c, k) is a function of (seed,
-    first_syndrome + s, c, k, chain s, the weights) alone: a batch cut into pieces, with first_syndrome moved along, draws the same chains.  A class
-    whose Z is 0 or not finite is refused by row and class."""
+    first_syndrome + s, c, k, chain s, the weights) alone: a batch cut into pieces, with first_syndrome moved along, draws the same chains.  A drawn
+    chain always has weight > 0, at every range.  A class whose Z is 0, not finite or below 2^-960 (LAW_FLOOR: the record is rounded in the subnormal
+    range, and the draws would not follow the law) is refused by row and class (QecmcError)."""
     return _sample(code, chains, _sample_w4(p, w4, eta, alpha), None, n_samples, seed, first_syndrome, size, lds_width, 0)
 
 
 def sample_chains_site(code, chains, site_weights, n_samples=1, seed=0, first_syndrome=0, size=None, lds_width=0):
     """sample_chains under a weight per qubit, or per (syndrome, qubit) (qecmc_class_sample_site): site_weights as class_sweep_site takes them --
-    erasure_site_w4, depolarizing_site_w4, any per-shot prior.  A weight of 0 is never drawn: under erasure_site_w4 with base (1, 0, 0, 0) no sample
-    carries an error off the erased set."""
+    erasure_site_w4, depolarizing_site_w4, any per-shot prior.  A weight of 0 is never drawn, whatever the range of Z: under erasure_site_w4 with base
+    (1, 0, 0, 0) no sample carries an error off the erased set."""
     return _sample(code, chains, None, site_weights, n_samples, seed, first_syndrome, size, lds_width, 0)
 
 
@@ -753,7 +754,8 @@ def sample_posterior(code, chains, p=None, w4=None, eta=None, alpha=None, site_w
     """Exact, independent draws from P(chain | syndrome): the class first, with probability Z_c / Z, then a chain of it.  The weights are sample_chains',
     or site_weights as sample_chains_site takes them.
     Returns dict(chains uint8[N, n_samples, ...], cls int32[N, n_samples], z float64[N, ncls], width, held); chains[s, k] is sample_chains' chains[s,
-    cls[s, k], k] under the same seed.  A row whose class weights total 0, or are not finite, is refused by name."""
+    cls[s, k], k] under the same seed.  A row whose class weights total 0, are not finite, or total less than 2^-960 (LAW_FLOOR) is refused by name
+    (QecmcError); a class of weight 0 is never drawn."""
     if site_weights is not None:
         if p is not None or w4 is not None:
             raise ValueError("site_weights replace p and w4")
@@ -764,7 +766,7 @@ def sample_posterior(code, chains, p=None, w4=None, eta=None, alpha=None, site_w
 def posterior_error_counts(code, chains, p, n_samples, seed=0, eta=None, alpha=None, first_syndrome=0, size=None, lds_width=0):
     """float64[N]: the mean number of errors (cells that hold X, Y or Z) of n_samples exact draws from P(chain | syndrome) at error rate p -- what a
     sampler's rung at p converges to, with an error bar that shrinks as 1 / sqrt(n_samples).  exact_error_counts(...)["posterior"] is the exact value
-    this estimates, without draws"""
+    this estimates, without draws.  Refused where sample_posterior refuses (QecmcError): a row total of 0, not finite or below 2^-960"""
     r = sample_posterior(code, chains, p=p, eta=eta, alpha=alpha, n_samples=n_samples, seed=seed, first_syndrome=first_syndrome, size=size, lds_width=lds_width)
     c = r["chains"]
     return (c.reshape(c.shape[0], c.shape[1], -1) != 0).sum(axis=2).mean(axis=1)
@@ -789,12 +791,35 @@ def _marginals(code, chains, w, site_weights, size, lds_width):
     return dict(weights=weights.reshape((n, ncls) + state + (4,)), z=z, cls=cls, width=info["width"], held=info["held"])
 
 
+def _judge_range(v, what):
+    """The one place where the marginals' raw class weights are judged: v float64[N, ncls] -- every class weight -- or float64[N] -- every row's
+    total; what: the quantity asked for.  Raises FloatingPointError naming the first offending row (and class) and the end of float64's range it met,
+    in law_from_class_weights' wording: 0 or not finite; or below 2^-960 (LAW_FLOOR, compared at half of it) -- the backward sweep's weights were
+    rounded in the subnormal range, and their ratios are no longer the marginals."""
+    v = np.asarray(v, dtype=np.float64)
+    per_class = v.ndim == 2
+    bad = ~(np.isfinite(v) & (v >= LAW_FLOOR))
+    if not bad.any():
+        return
+    at = tuple(int(x) for x in np.argwhere(bad)[0])
+    x = float(v[at])
+    where = f"row {at[0]}, class {at[1]}: the class weight is" if per_class else f"row {at[0]}: the class weights total"
+    if not (np.isfinite(x) and x > 0.0):
+        whose = "a class whose weight" if per_class else "a row whose total"
+        raise FloatingPointError(f"{where} {x:.3g} -- {whose} is 0 or not finite has no {what}")
+    they = "it underflows" if per_class else "they underflow"
+    raise FloatingPointError(f"{where} {x:.3g}, below 2^-960 = {2.0 * LAW_FLOOR:.3g}: {they} into the subnormal range of float64, where the ratios of the "
+                             f"weights are rounded away, and the {what} of that {'class' if per_class else 'row'} are not representable")
+
+
 def _normalized(res, normalize):
-    """res with marginals = weights / their sum over the last axis; a (row, class) whose four weights total 0 or are not finite is refused by name"""
+    """res with marginals = weights / their sum over the last axis; a (row, class) whose class weight _judge_range refuses, or whose four weights total
+    0 or are not finite at some qubit, is refused by name.  normalize=False: res as it is, raw -- subnormals, zeros and inf included"""
     w = res["weights"]
     if not normalize:
         return res
     n, ncls = w.shape[:2]
+    _judge_range(res["z"], "marginals")
     with np.errstate(over="ignore", invalid="ignore"):
         tot = w.sum(axis=-1)
     bad = ~(np.isfinite(tot) & (tot > 0.0)).reshape(n, ncls, -1).all(axis=2)
@@ -806,14 +831,24 @@ def _normalized(res, normalize):
     return res
 
 
+def _posterior_of(r, what):
+    """float64[N, nq..., 4]: sum_c weights_c / sum_c z_c of a _marginals result, the row total judged by _judge_range"""
+    with np.errstate(over="ignore", invalid="ignore"):
+        tot = r["z"].sum(axis=1)
+        num = r["weights"].sum(axis=1)
+    _judge_range(np.where(np.isfinite(num.reshape(len(tot), -1)).all(axis=1), tot, np.inf), what)
+    return num / tot.reshape((-1,) + (1,) * (num.ndim - 1))
+
+
 def class_marginals(code, chains, p=None, w4=None, eta=None, alpha=None, size=None, lds_width=0, normalize=True):
     """The exact marginals of every qubit in every class, on the GPU (qecmc_class_marginals): the cut-set sweep run forward with a
     record of every CLOSE, and a backward sweep over the same stream.  code and chains as class_sweep_cut takes them; the weights are w4 -- finite and
     >= 0, zeros allowed -- or the noise model of p / (p, eta) / (p as pz_tilde, alpha).
     Returns dict(weights float64[N, ncls, ..., 4]: weights[s, c, q, P] = the sum of w(chain) over the chains of class c with the syndrome of chain s
     that carry Pauli P (I, X, Y, Z) at q; marginals = weights / their sum over the last axis (normalize=True): P(q carries P | syndrome, class);
-    z float64[N, ncls]: class_sweep_cut's Z, bit for bit; cls int32[N]; width, held).  With normalize=True a (row, class) whose four weights total 0
-    or are not finite raises FloatingPointError naming row and class."""
+    z float64[N, ncls]: class_sweep_cut's Z, bit for bit; cls int32[N]; width, held).  With normalize=True a (row, class) whose class weight is 0, not
+    finite or below 2^-960 (LAW_FLOOR: the weights were rounded in the subnormal range, and their ratios are not the marginals) raises FloatingPointError
+    naming row, class and the end of the range it met; at or above 2^-960 the marginals are right to 1e-12.  normalize=False returns the raw weights."""
     return _normalized(_marginals(code, chains, _sample_w4(p, w4, eta, alpha), None, size, lds_width), normalize)
 
 
@@ -826,36 +861,27 @@ def class_marginals_site(code, chains, site_weights, size=None, lds_width=0, nor
 
 def posterior_marginals(code, chains, p=None, w4=None, eta=None, alpha=None, site_weights=None, size=None, lds_width=0):
     """float64[N, ..., 4]: P(q carries P | syndrome), the classes mixed with Z_c / Z: sum_c weights_c / sum_c z_c.  The weights are class_marginals',
-    or site_weights as class_marginals_site takes them.  A row whose class weights total 0, or are not finite, is refused by name."""
+    or site_weights as class_marginals_site takes them.  A row whose class weights total 0, are not finite, or total less than 2^-960 (LAW_FLOOR) raises
+    FloatingPointError naming the row; a class that underflows beside a total above the floor stays: its share is below 2^-60."""
     if site_weights is not None:
         if p is not None or w4 is not None:
             raise ValueError("site_weights replace p and w4")
         r = _marginals(code, chains, None, site_weights, size, lds_width)
     else:
         r = _marginals(code, chains, _sample_w4(p, w4, eta, alpha), None, size, lds_width)
-    with np.errstate(over="ignore", invalid="ignore"):
-        tot = r["z"].sum(axis=1)
-        num = r["weights"].sum(axis=1)
-    bad = ~(np.isfinite(tot) & (tot > 0.0) & np.isfinite(num.reshape(len(tot), -1)).all(axis=1))
-    if bad.any():
-        row = int(np.flatnonzero(bad)[0])
-        raise FloatingPointError(f"row {row}: the class weights total {float(tot[row]):.3g} -- a row whose total is 0 or not finite has no posterior marginals")
-    return num / tot.reshape((-1,) + (1,) * (num.ndim - 1))
+    return _posterior_of(r, "posterior marginals")
 
 
 def exact_error_counts(code, chains, p, eta=None, alpha=None, size=None, lds_width=0):
     """dict(per_class float64[N, ncls], posterior float64[N]): the exact mean number of errors (cells that hold X, Y or Z) of a chain of class c, and of
     a chain drawn from P(chain | syndrome), at error rate p: sum_q (1 - marginal[q][I]) over the cells that hold a qubit.  posterior is the exact
-    value of what posterior_error_counts estimates with n_samples draws.  A class, or a row, of weight 0 is refused by name."""
+    value of what posterior_error_counts estimates with n_samples draws.  A class of weight 0, not finite or below 2^-960 is refused by row and class
+    (FloatingPointError), as class_marginals refuses it."""
     r = class_marginals(code, chains, p=p, eta=eta, alpha=alpha, size=size, lds_width=lds_width, normalize=True)
     n, ncls = r["z"].shape
     m = r["marginals"].reshape(n, ncls, -1, 4)
     per_class = (1.0 - m[..., 0]).sum(axis=2)                                   # (a cell that holds no qubit carries the representative's I: 1 - 1)
-    ztot = r["z"].sum(axis=1)
-    if not (np.isfinite(ztot) & (ztot > 0.0)).all():
-        row = int(np.flatnonzero(~(np.isfinite(ztot) & (ztot > 0.0)))[0])
-        raise FloatingPointError(f"row {row}: the class weights total {float(ztot[row]):.3g} -- a row whose total is 0 or not finite has no posterior")
-    post = r["weights"].reshape(n, ncls, -1, 4).sum(axis=1) / ztot[:, None, None]
+    post = _posterior_of(r, "posterior").reshape(n, -1, 4)
     return dict(per_class=per_class, posterior=(1.0 - post[..., 0]).sum(axis=1))
 
 
