@@ -2282,6 +2282,3 @@ int qecmc_ptdc_batch_xyz(const qecmc_params *params, const uint8_t *init, uint64
 }
 
 }  // extern "C"
-
-// the kernels of qecmc_class_sample / _site and their launch functions: this unit's only device code (class_sample.inc says why it is here)
-#include "class_sample.inc"

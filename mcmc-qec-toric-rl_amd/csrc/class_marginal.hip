@@ -21,13 +21,9 @@
 // on the held bits in ascending order of the bit with one barrier per bit, n_close * 4 sums side by side; then writes weights[s][c][q][P] =
 // M[ci of q][pauli_to_xz(P)] * scale, and for a cell no CLOSE names z at the representative's byte and 0 elsewhere.
 //
-// This file is compiled as the tail of primitives.hip, not as a unit of its own: the set of HIP units is pinned (tests/test_build_rules_cpu.py), the kernel
-// lists of the class_* units and of capi are pinned by their resource tests, and primitives.hip is the one unit whose list is not.  The pragma below
-// stands in for the -ffp-contract=off of the sum-product units (it holds to the end of the translation unit: include this file last); doubles keep
-// their denormals on this target whatever the flags.  Every product here is stored before anything is added to it.
+// The unit is built without floating-point contraction, as class_sweep_cut.hip (the Makefile's -ffp-contract=off line); doubles keep their denormals
+// on this target whatever the flags.  Every product here is stored before anything is added to it.
 #include "class_marginal.hpp"
-
-#pragma clang fp contract(off)
 
 namespace qecmc {
 

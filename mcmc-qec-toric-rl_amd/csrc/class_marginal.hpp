@@ -22,7 +22,7 @@
 // The order of every add is a function of the plan and of kFoldLanes alone: not of N, the launch grouping, the number of workgroups or the threads
 // of a workgroup (the lanes of the fold are the rule's 64, whatever walks them).  Every quantity is a product or a sum of non-negative numbers: no
 // subtraction, no division; a weight of 0 gives exact zeros.  The sum over x of M_h[ci][x] is P[h] up to rounding, at every ci.
-// The kernels (class_marginal.inc) and the twin below (marginal_host) are written apart, both without floating-point contraction, and agree bit for bit.
+// The kernels (class_marginal.hip) and the twin below (marginal_host) are written apart, both without floating-point contraction, and agree bit for bit.
 //
 // MEMORY.  The forward record of a job is n_close * 2^width * 8 bytes (15.1 MiB at rotated L = 11, 3.1 MiB at toric L = 5 under width 13);
 // marginal_launch_group bounds the records of one launch by kMarginalWorkspaceBytes, and the syndromes of one group so that the M_h of the group
@@ -229,7 +229,7 @@ inline void marginal_host(const MarginalPlan &mp, uint64_t N, const uint8_t *cha
 
 }  // namespace marginal
 
-// class_marginal.inc: all pointers are device pointers.  ops, held and reps as class_sweep_cut.hip takes them; close_op uint32[n_close], close_of
+// class_marginal.hip: all pointers are device pointers.  ops, held and reps as class_sweep_cut.hip takes them; close_op uint32[n_close], close_of
 // int32[nq].  The jobs of a group of S syndromes are numbered job = ((s * ncls + c) << n_held) + h, as k_class_sweep_cut numbers its workgroups;
 // a launch takes jobs [job0, job0 + jobs).
 struct MarginalArgs {

@@ -2,10 +2,7 @@
 // the reduce are the shipped kernels', unchanged; the three kernels here run after them on the same stream.  Stream order is the only
 // synchronisation: no atomics, no flags, no scratch, no static LDS, no inline assembly.
 //
-// This file is compiled as the tail of ladder_colour_shortest.hip.  The set of .hip units is fixed at thirty and every unit outside the ladder /
-// wave / colour families has its exact kernel list pinned, so the kernels live in a unit whose kernels are pinned through their name heads alone:
-// of the two shortest-chain units this is the smaller one (two kernels), it is built with the Makefile's default flags -- the kernels are integer
-// throughout and want no floating-point flag --, and nothing of ladder_colour.hpp is used here or changed by this.
+// The unit is built with the Makefile's default flags: the kernels are integer throughout and want no floating-point flag.
 //
 // k_class_minplus_tiled_trace, k_class_minplus_tiled_trace_site: the grid (live tiles, pairs of the pass), the block (tiled_threads), the dynamic LDS
 // (one tile, 64 KiB at most: within the default limit, no attribute) and the gather / write-back of k_class_minplus_tiled(_site); hbits = pick[pair],

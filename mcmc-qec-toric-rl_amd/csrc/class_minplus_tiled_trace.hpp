@@ -260,7 +260,7 @@ inline void minplus_tiled_trace_site_host(const TiledTracePlan &ttp, uint64_t N,
 
 }  // namespace minplus
 
-// class_minplus_tiled_trace.inc: all pointers are device pointers.  dev_ops, held, reps as class_minplus_tiled.hip takes them; wide_ops
+// class_minplus_tiled_trace.hip: all pointers are device pointers.  dev_ops, held, reps as class_minplus_tiled.hip takes them; wide_ops
 // uint32[n_ops][kTiledOpWords]; pick uint32[S * ncls] (launch_minplus_pick); forget_tile uint32[n_forget][kForgetTileWords]; forget_words
 // uint32[n_forget][W]; work uint64[pairs][2^state_bits] and D uint64[pairs][words_per_pair]: the state vectors and the decisions of one trace pass,
 // both dirty; cw as the site sweep's; chain_out uint8[S * ncls][nq]: rows pair_first .. pair_first + pairs are overwritten.

@@ -16,14 +16,10 @@
 // draws (one block serves two FORGETs; the block changes under wave-uniform control flow, fi being the same in every lane) and its chain, kMaxWords
 // statically indexed registers.  The ops and the forget words are wave-uniform scalar loads; the record pair is one 16-byte load per lane.
 //
-// This file is compiled as the tail of capi.hip, not as a unit of its own: the set of HIP units is pinned (tests/test_build_rules_cpu.py), and capi.hip
-// held no kernel, so no existing kernel shares a translation unit with these.  The pragma below stands in for the -ffp-contract=off of the sum-product
-// units (it holds to the end of the translation unit: include this file last); doubles keep their denormals on this target whatever the flags, and
-// no multiply here feeds an add: every product is stored or compared.
+// The unit is built without floating-point contraction, as class_sweep_cut.hip (the Makefile's -ffp-contract=off line); doubles keep their denormals
+// on this target whatever the flags, and no multiply here feeds an add: every product is stored or compared.
 #include "class_sample.hpp"
 #include "philox.hpp"
-
-#pragma clang fp contract(off)
 
 namespace qecmc {
 

@@ -28,7 +28,7 @@
 // weight > 0 -- pure erasure is exact, and so is a subnormal s, where u * s rounds back up to s and the first compare alone would decline a forced
 // branch.  In the normal range the second compare of either rule is implied by the first (u <= 1 - 2^-53): no draw there depends on it.  THE LAW is a
 // question of range: below kSampleFloor the pairs are rounded subnormals and their ratios are no longer the law, so check_sample_z refuses by name.
-// The kernels (class_sample.inc) and the twin below run the same single multiplies, adds and compares -- both built without floating-point
+// The kernels (class_sample.hip) and the twin below run the same single multiplies, adds and compares -- both built without floating-point
 // contraction -- and agree byte for byte.
 //
 // THE JOB is what one record serves.  With nothing held it is the (syndrome, class) pair: all K samples of the pair walk one record.  With held
@@ -302,7 +302,7 @@ inline Refusal sample_host(const SamplePlan &sp, const char *name, uint64_t N, c
 
 }  // namespace sample
 
-// class_sample.inc: all pointers are device pointers.  ops, held and reps as class_sweep_cut.hip takes them; forget_words uint32[n_forget][W].
+// class_sample.hip: all pointers are device pointers.  ops, held and reps as class_sweep_cut.hip takes them; forget_words uint32[n_forget][W].
 // The samples of one launch are numbered [s][c][kk] (mode 0) or [s][kk] (mode 1), kk < k_chunk, sample k = k0 + kk; pair = s * ncls + c.
 struct SampleArgs {
     int ncls, W, width, n_ops, n_held, n_forget, nq, per_syndrome, mode;

@@ -216,7 +216,7 @@ struct LdsOptIn {
 hipError_t cut_allow_lds(const void *kernel, LdsOptIn &opt, int width);
 hipError_t class_sweep_cut_allow_lds(int width);      // hipSuccess: a state vector of this width can be launched on the current device
 hipError_t launch_class_sweep_cut(const SweepCutArgs &a, const uint32_t *ops, const uint32_t *held, const uint32_t *reps, double *P, double *z, hipStream_t stream);
-// k_class_sweep_cut alone: the unscaled partials, left as they are (class_sample.inc picks an assignment from them before anything folds them)
+// k_class_sweep_cut alone: the unscaled partials, left as they are (class_sample.hip picks an assignment from them before anything folds them)
 hipError_t launch_class_sweep_cut_partials(const SweepCutArgs &a, const uint32_t *ops, const uint32_t *held, const uint32_t *reps, double *P, hipStream_t stream);
 // k_class_sweep_reduce alone, on the partials of a.S syndromes (n_held, ncls and scale are read): class_sweep_tiled.hip forms its partials itself
 hipError_t launch_class_sweep_reduce(const SweepCutArgs &a, double *P, double *z, hipStream_t stream);

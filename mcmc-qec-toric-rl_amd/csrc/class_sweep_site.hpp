@@ -157,7 +157,7 @@ hipError_t launch_class_sweep_site(const SweepSiteArgs &a, const uint32_t *ops, 
 hipError_t class_sweep_cut_site_allow_lds(int width);  // class_sweep_cut_allow_lds() for k_class_sweep_cut_site
 hipError_t launch_class_sweep_cut_site(const SweepSiteArgs &a, const uint32_t *ops, const uint32_t *held, const uint32_t *reps, const double *wq, double *P, double *z,
                                        hipStream_t stream);
-// k_class_sweep_cut_site alone: the unscaled partials, left as they are (class_sample.inc picks an assignment from them)
+// k_class_sweep_cut_site alone: the unscaled partials, left as they are (class_sample.hip picks an assignment from them)
 hipError_t launch_class_sweep_cut_site_partials(const SweepSiteArgs &a, const uint32_t *ops, const uint32_t *held, const uint32_t *reps, const double *wq, double *P,
                                                 hipStream_t stream);
 struct SweepTiledSiteArgs {

@@ -11,6 +11,3 @@ struct ColourShortestSet {
 const void *colour_shortest_kernel(const KernelKey &k) { return find_kernel<ColourShortestSet<kCodeXzzx>, ColourShortestSet<kCodeRotated>>(k); }
 
 }  // namespace qecmc
-
-// the traceback kernels of the tiled (min, +) sweep (class_minplus_tiled_trace.hpp) are built as the tail of this unit: the .inc says why
-#include "class_minplus_tiled_trace.inc"

@@ -1,7 +1,6 @@
 // Batched byte-state kernels behind the Toric_code / Chain API surface
 // (src/toric_model.py:33-56, src/mcmc.py:19-43).  One thread per state; these
 // are the compatibility path (drop-in single calls), not the throughput path.
-// The tail of this unit is csrc/class_marginal.inc, the kernels of qecmc_class_marginals / _site (that file says why it is compiled here).
 #include "kernels.hpp"
 #include "philox.hpp"
 #include "stencil_bytes.hpp"
@@ -300,7 +299,3 @@ hipError_t launch_chain_update(const ChainArgs &a, hipStream_t s)
 }
 
 }  // namespace qecmc
-
-// the kernels of qecmc_class_marginals / _site and their launch functions (class_marginal.inc says why they are here): include last -- its pragma holds
-// to the end of the unit
-#include "class_marginal.inc"

@@ -10,7 +10,11 @@ import pytest
 
 from hostlib import CSRC
 
-HEADERS = ["ladder_wu.hpp", "ladder_colour.hpp", "class_sweep_ops.hpp", "corrections.hpp", "kernel_choice.hpp", "../../include/qecmc.h"]
+HEADERS = ["ladder_wu.hpp", "ladder_colour.hpp", "class_sweep_ops.hpp", "corrections.hpp", "kernel_choice.hpp", "../../include/qecmc.h", "class_sample.hpp", "class_marginal.hpp",
+           "class_minplus_tiled_trace.hpp"]
+# a kernel family's header is read by its own unit and by the C-ABI host file, and by no other unit (class_marginal.hpp reads class_sample.hpp)
+FAMILY = {"class_sample.hpp": {"capi.hip", "class_sample.hip", "class_marginal.hip"}, "class_marginal.hpp": {"capi.hip", "class_marginal.hip"},
+          "class_minplus_tiled_trace.hpp": {"capi.hip", "class_minplus_tiled_trace.hip"}}
 
 
 def closure(name, seen=None):
@@ -46,7 +50,18 @@ def built():
 
 
 def test_the_units_are_the_hip_files_of_csrc():
-    assert sorted(units()) == sorted(f for f in os.listdir(CSRC) if f.endswith(".hip")) and len(units()) == 30
+    assert sorted(units()) == sorted(f for f in os.listdir(CSRC) if f.endswith(".hip")) and len(units()) == 33
+
+
+def test_no_unit_includes_an_inc():
+    """a kernel family is a unit named after its header, never the tail of another unit: the two .inc files left are the kernel bodies their headers
+    instantiate"""
+    for u in units():
+        assert not re.findall(r'^[ \t]*#[ \t]*include[ \t]*"[^"]+\.inc"', open(os.path.join(CSRC, u), errors="replace").read(), re.M), u
+    names = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp", ".cpp")))
+    readers = {inc: [f for f in names if re.search(r'#[ \t]*include[ \t]*"%s"' % re.escape(inc), open(os.path.join(CSRC, f), errors="replace").read())]
+               for inc in sorted(f for f in os.listdir(CSRC) if f.endswith(".inc"))}
+    assert readers == {"ladder_colour_body.inc": ["ladder_colour.hpp"], "ladder_wu_body.inc": ["ladder_wu.hpp"]}, readers
 
 
 @pytest.mark.parametrize("header", HEADERS)
@@ -54,6 +69,8 @@ def test_a_header_rebuilds_exactly_the_units_that_read_it(built, header):
     want = {u for u in units() if header in closure(u)}
     assert want, header
     assert would_rebuild(header) == want
+    if header in FAMILY:
+        assert want == FAMILY[header]
 
 
 def test_ladder_wu_hpp_rebuilds_the_eight_wave_units_and_nothing_else(built):

@@ -1,12 +1,12 @@
-"""The tiled traceback's kernels in the build's resource tables.  They are built as the tail of ladder_colour_shortest.hip (csrc/class_minplus_tiled_trace.inc
-says why): exactly three kernels next to that unit's sealed ones -- the two trace kernels, no scratch, no static LDS (their LDS is the dynamic window of
-one tile, 64 KiB at most), within the 32 VGPRs that keep the tiled sweeps' full 8 waves per SIMD, and the walk, one wave per pair, within 64 --, their
-names outside the sealed registry of ladder / wave / colour kernels, and that unit's sealed kernels as the parent built them.  Then the stand-alone
-selftest of the plan, the twins and the device layout under AddressSanitizer + UBSan."""
+"""The tiled traceback's kernels in the build's resource tables.  csrc/class_minplus_tiled_trace.hip is a unit of its own: exactly three kernels -- the two
+trace kernels, no scratch, no static LDS (their LDS is the dynamic window of one tile, 64 KiB at most), within the 32 VGPRs that keep the tiled sweeps'
+full 8 waves per SIMD, and the walk, one wave per pair, within 64 --, their names outside the sealed registry of ladder / wave / colour kernels;
+ladder_colour_shortest.hip holds exactly its two sealed kernels, as they were built before the traceback.  Then the stand-alone selftest of the plan,
+the twins and the device layout under AddressSanitizer + UBSan."""
 import kernel_cases
 from hostlib import SEALED_HEADS, resource_rows, run_selftest, static_lds
 
-UNIT = "ladder_colour_shortest"
+UNIT, COLOUR = "class_minplus_tiled_trace", "ladder_colour_shortest"
 TRACE, WALK = ["k_class_minplus_tiled_trace", "k_class_minplus_tiled_trace_site"], "k_minplus_tiled_walk"
 SEALED = {"colour-shortest<1024,4,rotated>": (110, 4), "colour-shortest<1024,4,xzzx>": (110, 4)}         # label: (VGPRs, occupancy), profiles/r08_shortest_kernel_rows.txt
 
@@ -17,7 +17,7 @@ def rows():
 
 def test_three_kernels_without_scratch_within_the_tiled_sweeps_budget():
     got = rows()
-    assert sorted(lab for lab in got if not lab.startswith(SEALED_HEADS)) == sorted(TRACE + [WALK]), sorted(got)
+    assert sorted(got) == sorted(TRACE + [WALK]), sorted(got)
     theirs = {r["label"]: r for r in resource_rows(["class_minplus_tiled"])}["k_class_minplus_tiled"]
     for lab in TRACE:
         r = got[lab]
@@ -30,7 +30,8 @@ def test_three_kernels_without_scratch_within_the_tiled_sweeps_budget():
 
 def test_no_static_lds():
     static = static_lds(UNIT)
-    assert static == [0] * 5, static
+    assert static == [0] * 3, static
+    assert static_lds(COLOUR) == [0, 0]
 
 
 def test_the_traceback_kernels_stay_out_of_the_sealed_registry():
@@ -39,8 +40,8 @@ def test_the_traceback_kernels_stay_out_of_the_sealed_registry():
 
 
 def test_the_host_units_sealed_kernels_are_unchanged():
-    got = rows()
-    assert {lab for lab in got if lab.startswith(SEALED_HEADS)} == set(SEALED)
+    got = {r["label"]: r for r in resource_rows([COLOUR])}
+    assert set(got) == set(SEALED)
     for lab, (vgprs, occupancy) in SEALED.items():
         assert (got[lab]["VGPRs"], got[lab]["Occupancy"], got[lab]["ScratchSize"]) == (vgprs, occupancy, 0), got[lab]
     # ... and the shipped sweep units keep their kernels: the traceback adds none to them
