@@ -440,6 +440,35 @@ int qecmc_class_minplus_tiled_chains(int code, int L, uint64_t N, const uint8_t 
 int qecmc_class_minplus_tiled_chains_site(int code, int L, uint64_t N, const uint8_t *chains, const uint8_t *cq, uint64_t cq_rows, int hbm_width,
                                           int tile_width, uint8_t *chain_out, uint32_t *cost_out, uint64_t *count_out, int32_t *class_out);
 
+/* ---- exact chains of every class on the tiled route: forward filtering and backward sampling on the state vector tiled over HBM
+ * (csrc/class_sample_tiled.hpp) ----
+ * qecmc_class_sample and qecmc_class_sample_site on the plans of qecmc_class_sweep_tiled: K, seed, first_syndrome, mode, chain_out, class_out
+ * (not looked at in mode 0; required in mode 1) and z_out are those functions', hbm_width and tile_width are qecmc_class_sweep_tiled's, and
+ * z_out is qecmc_class_sweep_tiled's bits.  A sample is a function of (seed, first_syndrome + s, c, k, the plan's stream and holds, chain s,
+ * the weights) alone: it does not depend on tile_width, N, K or record_bytes, and where the tiled plan's stream and holds are the cut plan's
+ * (hbm_width = its lds_width) it is qecmc_class_sample's chain byte for byte.  One more tiled pass per job -- a (syndrome, class) pair, or with
+ * held generators a (syndrome, class, sample) triple -- records 16 bytes per FORGET and live state in a device block of its own, kept per
+ * device.  record_bytes caps the block of one call: 0 is the default of 4 GiB (xzzx / rotated up to L = 17), other values are taken up to
+ * 64 GiB; a block grown past the default is freed before the call returns.  A plan whose single job takes more than the cap is refused by
+ * name with the bytes it needs (rotated L = 21: about 39 GB).
+ * qecmc_class_sample_tiled_info: n_forget, bytes_per_job and jobs_per_pass (all three (nullable)) of the plan under that cap -- the FORGETs of
+ * the stream, the record of one job, and the jobs one record pass carries when many are left; a plan refused for the cap alone still reports
+ * the first two before it returns the refusal.
+ * Additive: QECMC_ABI_VERSION stays.  Refused before a device is looked for, the message prefixed "qecmc_class_sample_tiled:" /
+ * "qecmc_class_sample_tiled_site:": a NULL chains / w / wq / chain_out / z_out (class_out in mode 1); what qecmc_class_sample refuses of
+ * (N, K, first_syndrome, mode, weights); a record_bytes above 64 GiB; what qecmc_class_sweep_tiled / _tiled_site refuses of (code, L,
+ * hbm_width, tile_width, wq, wq_rows), with its codes; the record cap (QECMC_ERR_UNSUPPORTED).  Refused once z is known, as
+ * qecmc_class_sample: a class weight (mode 0) or a row total (mode 1) that is 0, not finite or below 2^-960.  N == 0 succeeds.  Host
+ * pointers only; device 0. */
+int qecmc_class_sample_tiled(int code, int L, uint64_t N, const uint8_t *chains, const double w[4], int hbm_width, int tile_width,
+                             uint64_t record_bytes, uint64_t K, uint64_t seed, uint32_t first_syndrome, int mode, uint8_t *chain_out,
+                             int32_t *class_out, double *z_out);
+int qecmc_class_sample_tiled_site(int code, int L, uint64_t N, const uint8_t *chains, const double *wq, uint64_t wq_rows, int hbm_width,
+                                  int tile_width, uint64_t record_bytes, uint64_t K, uint64_t seed, uint32_t first_syndrome, int mode,
+                                  uint8_t *chain_out, int32_t *class_out, double *z_out);
+int qecmc_class_sample_tiled_info(int code, int L, int hbm_width, int tile_width, uint64_t record_bytes, int32_t *n_forget,
+                                  uint64_t *bytes_per_job, uint32_t *jobs_per_pass);
+
 /* ---- chain / ladder on caller-owned state (host pointers) ----------------- */
 
 /* The supported range of a start index.  A Philox counter holds a proposal index (the swap stream: a ladder-step index) in 48 bits,

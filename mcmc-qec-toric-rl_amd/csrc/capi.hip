@@ -32,6 +32,7 @@
 #include "class_minplus_tiled_trace.hpp"
 #include "class_sample.hpp"
 #include "class_marginal.hpp"
+#include "class_sample_tiled.hpp"
 #include "enumerate.hpp"
 #include "syndrome_lift.hpp"
 #include "tables.hpp"
@@ -1570,6 +1571,208 @@ int qecmc_class_minplus_tiled_chains_site(int code, int L, uint64_t N, const uin
 {
     if (!cq) return fail(QECMC_ERR_INVALID, "qecmc_class_minplus_tiled_chains_site: NULL buffer");
     return tiled_chains_impl("qecmc_class_minplus_tiled_chains_site", code, L, N, chains, nullptr, cq, cq_rows, hbm_width, tile_width, chain_out, cost_out, count_out, class_out);
+}
+
+// ---------------------------------------------------------------- exact chains of every class on the tiled route (class_sample_tiled.hpp)
+namespace {
+static_assert(sample::kTiledLaunchSamples == sample::kLaunchSamples, "the pick of class_sample.hip serves both routes");
+
+// The records of one record pass: one block per device, taken when a call first needs more than is there and kept up to kTiledSampleRecordBytes; a
+// block a raised cap grew past that is freed when the call ends (Trim).  Never cleared.  Only the tiled sampler touches it, and only while it holds
+// the tiled workspace's lock.
+struct TiledSampleBlock {
+    void *p[TiledWorkspace::kDevices] = {};
+    size_t bytes[TiledWorkspace::kDevices] = {};
+    static TiledSampleBlock &get() { static TiledSampleBlock *b = new TiledSampleBlock; return *b; }   // (never destroyed, as DevPool)
+    hipError_t take(size_t want, uint64_t cap, void **out)                        // under TiledWorkspace::mu
+    {
+        int dev = 0;
+        if (hipError_t e = hipGetDevice(&dev)) return e;
+        if (dev < 0 || dev >= TiledWorkspace::kDevices || want > cap || cap > sample::kTiledSampleRecordBytesMax) return hipErrorInvalidValue;
+        if (bytes[dev] < want) {
+            if (p[dev]) { (void)hipFree(p[dev]); p[dev] = nullptr; bytes[dev] = 0; }
+            if (hipError_t e = hipMalloc(&p[dev], want)) return e;
+            bytes[dev] = want;
+        }
+        *out = p[dev];
+        return hipSuccess;
+    }
+    struct Trim {                                                                 // under TiledWorkspace::mu: declared after the lock, so it runs before the unlock
+        ~Trim()
+        {
+            TiledSampleBlock &b = TiledSampleBlock::get();
+            int dev = 0;
+            if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= TiledWorkspace::kDevices) return;
+            if (b.bytes[dev] > sample::kTiledSampleRecordBytes) { (void)hipFree(b.p[dev]); b.p[dev] = nullptr; b.bytes[dev] = 0; }
+        }
+    };
+};
+
+// both entry points: w (the four weights) or wq (a site table).  Per group of syndromes: the sweep passes of qecmc_class_sweep_tiled(_site) with the
+// partials left unfolded, the reduce on a copy, the checks Z decides; then per chunk of samples the pick of class_sample.hip and record passes of
+// jobs -- as many as the state workspace and the record block take -- each ending with the walk of its samples.
+int class_sample_tiled_impl(const char *name, int code, int L, uint64_t N, const uint8_t *chains, const double *w, const double *wq, uint64_t wq_rows, int hbm_width,
+                            int tile_width, uint64_t record_bytes, uint64_t K, uint64_t seed, uint32_t first_syndrome, int mode, uint8_t *chain_out, int32_t *class_out,
+                            double *z_out)
+{
+    const bool site = w == nullptr;
+    if (!chains || (site && !wq) || !chain_out || !z_out || (mode == 1 && !class_out)) return fail(QECMC_ERR_INVALID, "%s: NULL buffer", name);
+    if (int rc = report(sample::check_sample_args(name, N, K, first_syndrome, mode))) return rc;
+    if (!site)
+        if (int rc = report(sample::check_sample_weights(name, w))) return rc;
+    uint64_t cap = 0;
+    if (int rc = report(sample::check_record_bytes(name, record_bytes, &cap))) return rc;
+    const sample::TiledSamplePlan tsp = sample::build_tiled_sample_plan(code, L, hbm_width, tile_width, name, cap);
+    const sweep::TiledPlan &tp = tsp.tiled;
+    const sweep::Plan &p = tp.plan;
+    if (int rc = report(p.refusal)) return rc;
+    if (site)
+        if (int rc = report(sample::check_sample_tiled_site(name, N, wq, wq_rows, tp))) return rc;
+    if (int rc = use_device(0)) return rc;
+    if (N == 0) return 0;
+    const uint64_t job_bytes = sample::tiled_sample_bytes_per_job(tsp);
+    const uint32_t pass = sweep::tiled_pass_units(tp.state_bits);
+    const size_t partials = (size_t)p.ncls << tp.n_held, per_syndrome = mode ? 1u : (size_t)p.ncls;
+    SweepBatch b(p, sweep::cut_launch_group(N, p.ncls, tp.n_held));
+    uint64_t kc_max = sample::kTiledLaunchSamples / ((uint64_t)b.group * (uint64_t)p.ncls);
+    if (kc_max < 1ull) kc_max = 1ull;
+    const uint32_t k_chunk = (uint32_t)(K < kc_max ? K : kc_max);
+    const size_t pairs = (size_t)b.group * p.ncls, max_samples = (size_t)b.group * per_syndrome * k_chunk;
+    const uint64_t group_units = (uint64_t)b.group * partials, max_jobs = tp.n_held == 0 ? (uint64_t)pairs : (uint64_t)max_samples;
+    DevBuf dwide, dftile, dfwords, dpart, dfold, dz, dcls, dspair, dsh, djob, drec, dchain;
+    SiteRows rows;
+    if (int rc = b.open(tp.dev_ops, &tp.held_words)) return rc;
+    HIP_TRY(dwide.alloc(tp.ops.size() * sizeof(uint32_t)));
+    HIP_TRY(dftile.alloc(tsp.forget_tile.size() * sizeof(uint32_t)));
+    HIP_TRY(dfwords.alloc(tsp.forget_words.size() * sizeof(uint32_t)));
+    HIP_TRY(dpart.alloc((size_t)group_units * sizeof(double)));                 // kCutGridMax doubles at most; dirty: every partial is written before it is read
+    HIP_TRY(dfold.alloc((size_t)group_units * sizeof(double)));                 // the copy the reduce folds: the pick reads the partials as they were
+    HIP_TRY(dz.alloc(pairs * sizeof(double)));
+    HIP_TRY(dcls.alloc(max_samples * sizeof(int32_t)));
+    HIP_TRY(dspair.alloc(max_samples * sizeof(uint32_t)));
+    HIP_TRY(dsh.alloc(max_samples * sizeof(uint32_t)));
+    HIP_TRY(djob.alloc(pairs * sizeof(uint32_t)));
+    HIP_TRY(drec.alloc(pairs * sizeof(uint32_t)));
+    HIP_TRY(dchain.alloc(max_samples * (size_t)p.nq));
+    HIP_TRY(hipMemcpy(dwide.p, tp.ops.data(), tp.ops.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dftile.p, tsp.forget_tile.data(), tsp.forget_tile.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dfwords.p, tsp.forget_words.data(), tsp.forget_words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (site)
+        if (int rc = rows.open(wq, wq_rows, p.nq, b.group)) return rc;
+    double wxz[4] = {0.0, 0.0, 0.0, 0.0};
+    if (!site) sweep::weights_xz(w, wxz);
+    const double *dwq = site ? rows.d.as<double>() : nullptr;
+    SweepCutArgs ra = cut_args(p, tp.n_held);                                   // k_class_sweep_reduce's
+    SampleArgs pa = {};                                                         // k_class_sample_pick's: it reads the counts, the mode, the holds and the draws' address alone
+    pa.ncls = p.ncls; pa.n_held = tp.n_held; pa.mode = mode;
+    pa.seed_lo = (uint32_t)seed; pa.seed_hi = (uint32_t)(seed >> 32);
+    SampleTiledWalkArgs wa = {};
+    wa.ncls = p.ncls; wa.W = p.W; wa.n_held = tp.n_held; wa.n_ops = p.n_ops; wa.n_forget = tsp.n_forget; wa.nq = p.nq; wa.tile_width = tp.tile_width;
+    wa.seed_lo = pa.seed_lo; wa.seed_hi = pa.seed_hi; wa.pairs_per_job = tsp.pairs_per_job;
+    std::vector<int32_t> cls_h(max_samples);
+    std::vector<uint32_t> job_h(pairs), rec_h(pairs);
+    std::vector<uint8_t> chain_h(max_samples * (size_t)p.nq);
+    TiledWorkspace &ws = TiledWorkspace::get();                                 // the state vectors: the tiled sweeps' block, cap and lock
+    std::lock_guard<std::mutex> hold(ws.mu);
+    TiledSampleBlock::Trim trim;
+    void *work_p = nullptr;
+    const uint64_t most = group_units > max_jobs ? group_units : max_jobs;
+    HIP_TRY(ws.take((size_t)(most < pass ? most : pass) * (sizeof(double) << tp.state_bits), &work_p));
+    double *work = static_cast<double *>(work_p);
+    return b.run(N, chains, nullptr, [&](uint64_t first, uint64_t here) {
+        if (site)
+            if (int rc = rows.group(first, here)) return rc;
+        const uint64_t units = here * partials;
+        for (uint64_t u = 0; u < units; u += pass) {
+            const uint32_t n = (uint32_t)(units - u < pass ? units - u : pass);
+            if (site) HIP_TRY(launch_class_sweep_tiled_site(tp, rows.per_syndrome, (uint32_t)u, n, b.ops(), b.held(), b.rep(), dwq, work, dpart.as<double>(), 0));
+            else HIP_TRY(launch_class_sweep_tiled(tp, wxz, (uint32_t)u, n, b.ops(), b.held(), b.rep(), work, dpart.as<double>(), 0));
+        }
+        HIP_TRY(hipMemcpyAsync(dfold.p, dpart.p, (size_t)units * sizeof(double), hipMemcpyDeviceToDevice, 0));
+        ra.S = (uint32_t)here;
+        HIP_TRY(launch_class_sweep_reduce(ra, dfold.as<double>(), dz.as<double>(), 0));
+        if (int rc = b.fetch(z_out, dz, first, here)) return rc;
+        for (uint64_t s = 0; s < here; ++s)
+            if (int rc = report(sample::check_sample_z(name, first + s, z_out + (first + s) * (uint64_t)p.ncls, p.ncls, mode))) return rc;
+        pa.syndrome0 = wa.syndrome0 = first_syndrome + (uint32_t)first;
+        for (uint64_t k0 = 0; k0 < K; k0 += k_chunk) {
+            const uint32_t kc = (uint32_t)(K - k0 < k_chunk ? K - k0 : k_chunk);
+            pa.k0 = wa.k0 = (uint32_t)k0; pa.k_chunk = wa.k_chunk = kc; pa.n_samples = (uint32_t)(here * per_syndrome * kc);
+            HIP_TRY(launch_sample_pick(pa, dpart.as<double>(), dz.as<double>(), dcls.as<int32_t>(), dspair.as<uint32_t>(), dsh.as<uint32_t>(), 0));
+            if (mode) {
+                HIP_TRY(hipMemcpy(cls_h.data(), dcls.p, (size_t)pa.n_samples * sizeof(int32_t), hipMemcpyDeviceToHost));
+                for (uint64_t s = 0; s < here; ++s) std::memcpy(class_out + (first + s) * K + k0, cls_h.data() + s * kc, (size_t)kc * sizeof(int32_t));
+            }
+            uint32_t jobs = 0;
+            const uint32_t *job_pair = dspair.as<uint32_t>(), *job_hbits = dsh.as<uint32_t>(), *rec_of_pair = nullptr;      // a job per sample
+            if (tp.n_held == 0) {                                               // a job per pair: every pair in mode 0, the drawn pairs in mode 1
+                std::fill(rec_h.begin(), rec_h.end(), 0xFFFFFFFFu);
+                if (mode) {
+                    for (uint32_t i = 0; i < pa.n_samples; ++i) {
+                        const uint32_t pair = (i / kc) * (uint32_t)p.ncls + (uint32_t)cls_h[i];
+                        if (cls_h[i] < 0 || cls_h[i] >= p.ncls) return fail(QECMC_ERR_HIP, "%s: internal: sample %u drew a class outside the %d of the code", name, i, p.ncls);
+                        if (rec_h[pair] == 0xFFFFFFFFu) { rec_h[pair] = jobs; job_h[jobs++] = pair; }
+                    }
+                } else
+                    for (; jobs < (uint32_t)(here * p.ncls); ++jobs) rec_h[jobs] = job_h[jobs] = jobs;
+                HIP_TRY(hipMemcpy(djob.p, job_h.data(), (size_t)jobs * sizeof(uint32_t), hipMemcpyHostToDevice));
+                HIP_TRY(hipMemcpy(drec.p, rec_h.data(), (size_t)here * p.ncls * sizeof(uint32_t), hipMemcpyHostToDevice));
+                job_pair = djob.as<uint32_t>(); job_hbits = nullptr; rec_of_pair = drec.as<uint32_t>();
+            } else
+                jobs = pa.n_samples;
+            void *rec_p = nullptr;
+            HIP_TRY(TiledSampleBlock::get().take((size_t)(sample::tiled_sample_pass_jobs(tp.state_bits, job_bytes, jobs, cap) * job_bytes), cap, &rec_p));
+            sample::PairRecord *R = static_cast<sample::PairRecord *>(rec_p);
+            for (uint32_t j0 = 0; j0 < jobs;) {
+                const uint32_t n = sample::tiled_sample_pass_jobs(tp.state_bits, job_bytes, jobs - j0, cap);
+                HIP_TRY(launch_sample_tiled_record(tsp, site ? nullptr : wxz, site ? rows.per_syndrome : 0, j0, n, b.ops(), b.held(), b.rep(), dwq, job_pair, job_hbits,
+                                                   dftile.as<uint32_t>(), work, R, 0));
+                // the samples of the pass: contiguous where a job is a sample, or a pair in every-class mode ([s][c][kk]); every sample of the chunk in
+                // posterior mode, where those of another pass leave at once
+                wa.rec_first = j0; wa.records = n;
+                if (tp.n_held > 0) { wa.first = j0; wa.count = n; }
+                else if (mode == 0) { wa.first = j0 * kc; wa.count = n * kc; }
+                else { wa.first = 0; wa.count = pa.n_samples; }
+                HIP_TRY(launch_sample_tiled_walk(tsp, wa, dwide.as<uint32_t>(), b.held(), b.rep(), dfwords.as<uint32_t>(), dftile.as<uint32_t>(), dspair.as<uint32_t>(),
+                                                 dsh.as<uint32_t>(), rec_of_pair, R, dchain.as<uint8_t>(), 0));
+                j0 += n;
+            }
+            HIP_TRY(hipMemcpy(chain_h.data(), dchain.p, (size_t)pa.n_samples * p.nq, hipMemcpyDeviceToHost));
+            const size_t run = (size_t)kc * p.nq;                               // the kc chains of one (syndrome[, class]) are contiguous on both sides
+            for (uint64_t r = 0; r < here * per_syndrome; ++r) std::memcpy(chain_out + ((first * per_syndrome + r) * K + k0) * (uint64_t)p.nq, chain_h.data() + r * run, run);
+        }
+        return 0;
+    });
+}
+}  // namespace
+
+int qecmc_class_sample_tiled(int code, int L, uint64_t N, const uint8_t *chains, const double w[4], int hbm_width, int tile_width, uint64_t record_bytes, uint64_t K,
+                             uint64_t seed, uint32_t first_syndrome, int mode, uint8_t *chain_out, int32_t *class_out, double *z_out)
+{
+    if (!w) return fail(QECMC_ERR_INVALID, "qecmc_class_sample_tiled: NULL buffer");
+    return class_sample_tiled_impl("qecmc_class_sample_tiled", code, L, N, chains, w, nullptr, 0, hbm_width, tile_width, record_bytes, K, seed, first_syndrome, mode, chain_out,
+                                   class_out, z_out);
+}
+
+int qecmc_class_sample_tiled_site(int code, int L, uint64_t N, const uint8_t *chains, const double *wq, uint64_t wq_rows, int hbm_width, int tile_width, uint64_t record_bytes,
+                                  uint64_t K, uint64_t seed, uint32_t first_syndrome, int mode, uint8_t *chain_out, int32_t *class_out, double *z_out)
+{
+    return class_sample_tiled_impl("qecmc_class_sample_tiled_site", code, L, N, chains, nullptr, wq, wq_rows, hbm_width, tile_width, record_bytes, K, seed, first_syndrome, mode,
+                                   chain_out, class_out, z_out);
+}
+
+int qecmc_class_sample_tiled_info(int code, int L, int hbm_width, int tile_width, uint64_t record_bytes, int32_t *n_forget, uint64_t *bytes_per_job, uint32_t *jobs_per_pass)
+{
+    uint64_t cap = 0;
+    if (int rc = report(sample::check_record_bytes("qecmc_class_sample_tiled_info", record_bytes, &cap))) return rc;
+    const sample::TiledSamplePlan tsp = sample::build_tiled_sample_plan(code, L, hbm_width, tile_width, "qecmc_class_sample_tiled_info", cap);
+    if (tsp.n_forget > 0) {                                                     // (a plan refused for the cap alone has its tables)
+        if (n_forget) *n_forget = tsp.n_forget;
+        if (bytes_per_job) *bytes_per_job = sample::tiled_sample_bytes_per_job(tsp);
+    }
+    if (int rc = report(tsp.tiled.plan.refusal)) return rc;
+    if (jobs_per_pass) *jobs_per_pass = sample::tiled_sample_pass_jobs(tsp.tiled.state_bits, sample::tiled_sample_bytes_per_job(tsp), ~0ull, cap);
+    return 0;
 }
 
 // ---------------------------------------------------------------- chain / ladder

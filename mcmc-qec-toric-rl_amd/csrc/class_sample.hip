@@ -182,9 +182,17 @@ static bool sample_args_ok(const SampleArgs &a)
            a.n_samples <= sample::kLaunchSamples;
 }
 
+// what k_class_sample_pick reads of its arguments, and nothing else: the counts, the mode and the holds (the draws' address is taken as it is).  The
+// tiled route (class_sample_tiled.hpp) launches the pick on plans whose width and chain words are not a cut plan's
+static bool pick_args_ok(const SampleArgs &a)
+{
+    return (a.ncls == 4 || a.ncls == 16) && a.n_held >= 0 && a.n_held <= sweep::kMaxHeld && (a.mode == 0 || a.mode == 1) && a.k_chunk >= 1 && a.n_samples >= 1 &&
+           a.n_samples % a.k_chunk == 0 && a.n_samples <= sample::kLaunchSamples;
+}
+
 hipError_t launch_sample_pick(const SampleArgs &a, const double *P, const double *z, int32_t *cls, uint32_t *spair, uint32_t *sh, hipStream_t stream)
 {
-    if (!sample_args_ok(a) || !z || !spair || !sh || (a.mode && !cls) || (a.n_held > 0 && !P)) return hipErrorInvalidValue;
+    if (!pick_args_ok(a) || !z || !spair || !sh || (a.mode && !cls) || (a.n_held > 0 && !P)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_class_sample_pick, dim3((a.n_samples + kSampleWave - 1u) / kSampleWave), dim3(kSampleWave), 0, stream, a, P, z, cls, spair, sh);
     return hipGetLastError();
 }

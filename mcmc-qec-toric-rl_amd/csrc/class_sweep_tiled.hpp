@@ -303,6 +303,8 @@ struct TileRep {
 // (the first segment sets A[0] = 1), run the segment's ops there, store the entries live after its last op (the last segment: P[unit]).  Args is
 // SweepTiledArgs or SweepTiledSiteArgs (or the (min, +) pair of class_minplus_tiled.hpp); src: the factors of a CLOSE.  Alg is the entry algebra and T
 // its entry -- SumProduct over double, minplus::MinPlus over uint64_t --, T(1) the entry of the empty frontier: 1.0, or (cost 0, count 1).
+// The gather and the write-back are restated, around a FORGET of their own, by minplus::tile_sweep_traced (class_minplus_tiled_trace.hpp) and by
+// tile_sweep_recorded (class_sample_tiled.hip): a change to either loop here goes to both copies.
 template <class Alg, class T, class Args, class Src>
 __device__ __forceinline__ void tile_sweep(T *lds, const Args &a, const uint32_t *__restrict__ ops, const uint32_t *__restrict__ held,
                                            const uint32_t *__restrict__ reps, T *__restrict__ work, T *__restrict__ P, const Src &src)

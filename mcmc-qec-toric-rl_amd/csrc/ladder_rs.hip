@@ -1,5 +1,5 @@
 // The one launch path of the ladder kernels: choose_kernel() (kernel_choice.hpp) names the kernel of a launch, the instantiation units
-// (ladder_toric / ladder_surf / ladder_biased / ladder_sweep / ladder_uset / ladder_colour* / ladder_wu*.hip, built in parallel) hold it,
+// (ladder_toric / ladder_surf / ladder_biased / ladder_uset / ladder_colour* / ladder_wu*.hip, built in parallel) hold it,
 // and the launch runs it on the grid its family implies.  A key no unit holds is an error, never a neighbouring kernel.
 #include "kernels.hpp"
 #include "plan_host.hpp"   // kernel_shape(): what the choice reads of a launch

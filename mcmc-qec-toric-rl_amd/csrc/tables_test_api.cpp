@@ -14,6 +14,7 @@
 #include "class_minplus_tiled_trace.hpp"
 #include "class_sample.hpp"
 #include "class_marginal.hpp"
+#include "class_sample_tiled.hpp"
 #include "corrections.hpp"
 #include "enumerate.hpp"
 #include "kernel_choice.hpp"
@@ -749,6 +750,55 @@ int qt_class_minplus_tiled_trace_plan(int code, int L, int hbm_width, int tile_w
 uint32_t qt_class_minplus_tiled_trace_pass(int state_bits, uint64_t bytes_per_pair, uint64_t pairs_left, uint64_t cap)
 {
     return minplus::tiled_trace_pass_pairs(state_bits, bytes_per_pair, pairs_left, cap ? cap : minplus::kTiledTraceWorkspaceBytes);
+}
+// the exact sampler on the tiled plans (class_sample_tiled.hpp).  qt_class_sample_tiled: the host twin of qecmc_class_sample_tiled (w given) and
+// qecmc_class_sample_tiled_site (w NULL) behind the same host checks, in the same order -- the QECMC_ERR_* code of the refusal, its message in msg
+// (nullable); qt_class_sample_tiled_plan: forget_gen int32[n_forget], forget_words uint32[n_forget][W], forget_tile uint32[n_forget][4], pair_off
+// uint64[n_forget + 1] and seg_forget uint32[n_segments] (all nullable) under a record block of `cap` bytes (0: the library's default) -> n_forget, -1
+// where refused (the message in msg) or too small a buffer (cap_forget rows); through out8 (nullable, written for a plan refused for the cap alone as
+// well) n_forget, bytes_per_job, W, the default cap, the largest cap, state_bits, n_segments and n_held; qt_class_sample_tiled_pass: the jobs of one
+// record pass
+int qt_class_sample_tiled(int code, int L, uint64_t N, const uint8_t *chains, const double *w, const double *wq, uint64_t wq_rows, int hbm_width, int tile_width,
+                          uint64_t record_bytes, uint64_t K, uint64_t seed, uint32_t first_syndrome, int mode, uint8_t *chain_out, int32_t *class_out, double *z_out, char *msg,
+                          int msg_cap)
+{
+    const char *name = w ? "qecmc_class_sample_tiled" : "qecmc_class_sample_tiled_site";
+    if (!chains || (!w && !wq) || !chain_out || !z_out || (mode == 1 && !class_out)) return site_answer(refuse_params(QECMC_ERR_INVALID, "%s: NULL buffer", name), msg, msg_cap);
+    if (const Refusal r = sample::check_sample_args(name, N, K, first_syndrome, mode); r.code) return site_answer(r, msg, msg_cap);
+    if (w)
+        if (const Refusal r = sample::check_sample_weights(name, w); r.code) return site_answer(r, msg, msg_cap);
+    uint64_t cap = 0;
+    if (const Refusal r = sample::check_record_bytes(name, record_bytes, &cap); r.code) return site_answer(r, msg, msg_cap);
+    const sample::TiledSamplePlan tsp = sample::build_tiled_sample_plan(code, L, hbm_width, tile_width, name, cap);
+    if (tsp.tiled.plan.refusal.code) return site_answer(tsp.tiled.plan.refusal, msg, msg_cap);
+    if (!w)
+        if (const Refusal r = sample::check_sample_tiled_site(name, N, wq, wq_rows, tsp.tiled); r.code) return site_answer(r, msg, msg_cap);
+    return site_answer(sample::sample_tiled_host(tsp, name, N, chains, w, wq, wq_rows, K, seed, first_syndrome, mode, chain_out, class_out, z_out), msg, msg_cap);
+}
+int qt_class_sample_tiled_plan(int code, int L, int hbm_width, int tile_width, uint64_t cap, int32_t *forget_gen, uint32_t *forget_words, uint32_t *forget_tile,
+                               uint64_t *pair_off, uint32_t *seg_forget, int cap_forget, uint64_t *out8, char *msg, int msg_cap)
+{
+    const sample::TiledSamplePlan tsp =
+        sample::build_tiled_sample_plan(code, L, hbm_width, tile_width, "qecmc_class_sample_tiled", cap ? cap : sample::kTiledSampleRecordBytes);
+    const sweep::TiledPlan &tp = tsp.tiled;
+    if (out8 && tsp.n_forget > 0) {
+        out8[0] = (uint64_t)tsp.n_forget; out8[1] = sample::tiled_sample_bytes_per_job(tsp); out8[2] = (uint64_t)tp.plan.W; out8[3] = sample::kTiledSampleRecordBytes;
+        out8[4] = sample::kTiledSampleRecordBytesMax; out8[5] = (uint64_t)tp.state_bits; out8[6] = (uint64_t)tp.segments.size(); out8[7] = (uint64_t)tp.n_held;
+    }
+    if (tp.plan.refusal.code) { site_answer(tp.plan.refusal, msg, msg_cap); return -1; }
+    if ((forget_gen || forget_words || forget_tile || pair_off) && tsp.n_forget > cap_forget) return -1;
+    if (seg_forget && (int)tp.segments.size() > cap_forget) return -1;
+    if (forget_gen)
+        for (int i = 0; i < tsp.n_forget; ++i) forget_gen[i] = tsp.forget_gen[(size_t)i];
+    if (forget_words) std::memcpy(forget_words, tsp.forget_words.data(), tsp.forget_words.size() * sizeof(uint32_t));
+    if (forget_tile) std::memcpy(forget_tile, tsp.forget_tile.data(), tsp.forget_tile.size() * sizeof(uint32_t));
+    if (pair_off) std::memcpy(pair_off, tsp.pair_off.data(), tsp.pair_off.size() * sizeof(uint64_t));
+    if (seg_forget) std::memcpy(seg_forget, tsp.seg_forget.data(), tsp.seg_forget.size() * sizeof(uint32_t));
+    return tsp.n_forget;
+}
+uint32_t qt_class_sample_tiled_pass(int state_bits, uint64_t bytes_per_job, uint64_t jobs_left, uint64_t cap)
+{
+    return sample::tiled_sample_pass_jobs(state_bits, bytes_per_job, jobs_left, cap ? cap : sample::kTiledSampleRecordBytes);
 }
 // the top rung's frames of a pick window (wu_frames.hpp) for an accepted scan = wave block, from the window's 64 pick blocks picks[64][4]: the plan's
 // descriptors and logical masks (rows padded to the kernel's WV words, as the kernel stages them), thr16 from the plan's thr_logical as wu_run forms it.

@@ -20,7 +20,8 @@ from .exact import (coset_enumerator, class_weights, depolarizing_weight, biased
                     class_minplus_site, shortest_chains_site, min_weight_classes_site, min_weight_corrections_site, erasure_site_costs, llr_site_costs,
                     sample_chains, sample_chains_site, sample_posterior, posterior_error_counts,
                     class_marginals, class_marginals_site, posterior_marginals, exact_error_counts,
-                    class_minplus_tiled, class_minplus_tiled_site, shortest_chains_tiled, shortest_chains_tiled_site)
+                    class_minplus_tiled, class_minplus_tiled_site, shortest_chains_tiled, shortest_chains_tiled_site,
+                    sample_chains_tiled, sample_chains_tiled_site, sample_tiled_info)
 
 __all__ = ["QecmcError", "device_count", "lib", "TORIC", "XZZX", "ROTATED", "PLANAR", "Toric_code", "xzzx_code", "RotSurCode", "Planar_code",
            "Chain", "Ladder", "Chain_xyz", "Chain_biased", "Ladder_biased", "Chain_alpha", "Ladder_alpha", "PTEQ", "PTDC", "STDC", "STRC", "PTRC", "STDC_general_noise", "STDC_general_noise_shortest", "STDC_Nall_n_alpha", "single_temp", "PTEQ_biased", "PTEQ_alpha", "PTEQ_alpha_with_shortest", "pteq_shortest_batch", "shortest_distribution", "ptdc_batch", "ptdc_distribution", "pteq_batch", "percent_from_counts", "chains_from_syndromes", "corrections",
@@ -31,4 +32,5 @@ __all__ = ["QecmcError", "device_count", "lib", "TORIC", "XZZX", "ROTATED", "PLA
            "class_minplus_site", "shortest_chains_site", "min_weight_classes_site", "min_weight_corrections_site", "erasure_site_costs", "llr_site_costs",
            "sample_chains", "sample_chains_site", "sample_posterior", "posterior_error_counts",
            "class_marginals", "class_marginals_site", "posterior_marginals", "exact_error_counts",
-           "class_minplus_tiled", "class_minplus_tiled_site", "shortest_chains_tiled", "shortest_chains_tiled_site"]
+           "class_minplus_tiled", "class_minplus_tiled_site", "shortest_chains_tiled", "shortest_chains_tiled_site",
+           "sample_chains_tiled", "sample_chains_tiled_site", "sample_tiled_info"]

@@ -113,6 +113,11 @@ SIGNATURES = {
                                      C.POINTER(C.c_double)]),
     "qecmc_class_sample_site": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, C.POINTER(C.c_double), C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, _u8p,
                                           _i32p, C.POINTER(C.c_double)]),
+    "qecmc_class_sample_tiled": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
+                                           C.c_int, _u8p, _i32p, C.POINTER(C.c_double)]),
+    "qecmc_class_sample_tiled_site": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, C.POINTER(C.c_double), C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64,
+                                                C.c_uint32, C.c_int, _u8p, _i32p, C.POINTER(C.c_double)]),
+    "qecmc_class_sample_tiled_info": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, _i32p, _u64p, _u32p]),
     "qecmc_chain_update": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, C.c_double, C.c_double, C.c_uint64,
                                      C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64]),
     "qecmc_chain_update_biased": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u8p, C.c_double, C.c_double, C.c_double,

@@ -36,6 +36,10 @@ Exact marginals (qecmc_class_marginals, qecmc_class_marginals_site, DESIGN.md 4.
 backward sweep over the same stream -- class_marginals and class_marginals_site give, per class, the weight with which every qubit carries I, X, Y
 or Z; posterior_marginals mixes the classes with Z_c / Z; exact_error_counts is the exact value of what posterior_error_counts estimates.
 
+Exact draws on the tiled route (qecmc_class_sample_tiled, _tiled_site): sample_chains_tiled and sample_chains_tiled_site draw at the
+shapes past the cut plans (xzzx / rotated L = 13 .. 17 under the default record cap); sample_posterior and posterior_error_counts take
+method="tiled".
+
 The traceback on the tiled route (qecmc_class_minplus_tiled_chains, _chains_site): shortest_chains_tiled and
 shortest_chains_tiled_site return a shortest chain of every class at the shapes only the tiled sweep takes; min_weight_corrections and
 min_weight_corrections_site reach them with method="tiled"."""
@@ -707,7 +711,8 @@ def _sample_w4(p, w4, eta, alpha):
     return w
 
 
-def _sample(code, chains, w, site_weights, n_samples, seed, first_syndrome, size, lds_width, mode):
+def _sample(code, chains, w, site_weights, n_samples, seed, first_syndrome, size, lds_width, mode, tiled=None):
+    """both routes: tiled is None on the cut plans (lds_width), or (hbm_width, tile_width, record_bytes) on the plans tiled over HBM"""
     code = _CODES.get(code, code)
     flat, L = _as_chains(code, chains, size)
     n, nq, ncls, K = flat.shape[0], flat.shape[1], 16 if code == L_.TORIC else 4, int(n_samples)
@@ -717,18 +722,69 @@ def _sample(code, chains, w, site_weights, n_samples, seed, first_syndrome, size
     cls = np.zeros((n, K), dtype=np.int32)
     z = np.zeros((n, ncls), dtype=np.float64)
     f64p = C.POINTER(C.c_double)
-    tail = (int(lds_width), K, int(seed), int(first_syndrome), mode, L_.u8(out), L_.i32(cls), z.ctypes.data_as(f64p))
+    tail = (K, int(seed), int(first_syndrome), mode, L_.u8(out), L_.i32(cls), z.ctypes.data_as(f64p))
+    if tiled is None:
+        widths, uniform, site = (int(lds_width),), L_.lib().qecmc_class_sample, L_.lib().qecmc_class_sample_site
+    else:
+        hbm_width, tile_width, record_bytes = (int(v) for v in tiled)
+        if not 0 <= record_bytes < 2 ** 64:
+            raise ValueError(f"record_bytes={record_bytes!r}: the cap of the record block in bytes, or 0 for the default")
+        widths, uniform, site = (hbm_width, tile_width, record_bytes), L_.lib().qecmc_class_sample_tiled, L_.lib().qecmc_class_sample_tiled_site
     if site_weights is None:
-        L_.check(L_.lib().qecmc_class_sample(code, L, n, L_.u8(flat), w.ctypes.data_as(f64p), *tail))
+        L_.check(uniform(code, L, n, L_.u8(flat), w.ctypes.data_as(f64p), *widths, *tail))
     else:
         wq, rows = _as_site_weights(code, site_weights, L, n)
-        L_.check(L_.lib().qecmc_class_sample_site(code, L, n, L_.u8(flat), wq.ctypes.data_as(f64p), rows, *tail))
-    info = sweep_cut_info(code, L, lds_width)
+        L_.check(site(code, L, n, L_.u8(flat), wq.ctypes.data_as(f64p), rows, *widths, *tail))
+    info = sweep_cut_info(code, L, lds_width) if tiled is None else sweep_tiled_info(code, L, widths[0], widths[1])
     state = (2, L, L) if code in (L_.TORIC, L_.PLANAR) else (L, L)
     res = dict(chains=out.reshape(out.shape[:-1] + state), z=z, width=info["width"], held=info["held"])
     if mode:
         res["cls"] = cls
     return res
+
+
+_SAMPLE_METHODS = ("cut", "tiled")
+
+
+def _sample_route(method, lds_width, hbm_width, tile_width, record_bytes):
+    """the `tiled` argument of _sample for a method: None on the cut plans (the default everywhere), the widths and the cap where "tiled" is named; a
+    width of the other route is refused by name, as min_weight_corrections refuses it"""
+    if method not in _SAMPLE_METHODS:
+        raise ValueError(f"method={method!r}: the exact sampler runs on the cut plans ('cut') or tiled over HBM ('tiled')")
+    if method == "cut":
+        if hbm_width or tile_width or record_bytes:
+            raise ValueError("hbm_width, tile_width and record_bytes belong to method='tiled'; method='cut' takes lds_width")
+        return None
+    if lds_width:
+        raise ValueError("lds_width belongs to method='cut'; method='tiled' takes hbm_width, tile_width and record_bytes")
+    return hbm_width, tile_width, record_bytes
+
+
+def sample_tiled_info(code, size, hbm_width=0, tile_width=0, record_bytes=0):
+    """dict(n_forget, bytes_per_job, jobs_per_pass) of the tiled sampler's plan (qecmc_class_sample_tiled_info): the FORGETs of the stream, the bytes one
+    job's record takes on the device and the jobs of one record pass under a record block of record_bytes (0: 4 GiB).  A plan whose single job does not
+    fit is refused by name with its bytes (QecmcError)"""
+    code = _CODES.get(code, code)
+    nf, b, j = C.c_int32(), C.c_uint64(), C.c_uint32()
+    L_.check(L_.lib().qecmc_class_sample_tiled_info(code, int(size), int(hbm_width), int(tile_width), int(record_bytes), C.byref(nf), C.byref(b), C.byref(j)))
+    return dict(n_forget=nf.value, bytes_per_job=b.value, jobs_per_pass=j.value)
+
+
+def sample_chains_tiled(code, chains, p=None, w4=None, eta=None, alpha=None, n_samples=1, seed=0, first_syndrome=0, size=None, hbm_width=0, tile_width=0,
+                        record_bytes=0):
+    """sample_chains on the state vector tiled over HBM (qecmc_class_sample_tiled): exact, independent chains of every class at xzzx /
+    rotated L = 13 .. 17 under the default record cap -- L = 21, planar L = 8 .. 12 and toric L = 7 under a raised one.  The arguments and the result are
+    sample_chains' with lds_width replaced by hbm_width and tile_width as class_sweep_tiled takes them; z is class_sweep_tiled's, bit for bit.
+    record_bytes caps the device block of the records (0: 4 GiB; up to 64 GiB): a plan whose single job takes more is refused by name with its bytes
+    (QecmcError; sample_tiled_info tells beforehand).  A sample does not depend on tile_width or record_bytes, and where the tiled plan's holds are the
+    cut plan's (hbm_width = its lds_width) it is sample_chains' chain byte for byte."""
+    return _sample(code, chains, _sample_w4(p, w4, eta, alpha), None, n_samples, seed, first_syndrome, size, 0, 0, tiled=(hbm_width, tile_width, record_bytes))
+
+
+def sample_chains_tiled_site(code, chains, site_weights, n_samples=1, seed=0, first_syndrome=0, size=None, hbm_width=0, tile_width=0, record_bytes=0):
+    """sample_chains_tiled under a weight per qubit, or per (syndrome, qubit) (qecmc_class_sample_tiled_site): site_weights as sample_chains_site takes
+    them"""
+    return _sample(code, chains, None, site_weights, n_samples, seed, first_syndrome, size, 0, 0, tiled=(hbm_width, tile_width, record_bytes))
 
 
 def sample_chains(code, chains, p=None, w4=None, eta=None, alpha=None, n_samples=1, seed=0, first_syndrome=0, size=None, lds_width=0):
@@ -750,24 +806,31 @@ def sample_chains_site(code, chains, site_weights, n_samples=1, seed=0, first_sy
     return _sample(code, chains, None, site_weights, n_samples, seed, first_syndrome, size, lds_width, 0)
 
 
-def sample_posterior(code, chains, p=None, w4=None, eta=None, alpha=None, site_weights=None, n_samples=1, seed=0, first_syndrome=0, size=None, lds_width=0):
+def sample_posterior(code, chains, p=None, w4=None, eta=None, alpha=None, site_weights=None, n_samples=1, seed=0, first_syndrome=0, size=None, lds_width=0,
+                     method="cut", hbm_width=0, tile_width=0, record_bytes=0):
     """Exact, independent draws from P(chain | syndrome): the class first, with probability Z_c / Z, then a chain of it.  The weights are sample_chains',
     or site_weights as sample_chains_site takes them.
     Returns dict(chains uint8[N, n_samples, ...], cls int32[N, n_samples], z float64[N, ncls], width, held); chains[s, k] is sample_chains' chains[s,
     cls[s, k], k] under the same seed.  A row whose class weights total 0, are not finite, or total less than 2^-960 (LAW_FLOOR) is refused by name
-    (QecmcError); a class of weight 0 is never drawn."""
+    (QecmcError); a class of weight 0 is never drawn.
+    method="tiled" draws on the state vector tiled over HBM instead (sample_chains_tiled; hbm_width, tile_width and record_bytes as it takes them): the
+    shapes past the cut plans.  A width of the other route is refused by name."""
+    tiled = _sample_route(method, lds_width, hbm_width, tile_width, record_bytes)
     if site_weights is not None:
         if p is not None or w4 is not None:
             raise ValueError("site_weights replace p and w4")
-        return _sample(code, chains, None, site_weights, n_samples, seed, first_syndrome, size, lds_width, 1)
-    return _sample(code, chains, _sample_w4(p, w4, eta, alpha), None, n_samples, seed, first_syndrome, size, lds_width, 1)
+        return _sample(code, chains, None, site_weights, n_samples, seed, first_syndrome, size, lds_width, 1, tiled=tiled)
+    return _sample(code, chains, _sample_w4(p, w4, eta, alpha), None, n_samples, seed, first_syndrome, size, lds_width, 1, tiled=tiled)
 
 
-def posterior_error_counts(code, chains, p, n_samples, seed=0, eta=None, alpha=None, first_syndrome=0, size=None, lds_width=0):
+def posterior_error_counts(code, chains, p, n_samples, seed=0, eta=None, alpha=None, first_syndrome=0, size=None, lds_width=0, method="cut", hbm_width=0, tile_width=0,
+                           record_bytes=0):
     """float64[N]: the mean number of errors (cells that hold X, Y or Z) of n_samples exact draws from P(chain | syndrome) at error rate p -- what a
     sampler's rung at p converges to, with an error bar that shrinks as 1 / sqrt(n_samples).  exact_error_counts(...)["posterior"] is the exact value
-    this estimates, without draws.  Refused where sample_posterior refuses (QecmcError): a row total of 0, not finite or below 2^-960"""
-    r = sample_posterior(code, chains, p=p, eta=eta, alpha=alpha, n_samples=n_samples, seed=seed, first_syndrome=first_syndrome, size=size, lds_width=lds_width)
+    this estimates, without draws.  Refused where sample_posterior refuses (QecmcError): a row total of 0, not finite or below 2^-960.
+    method, hbm_width, tile_width and record_bytes are sample_posterior's: method="tiled" is the yardstick at the shapes past the cut plans."""
+    r = sample_posterior(code, chains, p=p, eta=eta, alpha=alpha, n_samples=n_samples, seed=seed, first_syndrome=first_syndrome, size=size, lds_width=lds_width,
+                         method=method, hbm_width=hbm_width, tile_width=tile_width, record_bytes=record_bytes)
     c = r["chains"]
     return (c.reshape(c.shape[0], c.shape[1], -1) != 0).sum(axis=2).mean(axis=1)
 
